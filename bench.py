@@ -7,11 +7,16 @@ streams per GPU (one stream per channel), `blocks` reference callbacks (1024 out
 of signal) per channel; every step ends with the decoded blocks delivered to the host.  The batch is
 sized so that 20 steps make a timed region of >= 0.5 s.
 
-`value` is BASELINE.json configs[2] (1024 channels x 2.5 Msps).  The same invocation also times, under
-"also", the north-star regime (>= 10 000 independent channels on one GPU), BASELINE configs[4]
-(4096 channels, 192-tap low-pass), configs[3]'s per-GPU share (2048 channels) and the other front ends'
-sample formats, each with its own parity gate, down-converter roofline and whole-job fraction of HBM
-bandwidth.
+`value` is BASELINE.json configs[2] (1024 channels x 2.5 Msps).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what that figure needs: it builds the seeded input, warms up
+with W steps, times K steps of one pass each, writes the outputs of the last step if --dump-outputs DIR is given
+(benchlib/dump.py) and prints the result line.  --full adds everything else, as every run did before the option existed:
+the parity gate of every case against the CPU checkers and the reference's builds, the burst and the sustained steps
+(--sustain: a step becomes as many passes as make the timed region last that long), the pure-reader HBM probe, the
+live PMC traffic passes, the CPU baseline and, under "also", the north-star regime (>= 10 000 independent channels on one
+GPU), BASELINE configs[4] (4096 channels, 192-tap low-pass), configs[3]'s per-GPU share (2048 channels) and the other
+front ends' sample formats, each with its own parity gate, down-converter roofline and whole-job fraction of HBM bandwidth.
 
 What is timed is what the product DELIVERS: contexts are created with ACG_F_REPAIR and every step ends with
 acg_collect_msgs -- the block thread's check / repair (acars.c:93-215) and outputmsg()'s field split
@@ -101,9 +106,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=sorted(CASES), default="throughput", help="the case reported as `value`")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the parity gates, the burst and sustained steps, the \"also\" cases, "
+                         "the pure-reader probe, the live traffic passes and the CPU baseline (a plain run: set-up, warm-up, timed "
+                         "steps, result line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step delivered (records of its last pass, dm and per-bit "
+                         "records of its last call for a seeded sample of channels) as DIR/<name>.npy, float32 / float64, <= 64 MB")
     ap.add_argument("--also", default=None,
-                    help="comma-separated cases timed in the same invocation and reported under \"also\" (default: wide,stress on "
-                         "one GPU; shard2048 on several; 'none' to skip)")
+                    help="comma-separated cases timed in the same invocation and reported under \"also\" (default with --full: "
+                         "all of them on one GPU, shard2048 on several; without --full: none; 'none' to skip)")
     ap.add_argument("--channels", type=int, default=None, help="channels per GPU (overrides the case; also: no \"also\" cases)")
     ap.add_argument("--decim", type=int, default=None, help="rtlMult: 200 = 2.5 Msps")
     ap.add_argument("--ntaps", type=int, default=None)
@@ -138,9 +150,9 @@ def main():
     ap.add_argument("--decoders", type=int, default=1, help="measurement aid: time this many decoders (separate allocations) in the same process")
     ap.add_argument("--ab", default=None, help="measurement aid: comma-separated ACG_FIR_VARIANT values (or NAME=v1,v2 for another per-launch "
                                                "switch, e.g. ACG_MSK_LPC_LIVE=2,4) timed after the run in the same process, same decoder")
-    ap.add_argument("--sustain", type=float, default=5.0,
+    ap.add_argument("--sustain", type=float, default=None,
                     help="seconds the timed region of every case should last at least: a step becomes as many passes over the resident "
-                         "batch as that takes (0 = one pass per step, the short burst of rounds 1-2)")
+                         "batch as that takes (0 = one pass per step, the short burst of rounds 1-2).  Default: 5 with --full, else 0")
     ap.add_argument("--sustain-hbm", type=float, default=20.0,
                     help="seconds the timed region of the cases that saturate HBM (benchlib.cases.SUSTAIN_HBM: wide, stress, cs16, f32) lasts at "
                          "least: at the power cap their rate sinks with the shader clock for tens of seconds, the first 5 s are reported "
@@ -165,6 +177,8 @@ def main():
     ap.add_argument("--cpu-child", nargs=4, default=None)
     ap.add_argument("--rtl8-cpu-child", nargs=3, default=None)
     args = ap.parse_args()
+    if args.sustain is None:
+        args.sustain = 5.0 if args.full else 0.0
     if args.rtl8_cpu_child:
         rtl8_cpu_child(*args.rtl8_cpu_child)
         return
@@ -237,7 +251,7 @@ def main():
         case["blocks"] = 8
     if args.also is not None:
         also = [] if args.also in ("", "none") else args.also.split(",")
-    elif overridden or args.format != "u8" or args.share > 1:
+    elif not args.full or overridden or args.format != "u8" or args.share > 1:
         also = []
     else:
         # (order: the two cases whose step the demodulator sets -- they follow the shader clock -- before the cases that saturate
@@ -273,12 +287,16 @@ def main():
 
     if rank == 0:
         head = res[0]
+        if args.dump_outputs:
+            from benchlib.dump import write_outputs
+            head["outputs"] = {"dir": args.dump_outputs, "shapes": write_outputs(J.dump, args.dump_outputs)}
+            del J.dump
         # what a pure streaming reader gets out of HBM on this very buffer (outside the timed regions): the
         # practical read ceiling next to the 8 TB/s spec figure
         import ctypes as C
         gbs = C.c_double(0)
         nbytes = min(J.iq_all.numel(), 1 << 34)
-        if J.L.acg_probe_read_dev(J.iq_all.data_ptr(), nbytes, 3, C.byref(gbs)) == 0:
+        if args.full and J.L.acg_probe_read_dev(J.iq_all.data_ptr(), nbytes, 3, C.byref(gbs)) == 0:
             for r in res:
                 r["roofline"]["pure_reader_GBs_measured_this_run"] = round(gbs.value, 1)
                 r["roofline"]["frac_of_pure_reader"] = round(r["roofline"]["achieved"] / gbs.value, 4)
@@ -307,7 +325,7 @@ def main():
             except subprocess.TimeoutExpired:
                 hostfed = {"error": "hostfed child did not finish within 240 s"}
         # roofline.traffic of the headline's launch shape, measured here and now (the committed passes stay as the fall-back)
-        if world == 1 and not args.no_live_traffic and not overridden and args.format == "u8" and args.share == 1:
+        if args.full and world == 1 and not args.no_live_traffic and not overridden and args.format == "u8" and args.share == 1:
             if "iq_all" in J.__dict__:
                 del J.iq_all
                 torch.cuda.empty_cache()
@@ -333,7 +351,8 @@ def main():
             "dtype": "f32",
         }
         for k in ("data", "config", "roofline", "whole_job_frac_of_hbm", "whole_job_GBs_per_gpu", "time_dominant_kernel",
-                  "timed_region_s", "sustain", "burst", "kernels", "parity", "per_gpu", "valu", "ab_same_process", "placement_trials", "roofline_msk"):
+                  "timed_region_s", "sustain", "burst", "kernels", "parity", "per_gpu", "valu", "ab_same_process", "placement_trials", "roofline_msk",
+                  "outputs"):
             if k in head:
                 out[k] = head[k]
         if out["time_dominant_kernel"] != out["roofline"]["kernel"]:
@@ -350,7 +369,7 @@ def main():
             out.setdefault("also", {})["hostfed"] = hostfed
         if rtl8 is not None:
             out.setdefault("also", {})["rtl8"] = rtl8
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = run_cpu_baseline(case["decim"])
             out["cpu_baseline"]["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
         out["multi_gpu"] = MULTI_GPU_NOTE

@@ -9,14 +9,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")          # the entry point the child processes of a run re-enter
 
 from .cases import CARRIER, COPY_CEILING_GBS, DEPTH, HBM_PEAK_GBS, SCALE, SNR_DB, make_taps
+from .dump import last_step_outputs
 from .probes import _probe_ab, _probe_decoders
 from .telemetry import gpu_clock_mhz, gpu_telemetry
 from .traffic import lookup_traffic
 
 
 def run_case(J, name, case, args, steps, warmup, headline):
-    """Builds the input of one workload in J.iq, checks the first pass against the oracle, times `steps`
+    """Builds the input of one workload in J.iq, checks the first pass against the oracle (--full), times `steps`
     steps.  Returns the dict that goes into the JSON line (rank 0) or None."""
+    import ctypes as C
     import numpy as np
     import torch
     from acarsdec_amd import decoder as D, synth as S, _capi as K, shard
@@ -198,13 +200,16 @@ def run_case(J, name, case, args, steps, warmup, headline):
     dec0 = dec
     maxfr = max(8192, int(nch * (cb / 3.0 + 2)))
     cb_bytes = cb * 1024 * M * bps
+    passes = [0]                                    # passes of dec0 since its last reset (the gate resets it once)
 
-    def step(lag=None, sink=None, dec=None, dm_sink=None, frames=False):
+    def step(lag=None, sink=None, dec=None, dm_sink=None, frames=False, raw=None):
         """one pass of the hot path over the batch; the results (acg_msg records; blocks with frames=True or --raw-blocks) are
         delivered to the host --collect-lag calls behind (default 2: the host then never waits for the block repair of the call
         before the newest one before it may hand over the next -- with a lag of 1 that wait sat between every two calls)"""
         lag = args.collect_lag if lag is None else lag
         n = 0
+        if dec is None:
+            passes[0] += 1
         dec = dec or dec0
         for k in range(ncall):
             part = iq[:, k * cb_bytes:(k + 1) * cb_bytes]
@@ -219,6 +224,7 @@ def run_case(J, name, case, args, steps, warmup, headline):
                     mm, fb, more = dec.collect_msgs_raw(lag, maxfr)
                     if sink is not None:
                         sink += [K.Msg.from_buffer_copy(fb[i]) for i in range(mm)]
+                    keep_raw(raw, fb, mm)
                     m += mm
                     if not more:
                         break
@@ -226,20 +232,29 @@ def run_case(J, name, case, args, steps, warmup, headline):
                 m, fb = dec.collect_frames_raw(lag, maxfr)
                 if sink is not None:
                     sink += [K.Frame.from_buffer_copy(fb[i]) for i in range(m)]
+                keep_raw(raw, fb, m)
             if dm_sink is not None:                     # (gate only) the 12.5 kHz samples this call's demodulator consumed
                 for c in dm_sink:
                     dm_sink[c].append(dec.dm(c, cb * 1024))
             n += m
         return n
 
-    def drain(dec=None):
+    def keep_raw(raw, fb, m):
+        """(--dump-outputs) the first m records of the library's reused result array, as bytes: one copy, parsed after the timed region"""
+        if raw is not None and m:
+            raw.append(C.string_at(C.addressof(fb), m * C.sizeof(fb._type_)))
+
+    def drain(dec=None, raw=None):
         """everything still queued, through the delivered path; returns the count"""
         dec = dec or dec0
         if not repair:
-            return dec.drain_frames_raw(maxfr)[0]
+            m, fb = dec.drain_frames_raw(maxfr)
+            keep_raw(raw, fb, m)
+            return m
         m = 0
         while True:
-            mm, _, more = dec.drain_msgs_raw(maxfr)
+            mm, fb, more = dec.drain_msgs_raw(maxfr)
+            keep_raw(raw, fb, mm)
             m += mm
             if not more:
                 return m
@@ -250,14 +265,20 @@ def run_case(J, name, case, args, steps, warmup, headline):
             dist.barrier(device_ids=[J.local]) if J.backend == "nccl" else dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- correctness gate on the first pass (state starts from reset): benchlib/gate.py
-    from types import SimpleNamespace
-    from . import gate
-    # channels the gate looks at: --check-channels (64), more where a case says so (wide: 8 callbacks = 0.66 s of signal per
-    # channel is half a block per channel -- VERDICT r05 weak 1: "also.wide gates on 32 blocks")
-    check = case.get("check_channels", args.check_channels) if args.check_channels == 64 else args.check_channels
-    parity = gate.first_pass(SimpleNamespace(check=check, args=args, J=J, name=name, rank=rank, nch=nch, share=share, fmt=fmt, M=M, taps=taps, ntaps=ntaps, iq=iq, row=row,
-                                             nout=nout, cb=cb, ncall=ncall, cb_bytes=cb_bytes, stream=stream, maxfr=maxfr, repair=repair, dec=dec, step=step))
+    # ---- correctness gate on the first pass (state starts from reset): benchlib/gate.py.  A comparison with the CPU checkers, so
+    # --full only: a plain run goes from set-up straight to warm-up (tests/ hold the parity of every kernel)
+    parity = None
+    gate_passes = 0
+    if args.full:
+        from types import SimpleNamespace
+        from . import gate
+        # channels the gate looks at: --check-channels (64), more where a case says so (wide: 8 callbacks = 0.66 s of signal per
+        # channel is half a block per channel -- VERDICT r05 weak 1: "also.wide gates on 32 blocks")
+        check = case.get("check_channels", args.check_channels) if args.check_channels == 64 else args.check_channels
+        parity = gate.first_pass(SimpleNamespace(check=check, args=args, J=J, name=name, rank=rank, nch=nch, share=share, fmt=fmt, M=M, taps=taps, ntaps=ntaps, iq=iq, row=row,
+                                                 nout=nout, cb=cb, ncall=ncall, cb_bytes=cb_bytes, stream=stream, maxfr=maxfr, repair=repair, dec=dec, step=step))
+        gate_passes = 2 if repair else 1                # (in the demodulator's warm-up event sums below)
+        passes[0] = 1                                   # the gate's last pass runs from a reset (repair) or from creation
 
     # ---- timing.  A "pass" = the hot path once over the resident batch (the step of rounds 1-2).  `burst`: `steps` single
     # passes, timed as before (about half a second at the headline case: too short to be seen by an outside observer, and
@@ -271,9 +292,21 @@ def run_case(J, name, case, args, steps, warmup, headline):
     sustain_s = args.sustain_hbm if (name in SUSTAIN_HBM and args.sustain > 0 and not args.channels) else args.sustain
 
     from .timing import timed_region
-    T = timed_region(step, drain, barrier, dec, steps, warmup, sustain_s, J, sync=torch.cuda.synchronize)
+    # --dump-outputs: what the host receives in the last pass of the last step (and the drain behind it), kept as raw records
+    dump = bool(headline and rank == 0 and getattr(args, "dump_outputs", None))
+    last_raw, last_start = [], []
+
+    def last_pass():
+        last_start.append(passes[0] * nout)             # 12.5 kHz samples per channel since the reset before this pass
+        return step(raw=last_raw)
+    # a plain run times one pass per step and has no burst; --full (or --sustain) adds the burst and sizes the step by it
+    T = timed_region(step, drain, barrier, dec, steps, warmup, sustain_s, J, sync=torch.cuda.synchronize,
+                     burst=bool(args.full or sustain_s > 0), last_pass=last_pass if dump else None,
+                     last_drain=(lambda: drain(raw=last_raw)) if dump else None)
     warm, tim_b, dt_burst, reps, clk0, clk_mid, clk1, tele_mid = (T[k] for k in ('warm', 'tim_b', 'dt_burst', 'reps', 'clk0', 'clk_mid', 'clk1', 'tele_mid'))
     dt_local, tim, step_ms, dt, nfr_total, per_rank = (T[k] for k in ('dt_local', 'tim', 'step_ms', 'dt', 'nfr_total', 'per_rank'))
+    if dump:                                            # (before the probes below touch the decoder)
+        J.dump = last_step_outputs(dec, last_raw, last_start[0], nch, cb * 1024, repair, bool(args.bitlog), K)
     # measurement aids (--ab, --decoders: same-process A/B of a per-launch switch, further decoders in the same process); not part
     # of the reported value, dead in the default run, and kept out of this function (the timed path must be auditable)
     ab = _probe_ab(args, J, step, drain, steps, nch, nout, M) if (args.ab and world == 1) else None
@@ -295,11 +328,13 @@ def run_case(J, name, case, args, steps, warmup, headline):
     fir_avg_ms = tim["fir_ms"] / max(1, tim["fir_launches"])
     achieved = fir_bytes / (fir_avg_ms * 1e-3) / 1e9
     fir_ms_step = tim["fir_ms"] / steps
-    burst = {"value": round(world * samples_per_pass * steps / dt_burst / 1e6, 1), "ms_per_pass": round(dt_burst / steps * 1e3, 4),
-             "timed_region_s": round(dt_burst, 4), "whole_job_frac_of_hbm": round(pass_bytes * steps / dt_burst / 1e9 / HBM_PEAK_GBS, 4),
-             "roofline_frac": round(fir_bytes / (tim_b["fir_ms"] / max(1, tim_b["fir_launches"]) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-             "note": "`steps` single passes over the batch from a cold-ish device, as rounds 1-2 timed them; not the reported value"}
-    msk_ms_step = warm["msk_ms"] / (warmup + (2 if repair else 1)) * reps      # (the gate's one or two passes are in the sum)
+    burst = None
+    if dt_burst is not None:
+        burst = {"value": round(world * samples_per_pass * steps / dt_burst / 1e6, 1), "ms_per_pass": round(dt_burst / steps * 1e3, 4),
+                 "timed_region_s": round(dt_burst, 4), "whole_job_frac_of_hbm": round(pass_bytes * steps / dt_burst / 1e9 / HBM_PEAK_GBS, 4),
+                 "roofline_frac": round(fir_bytes / (tim_b["fir_ms"] / max(1, tim_b["fir_launches"]) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                 "note": "`steps` single passes over the batch from a cold-ish device, as rounds 1-2 timed them; not the reported value"}
+    msk_ms_step = warm["msk_ms"] / max(1, warmup + gate_passes) * reps          # (the gate's one or two passes are in the sum)
     mm = share > 1 and M in (160, 192, 200) and (cb * 1024) % 64 == 0             # (mirrors acg_fir_mm_takes)
     if fmt == 0:
         # (fir_mm.hip: two tiles in flight on one wave per SIMD where the demodulator shares the CUs -- no CU partition above 2048 channels)
@@ -324,10 +359,10 @@ def run_case(J, name, case, args, steps, warmup, headline):
     # issues ~275 instructions per bit period (msk_lean.hip, 8 lanes per channel -- 4: ~40 more --: 261 in a period inside a segment + the segment's
     # set-up and framing spread over its 8 bits; counted in the product's ISA, tests/test_host_logic.py) or ~325 (msk.hip, the other
     # launch shapes) from one wave per SIMD at >= 4 cycles each (profiles/r05_probe_msk_phase_stamps.txt)
-    msk_launches = max(1, warm["msk_launches"]) if "msk_launches" in warm else None
+    msk_launches = max(1, warm["msk_launches"]) if warm.get("msk_launches") else None     # (none without warm-up and gate)
     roofline_msk = None
     if msk_launches and clk_mid:
-        us_bit = warm["msk_ms"] / msk_launches * 1e3 / ((nblk * (warmup + (2 if repair else 1)) * 1024 / msk_launches) * 2400.0 / 12500.0)
+        us_bit = warm["msk_ms"] / msk_launches * 1e3 / ((nblk * (warmup + gate_passes) * 1024 / msk_launches) * 2400.0 / 12500.0)
         # (mirrors acg_create: lanes per channel by channel count; <= 2048 channels: the demodulator's own CU partition of 2.5 x its
         #  one-wave-per-SIMD minimum, at most 80 CUs)
         dec_lpc = 8 if nch <= 8192 else 4 if nch <= 16384 else 2 if nch <= 32768 else 1
@@ -356,7 +391,6 @@ def run_case(J, name, case, args, steps, warmup, headline):
                     "note": "a step = passes_per_step passes over the resident batch (chosen from the burst rate so that the timed region lasts "
                             ">= --sustain seconds); step times from host time stamps at the step boundaries (the host runs at most one call ahead "
                             "of the device); clocks from sysfs while the device is busy (null where the box does not expose them)"},
-        "burst": burst,
         "data": "synthetic: " + data_desc,
         "config": {"workload": "%s: %d channels/GPU x %.1f Msps %s, one stream per channel, rtlMult=%d, ntaps=%d; step = %d pass(es) over a resident batch of "
                                "%d callbacks/channel in calls of %d; FIR decimate + MSK demod + framing%s, delivered to the host %d call(s) behind"
@@ -397,6 +431,8 @@ def run_case(J, name, case, args, steps, warmup, headline):
                             "demodulator of i); the demodulator figure is taken during warm-up (its events are off in the timed region)"},
         "parity": parity,
     }
+    if burst is not None:
+        out["burst"] = burst
     if roofline_msk:
         out["roofline_msk"] = roofline_msk
     import re

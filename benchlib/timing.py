@@ -5,13 +5,17 @@ import time
 from .telemetry import gpu_clock_mhz, gpu_telemetry
 
 
-def timed_region(step, drain, barrier, dec, steps, warmup, sustain_s, J, sync=None):
+def timed_region(step, drain, barrier, dec, steps, warmup, sustain_s, J, sync=None, burst=True, last_pass=None, last_drain=None):
     """warm-up, the burst of `steps` single passes, then the reported region: `steps` steps of `reps` passes each, bracketed
     by barrier + synchronize on both sides; everything a step does is inside step() / drain() above: the process call(s) of
     the hot path and the collect of the delivered records.  Returns the raw clocks and counters; no probe, no switch.
     step() -> records delivered by one pass; drain() -> records still queued; barrier(): device synchronize + rank barrier;
     dec.timing() / dec.set_timing(): the library's event sums.  (bench.py --dry-run rehearses exactly this function, with a
-    stub in place of the decoder, on 8 gloo ranks without a GPU: tests/test_shard_gloo.py.)"""
+    stub in place of the decoder, on 8 gloo ranks without a GPU: tests/test_shard_gloo.py.)
+    burst=False (only with sustain_s == 0): no burst region, a step is one pass (dt_burst / tim_b come back None).
+    last_pass / last_drain: stand-ins for step() / drain() in the last pass of the last step and the drain behind it (the same
+    work, plus keeping the records the host receives there: bench.py --dump-outputs)."""
+    assert burst or sustain_s <= 0, "passes per step come from the burst rate"
     import numpy as np
     from acarsdec_amd import shard
     world, cdev = J.world, J.cdev
@@ -21,16 +25,18 @@ def timed_region(step, drain, barrier, dec, steps, warmup, sustain_s, J, sync=No
     warm = dec.timing()               # event sums of warm-up: the demodulator's launches are timed here only --
     dec.set_timing(2)                 # in the timed region only the down-converter (roofline) is bracketed,
                                       # event records on the demodulator stream sit on its serial launch chain
-    barrier()
-    t0 = time.perf_counter()
-    nfr_b = 0
-    for _ in range(steps):
-        nfr_b += step()
-    nfr_b += drain()
-    barrier()
-    dt_burst = time.perf_counter() - t0
-    tim_b = dec.timing()
-    dt_burst, _ = shard.reduce_timing(dt_burst, nfr_b, world, J.coll, cdev)
+    dt_burst, tim_b = None, None
+    if burst:
+        barrier()
+        t0 = time.perf_counter()
+        nfr_b = 0
+        for _ in range(steps):
+            nfr_b += step()
+        nfr_b += drain()
+        barrier()
+        dt_burst = time.perf_counter() - t0
+        tim_b = dec.timing()
+        dt_burst, _ = shard.reduce_timing(dt_burst, nfr_b, world, J.coll, cdev)
     reps = 1
     if sustain_s > 0:
         reps = max(1, int(np.ceil(sustain_s / max(dt_burst, 1e-6))))
@@ -44,15 +50,15 @@ def timed_region(step, drain, barrier, dec, steps, warmup, sustain_s, J, sync=No
     clk_mid, tele_mid = None, None
     tele0 = gpu_telemetry(J.local)
     for k_ in range(steps):
-        for _ in range(reps):
-            nfr += step()
+        for r_ in range(reps):
+            nfr += (last_pass if (last_pass is not None and k_ == steps - 1 and r_ == reps - 1) else step)()
         marks.append(time.perf_counter())
         if k_ == steps // 2:
             clk_mid = gpu_clock_mhz(J.local)
             tele_mid = gpu_telemetry(J.local)
     clk1 = gpu_clock_mhz(J.local)              # the last call(s) are still running
     tele1 = gpu_telemetry(J.local)
-    nfr += drain()                             # the last call's results: all K steps fully delivered inside the timed region
+    nfr += (last_drain or drain)()             # the last call's results: all K steps fully delivered inside the timed region
     if sync is not None:
         sync()                                 # this rank's device is idle: its OWN time (per_gpu), before it waits for the others
     dt_own = time.perf_counter() - t0

@@ -3,7 +3,7 @@
 #   usage (as ONE gpurun call):  bash profiles/probe/run.sh <outdir-tag> <stage> [<stage> ...]
 # stages:
 #   tests            pytest tests -m gpu
-#   bench            the default bench line                       -> bench_line.json
+#   bench            the full bench line (bench.py --full)         -> bench_line.json
 #   stats            rocprofv3 --kernel-trace --stats per case    -> <case>_stats.txt, bench_line_<case>_under_rocprof.json
 #   pmc              rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes per case (separate runs) -> <case>_fetch.txt / _write.txt
 #   ab:<case>:<spec> same-process A/B of a per-launch switch (bench.py --ab), e.g. ab:wide:ACG_MSK_LPC_LIVE=4,2,1  ab:stress:5,55,8
@@ -34,7 +34,7 @@ PY
 for st in "$@"; do
   case $st in
     tests) timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -25 | tee $O/pytest_gpu.txt ;;
-    bench) timeout 900 python bench.py --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench_err.txt; line $O/bench_line.json bench; tail -5 $O/bench_err.txt ;;
+    bench) timeout 900 python bench.py --full --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench_err.txt; line $O/bench_line.json bench; tail -5 $O/bench_err.txt ;;
     stats|pmc)
       cd /tmp
       for c in $CASES; do

@@ -8,6 +8,7 @@ Outputs (all derived data, no reference source):
   testwav_golden.json   raw blocks queued by decodeAcars, final channel_t state, stdout of the
                         reference program (-o 1/2/4) and its md5s, rtl-path blocks
   testwav_bits.npz      per-bit matched-filter outputs (msk.c:110) of every channel
+  syndrom_table.npy     the reference's CRC syndrome table (syndrom.h) as uint16 [1936]
 """
 import hashlib
 import json
@@ -90,8 +91,19 @@ def child_rtl():
     print(json.dumps(out))
 
 
+def syndrome_table():
+    """syndrom.h's table, as data: what tests/test_oracle_vs_ref.py compares the oracle's regenerated table with"""
+    import re
+    txt = open(os.path.join(os.path.dirname(WAV), "syndrom.h")).read()
+    body = txt[txt.index("static const unsigned short syndrom[]"):]
+    vals = np.array([int(x, 16) for x in re.findall(r"0x[0-9a-fA-F]+", body)], dtype=np.uint16)
+    assert vals.size == 1936
+    np.save(os.path.join(HERE, "syndrom_table.npy"), vals)
+
+
 def main():
     O.build()
+    syndrome_table()
     rate, pcm = O.read_wav_pcm16(WAV)
     np.savez_compressed(os.path.join(HERE, "testwav_pcm16.npz"), pcm=pcm, rate=rate)
     # the reference is all global state: one process per scenario

@@ -37,7 +37,7 @@ def par_msgs(d):
 
 
 def test_bench_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--channels", "256", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--channels", "256", "--steps", "4", "--warmup", "1",
                         "--no-cpu-baseline", "--sustain", "0"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
@@ -73,6 +73,41 @@ def test_bench_line_contract():
     assert d["roofline"]["pure_reader_GBs_measured_this_run"] > 1000
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full): no gate, no burst, no "also" cases -- K timed steps of one pass each, and --dump-outputs writes what
+    the last of them delivered as float32 / float64 .npy files; a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        out = str(tmp_path / ("run%d" % k))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--channels", "256", "--steps", "5", "--warmup", "2",
+                            "--dump-outputs", out], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = last_json(r.stdout)
+        c = compact_json(r.stdout)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert c[key] == d[key], key
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["sustain"]["passes_per_step"] == 1 and d["parity"] is None
+        assert "also" not in d and "burst" not in d and "cpu_baseline" not in d and "pure_reader_GBs_measured_this_run" not in d["roofline"]
+        # (timed_region_s is rounded to 0.1 ms and ms_per_step to 0.1 us: the product differs by that rounding at most)
+        assert abs(d["timed_region_s"] - 5 * d["ms_per_step"] * 1e-3) <= 0.5e-4 + 5 * 0.5e-7 + 1e-9
+        assert abs(d["value"] - 256 * 8 * 1024 * 200 * 5 / (d["ms_per_step"] * 5e-3) / 1e6) < 1e-3 * d["value"]
+        names = sorted(f for f in os.listdir(out))
+        assert names == sorted(n + ".npy" for n in d["outputs"]["shapes"]) and "msg_fields.npy" in names and "dm.npy" in names
+        arrs = {n: np.load(os.path.join(out, n)) for n in names}
+        assert all(a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        n_bits = arrs["bits_count.npy"].astype(int)
+        assert n_bits.shape == (128,) and n_bits.max() == arrs["bits_vo.npy"].shape[1] and n_bits.min() > 0
+        f = arrs["msg_fields.npy"]
+        # the records of the last pass only: they end inside it (column 5 = end_sample; 2 + 4 passes of 8 callbacks before it)
+        assert f.shape[0] > 0 and np.all(f[:, 5] >= 6 * 8 * 1024) and np.all(f[:, 5] < 7 * 8 * 1024)
+        assert arrs["dm.npy"].shape == (128, 8 * 1024) and np.all(np.isfinite(arrs["dm.npy"]))
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n], equal_nan=True), n
+
+
 def test_bench_also_cases_in_one_line():
     """one invocation = the headline case plus the cases under "also", each with its own parity gate, down-converter
     roofline and whole-job fraction of HBM bandwidth (here at reduced sizes through the case table)."""
@@ -82,7 +117,7 @@ def test_bench_also_cases_in_one_line():
             "bench.CASES['shard2048'].update(channels=192, blocks=4); "
             "bench.CASES['m160'].update(channels=256, blocks=4); bench.CASES['m192'].update(channels=256, blocks=4); "
             "bench.CASES['split16'].update(channels=256, blocks=4); bench.CASES['share8'].update(channels=512, blocks=4); "
-            "sys.argv = ['bench.py', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--sustain', '0.5', '--sustain-hbm', '0.5', "
+            "sys.argv = ['bench.py', '--full', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--sustain', '0.5', '--sustain-hbm', '0.5', "
             "'--hostfed-channels', '320']; bench.main()")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
@@ -150,7 +185,7 @@ def test_bench_gpus_flag_self_launch():
     the box's GPU over gloo, because RCCL wants one GPU per rank), rank 0 alone prints the line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["ACG_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--channels", "256", "--steps", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--channels", "256", "--steps", "4",
                         "--warmup", "1", "--no-cpu-baseline", "--sustain", "0"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     d = last_json(r.stdout)
@@ -169,7 +204,7 @@ def test_bench_gpus_flag_self_launch():
 def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, ACG_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--channels", "256", "--steps", "4",
+           "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--channels", "256", "--steps", "4",
            "--warmup", "1", "--no-cpu-baseline", "--sustain", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
@@ -187,7 +222,7 @@ def test_bench_rccl_path_runs_with_world_size_one():
     all-reduces and the all-gather of the per-rank times all go through it instead of the world == 1 short-cuts -- the calls
     the 8-GPU run makes, executed once on hardware."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "ACG_BENCH_BACKEND")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rccl-selftest", "--channels", "256", "--steps", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--rccl-selftest", "--channels", "256", "--steps", "4",
                         "--warmup", "1", "--no-cpu-baseline", "--sustain", "0", "--no-ref-leg"], capture_output=True, text=True, timeout=900,
                        cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-2500:])
