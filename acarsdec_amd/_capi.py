@@ -43,6 +43,20 @@ class Msg(C.Structure):
                 ("down", C.c_char), ("txt", C.c_ubyte * 242), ("reserved3", C.c_int)]
 
 
+MSGF_DOWNLINK_ONLY, MSGF_SKIP_EMPTY, MSGF_MAXLABELS = 1, 2, 64
+
+
+class MsgFilter(C.Structure):
+    """acg_msg_filter: the CLI's -A / -e flags and -b label list"""
+    _fields_ = [("flags", C.c_uint32), ("nlabels", C.c_int), ("labels", (C.c_char * 4) * MSGF_MAXLABELS)]
+
+
+class Oooi(C.Structure):
+    """acg_oooi: label.c's oooi_t (acarsdec.h:94-102) and DecodeLabel()'s return value"""
+    _fields_ = [("da", C.c_char * 5), ("sa", C.c_char * 5), ("eta", C.c_char * 5), ("gout", C.c_char * 5), ("gin", C.c_char * 5),
+                ("woff", C.c_char * 5), ("won", C.c_char * 5), ("decoded", C.c_char), ("reserved", C.c_char * 4)]
+
+
 BIT_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_float, C.c_float)
 
 # name -> (restype, argtypes): every symbol include/acarsdec_amd.h (the product API) and include/acarsdec_amd_lab.h (measurement
@@ -79,6 +93,10 @@ SYMBOLS = {
     "acg_collect_frames": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Frame), C.c_int, C.POINTER(C.c_int)]),
     "acg_drain_msgs": (C.c_int, [C.c_void_p, C.POINTER(Msg), C.c_int, C.POINTER(C.c_int)]),
     "acg_collect_msgs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Msg), C.c_int, C.POINTER(C.c_int)]),
+    "acg_parse_label_filter": (C.c_int, [C.c_char_p, C.POINTER(MsgFilter)]),
+    "acg_set_msg_filter": (C.c_int, [C.c_void_p, C.POINTER(MsgFilter)]),
+    "acg_drain_msgs_oooi": (C.c_int, [C.c_void_p, C.POINTER(Msg), C.POINTER(Oooi), C.c_int, C.POINTER(C.c_int)]),
+    "acg_collect_msgs_oooi": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Msg), C.POINTER(Oooi), C.c_int, C.POINTER(C.c_int)]),
     "acg_read_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "acg_read_bits_all": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acg_bit_capacity": (C.c_int, [C.c_void_p]),
@@ -111,6 +129,7 @@ LAB_SYMBOLS = {
     "acg_probe_read_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "acg_selftest_div2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "acg_selftest_sincos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "acg_selftest_msg_labels": (C.c_int, [C.POINTER(Msg), C.c_int, C.POINTER(MsgFilter), C.c_void_p, C.POINTER(Oooi)]),
     "acg_lab_set_block_counter": (C.c_int, [C.c_void_p, C.c_uint]),
     "acg_lab_block_ring_size": (C.c_uint, [C.c_void_p]),
 }

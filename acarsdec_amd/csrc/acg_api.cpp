@@ -207,6 +207,13 @@ struct acg_ctx {
     AcgMsgRec* d_msgs = nullptr;            // device + host staging for acg_collect_msgs / acg_drain_msgs
     AcgMsgRec* h_msgs = nullptr;
     size_t msgs_cap = 0;
+    bool msg_filter_on = false;             // acg_set_msg_filter: the sink's filters (label.hip) run on every message entry point
+    AcgLabelFilter msg_filter{};
+    AcgMsgRec* d_kmsgs = nullptr;           // label.hip's output: the kept records, their labels decoded, their count
+    acg_oooi* d_oooi = nullptr;
+    acg_oooi* h_oooi = nullptr;
+    unsigned int* d_kwork = nullptr;        // [kmsgs_cap / 256 + 1] per-workgroup counts, then the total
+    size_t kmsgs_cap = 0;
     unsigned int* d_work = nullptr;     // FIR run dispensers, ACG_DISP_WORDS words per chunk slot
     bool stream_identity = true;        // channel c reads stream c
     unsigned short* d_crctab = nullptr; // [256] + syndromes [1936] (ACG_F_REPAIR)
@@ -288,6 +295,7 @@ static void free_all(acg_ctx* c)
     hipFree(c->d_h); hipFree(c->d_sctab); hipFree(c->d_txt); hipFree(c->d_frames); hipFree(c->d_frame_count);
     hipFree(c->d_stamp);
     hipFree(c->d_msgs); std::free(c->h_msgs);
+    hipFree(c->d_kmsgs); hipFree(c->d_oooi); hipFree(c->d_kwork); std::free(c->h_oooi);
     hipFree(c->d_bits); hipFree(c->d_nbits); hipFree(c->d_stage[0]); hipFree(c->d_stage[1]); hipFree(c->d_work); hipFree(c->d_msk_done); std::free(c->h_stage); hipFree(c->d_crctab); hipFree(c->d_rep_upto);
     for (auto& p : c->fir_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& p : c->msk_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
@@ -1236,7 +1244,7 @@ extern "C" int acg_drain_frames(acg_ctx* ctx, acg_frame* out, int max_frames, in
 // ------------------------------------------------------------------------------------------
 // blocks [consumed, upto) of the ring through the device-side field split (blk.hip msg_split_kernel)
 static_assert(sizeof(AcgMsgRec) == sizeof(acg_msg), "device record and public record must have one layout");
-static int fetch_msgs(acg_ctx* ctx, unsigned int upto, acg_msg* out, int max_msgs, int* nmsgs)
+static int fetch_msgs(acg_ctx* ctx, unsigned int upto, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
 {
     if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
     unsigned int pending = upto - ctx->consumed;
@@ -1265,18 +1273,47 @@ static int fetch_msgs(acg_ctx* ctx, unsigned int upto, acg_msg* out, int max_msg
         if (!ctx->h_msgs) return fail(ctx, ACG_ENOMEM, "message staging");
         ctx->msgs_cap = want;
     }
+    // label.hip's pass (filters, label decoding, compaction) runs when a filter is set or the labels are asked for; without
+    // both the call launches and copies exactly what it did before the pass existed
+    const bool labels = oooi != nullptr || ctx->msg_filter_on;
+    if (labels && take > ctx->kmsgs_cap) {
+        hipFree(ctx->d_kmsgs); hipFree(ctx->d_oooi); hipFree(ctx->d_kwork);
+        std::free(ctx->h_oooi);
+        ctx->d_kmsgs = nullptr; ctx->d_oooi = nullptr; ctx->d_kwork = nullptr; ctx->h_oooi = nullptr;
+        ctx->kmsgs_cap = 0;
+        const size_t want = std::max<size_t>(take, 4096);
+        HIPCHK(ctx, hipMalloc(&ctx->d_kmsgs, want * sizeof(AcgMsgRec)));
+        HIPCHK(ctx, hipMalloc(&ctx->d_oooi, want * sizeof(acg_oooi)));
+        HIPCHK(ctx, hipMalloc(&ctx->d_kwork, (want / 256 + 2) * sizeof(unsigned int)));
+        ctx->h_oooi = (acg_oooi*)std::malloc(want * sizeof(acg_oooi));
+        if (!ctx->h_oooi) return fail(ctx, ACG_ENOMEM, "label staging");
+        ctx->kmsgs_cap = want;
+    }
+    unsigned int nrec = take;                                     // records that cross to the host
     if (take) {
         // the split writes every byte of a record (text tail zeroed), so nothing stale crosses the ABI
-        if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, take, ctx->d_msgs, ctx->copy_stream) != 0)
+        unsigned int* d_total = ctx->d_kwork + ctx->kmsgs_cap / 256 + 1;
+        const AcgLabelPass pass{&ctx->msg_filter, ctx->d_kwork, ctx->d_kmsgs, ctx->d_oooi, d_total, nullptr};
+        if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, take, ctx->d_msgs, ctx->copy_stream, labels ? &pass : nullptr) != 0)
             return fail(ctx, ACG_EHIP, "message split launch failed");
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_msgs, ctx->d_msgs, (size_t)take * sizeof(AcgMsgRec), hipMemcpyDeviceToHost, ctx->copy_stream));
+        if (labels) {
+            HIPCHK(ctx, hipMemcpyAsync(&nrec, d_total, sizeof(nrec), hipMemcpyDeviceToHost, ctx->copy_stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+            if (nrec > take) return fail(ctx, ACG_EHIP, "message label pass: count out of range");
+            if (nrec) {
+                HIPCHK(ctx, hipMemcpyAsync(ctx->h_msgs, ctx->d_kmsgs, (size_t)nrec * sizeof(AcgMsgRec), hipMemcpyDeviceToHost, ctx->copy_stream));
+                HIPCHK(ctx, hipMemcpyAsync(ctx->h_oooi, ctx->d_oooi, (size_t)nrec * sizeof(acg_oooi), hipMemcpyDeviceToHost, ctx->copy_stream));
+            }
+        } else {
+            HIPCHK(ctx, hipMemcpyAsync(ctx->h_msgs, ctx->d_msgs, (size_t)take * sizeof(AcgMsgRec), hipMemcpyDeviceToHost, ctx->copy_stream));
+        }
         HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
     }
     const AcgMsgRec* rec = ctx->h_msgs;
     ctx->consumed += take;
     std::vector<unsigned int> order;
-    order.reserve(take);
-    for (unsigned int i = 0; i < take; ++i)
+    order.reserve(nrec);
+    for (unsigned int i = 0; i < nrec; ++i)
         if (rec[i].valid) order.push_back(i);                     // (blocks the repair dropped yield nothing)
     std::sort(order.begin(), order.end(), [rec](unsigned int x, unsigned int y) {
         return rec[x].chn != rec[y].chn ? rec[x].chn < rec[y].chn : rec[x].end_bit < rec[y].end_bit;
@@ -1290,6 +1327,7 @@ static int fetch_msgs(acg_ctx* ctx, unsigned int upto, acg_msg* out, int max_msg
         m.reserved1 = 0;
         m.reserved2 = 0;
         m.reserved3 = 0;
+        if (oooi) oooi[kept - 1] = ctx->h_oooi[i];
     }
     *nmsgs = (int)kept;
     if (rc != ACG_OK) return rc;
@@ -1297,9 +1335,8 @@ static int fetch_msgs(acg_ctx* ctx, unsigned int upto, acg_msg* out, int max_msg
     return ACG_OK;
 }
 
-extern "C" int acg_collect_msgs(acg_ctx* ctx, int lag, acg_msg* out, int max_msgs, int* nmsgs)
+static int collect_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
 {
-    if (!ctx || !nmsgs || (max_msgs > 0 && !out) || lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
     *nmsgs = 0;
     if (lag > ctx->lag_max) return fail(ctx, ACG_EINVAL, "lag above acg_max_lag(): the block queue of this context holds fewer calls");
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
@@ -1308,18 +1345,145 @@ extern "C" int acg_collect_msgs(acg_ctx* ctx, int lag, acg_msg* out, int max_msg
     const int slot = (int)(call % acg_ctx::NCALL);
     HIPCHK(ctx, hipEventSynchronize(ctx->call_done[slot]));
     if ((int)(ctx->h_call_count[slot] - ctx->consumed) <= 0) return ACG_OK;      // (behind the consumer after a drain: see acg_collect_frames)
-    return fetch_msgs(ctx, ctx->h_call_count[slot], out, max_msgs, nmsgs);
+    return fetch_msgs(ctx, ctx->h_call_count[slot], out, oooi, max_msgs, nmsgs);
+}
+
+static int drain_msgs(acg_ctx* ctx, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    unsigned int count = 0;
+    HIPCHK(ctx, hipMemcpy(&count, ctx->d_frame_count, sizeof(count), hipMemcpyDeviceToHost));
+    return fetch_msgs(ctx, count, out, oooi, max_msgs, nmsgs);
+}
+
+extern "C" int acg_collect_msgs(acg_ctx* ctx, int lag, acg_msg* out, int max_msgs, int* nmsgs)
+{
+    if (!ctx || !nmsgs || (max_msgs > 0 && !out) || lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
+    *nmsgs = 0;
+    return collect_msgs(ctx, lag, out, nullptr, max_msgs, nmsgs);
 }
 
 extern "C" int acg_drain_msgs(acg_ctx* ctx, acg_msg* out, int max_msgs, int* nmsgs)
 {
     if (!ctx || !nmsgs || (max_msgs > 0 && !out)) return ACG_EINVAL;
     *nmsgs = 0;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    HIPCHK(ctx, hipDeviceSynchronize());
-    unsigned int count = 0;
-    HIPCHK(ctx, hipMemcpy(&count, ctx->d_frame_count, sizeof(count), hipMemcpyDeviceToHost));
-    return fetch_msgs(ctx, count, out, max_msgs, nmsgs);
+    return drain_msgs(ctx, out, nullptr, max_msgs, nmsgs);
+}
+
+extern "C" int acg_collect_msgs_oooi(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
+{
+    if (!ctx || !nmsgs || (max_msgs > 0 && (!out || !oooi)) || lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
+    *nmsgs = 0;
+    acg_oooi none;
+    return collect_msgs(ctx, lag, out, oooi ? oooi : &none, max_msgs, nmsgs);
+}
+
+extern "C" int acg_drain_msgs_oooi(acg_ctx* ctx, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
+{
+    if (!ctx || !nmsgs || (max_msgs > 0 && (!out || !oooi))) return ACG_EINVAL;
+    *nmsgs = 0;
+    acg_oooi none;
+    return drain_msgs(ctx, out, oooi ? oooi : &none, max_msgs, nmsgs);
+}
+
+// ---- the sink's filters (label.c:9-23 build_label_filter, acarsdec.c -A / -b / -e) --------------------------------------
+static_assert(ACG_LBL_MAXTOK == ACG_MSGF_MAXLABELS, "token capacity");
+static_assert(sizeof(acg_oooi) == 40 && offsetof(acg_oooi, decoded) == 35 && offsetof(acg_oooi, won) == 30,
+              "acg_oooi: oooi_t (acarsdec.h:94-102), decoded, padding");
+
+extern "C" int acg_parse_label_filter(const char* arg, acg_msg_filter* f)
+{
+    if (!f) return ACG_EINVAL;
+    int n = 0;
+    char tok[ACG_MSGF_MAXLABELS][4] = {};
+    for (const char* p = arg; p && *p;) {
+        if (*p == ':') { ++p; continue; }                         // strtok: runs of separators delimit nothing
+        const char* e = p;
+        while (*e && *e != ':') ++e;
+        if (n == ACG_MSGF_MAXLABELS) return ACG_EINVAL;
+        const size_t len = std::min<size_t>((size_t)(e - p), 3);   // a longer token never matches a label (at most 2 chars) either
+        std::memcpy(tok[n++], p, len);
+        p = e;
+    }
+    f->nlabels = n;
+    std::memcpy(f->labels, tok, sizeof(tok));
+    return ACG_OK;
+}
+
+// the device form of a filter (label.hip); ACG_EINVAL when it is not one acg_parse_label_filter could have made
+static int label_filter_dev(const acg_msg_filter* f, AcgLabelFilter* d)
+{
+    std::memset(d, 0, sizeof(*d));
+    if (!f) return ACG_OK;
+    if ((f->flags & ~(ACG_MSGF_DOWNLINK_ONLY | ACG_MSGF_SKIP_EMPTY)) || f->nlabels < 0 || f->nlabels > ACG_MSGF_MAXLABELS) return ACG_EINVAL;
+    d->flags = f->flags;
+    d->nlabels = f->nlabels;
+    for (int i = 0; i < f->nlabels; ++i) {
+        const char* t = f->labels[i];
+        if (!t[0] || std::memchr(t, 0, 4) == nullptr) return ACG_EINVAL;
+        unsigned int w = 0;
+        for (int k = 0; k < 3 && t[k]; ++k) w |= (unsigned int)(unsigned char)t[k] << (8 * k);
+        d->tok[i] = w;
+    }
+    return ACG_OK;
+}
+
+extern "C" int acg_set_msg_filter(acg_ctx* ctx, const acg_msg_filter* f)
+{
+    if (!ctx) return ACG_EINVAL;
+    AcgLabelFilter d;
+    if (label_filter_dev(f, &d) != ACG_OK) return fail(ctx, ACG_EINVAL, "message filter: unknown flag, label count or empty token");
+    ctx->msg_filter = d;
+    ctx->msg_filter_on = f != nullptr;
+    return ACG_OK;
+}
+
+extern "C" int acg_selftest_msg_labels(const acg_msg* in, int n, const acg_msg_filter* f, unsigned char* keep, acg_oooi* oooi)
+{
+    if (n < 0 || (n > 0 && (!in || !keep || !oooi))) return ACG_EINVAL;
+    AcgLabelFilter d;
+    if (label_filter_dev(f, &d) != ACG_OK) return ACG_EINVAL;
+    if (n == 0) return ACG_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
+    std::vector<AcgMsgRec> h((size_t)n);
+    std::memcpy(h.data(), in, (size_t)n * sizeof(AcgMsgRec));
+    for (auto& r : h) r.valid = 1;                                 // (acg_msg: reserved2) records as the sink hands them out
+    const size_t by = (size_t)n * sizeof(AcgMsgRec);
+    AcgMsgRec *d_in = nullptr, *d_out = nullptr;
+    acg_oooi* d_oooi = nullptr;
+    unsigned int* d_work = nullptr;
+    unsigned char* d_keep = nullptr;
+    const size_t nwg = (size_t)n / 256 + 1;
+    std::vector<AcgMsgRec> kept((size_t)n);
+    std::vector<acg_oooi> ko((size_t)n);
+    unsigned int total = 0;
+    int rc = ACG_EHIP;
+    const bool alloc = hipMalloc(&d_in, by) == hipSuccess && hipMalloc(&d_out, by) == hipSuccess &&
+                       hipMalloc(&d_oooi, (size_t)n * sizeof(acg_oooi)) == hipSuccess &&
+                       hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) == hipSuccess && hipMalloc(&d_keep, (size_t)n) == hipSuccess;
+    const AcgLabelPass pass{&d, d_work, d_out, d_oooi, d_work + nwg, d_keep};
+    if (alloc && hipMemcpy(d_in, h.data(), by, hipMemcpyHostToDevice) == hipSuccess &&
+        acg_launch_msg_split(nullptr, 0, 0, (unsigned int)n, d_in, nullptr, &pass) == 0 &&
+        hipMemcpy(&total, d_work + nwg, sizeof(total), hipMemcpyDeviceToHost) == hipSuccess && total <= (unsigned int)n &&
+        hipMemcpy(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
+        hipMemcpy(kept.data(), d_out, (size_t)total * sizeof(AcgMsgRec), hipMemcpyDeviceToHost) == hipSuccess &&
+        hipMemcpy(ko.data(), d_oooi, (size_t)total * sizeof(acg_oooi), hipMemcpyDeviceToHost) == hipSuccess) {
+        // the compaction's own check: the kept records, in input order, and nothing else
+        rc = ACG_OK;
+        unsigned int j = 0;
+        for (int i = 0; i < n; ++i) {
+            std::memset(&oooi[i], 0, sizeof(acg_oooi));
+            if (!keep[i]) continue;
+            if (j >= total || std::memcmp(&kept[j], &h[i], sizeof(AcgMsgRec)) != 0) rc = ACG_ESTATE;
+            else oooi[i] = ko[j];
+            ++j;
+        }
+        if (j != total) rc = ACG_ESTATE;
+    }
+    hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work); hipFree(d_keep);
+    return rc;
 }
 
 extern "C" int acg_bit_capacity(const acg_ctx* ctx) { return ctx ? ctx->bit_cap : 0; }

@@ -73,6 +73,15 @@ struct AcgMsgRec {
     int soh_back;               // (acg_msg: the host turns it into soh_sample) end_sample - sample of the SOH byte
 };
 
+// The batch sink's filters as the device takes them (label.hip): acg_msg_filter with every token packed into one word, its chars
+// from the low byte up and zero behind the NUL, so that a label compares as one word (acg_set_msg_filter normalises).
+#define ACG_LBL_MAXTOK 64       // == ACG_MSGF_MAXLABELS of the public header
+struct AcgLabelFilter {
+    unsigned int flags;         // ACG_MSGF_*
+    int nlabels;                // 0 = no label filter
+    unsigned int tok[ACG_LBL_MAXTOK];
+};
+
 struct FirArgs {
     const uint8_t* iq;          // [nstreams] rows
     size_t pitch;               // bytes between stream rows (multiple of 16)
@@ -172,7 +181,20 @@ int acg_launch_msk_lean(const MskArgs* a, int lanes_per_channel, int waves_per_g
 int acg_launch_msk2(const MskArgs* a, int pairs_per_group, void* stream);     // msk2.hip: the stream split over two waves (8 lanes per channel)
 int acg_launch_blk_repair(AcgFrameRec* frames, unsigned int cap, const unsigned int* upto, unsigned int* done_upto,
                           unsigned int* done_ctr, const unsigned short* synd, const unsigned short* crctab, int nch, void* stream);
-int acg_launch_msg_split(const AcgFrameRec* frames, unsigned int cap, unsigned int first, unsigned int n, AcgMsgRec* out, void* stream);
+// blk.hip: the field split of blocks [first, first + n) of the ring into out[n]; with `labels`, label.hip's pass over those records
+// follows on the same stream (frames == null: out already holds the records, only the label pass runs)
+struct AcgLabelPass {
+    const AcgLabelFilter* f;
+    unsigned int* wg_count;     // ceil(n / 256) words of scratch
+    AcgMsgRec* kept;            // the records kept, in order
+    void* oooi;                 // acg_oooi[]: their labels decoded
+    unsigned int* total;        // how many were kept
+    unsigned char* keep_out;    // or null: the decision per input record
+};
+int acg_launch_msg_split(const AcgFrameRec* frames, unsigned int cap, unsigned int first, unsigned int n, AcgMsgRec* out, void* stream,
+                         const AcgLabelPass* labels = nullptr);
+// label.hip: filter, label decoding and compaction of n split records (reached through acg_launch_msg_split)
+int acg_launch_msg_labels(const AcgMsgRec* recs, unsigned int n, const AcgLabelPass* p, void* stream);
 int acg_launch_sincos_selftest(const double* x, double* s, double* c, int n, const double* sctab, void* stream);
 int acg_launch_div2_selftest(const double* n0, const double* n1, const double* d, double* out, int n, void* stream);
 int acg_launch_synth_iq(uint8_t* iq, size_t pitch, int nrows, int nout, int decim, const float* env,

@@ -348,11 +348,15 @@ __global__ __launch_bounds__(64 * SPLIT_WAVES) void msg_split_kernel(const AcgFr
 }
 
 extern "C" int acg_launch_msg_split(const AcgFrameRec* frames, unsigned int cap, unsigned int first, unsigned int n,
-                                    AcgMsgRec* out, void* stream)
+                                    AcgMsgRec* out, void* stream, const AcgLabelPass* labels)
 {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(msg_split_kernel, dim3((n + SPLIT_WAVES - 1) / SPLIT_WAVES), dim3(64 * SPLIT_WAVES), 0, (hipStream_t)stream, frames, cap, first, n, out);
-    return (int)hipGetLastError();
+    if (frames) {
+        hipLaunchKernelGGL(msg_split_kernel, dim3((n + SPLIT_WAVES - 1) / SPLIT_WAVES), dim3(64 * SPLIT_WAVES), 0, (hipStream_t)stream, frames, cap, first, n, out);
+        const int e = (int)hipGetLastError();
+        if (e) return e;
+    }
+    return labels ? acg_launch_msg_labels(out, n, labels, stream) : 0;
 }
 
 extern "C" int acg_launch_blk_repair(AcgFrameRec* frames, unsigned int cap, const unsigned int* upto,

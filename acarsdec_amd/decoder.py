@@ -225,11 +225,14 @@ class Decoder:
             self._mbuf_cap = max_msgs
         return self._mbuf
 
-    def drain_msgs(self, max_msgs=4096):
+    def drain_msgs(self, max_msgs=4096, oooi=False):
         """outputmsg()'s field split of every block completed since the last drain (needs repair=True): K.Msg records.
         The C side hands out the oldest messages that fit and says ACG_EAGAIN ("call again, nothing lost") while more are
         queued: this wrapper calls again until the queue is empty, so the list is complete whatever max_msgs is (per call the
-        records are ordered by (chn, end_bit); across calls the order is completion order)."""
+        records are ordered by (chn, end_bit); across calls the order is completion order).
+        oooi=True: (K.Msg, K.Oooi) pairs from acg_drain_msgs_oooi (the labels decoded on the device)."""
+        if oooi:
+            return self._msgs_oooi(self.L.acg_drain_msgs_oooi, max_msgs)
         buf = self._msg_buf(max(1, max_msgs))
         out = []
         while True:
@@ -254,13 +257,41 @@ class Decoder:
         rc = self._chk(self.L.acg_collect_msgs(self.ctx, lag, buf, self._mbuf_cap, C.byref(n)), allow=(K.EAGAIN,))
         return n.value, buf, rc == K.EAGAIN
 
-    def collect_msgs(self, lag=1, max_msgs=4096):
-        """list of K.Msg of all calls but the `lag` newest (loops while the C side says "call again")"""
+    def collect_msgs(self, lag=1, max_msgs=4096, oooi=False):
+        """list of K.Msg of all calls but the `lag` newest (loops while the C side says "call again"); oooi=True: (K.Msg, K.Oooi)
+        pairs from acg_collect_msgs_oooi"""
+        if oooi:
+            return self._msgs_oooi(self.L.acg_collect_msgs_oooi, max_msgs, lag)
         out = []
         while True:
             n, buf, more = self.collect_msgs_raw(lag, max_msgs)
             out += [K.Msg.from_buffer_copy(buf[i]) for i in range(n)]
             if not more:
+                return out
+
+    # ---- the sink's filters and label decoding (acg_set_msg_filter, acg_*_msgs_oooi) -------------------------------------
+    def set_msg_filter(self, downlink_only=False, skip_empty=False, labels=None):
+        """The CLI's -A (downlink_only), -e (skip_empty) and -b (labels: a list of labels or a -b string "H1:Q1") for every
+        message entry point from now on.  All defaults = no filter (what a new context has)."""
+        if not downlink_only and not skip_empty and labels is None:
+            self._chk(self.L.acg_set_msg_filter(self.ctx, None))
+            return
+        f = make_msg_filter(downlink_only, skip_empty, labels, self.L)
+        self._chk(self.L.acg_set_msg_filter(self.ctx, C.byref(f)))
+
+    def _msgs_oooi(self, fn, max_msgs, *lead):
+        max_msgs = max(1, int(max_msgs))
+        if getattr(self, "_obuf_cap", 0) < max_msgs:
+            self._obuf = (K.Oooi * max_msgs)()
+            self._obuf_cap = max_msgs
+        buf = self._msg_buf(max_msgs)
+        cap = min(self._mbuf_cap, self._obuf_cap)
+        out = []
+        while True:
+            n = C.c_int(0)
+            rc = self._chk(fn(self.ctx, *lead, buf, self._obuf, cap, C.byref(n)), allow=(K.EAGAIN,))
+            out += [(K.Msg.from_buffer_copy(buf[i]), K.Oooi.from_buffer_copy(self._obuf[i])) for i in range(n.value)]
+            if rc == K.OK:
                 return out
 
     def bits(self, ch):
@@ -299,6 +330,42 @@ class Decoder:
         nf, nm = C.c_int(0), C.c_int(0)
         self._chk(self.L.acg_get_timing(self.ctx, C.byref(f), C.byref(nf), C.byref(m), C.byref(nm)))
         return dict(fir_ms=f.value, fir_launches=nf.value, msk_ms=m.value, msk_launches=nm.value)
+
+
+def make_msg_filter(downlink_only=False, skip_empty=False, labels=None, lib=None):
+    """K.MsgFilter for acg_set_msg_filter / acg_selftest_msg_labels.  labels: None (no label filter), a -b string (split by
+    acg_parse_label_filter exactly as label.c does) or a list of labels."""
+    f = K.MsgFilter()
+    f.flags = (K.MSGF_DOWNLINK_ONLY if downlink_only else 0) | (K.MSGF_SKIP_EMPTY if skip_empty else 0)
+    if isinstance(labels, (str, bytes)):
+        arg = labels.encode("latin1") if isinstance(labels, str) else labels
+        _chk(None, (lib or K.load()).acg_parse_label_filter(arg, C.byref(f)))
+    elif labels is not None:
+        labels = [l.encode("latin1") if isinstance(l, str) else bytes(l) for l in labels]
+        if len(labels) > K.MSGF_MAXLABELS or not all(labels):
+            raise ValueError("at most %d non-empty labels" % K.MSGF_MAXLABELS)
+        f.nlabels = len(labels)
+        for i, l in enumerate(labels):
+            f.labels[i].value = l[:3]
+    return f
+
+
+# oooi_t field -> the reference JSON's key (output.c:280-295, in the order buildjson adds them)
+OOOI_JSON_KEYS = (("sa", "depa"), ("da", "dsta"), ("eta", "eta"), ("gout", "gtout"), ("gin", "gtin"), ("woff", "wloff"), ("won", "wlin"))
+
+
+def oooi_json(msg, oooi):
+    """The OOOI keys buildjson adds for (msg, oooi) (output.c:280-295): a key only when the label was decoded and the field's
+    first byte is not NUL; its value is the field as a C string.  msg is the K.Msg the record belongs to (kept for symmetry
+    with the other JSON keys a host builds from it)."""
+    out = {}
+    if oooi.decoded in (b"\x00", 0):
+        return out
+    for field, key in OOOI_JSON_KEYS:
+        v = getattr(oooi, field)                      # (ctypes c_char arrays read up to the first NUL)
+        if v:
+            out[key] = v.decode("latin1")
+    return out
 
 
 def frame_tuple(f):

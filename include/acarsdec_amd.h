@@ -127,7 +127,7 @@ typedef struct {
 /* A message as outputmsg() splits it out of a processed block (acarsmsg_t, acarsdec.h:108-124; output.c:486-560,
  * 566-568,623-631 in the build without libacars): the fixed binary record every sink (printmsg, buildjson, Netout*)
  * formats from.  Strings are NUL terminated like the reference's; txt is txt_len bytes, not terminated.  The CLI's
- * filters (-A airflt, label_filter) are not applied. */
+ * filters (-A airflt, -b label_filter, -e emptymsg) apply only once a host sets them (acg_set_msg_filter). */
 #define ACG_MSGTXTMAX   242
 typedef struct {
 	int chn;
@@ -250,6 +250,55 @@ int  acg_max_lag(const acg_ctx *ctx);
  * Every byte of a record is defined (unused text bytes are 0). */
 int  acg_drain_msgs(acg_ctx *ctx, acg_msg *out, int max_msgs, int *nmsgs);
 int  acg_collect_msgs(acg_ctx *ctx, int lag, acg_msg *out, int max_msgs, int *nmsgs);
+
+/* ---- the batch sink's filters and label decoding (output.c:537-540,650; label.c) ---------- */
+/* The CLI's three message filters, in the order outputmsg() applies them to a repaired block:
+ *   ACG_MSGF_DOWNLINK_ONLY  -A: drop uplinks (msg->down == 0)
+ *   label list              -b: keep only labels (as the C string the split reports: DEL second char -> 'd') equal to one of the
+ *                           tokens; a label whose first byte is NUL matches nothing; nlabels == 0 = no label filter
+ *   ACG_MSGF_SKIP_EMPTY     -e: drop when txt[0] == 0 -- NOT txt_len == 0: a text that starts with a NUL byte goes too
+ * A token slot holds up to 3 chars + NUL.  Labels have at most 2, so a longer token (stored as its first 3 chars) never matches
+ * but still switches the label filter on, as in the reference. */
+#define ACG_MSGF_DOWNLINK_ONLY  1u
+#define ACG_MSGF_SKIP_EMPTY     2u
+#define ACG_MSGF_MAXLABELS      64
+typedef struct {
+	uint32_t flags;               /* ACG_MSGF_* */
+	int nlabels;                  /* 0 .. ACG_MSGF_MAXLABELS tokens in use */
+	char labels[ACG_MSGF_MAXLABELS][4];   /* NUL terminated, non-empty */
+} acg_msg_filter;
+
+/* label.c build_label_filter(): splits a -b argument on ':' the way strtok does (empty tokens skipped: "::H1:" = {H1}).
+ * NULL or "" (or only separators) leaves the label list empty.  Only f->nlabels and f->labels are written (flags are the
+ * caller's).  ACG_EINVAL: f is NULL, or more than ACG_MSGF_MAXLABELS tokens. */
+int  acg_parse_label_filter(const char *arg, acg_msg_filter *f);
+/* Sets the filters of every message entry point (acg_drain_msgs, acg_collect_msgs and the _oooi pair below) from the next call
+ * on; NULL = no filter (the default).  A block a filter drops is consumed and yields nothing.  acg_drain_frames /
+ * acg_collect_frames are never filtered (they sit before outputmsg()).  With no filter set, acg_drain_msgs / acg_collect_msgs do
+ * exactly what they did before: no extra pass, nothing extra copied.  ACG_EINVAL: unknown flag bits, nlabels outside
+ * 0..ACG_MSGF_MAXLABELS, an empty or unterminated token. */
+int  acg_set_msg_filter(acg_ctx *ctx, const acg_msg_filter *f);
+
+/* label.c DecodeLabel() (run by printmsg, buildjson and the flight monitor: output.c:206-215,280-295,391-399) as a fixed record:
+ * oooi_t (acarsdec.h:94-102) field for field, then its return value.  Fields are 4 chars + NUL, copied from the text at fixed
+ * offsets; the JSON keys are depa = sa, dsta = da, eta, gtout = gout, gtin = gin, wloff = woff, wlin = won, each present when
+ * decoded != 0 and the field's first byte is not NUL.  When decoded == 0 every field is zero (the reference discards a partial
+ * fill); every byte of the record is defined.
+ * Bytes at or past txt_len read as 0.  The reference reads its calloc(txt_len + 1) copy of the text there and, where an
+ * extractor reaches beyond txt_len + 1, heap memory (a Q1 downlink with an empty text prints "dsta":"U" or whatever lies there),
+ * so this record equals the reference's output wherever the label's extractor stays within the text and its NUL. */
+typedef struct {
+	char da[5], sa[5], eta[5], gout[5], gin[5], woff[5], won[5];
+	char decoded;                 /* DecodeLabel()'s return value: 1 = the label's checks passed */
+	char reserved[4];             /* 0 */
+} acg_oooi;
+
+/* acg_drain_msgs / acg_collect_msgs with each message's label decoded on the device: oooi[i] belongs to out[i].  Same contract:
+ * the oldest max_msgs queued blocks are looked at and consumed, results in (chn, end_bit) order, ACG_EAGAIN / ACG_EOVERFLOW as
+ * there; the filters of acg_set_msg_filter apply.  One extra device pass (filter, decode, compaction) per call; only the records
+ * kept cross to the host. */
+int  acg_drain_msgs_oooi(acg_ctx *ctx, acg_msg *out, acg_oooi *oooi, int max_msgs, int *nmsgs);
+int  acg_collect_msgs_oooi(acg_ctx *ctx, int lag, acg_msg *out, acg_oooi *oooi, int max_msgs, int *nmsgs);
 /* Per-bit records of the LAST process call for one channel (needs ACG_F_BITLOG):
  * vo = the value putbit() receives (msk.c:122-126), lvl = cabsf(v) (msk.c:110). */
 int  acg_read_bits(acg_ctx *ctx, int ch, float *vo, float *lvl, int max_bits, int *nbits);

@@ -64,6 +64,12 @@ int  acg_selftest_sincos(const double *x_host, double *sin_host, double *cos_hos
  * with x = n0^2 + n1^2 -- a test checks the pairs are bit-identical over the operand range the loop produces */
 int  acg_selftest_div2(const double *n0_host, const double *n1_host, const double *d_host, double *out_host, int n);
 
+/* diagnostics: the batch sink's filter / label-decoding / compaction pass (label.hip) on n caller-supplied records, taken as
+ * acg_drain_msgs hands them out (every record counts as kept by the block repair).  keep[i] = 1 when the filter f (NULL = none)
+ * keeps in[i]; oooi[i] = its decoded labels when kept, all zero when dropped.  Bytes of in[i].txt at or past txt_len (clamped to
+ * 0..ACG_MSGTXTMAX) read as 0; label[2] is not read.  Returns ACG_ESTATE when the compacted records are not the kept inputs,
+ * byte for byte and in order, ACG_EINVAL for a bad filter or n < 0. */
+int  acg_selftest_msg_labels(const acg_msg *in, int n, const acg_msg_filter *f, unsigned char *keep, acg_oooi *oooi);
 
 /* Test hook (the block ring across the wrap of its 32-bit counters): right after acg_reset, with nothing queued,
  * sets the device's block counter, the repair pass's mark and the host's consumer mark to `value`, as if that many blocks had
