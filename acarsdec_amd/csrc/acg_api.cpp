@@ -694,44 +694,49 @@ static void begin_dm(acg_ctx* ctx)
     ctx->gbase = ctx->dm_par * ctx->cfg.max_blocks;
 }
 
-static int launch_fir(acg_ctx* c, const uint8_t* iq_dev, size_t pitch, int nblocks, hipStream_t s, int block0 = 0, bool with_demod = true)
+// The down-converter's arguments that do not depend on the input format.  The caller adds its format's geometry; the
+// pipeline adds the chunk (iq, dm, nwin, work_counter) and, on the partition's stream, ncu.
+static FirArgs fir_args(const acg_ctx* c)
 {
     const acg_config& g = c->cfg;
     FirArgs a{};
-    a.iq = iq_dev + (size_t)block0 * ACG_BLOCK * g.decim * 2;
-    a.pitch = pitch;
     a.stream_of = c->d_stream_of;
     a.taps = c->d_taps;
-    a.dm = c->d_dm + (size_t)block0 * ACG_BLOCK;
     a.dm_pitch = c->dm_pitch;
     a.nch = g.nch;
     a.decim = g.decim;
     a.ntaps_pad = c->ntaps_pad;
     a.ntaps = g.ntaps;
-    a.nwin = nblocks * ACG_BLOCK;
-    a.row_bytes = 2 * g.decim;
-    a.work_counter = c->d_work + (size_t)ACG_DISP_WORDS * block0;     // one dispenser per chunk slot
     a.stream_identity = c->stream_identity ? 1 : 0;
     // >= 16 384 channels: both stages share every CU and the down-converter is by far the longer one (+3..5 % whole job
     // at 16 384 channels).  Below that the starved demodulator becomes the longer stage: 8192 channels lose 7 % with the
     // raise, 4096 channels 15 % (profiles/r02_experiments/bench_variants.txt, "v_" rows).
     a.high_prio = (!c->fir_stream && g.nch >= 16384) ? 1 : 0;
     a.high_prio = acg_tune_get("ACG_FIR_PRIO", a.high_prio) ? 1 : 0;
-    a.shares_cus = (with_demod && !c->fir_stream) ? 1 : 0;
+    a.shares_cus = c->fir_stream ? 0 : 1;       // no CU partition: demodulator workgroups run on the same CUs
+    return a;
+}
+
+// u8 I/Q input at iq_dev, rows pitch bytes apart
+static FirArgs u8_args(const acg_ctx* c, const uint8_t* iq_dev, size_t pitch)
+{
+    FirArgs a = fir_args(c);
+    a.iq = iq_dev;
+    a.pitch = pitch;
+    a.row_bytes = 2 * c->cfg.decim;
     // few channels: the demodulator's serial chain is the critical path; three resident workgroups per CU
     // cost the down-converter ~5 % of its bandwidth and give the demodulator waves ~10 % (whole job +5 %)
-    a.wg_per_cu = (g.nch <= 2048 && c->msk_high_prio && !c->fir_stream) ? 3 : 0;
+    a.wg_per_cu = (c->cfg.nch <= 2048 && c->msk_high_prio && !c->fir_stream) ? 3 : 0;
     a.wg_per_cu = acg_tune_get("ACG_FIR_WG_HINT", a.wg_per_cu);
-    a.ncu = (s == c->fir_stream) ? c->fir_ncu : 0;
-    const bool timing = c->timing_mode != 0;
-    EvPair ev{};
-    if (timing) {
-        int r;
-        if ((r = get_event(c, &ev.a)) != ACG_OK || (r = get_event(c, &ev.b)) != ACG_OK) return r;
-        HIPCHK(c, hipEventRecord(ev.a, s));
-    }
+    return a;
+}
+
+// The u8 I/Q down-converter kernel for this context, and the tap images it needs.  Returns what the kernel's launcher
+// returned (a HIP error, 0 = launched), or ACG_EHIP with the text in c->err when a tap image could not be made.
+static int launch_fir_u8(acg_ctx* c, FirArgs& a, hipStream_t s)
+{
+    const acg_config& g = c->cfg;
     int e;
-    RoctxRange range("acg:down-converter");                // named range around the launch (rocprofv3 --marker-trace)
     if (c->exact_fir) {
         // verification mode: rtl.c:335-353 in the reference's own order of operations (fir.hip, fir_u8_generic_kernel)
         a.nseg = 1;
@@ -797,6 +802,27 @@ static int launch_fir(acg_ctx* c, const uint8_t* iq_dev, size_t pitch, int nbloc
         a.nseg = 1;
         e = acg_launch_fir_generic(&a, s);
     }
+    return e;
+}
+
+// One down-converter launch on stream s: launch(c, a, s) is the format's kernel choice (launch_fir_u8 or acg_launch_fir_fmt),
+// bracketed by the timing pair (acg_set_timing) and a named range (rocprofv3 --marker-trace).
+template <class Launch>
+static int fir_launch(acg_ctx* c, FirArgs& a, hipStream_t s, Launch&& launch)
+{
+    const bool timing = c->timing_mode != 0;
+    EvPair ev{};
+    if (timing) {
+        int r;
+        if ((r = get_event(c, &ev.a)) != ACG_OK || (r = get_event(c, &ev.b)) != ACG_OK) return r;
+        HIPCHK(c, hipEventRecord(ev.a, s));
+    }
+    int e;
+    {
+        RoctxRange range("acg:down-converter");
+        e = launch(c, a, s);
+    }
+    if (e < 0) return e;                             // an ACG_* code: the text is in c->err
     if (e != 0) {
         c->err = std::string("FIR launch: ") + hipGetErrorString((hipError_t)e);
         return ACG_EHIP;
@@ -880,18 +906,30 @@ static int check_iq_args(acg_ctx* ctx, const void* p, size_t pitch, int nblocks)
     return ACG_OK;
 }
 
+// ... of device input, which the tiled kernels read in 16-byte chunks
+static int check_iq_dev_args(acg_ctx* ctx, const uint8_t* iq_dev, size_t pitch, int nblocks)
+{
+    const int r = check_iq_args(ctx, iq_dev, pitch, nblocks);
+    if (r == ACG_OK && ctx->tile_path && (((uintptr_t)iq_dev | pitch) & 15))
+        return fail(ctx, ACG_EINVAL, "I/Q base and pitch must be 16-byte aligned");
+    return r;
+}
+
 extern "C" int acg_fir_only_dev(acg_ctx* ctx, const uint8_t* iq_dev, size_t pitch_bytes, int nblocks,
                                 void* hip_stream)
 {
-    int r = check_iq_args(ctx, iq_dev, pitch_bytes, nblocks);
+    int r = check_iq_dev_args(ctx, iq_dev, pitch_bytes, nblocks);
     if (r != ACG_OK) return r;
-    if (ctx->tile_path && (((uintptr_t)iq_dev | pitch_bytes) & 15))
-        return fail(ctx, ACG_EINVAL, "I/Q base and pitch must be 16-byte aligned");
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     begin_dm(ctx);
     if ((r = guard_wait(ctx, s, 0, nblocks)) != ACG_OK) return r;
-    r = launch_fir(ctx, iq_dev, pitch_bytes, nblocks, s, 0, false);
+    FirArgs a = u8_args(ctx, iq_dev, pitch_bytes);
+    a.shares_cus = 0;                               // no demodulator launch runs beside it
+    a.dm = ctx->d_dm;
+    a.nwin = nblocks * ACG_BLOCK;
+    a.work_counter = ctx->d_work;
+    r = fir_launch(ctx, a, s, launch_fir_u8);
     if (r == ACG_OK) ctx->last_len = nblocks * ACG_BLOCK;
     return r;
 }
@@ -938,17 +976,20 @@ static int end_of_call(acg_ctx* ctx)
     return ACG_OK;
 }
 
-extern "C" int acg_process_iq_u8_dev(acg_ctx* ctx, const uint8_t* iq_dev, size_t pitch_bytes, int nblocks,
-                                     void* hip_stream)
+// Software pipeline of one process call over nwin windows of input at a.iq (win_bytes per window and plane), in chunks of
+// chunk_win windows; launch is the input format's down-converter (see fir_launch).  The (bandwidth-bound, wide)
+// down-converter chunks run on the CALLER's stream: they are the only consumers of the input, so whatever the caller
+// enqueues next on that stream (refilling the buffer, the next call) is ordered correctly.  The (latency-bound,
+// narrow) demodulator chunks run in order on the context's own stream -- they carry the
+// channel state -- each waiting for its chunk of dm.  A dm chunk slot is rewritten by the
+// next call only after the demodulator launch that read it has finished.  So FIR(k+1) overlaps
+// MSK(k) inside a call, and FIR of call i+1 overlaps the MSK tail of call i.
+template <class Launch>
+static int run_pipeline(acg_ctx* ctx, hipStream_t caller, FirArgs& a, size_t win_bytes, int nwin, int chunk_win, Launch&& launch)
 {
-    int r = check_iq_args(ctx, iq_dev, pitch_bytes, nblocks);
-    if (r != ACG_OK) return r;
-    if (ctx->tile_path && (((uintptr_t)iq_dev | pitch_bytes) & 15))
-        return fail(ctx, ACG_EINVAL, "I/Q base and pitch must be 16-byte aligned");
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    int r;
     if ((r = begin_call(ctx)) != ACG_OK) return r;
     begin_dm(ctx);
-    hipStream_t caller = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     hipStream_t s = caller;
     if (ctx->fir_stream) {
         // CU partition: the down-converter runs on its own masked stream, ordered after what the caller
@@ -956,42 +997,39 @@ extern "C" int acg_process_iq_u8_dev(acg_ctx* ctx, const uint8_t* iq_dev, size_t
         s = ctx->fir_stream;
         HIPCHK(ctx, hipEventRecord(ctx->fir_in, caller));
         HIPCHK(ctx, hipStreamWaitEvent(s, ctx->fir_in, 0));
+        a.ncu = ctx->fir_ncu;
     }
-    // Software pipeline.  The (bandwidth-bound, wide) down-converter chunks run on the CALLER's
-    // stream: they are the only consumers of the input, so whatever the caller enqueues next on
-    // that stream (refilling the buffer, the next call) is ordered correctly.  The (latency-bound,
-    // narrow) demodulator chunks run in order on the context's own stream -- they carry the
-    // channel state -- each waiting for its chunk of dm.  A dm chunk slot is rewritten by the
-    // next call only after the demodulator launch that read it has finished.  So FIR(k+1) overlaps
-    // MSK(k) inside a call, and FIR of call i+1 overlaps the MSK tail of call i.
-    int cb = acg_tune_get("ACG_PIPE_BLOCKS_LIVE", ctx->pipe_blocks);      // (per call: same-context A/B of the chunk size)
-    if (cb <= 0 || cb > nblocks) cb = nblocks;
+    // dispatch order: the demodulator launch of the previous chunk goes to the chip BEFORE this
+    // down-converter launch floods it (otherwise its few long-lived waves are placed into whatever the
+    // persistent workgroups left over and run ~20 % slower): wait until the demodulator stream has
+    // reached that launch.  Costs one cross-queue signal per chunk; the down-converter is then at
+    // most two chunks ahead, which is all the run-ahead the pipeline needs.
+    // (with a CU partition the two stages cannot take each other's CUs: no ordering of the dispatches is needed, and the
+    //  demodulator's serial chain is spared one barrier packet per launch -- every packet between two of its kernels is
+    //  ~7 us during which the stage that sets the step stands still)
+    const bool order_dispatch = ctx->fir_stream == nullptr;
+    const uint8_t* iq0 = a.iq;
     int k = 0;
-    for (int b0 = 0; b0 < nblocks; b0 += cb, ++k) {
-        const int nb = std::min(cb, nblocks - b0);
-        // dm blocks [b0, b0+nb) may still be read by demodulator launches of the previous call
-        if ((r = guard_wait(ctx, s, b0, b0 + nb)) != ACG_OK) return r;
-        // dispatch order: the demodulator launch of the previous chunk goes to the chip BEFORE this
-        // down-converter launch floods it (otherwise its few long-lived waves are placed into whatever the
-        // persistent workgroups left over and run ~20 % slower): wait until the demodulator stream has
-        // reached that launch.  Costs one cross-queue signal per chunk; the down-converter is then at
-        // most two chunks ahead, which is all the run-ahead the pipeline needs.
-        // (with a CU partition the two stages cannot take each other's CUs: no ordering of the dispatches is needed, and the
-        //  demodulator's serial chain is spared one barrier packet per launch -- every packet between two of its kernels is
-        //  ~7 us during which the stage that sets the step stands still)
-        const bool order_dispatch = ctx->fir_stream == nullptr;
+    for (int w0 = 0; w0 < nwin; w0 += chunk_win, ++k) {
+        const int nw = std::min(chunk_win, nwin - w0);
+        const int j0 = w0 / ACG_BLOCK;
+        const int j1 = std::min(ctx->cfg.max_blocks, (w0 + nw + ACG_BLOCK - 1) / ACG_BLOCK);
+        // dm blocks [j0, j1) may still be read by demodulator launches of the previous call
+        if ((r = guard_wait(ctx, s, j0, j1)) != ACG_OK) return r;
         if (order_dispatch && ctx->msk_go_valid) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->msk_go, 0));
-        r = launch_fir(ctx, iq_dev, pitch_bytes, nb, s, b0);
-        if (r != ACG_OK) return r;
+        a.iq = iq0 + (size_t)w0 * win_bytes;
+        a.dm = ctx->d_dm + w0;
+        a.nwin = nw;
+        a.work_counter = ctx->d_work + (size_t)ACG_DISP_WORDS * j0;     // one dispenser per chunk slot
+        if ((r = fir_launch(ctx, a, s, launch)) != ACG_OK) return r;
         HIPCHK(ctx, hipEventRecord(ctx->fir_done[(size_t)k], s));
         HIPCHK(ctx, hipStreamWaitEvent(ctx->msk_stream, ctx->fir_done[(size_t)k], 0));
         if (order_dispatch) {
             HIPCHK(ctx, hipEventRecord(ctx->msk_go, ctx->msk_stream));
             ctx->msk_go_valid = true;
         }
-        r = launch_msk(ctx, ctx->d_dm + (size_t)b0 * ACG_BLOCK, ctx->dm_pitch, nb * ACG_BLOCK, ctx->msk_stream, b0 > 0);
-        if (r != ACG_OK) return r;
-        if ((r = guard_record(ctx, b0, b0 + nb)) != ACG_OK) return r;
+        if ((r = launch_msk(ctx, ctx->d_dm + w0, ctx->dm_pitch, nw, ctx->msk_stream, w0 > 0)) != ACG_OK) return r;
+        if ((r = guard_record(ctx, j0, j1)) != ACG_OK) return r;
     }
     if (ctx->fir_stream) {
         // ... and whatever the caller enqueues next on its stream (refilling the input) waits for the
@@ -999,8 +1037,21 @@ extern "C" int acg_process_iq_u8_dev(acg_ctx* ctx, const uint8_t* iq_dev, size_t
         HIPCHK(ctx, hipEventRecord(ctx->fir_out, s));
         HIPCHK(ctx, hipStreamWaitEvent(caller, ctx->fir_out, 0));
     }
-    ctx->last_len = nblocks * ACG_BLOCK;
+    ctx->last_len = nwin;
     return end_of_call(ctx);
+}
+
+extern "C" int acg_process_iq_u8_dev(acg_ctx* ctx, const uint8_t* iq_dev, size_t pitch_bytes, int nblocks,
+                                     void* hip_stream)
+{
+    int r = check_iq_dev_args(ctx, iq_dev, pitch_bytes, nblocks);
+    if (r != ACG_OK) return r;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    int cb = acg_tune_get("ACG_PIPE_BLOCKS_LIVE", ctx->pipe_blocks);      // (per call: same-context A/B of the chunk size)
+    if (cb <= 0 || cb > nblocks) cb = nblocks;
+    FirArgs a = u8_args(ctx, iq_dev, pitch_bytes);
+    return run_pipeline(ctx, hip_stream ? (hipStream_t)hip_stream : ctx->stream, a, (size_t)a.row_bytes, nblocks * ACG_BLOCK,
+                        cb * ACG_BLOCK, launch_fir_u8);
 }
 
 static int ensure_stage(acg_ctx* c, size_t bytes)
@@ -1107,15 +1158,16 @@ extern "C" int acg_sync(acg_ctx* ctx)
     return ACG_OK;
 }
 
-extern "C" int acg_placement_trial(acg_ctx* ctx, const uint8_t* iq_dev, size_t pitch_bytes, int nblocks, int repeats,
-                                   void* hip_stream, double* ms_per_call)
+// A placement trial: one untimed process call (it also checks the arguments), `repeats` timed ones, then a reset
+template <class Call>
+static int placement_trial(acg_ctx* ctx, int repeats, double* ms_per_call, Call&& call)
 {
     if (!ctx || !ms_per_call || repeats < 1) return ACG_EINVAL;
-    int rc = acg_process_iq_u8_dev(ctx, iq_dev, pitch_bytes, nblocks, hip_stream);      // untimed (and the argument check)
+    int rc = call();
     if (rc != ACG_OK) return rc;
     HIPCHK(ctx, hipDeviceSynchronize());
     const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < repeats && rc == ACG_OK; ++i) rc = acg_process_iq_u8_dev(ctx, iq_dev, pitch_bytes, nblocks, hip_stream);
+    for (int i = 0; i < repeats && rc == ACG_OK; ++i) rc = call();
     HIPCHK(ctx, hipDeviceSynchronize());
     const auto t1 = std::chrono::steady_clock::now();
     *ms_per_call = std::chrono::duration<double, std::milli>(t1 - t0).count() / repeats;
@@ -1124,40 +1176,93 @@ extern "C" int acg_placement_trial(acg_ctx* ctx, const uint8_t* iq_dev, size_t p
     return rc != ACG_OK ? rc : rr;
 }
 
+extern "C" int acg_placement_trial(acg_ctx* ctx, const uint8_t* iq_dev, size_t pitch_bytes, int nblocks, int repeats,
+                                   void* hip_stream, double* ms_per_call)
+{
+    return placement_trial(ctx, repeats, ms_per_call,
+                           [&] { return acg_process_iq_u8_dev(ctx, iq_dev, pitch_bytes, nblocks, hip_stream); });
+}
+
 extern "C" int acg_placement_trial_samples(acg_ctx* ctx, int fmt, const void* dev, size_t pitch_bytes, size_t plane_bytes, int nblocks,
                                            int repeats, void* hip_stream, double* ms_per_call)
 {
-    if (!ctx || !ms_per_call || repeats < 1) return ACG_EINVAL;
-    int rc = acg_process_samples_dev(ctx, fmt, dev, pitch_bytes, plane_bytes, nblocks, hip_stream);      // untimed (and the argument check)
-    if (rc != ACG_OK) return rc;
-    HIPCHK(ctx, hipDeviceSynchronize());
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < repeats && rc == ACG_OK; ++i) rc = acg_process_samples_dev(ctx, fmt, dev, pitch_bytes, plane_bytes, nblocks, hip_stream);
-    HIPCHK(ctx, hipDeviceSynchronize());
-    const auto t1 = std::chrono::steady_clock::now();
-    *ms_per_call = std::chrono::duration<double, std::milli>(t1 - t0).count() / repeats;
-    int rr = acg_reset(ctx);
-    if (rr == ACG_OK) rr = acg_get_timing(ctx, nullptr, nullptr, nullptr, nullptr);
-    return rc != ACG_OK ? rc : rr;
+    return placement_trial(ctx, repeats, ms_per_call,
+                           [&] { return acg_process_samples_dev(ctx, fmt, dev, pitch_bytes, plane_bytes, nblocks, hip_stream); });
 }
 
 // ------------------------------------------------------------------------------------------
-// Hands blocks of the ring to the host: the oldest min(pending, max_frames) records of [consumed, upto), ordered by
-// (chn, end_bit) within the call.  What does not fit STAYS queued (ACG_EAGAIN: call again, nothing lost); only a ring
-// that the device has lapped loses blocks (ACG_EOVERFLOW, the count is in acg_last_error).
-static int fetch_frames(acg_ctx* ctx, unsigned int upto, acg_frame* out, int max_frames, int* nframes)
+// The host's side of the block ring.  A collect hands out blocks up to the mark of the call `lag` calls behind the newest
+// (the queue length when that call ended), a drain (lag = DRAIN) up to the device's count once everything has finished:
+// the oldest min(pending, max) records of [consumed, upto), ordered by (chn, end_bit) within the call.  What does not fit
+// STAYS queued (ACG_EAGAIN: call again, nothing lost); only a ring that the device has lapped loses blocks (ACG_EOVERFLOW,
+// the count is in acg_last_error).
+static constexpr int DRAIN = -1;
+
+// *upto: where this collect / drain ends; *any = false: a collect with nothing pending (it returns ACG_OK at once)
+static int ring_upto(acg_ctx* ctx, int lag, unsigned int* upto, bool* any)
 {
-    unsigned int pending = upto - ctx->consumed;                  // monotonic counters, wrap-safe
+    *any = false;
+    if (lag != DRAIN && lag > ctx->lag_max) return fail(ctx, ACG_EINVAL, "lag above acg_max_lag(): the block queue of this context holds fewer calls");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    if (lag == DRAIN) {
+        HIPCHK(ctx, hipDeviceSynchronize());
+        HIPCHK(ctx, hipMemcpy(upto, ctx->d_frame_count, sizeof(*upto), hipMemcpyDeviceToHost));
+        *any = true;
+        return ACG_OK;
+    }
+    if (ctx->call_seq <= (unsigned long long)lag) return ACG_OK;              // nothing old enough yet
+    const unsigned long long call = ctx->call_seq - 1 - (unsigned long long)lag;
+    const int slot = (int)(call % acg_ctx::NCALL);
+    HIPCHK(ctx, hipEventSynchronize(ctx->call_done[slot]));                   // only that call, not newer ones
+    *upto = ctx->h_call_count[slot];
+    // (a drain may already have handed out more than that call had queued: its mark then lies BEHIND the consumer -- nothing
+    //  is pending; the counters are monotonic and wrap, so the comparison is a signed difference)
+    *any = (int)(*upto - ctx->consumed) > 0;
+    return ACG_OK;
+}
+
+// Claims the oldest min(pending, max) blocks of [consumed, upto); ACG_EOVERFLOW when the device lapped the host
+static int ring_claim(acg_ctx* ctx, unsigned int upto, int max, unsigned int* pending, unsigned int* take)
+{
     int rc = ACG_OK;
-    if (pending > ctx->frame_cap) {                               // the device lapped the host: oldest lost
+    *pending = upto - ctx->consumed;                              // monotonic counters, wrap-safe
+    if (*pending > ctx->frame_cap) {                              // the device lapped the host: oldest lost
         char msg[96];
-        std::snprintf(msg, sizeof(msg), "block queue lapped: the %u oldest blocks are lost", pending - ctx->frame_cap);
+        std::snprintf(msg, sizeof(msg), "block queue lapped: the %u oldest blocks are lost", *pending - ctx->frame_cap);
         ctx->err = msg;
         ctx->consumed = upto - ctx->frame_cap;
-        pending = ctx->frame_cap;
+        *pending = ctx->frame_cap;
         rc = ACG_EOVERFLOW;
     }
-    unsigned int take = std::min(pending, (unsigned int)std::max(0, max_frames));
+    *take = std::min(*pending, (unsigned int)std::max(0, max));
+    return rc;
+}
+
+// ... and what the call returns once the claimed records are out: the lap (its text is already in ctx->err), or `again`
+// when some stayed queued
+static int ring_result(acg_ctx* ctx, int rc, unsigned int pending, unsigned int take, const char* again)
+{
+    if (rc != ACG_OK) return rc;
+    if (take < pending) return fail(ctx, ACG_EAGAIN, again);
+    return ACG_OK;
+}
+
+// per channel in order (the contract): sorts an index into the records, not the records
+template <class Rec>
+static void order_by_channel(std::vector<unsigned int>& order, const Rec* rec)
+{
+    std::sort(order.begin(), order.end(), [rec](unsigned int x, unsigned int y) {
+        return rec[x].chn != rec[y].chn ? rec[x].chn < rec[y].chn : rec[x].end_bit < rec[y].end_bit;
+    });
+}
+
+static int fetch_frames(acg_ctx* ctx, int lag, acg_frame* out, int max_frames, int* nframes)
+{
+    unsigned int upto = 0, pending = 0, take = 0;
+    bool any = false;
+    int rc = ring_upto(ctx, lag, &upto, &any);
+    if (rc != ACG_OK || !any) return rc;
+    rc = ring_claim(ctx, upto, max_frames, &pending, &take);
     if (take > ctx->h_stage_cap) {                                // host staging, grown on demand
         // Pageable on purpose: with a pinned destination (one SDMA transfer) the same copy, issued while the
         // down-converter saturates HBM, made every step 0.9 ms slower at 16 384 channels (10.3 -> 11.2 ms);
@@ -1183,13 +1288,9 @@ static int fetch_frames(acg_ctx* ctx, unsigned int upto, acg_frame* out, int max
         HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
     }
     ctx->consumed += take;
-    // per channel in order (the contract); sort an index, not the 304-byte records
     std::vector<unsigned int> order(take);
     for (unsigned int i = 0; i < take; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [rec](unsigned int x, unsigned int y) {
-        const AcgFrameRec &a = rec[x], &b = rec[y];
-        return a.chn != b.chn ? a.chn < b.chn : a.end_bit < b.end_bit;
-    });
+    order_by_channel(order, rec);
     unsigned int kept = 0;
     for (unsigned int i = 0; i < take; ++i) {
         const AcgFrameRec& r = rec[order[i]];
@@ -1208,59 +1309,37 @@ static int fetch_frames(acg_ctx* ctx, unsigned int upto, acg_frame* out, int max
         f.soh_sample = r.end_sample - (long long)r.soh_back;      // acars.c:290: where the reference stamps blk->tv
     }
     *nframes = (int)kept;
-    if (rc != ACG_OK) return rc;                                  // (the text is already in ctx->err)
-    if (take < pending) return fail(ctx, ACG_EAGAIN, "more blocks queued than fit: call again");
-    return ACG_OK;
+    return ring_result(ctx, rc, pending, take, "more blocks queued than fit: call again");
 }
 
 extern "C" int acg_collect_frames(acg_ctx* ctx, int lag, acg_frame* out, int max_frames, int* nframes)
 {
     if (!ctx || !nframes || (max_frames > 0 && !out) || lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
     *nframes = 0;
-    if (lag > ctx->lag_max) return fail(ctx, ACG_EINVAL, "lag above acg_max_lag(): the block queue of this context holds fewer calls");
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (ctx->call_seq <= (unsigned long long)lag) return ACG_OK;              // nothing old enough yet
-    const unsigned long long call = ctx->call_seq - 1 - (unsigned long long)lag;
-    const int slot = (int)(call % acg_ctx::NCALL);
-    HIPCHK(ctx, hipEventSynchronize(ctx->call_done[slot]));                   // only that call, not newer ones
-    const unsigned int upto = ctx->h_call_count[slot];
-    // (a drain may already have handed out more than that call had queued: its mark then lies BEHIND the consumer -- nothing
-    //  is pending; the counters are monotonic and wrap, so the comparison is a signed difference)
-    if ((int)(upto - ctx->consumed) <= 0) return ACG_OK;
-    return fetch_frames(ctx, upto, out, max_frames, nframes);
+    return fetch_frames(ctx, lag, out, max_frames, nframes);
 }
 
 extern "C" int acg_drain_frames(acg_ctx* ctx, acg_frame* out, int max_frames, int* nframes)
 {
     if (!ctx || !nframes || (max_frames > 0 && !out)) return ACG_EINVAL;
     *nframes = 0;
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    HIPCHK(ctx, hipDeviceSynchronize());
-    unsigned int count = 0;
-    HIPCHK(ctx, hipMemcpy(&count, ctx->d_frame_count, sizeof(count), hipMemcpyDeviceToHost));
-    return fetch_frames(ctx, count, out, max_frames, nframes);
+    return fetch_frames(ctx, DRAIN, out, max_frames, nframes);
 }
 
 // ------------------------------------------------------------------------------------------
-// blocks [consumed, upto) of the ring through the device-side field split (blk.hip msg_split_kernel)
+// the claimed blocks through the device-side field split (blk.hip msg_split_kernel)
 static_assert(sizeof(AcgMsgRec) == sizeof(acg_msg), "device record and public record must have one layout");
-static int fetch_msgs(acg_ctx* ctx, unsigned int upto, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
+static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
 {
+    unsigned int upto = 0, pending = 0, take = 0;
+    bool any = false;
+    int rc = ring_upto(ctx, lag, &upto, &any);
+    if (rc != ACG_OK || !any) return rc;
     if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
-    unsigned int pending = upto - ctx->consumed;
-    int rc = ACG_OK;
-    if (pending > ctx->frame_cap) {                               // the device lapped the host: oldest lost
-        char msg[96];
-        std::snprintf(msg, sizeof(msg), "block queue lapped: the %u oldest blocks are lost", pending - ctx->frame_cap);
-        ctx->err = msg;
-        ctx->consumed = upto - ctx->frame_cap;
-        pending = ctx->frame_cap;
-        rc = ACG_EOVERFLOW;
-    }
     // A call splits and copies the oldest min(pending, max_msgs) blocks only (a block yields at most one message, so they
     // all fit) and consumes exactly those: draining a long queue through a small buffer costs what it hands out, not the
     // square of it, and the staging follows the caller's buffer, not the ring.
-    const unsigned int take = std::min(pending, (unsigned int)std::max(0, max_msgs));
+    rc = ring_claim(ctx, upto, max_msgs, &pending, &take);
     if (take > ctx->msgs_cap) {
         hipFree(ctx->d_msgs);
         std::free(ctx->h_msgs);
@@ -1315,9 +1394,7 @@ static int fetch_msgs(acg_ctx* ctx, unsigned int upto, acg_msg* out, acg_oooi* o
     order.reserve(nrec);
     for (unsigned int i = 0; i < nrec; ++i)
         if (rec[i].valid) order.push_back(i);                     // (blocks the repair dropped yield nothing)
-    std::sort(order.begin(), order.end(), [rec](unsigned int x, unsigned int y) {
-        return rec[x].chn != rec[y].chn ? rec[x].chn < rec[y].chn : rec[x].end_bit < rec[y].end_bit;
-    });
+    order_by_channel(order, rec);
     unsigned int kept = 0;
     for (unsigned int i : order) {
         acg_msg& m = out[kept++];
@@ -1330,45 +1407,21 @@ static int fetch_msgs(acg_ctx* ctx, unsigned int upto, acg_msg* out, acg_oooi* o
         if (oooi) oooi[kept - 1] = ctx->h_oooi[i];
     }
     *nmsgs = (int)kept;
-    if (rc != ACG_OK) return rc;
-    if (take < pending) return fail(ctx, ACG_EAGAIN, "more messages queued than fit: call again");
-    return ACG_OK;
-}
-
-static int collect_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
-{
-    *nmsgs = 0;
-    if (lag > ctx->lag_max) return fail(ctx, ACG_EINVAL, "lag above acg_max_lag(): the block queue of this context holds fewer calls");
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (ctx->call_seq <= (unsigned long long)lag) return ACG_OK;
-    const unsigned long long call = ctx->call_seq - 1 - (unsigned long long)lag;
-    const int slot = (int)(call % acg_ctx::NCALL);
-    HIPCHK(ctx, hipEventSynchronize(ctx->call_done[slot]));
-    if ((int)(ctx->h_call_count[slot] - ctx->consumed) <= 0) return ACG_OK;      // (behind the consumer after a drain: see acg_collect_frames)
-    return fetch_msgs(ctx, ctx->h_call_count[slot], out, oooi, max_msgs, nmsgs);
-}
-
-static int drain_msgs(acg_ctx* ctx, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
-{
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    HIPCHK(ctx, hipDeviceSynchronize());
-    unsigned int count = 0;
-    HIPCHK(ctx, hipMemcpy(&count, ctx->d_frame_count, sizeof(count), hipMemcpyDeviceToHost));
-    return fetch_msgs(ctx, count, out, oooi, max_msgs, nmsgs);
+    return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
 }
 
 extern "C" int acg_collect_msgs(acg_ctx* ctx, int lag, acg_msg* out, int max_msgs, int* nmsgs)
 {
     if (!ctx || !nmsgs || (max_msgs > 0 && !out) || lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
     *nmsgs = 0;
-    return collect_msgs(ctx, lag, out, nullptr, max_msgs, nmsgs);
+    return fetch_msgs(ctx, lag, out, nullptr, max_msgs, nmsgs);
 }
 
 extern "C" int acg_drain_msgs(acg_ctx* ctx, acg_msg* out, int max_msgs, int* nmsgs)
 {
     if (!ctx || !nmsgs || (max_msgs > 0 && !out)) return ACG_EINVAL;
     *nmsgs = 0;
-    return drain_msgs(ctx, out, nullptr, max_msgs, nmsgs);
+    return fetch_msgs(ctx, DRAIN, out, nullptr, max_msgs, nmsgs);
 }
 
 extern "C" int acg_collect_msgs_oooi(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
@@ -1376,7 +1429,7 @@ extern "C" int acg_collect_msgs_oooi(acg_ctx* ctx, int lag, acg_msg* out, acg_oo
     if (!ctx || !nmsgs || (max_msgs > 0 && (!out || !oooi)) || lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
     *nmsgs = 0;
     acg_oooi none;
-    return collect_msgs(ctx, lag, out, oooi ? oooi : &none, max_msgs, nmsgs);
+    return fetch_msgs(ctx, lag, out, oooi ? oooi : &none, max_msgs, nmsgs);
 }
 
 extern "C" int acg_drain_msgs_oooi(acg_ctx* ctx, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
@@ -1384,7 +1437,7 @@ extern "C" int acg_drain_msgs_oooi(acg_ctx* ctx, acg_msg* out, acg_oooi* oooi, i
     if (!ctx || !nmsgs || (max_msgs > 0 && (!out || !oooi))) return ACG_EINVAL;
     *nmsgs = 0;
     acg_oooi none;
-    return drain_msgs(ctx, out, oooi ? oooi : &none, max_msgs, nmsgs);
+    return fetch_msgs(ctx, DRAIN, out, oooi ? oooi : &none, max_msgs, nmsgs);
 }
 
 // ---- the sink's filters (label.c:9-23 build_label_filter, acarsdec.c -A / -b / -e) --------------------------------------
@@ -1697,7 +1750,7 @@ extern "C" int acg_get_timing(acg_ctx* ctx, double* fir_ms, int* fir_launches, d
 // ------------------------------------------------------------------------------------------
 // The other front ends' sample formats: soapy.c (CS16), sdrplay.c (split int16),
 // air.c (real f32).  Same tile kernel, 4 bytes per input sample.
-static int fmt_geometry(acg_ctx* ctx, int fmt, FirArgs* a, int nwin)
+static int fmt_args(acg_ctx* ctx, int fmt, FirArgs* a)
 {
     const acg_config& g = ctx->cfg;
     if (fmt < ACG_FMT_CS16 || fmt > ACG_FMT_F32_REAL) return fail(ctx, ACG_EINVAL, "unknown sample format");
@@ -1705,16 +1758,7 @@ static int fmt_geometry(acg_ctx* ctx, int fmt, FirArgs* a, int nwin)
         return fail(ctx, ACG_EINVAL, "this sample format needs decim % 4 == 0 (split planes: % 8 and <= 208)");
     if (ctx->ntaps_pad % (fmt == ACG_FMT_S16_SPLIT ? 8 : 4))
         return fail(ctx, ACG_EINVAL, "this sample format needs ntaps % 4 == 0 when decim % 8 != 0");
-    std::memset(a, 0, sizeof(*a));
-    a->stream_of = ctx->d_stream_of;
-    a->taps = ctx->d_taps;
-    a->dm = ctx->d_dm;
-    a->dm_pitch = ctx->dm_pitch;
-    a->nch = g.nch;
-    a->decim = g.decim;
-    a->ntaps_pad = ctx->ntaps_pad;
-    a->ntaps = g.ntaps;
-    a->nwin = nwin;
+    *a = fir_args(ctx);
     a->row_bytes = 4 * g.decim;
     a->cpr_total = a->row_bytes / 16;
     a->kseg = (a->cpr_total + 51) / 52;                 // LDS slice <= 52 chunks per window (Airspy: 480 -> 3 x 40, 800 -> 4 x 50)
@@ -1723,80 +1767,13 @@ static int fmt_geometry(acg_ctx* ctx, int fmt, FirArgs* a, int nwin)
     a->cpr_magic = ((1u << 20) + (unsigned int)a->cpr - 1) / (unsigned int)a->cpr;
     a->nseg = 1;
     a->out_scale = fmt == ACG_FMT_CS16 ? 1.0f / 32768.0f : fmt == ACG_FMT_S16_SPLIT ? 0.25f : 1.0f;
-    a->work_counter = ctx->d_work;
-    a->stream_identity = ctx->stream_identity ? 1 : 0;
-    a->shares_cus = ctx->fir_stream ? 0 : 1;                       // no CU partition: demodulator workgroups run on the same CUs
-    a->high_prio = acg_tune_get("ACG_FIR_PRIO", (!ctx->fir_stream && g.nch >= 16384) ? 1 : 0) ? 1 : 0;      // as launch_fir
     return ACG_OK;
 }
 
-// Same software pipeline as acg_process_iq_u8_dev: down-converter chunks on stream s, demodulator
-// chunks in order on the context's stream, per-block guards on the dm buffer.
-static int run_fmt(acg_ctx* ctx, int fmt, FirArgs* a, hipStream_t caller)
+// pipeline chunk of the formats: 4-byte samples, half the callbacks per ~2 GB
+static int fmt_chunk_win(const acg_ctx* ctx)
 {
-    { const int br = begin_call(ctx); if (br != ACG_OK) return br; }
-    begin_dm(ctx);
-    hipStream_t s = caller;
-    if (ctx->fir_stream) {                       // CU partition, see acg_process_iq_u8_dev
-        s = ctx->fir_stream;
-        HIPCHK(ctx, hipEventRecord(ctx->fir_in, caller));
-        HIPCHK(ctx, hipStreamWaitEvent(s, ctx->fir_in, 0));
-        a->ncu = ctx->fir_ncu;
-    }
-    const int nwin = a->nwin;
-    const uint8_t* iq0 = a->iq;
-    const size_t win_bytes = (size_t)(fmt == ACG_FMT_S16_SPLIT ? a->row_bytes / 2 : a->row_bytes);
-    int cb = ctx->pipe_blocks > 0 ? (ctx->pipe_blocks + 1) / 2 : ctx->cfg.max_blocks;   // 4-byte samples: half the callbacks per ~2 GB
-    const int cw = cb * ACG_BLOCK;
-    const bool timing = ctx->timing_mode != 0;
-    int k = 0;
-    for (int w0 = 0; w0 < nwin; w0 += cw, ++k) {
-        const int nw = std::min(cw, nwin - w0);
-        const int j0 = w0 / ACG_BLOCK;
-        const int j1 = std::min(ctx->cfg.max_blocks, (w0 + nw + ACG_BLOCK - 1) / ACG_BLOCK);
-        { const int gr = guard_wait(ctx, s, j0, j1); if (gr != ACG_OK) return gr; }
-        a->iq = iq0 + (size_t)w0 * win_bytes;
-        a->dm = ctx->d_dm + w0;
-        a->nwin = nw;
-        EvPair ev{};
-        if (timing) {
-            int r;
-            if ((r = get_event(ctx, &ev.a)) != ACG_OK || (r = get_event(ctx, &ev.b)) != ACG_OK) return r;
-            HIPCHK(ctx, hipEventRecord(ev.a, s));
-        }
-        const bool order_dispatch = ctx->fir_stream == nullptr;                       // see acg_process_iq_u8_dev
-        if (order_dispatch && ctx->msk_go_valid) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->msk_go, 0));
-        int e;
-        {
-            RoctxRange range("acg:down-converter");
-            e = acg_launch_fir_fmt(a, fmt, s);
-        }
-        if (e != 0) {
-            ctx->err = std::string("FIR launch: ") + hipGetErrorString((hipError_t)e);
-            return ACG_EHIP;
-        }
-        if (timing) {
-            HIPCHK(ctx, hipEventRecord(ev.b, s));
-            ctx->fir_ev.push_back(ev);
-        }
-        HIPCHK(ctx, hipEventRecord(ctx->fir_done[(size_t)k], s));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->msk_stream, ctx->fir_done[(size_t)k], 0));
-        if (order_dispatch) {
-            HIPCHK(ctx, hipEventRecord(ctx->msk_go, ctx->msk_stream));
-            ctx->msk_go_valid = true;
-        }
-        int r = launch_msk(ctx, ctx->d_dm + w0, ctx->dm_pitch, nw, ctx->msk_stream, w0 > 0);
-        if (r != ACG_OK) return r;
-        if ((r = guard_record(ctx, j0, j1)) != ACG_OK) return r;
-    }
-    a->iq = iq0;
-    a->nwin = nwin;
-    if (ctx->fir_stream) {
-        HIPCHK(ctx, hipEventRecord(ctx->fir_out, s));
-        HIPCHK(ctx, hipStreamWaitEvent(caller, ctx->fir_out, 0));
-    }
-    ctx->last_len = nwin;
-    return end_of_call(ctx);
+    return (ctx->pipe_blocks > 0 ? (ctx->pipe_blocks + 1) / 2 : ctx->cfg.max_blocks) * ACG_BLOCK;
 }
 
 extern "C" int acg_process_samples_dev(acg_ctx* ctx, int fmt, const void* dev, size_t pitch_bytes, size_t plane_bytes,
@@ -1807,12 +1784,14 @@ extern "C" int acg_process_samples_dev(acg_ctx* ctx, int fmt, const void* dev, s
     if ((((uintptr_t)dev | pitch_bytes | plane_bytes) & 15)) return fail(ctx, ACG_EINVAL, "base, pitch and plane must be 16-byte aligned");
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     FirArgs a;
-    int r = fmt_geometry(ctx, fmt, &a, nblocks * ACG_BLOCK);
+    int r = fmt_args(ctx, fmt, &a);
     if (r != ACG_OK) return r;
     a.iq = (const uint8_t*)dev;
     a.pitch = pitch_bytes;
     a.plane = plane_bytes;
-    return run_fmt(ctx, fmt, &a, hip_stream ? (hipStream_t)hip_stream : ctx->stream);
+    const size_t win_bytes = (size_t)ctx->cfg.decim * (fmt == ACG_FMT_S16_SPLIT ? 2 : 4);      // of one plane
+    return run_pipeline(ctx, hip_stream ? (hipStream_t)hip_stream : ctx->stream, a, win_bytes, nblocks * ACG_BLOCK, fmt_chunk_win(ctx),
+                        [fmt](acg_ctx*, FirArgs& f, hipStream_t s) { return acg_launch_fir_fmt(&f, fmt, s); });
 }
 
 // Host feed with carry: windows may straddle feeds of any size (soapy.c:232-254, sdrplay.c:215-236,
@@ -1824,7 +1803,7 @@ extern "C" int acg_feed_samples_host(acg_ctx* ctx, int fmt, const void* p0, cons
     if (!ctx || !p0 || (fmt == ACG_FMT_S16_SPLIT && !p1)) return ACG_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     FirArgs a;
-    int r = fmt_geometry(ctx, fmt, &a, 0);
+    int r = fmt_args(ctx, fmt, &a);
     if (r != ACG_OK) return r;
     if (ctx->feed_fmt != fmt) { ctx->feed_fmt = fmt; ctx->feed_fill = 0; }
     const acg_config& g = ctx->cfg;
@@ -1855,11 +1834,11 @@ extern "C" int acg_feed_samples_host(acg_ctx* ctx, int fmt, const void* p0, cons
         const size_t nwin = have / M;
         if (nwin > 0) {
             HIPCHK(ctx, hipStreamWaitEvent(s, ctx->h2d_done, 0));
-            a.nwin = (int)nwin;
             a.iq = base;
             a.pitch = rowb;
             a.plane = plane;
-            if ((r = run_fmt(ctx, fmt, &a, s)) != ACG_OK) {
+            if ((r = run_pipeline(ctx, s, a, M * bps, (int)nwin, fmt_chunk_win(ctx),
+                                  [fmt](acg_ctx*, FirArgs& f, hipStream_t st) { return acg_launch_fir_fmt(&f, fmt, st); })) != ACG_OK) {
                 (void)hipEventSynchronize(ctx->h2d_done);   // the copy may still be reading the caller's buffers: not after we return
                 return r;
             }

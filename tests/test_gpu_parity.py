@@ -1178,8 +1178,8 @@ def test_host_fed_calls_reuse_their_buffer_and_equal_device_fed_calls(D, O, S, n
         assert [b for b in want[0] if b[0] == c] == sorted(O.frame_tuple(f) for f in ch.frames), c
 
 
-@pytest.mark.parametrize("pipe", ["", "1", "3"])
-def test_soak_mixed_call_sizes_device_input(D, O, S, pipe, tune):
+@pytest.mark.parametrize("pipe,cus", [("", ""), ("1", ""), ("3", ""), ("", "0")], ids=["", "1", "3", "cus0"])
+def test_soak_mixed_call_sizes_device_input(D, O, S, pipe, cus, tune):
     """a long stream cut into calls of 1..4 callbacks in random order, device input refilled in place between
     calls (the stream contract), lagged collection, two dm buffers, shared streams (3 dongles x 4/5/3
     channels), CU partition, every pipeline chunking: blocks bit-exact per channel against the oracle run
@@ -1187,6 +1187,8 @@ def test_soak_mixed_call_sizes_device_input(D, O, S, pipe, tune):
     import torch
     if pipe:
         tune("ACG_PIPE_BLOCKS", pipe)
+    if cus:
+        tune("ACG_MSK_CUS", cus)
     rng = np.random.default_rng(90210)
     M, maxb = 160, 4
     sizes = [int(x) for x in rng.integers(1, maxb + 1, size=14)]
@@ -1247,12 +1249,32 @@ def test_soak_mixed_call_sizes_device_input(D, O, S, pipe, tune):
 
 
 # ------------------------------------------------------------------------------------ other front ends' formats
-@pytest.mark.parametrize("M,feeds", [(160, [1000, 163841 - 1000, 70000, 999999]), (200, [5, 204800, 3 * 204800 + 17, 10 ** 7]), (192, [10 ** 7]),
-                                      (400, [123457, 10 ** 7])])
-def test_cs16_soapy_path_with_carry_matches_oracle(D, O, S, M, feeds):
+# ACG_PIPE_BLOCKS / ACG_MSK_CUS (both read at acg_create) that take the formats' pipeline down its other branches at 4 blocks
+# per call: one-block chunks (several per call, on the feed and on the device path) and no CU partition
+PIPE_CUS = {"pipe1": ("1", ""), "cus0": ("", "0"), "pipe1-cus0": ("1", "0")}
+
+
+def with_pipe_cus(cases, ids, extra):
+    """`cases` under their ids with the context's own pipeline, then cases[extra] once more under each PIPE_CUS setting"""
+    return [pytest.param(*c, "", "", id=i) for c, i in zip(cases, ids)] + \
+        [pytest.param(*cases[extra], p, c, id="-".join(x for x in (ids[extra], k) if x)) for k, (p, c) in PIPE_CUS.items()]
+
+
+def set_pipe_cus(tune, pipe, cus):
+    if pipe:
+        tune("ACG_PIPE_BLOCKS", pipe)
+    if cus:
+        tune("ACG_MSK_CUS", cus)
+
+
+@pytest.mark.parametrize("M,feeds,pipe,cus", with_pipe_cus([(160, [1000, 163841 - 1000, 70000, 999999]), (200, [5, 204800, 3 * 204800 + 17, 10 ** 7]),
+                                                            (192, [10 ** 7]), (400, [123457, 10 ** 7])],
+                                                           ["160-feeds0", "200-feeds1", "192-feeds2", "400-feeds3"], 0))
+def test_cs16_soapy_path_with_carry_matches_oracle(D, O, S, M, feeds, pipe, cus, tune):
     """soapy.c shape: CS16 samples fed in reads of arbitrary size (windows straddle reads).  dm within the
     stated tolerance, blocks bit-exact, and the result independent of how the stream was cut."""
     from acarsdec_amd import _capi as K
+    set_pipe_cus(tune, pipe, cus)
     rng = np.random.default_rng(M)
     nch, nblk = 5, 4
     nout = nblk * 1024
@@ -1301,11 +1323,13 @@ def test_cs16_soapy_path_with_carry_matches_oracle(D, O, S, M, feeds):
     dec.close()
 
 
-def test_split16_sdrplay_path_matches_oracle(D, O, S):
+@pytest.mark.parametrize("pipe,cus", with_pipe_cus([()], [""], 0))
+def test_split16_sdrplay_path_matches_oracle(D, O, S, pipe, cus, tune):
     """sdrplay.c (two int16 planes, |D|/4): arbitrary callback sizes
     with carry, then the window-aligned device path; dm within tolerance, blocks bit-exact."""
     import torch
     from acarsdec_amd import _capi as K
+    set_pipe_cus(tune, pipe, cus)
     rng = np.random.default_rng(2718)
     nch, nblk = 4, 4
     nout = nblk * 1024
@@ -1350,13 +1374,14 @@ def test_split16_sdrplay_path_matches_oracle(D, O, S):
     dec.close()
 
 
-@pytest.mark.parametrize("rate", [2500000, 6000000, 10000000])
-def test_f32_airspy_path_matches_oracle(D, O, S, rate):
+@pytest.mark.parametrize("rate,pipe,cus", with_pipe_cus([(2500000,), (6000000,), (10000000,)], ["2500000", "6000000", "10000000"], 0))
+def test_f32_airspy_path_matches_oracle(D, O, S, rate, pipe, cus, tune):
     """air.c (real float32 around Fs/4) at the rates Airspy devices offer (R2: 10 and 2.5 Msps, Mini:
     6 Msps -> windows of 800 / 200 / 480 samples; the long ones pass through LDS in column slices):
     arbitrary callback sizes with carry, then the window-aligned device path."""
     import torch
     from acarsdec_amd import _capi as K
+    set_pipe_cus(tune, pipe, cus)
     rng = np.random.default_rng(2718 + rate // 100000)
     nch, nblk = 4, 4
     nout = nblk * 1024
