@@ -36,7 +36,11 @@ __device__ __forceinline__ bool crc_acceptable(const unsigned short* synd, unsig
 // The repairs (fixprerr, fixdberr) are searched 64 candidates at a time in the reference's search order (see below).
 #define BLK_ROW 336     // LDS row of the field split: a block's 256 text bytes, then the 320-byte record built in place
 #define BLK_WAVES 4
-#define NSYND (8 * 243)
+// decodeAcars() queues blocks of at most 241 bytes (acars.c:319,334: 240 bytes pass the length test, the terminator may be the
+// 241st), and both repairs read row len - i + 1 of the table (acars.c:46,78): rows 0 .. 242.  The reference's table stops at row
+// 241 (syndrom.h:52-295) and is read out of bounds for byte 0 of a 241-byte block; here the row exists, by the table's own
+// recurrence (host_setup.c), as in the oracle: tests/test_gpu_repair.py and tests/test_repair_corpus.py go there on purpose.
+#define NSYND (8 * (241 + 2))
 
 __device__ __forceinline__ unsigned int synd_of_bits(const unsigned short* synd, unsigned int byte, int k8)
 {
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(64 * BLK_WAVES) void blk_repair_kernel(AcgFrameRec*
 #pragma unroll
         for (int s_ = 0; s_ < 4; ++s_) {
             const int i = lane + 64 * s_;
-            have[s_] = i < len;                                            // (len <= 250)
+            have[s_] = i < len;                                            // (len <= 241: see NSYND)
             c[s_] = have[s_] ? raw[s_] : 0u;
         }
         if (lane == 12) c[0] = (c[0] & (ETX | STX)) | (ETX & STX);         // acars.c:132-133

@@ -584,7 +584,12 @@ int orc_frame_check(const orc_frame *f)
 /* acars.c:39-215: the block thread's parity / CRC check and repair     */
 /* ------------------------------------------------------------------ */
 
-#define NSYND (8 * 242)
+/* decodeAcars() queues blocks of up to 241 bytes (acars.c:319,334: 240 bytes pass the length test and the
+ * terminator may be the 241st), and both repairs index row len - i + 1 (acars.c:46,78): row 242 for byte 0 of
+ * a 241-byte block.  The reference's table has rows 0..241 only (syndrom.h:52-295) and reads past it there;
+ * the oracle, like the device (host_setup.c, blk.hip), has the row the table's definition gives:
+ * 241 + 2 rows, defined on every block the framing can queue. */
+#define NSYND (8 * (241 + 2))
 static unsigned short g_synd[NSYND];
 static int g_synd_ready;
 

@@ -112,7 +112,9 @@ void orc_fir_f32r(const float *x, size_t nout, int M, const float *wf, float *dm
  * -1 = dropped (too short), -2 = crc error with clean parity. */
 int orc_frame_check(const orc_frame *f);
 unsigned short orc_crc_update(unsigned short crc, unsigned char c);   /* syndrom.h:49 */
-/* syndrom.h:52-295 regenerated from its definition (n <= 1936 entries) */
+/* syndrom.h:52-295 regenerated from its definition (any n; the reference has 1936 entries = rows 0..241, the
+ * block repair below 1944: row 242 is what byte 0 of a 241-byte block indexes, acars.c:46,78 -- the reference
+ * reads past its table there, the oracle and the device define the row by the same recurrence) */
 void orc_syndrome_table(unsigned short *out, int n);
 /* acars.c:123-207 blk_thread body: 1 + *out = the block outputmsg() gets, 0 = dropped */
 int orc_blk_process(const orc_frame *in, orc_frame *out);
