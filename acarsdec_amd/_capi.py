@@ -57,6 +57,28 @@ class Oooi(C.Structure):
                 ("woff", C.c_char * 5), ("won", C.c_char * 5), ("decoded", C.c_char), ("reserved", C.c_char * 4)]
 
 
+class FlightConfig(C.Structure):
+    """acg_flight_config: t0 of the sample clock, the CLI's -t, the table's capacity"""
+    _fields_ = [("t0_sec", C.c_longlong), ("t0_usec", C.c_int), ("mdly", C.c_int), ("max_flights", C.c_int)]
+
+
+class Flight(C.Structure):
+    """acg_flight: one entry of the flight table (flight_t, output.c:345-358)"""
+    _fields_ = [("addr", C.c_char * 8), ("fid", C.c_char * 7), ("rt", C.c_ubyte), ("nbm", C.c_int), ("first_chn", C.c_int),
+                ("last_chn", C.c_int), ("reserved1", C.c_int), ("chm", C.c_ulonglong), ("ts_sample", C.c_longlong),
+                ("tl_sample", C.c_longlong), ("ts_sec", C.c_longlong), ("tl_sec", C.c_longlong), ("ts_usec", C.c_int),
+                ("tl_usec", C.c_int), ("da", C.c_char * 5), ("sa", C.c_char * 5), ("eta", C.c_char * 5), ("gout", C.c_char * 5),
+                ("gin", C.c_char * 5), ("woff", C.c_char * 5), ("won", C.c_char * 5), ("reserved2", C.c_char * 5)]
+
+
+class Route(C.Structure):
+    """acg_route: one route record (routejson(), output.c:428-456)"""
+    _fields_ = [("soh_sample", C.c_longlong), ("sec", C.c_longlong), ("usec", C.c_int), ("chn", C.c_int), ("fid", C.c_char * 7),
+                ("sa", C.c_char * 5), ("da", C.c_char * 5), ("addr", C.c_char * 8), ("reserved", C.c_char * 7)]
+
+
+assert C.sizeof(Flight) == 120 and C.sizeof(Route) == 56
+
 BIT_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_float, C.c_float)
 
 # name -> (restype, argtypes): every symbol include/acarsdec_amd.h (the product API) and include/acarsdec_amd_lab.h (measurement
@@ -97,6 +119,9 @@ SYMBOLS = {
     "acg_set_msg_filter": (C.c_int, [C.c_void_p, C.POINTER(MsgFilter)]),
     "acg_drain_msgs_oooi": (C.c_int, [C.c_void_p, C.POINTER(Msg), C.POINTER(Oooi), C.c_int, C.POINTER(C.c_int)]),
     "acg_collect_msgs_oooi": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Msg), C.POINTER(Oooi), C.c_int, C.POINTER(C.c_int)]),
+    "acg_flights_enable": (C.c_int, [C.c_void_p, C.POINTER(FlightConfig)]),
+    "acg_flight_snapshot": (C.c_int, [C.c_void_p, C.POINTER(Flight), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "acg_drain_routes": (C.c_int, [C.c_void_p, C.POINTER(Route), C.c_int, C.POINTER(C.c_int)]),
     "acg_read_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "acg_read_bits_all": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acg_bit_capacity": (C.c_int, [C.c_void_p]),
@@ -130,6 +155,9 @@ LAB_SYMBOLS = {
     "acg_selftest_div2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "acg_selftest_sincos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "acg_selftest_msg_labels": (C.c_int, [C.POINTER(Msg), C.c_int, C.POINTER(MsgFilter), C.c_void_p, C.POINTER(Oooi)]),
+    "acg_selftest_flights": (C.c_int, [C.POINTER(Msg), C.POINTER(C.c_int), C.c_int, C.POINTER(FlightConfig), C.POINTER(MsgFilter),
+                                       C.POINTER(Flight), C.c_int, C.POINTER(C.c_int), C.POINTER(Route), C.c_int, C.POINTER(C.c_int),
+                                       C.POINTER(C.c_int)]),
     "acg_lab_set_block_counter": (C.c_int, [C.c_void_p, C.c_uint]),
     "acg_lab_block_ring_size": (C.c_uint, [C.c_void_p]),
 }

@@ -18,6 +18,7 @@
 #include "acarsdec_amd.h"
 #include "acarsdec_amd_lab.h"
 #include "acg_internal.h"
+#include "flights.h"
 
 extern "C" void acg_host_msk_h(float* h);
 extern "C" void acg_host_sincos_table(double* tab);
@@ -214,6 +215,7 @@ struct acg_ctx {
     acg_oooi* h_oooi = nullptr;
     unsigned int* d_kwork = nullptr;        // [kmsgs_cap / 256 + 1] per-workgroup counts, then the total
     size_t kmsgs_cap = 0;
+    AcgFlights* flights = nullptr;          // acg_flights_enable: the flight table (flights.cpp), updated by every message entry point
     unsigned int* d_work = nullptr;     // FIR run dispensers, ACG_DISP_WORDS words per chunk slot
     bool stream_identity = true;        // channel c reads stream c
     unsigned short* d_crctab = nullptr; // [256] + syndromes [1936] (ACG_F_REPAIR)
@@ -296,6 +298,8 @@ static void free_all(acg_ctx* c)
     hipFree(c->d_stamp);
     hipFree(c->d_msgs); std::free(c->h_msgs);
     hipFree(c->d_kmsgs); hipFree(c->d_oooi); hipFree(c->d_kwork); std::free(c->h_oooi);
+    if (c->flights) acg_fl_destroy(c->flights);
+    c->flights = nullptr;
     hipFree(c->d_bits); hipFree(c->d_nbits); hipFree(c->d_stage[0]); hipFree(c->d_stage[1]); hipFree(c->d_work); hipFree(c->d_msk_done); std::free(c->h_stage); hipFree(c->d_crctab); hipFree(c->d_rep_upto);
     for (auto& p : c->fir_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& p : c->msk_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
@@ -621,6 +625,7 @@ extern "C" int acg_reset(acg_ctx* ctx)
     if (zr != ACG_OK) return zr;
     ctx->last_len = 0;
     ctx->last_had_demod = false;
+    if (ctx->flights && acg_fl_reset(ctx->flights) != ACG_OK) return fail(ctx, ACG_EHIP, "flight table reset");
     return ACG_OK;
 }
 
@@ -1352,9 +1357,10 @@ static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int m
         if (!ctx->h_msgs) return fail(ctx, ACG_ENOMEM, "message staging");
         ctx->msgs_cap = want;
     }
-    // label.hip's pass (filters, label decoding, compaction) runs when a filter is set or the labels are asked for; without
-    // both the call launches and copies exactly what it did before the pass existed
-    const bool labels = oooi != nullptr || ctx->msg_filter_on;
+    // label.hip's pass (filters, label decoding, compaction) runs when a filter is set, the labels are asked for or the flight
+    // table is on (its pass hangs on this one and shares its round trip); without all three the call launches and copies exactly
+    // what it did before the pass existed
+    const bool labels = oooi != nullptr || ctx->msg_filter_on || ctx->flights != nullptr;
     if (labels && take > ctx->kmsgs_cap) {
         hipFree(ctx->d_kmsgs); hipFree(ctx->d_oooi); hipFree(ctx->d_kwork);
         std::free(ctx->h_oooi);
@@ -1372,7 +1378,11 @@ static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int m
     if (take) {
         // the split writes every byte of a record (text tail zeroed), so nothing stale crosses the ABI
         unsigned int* d_total = ctx->d_kwork + ctx->kmsgs_cap / 256 + 1;
-        const AcgLabelPass pass{&ctx->msg_filter, ctx->d_kwork, ctx->d_kmsgs, ctx->d_oooi, d_total, nullptr};
+        AcgLabelPass pass{&ctx->msg_filter, ctx->d_kwork, ctx->d_kmsgs, ctx->d_oooi, d_total, nullptr, nullptr};
+        if (ctx->flights) {                                       // over exactly the blocks this call consumes, before -e drops any
+            const int fr = acg_fl_prepare(ctx->flights, take, ctx->copy_stream, &pass.flights);
+            if (fr != ACG_OK) return fail(ctx, fr, "flight table: work space");
+        }
         if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, take, ctx->d_msgs, ctx->copy_stream, labels ? &pass : nullptr) != 0)
             return fail(ctx, ACG_EHIP, "message split launch failed");
         if (labels) {
@@ -1536,6 +1546,103 @@ extern "C" int acg_selftest_msg_labels(const acg_msg* in, int n, const acg_msg_f
         if (j != total) rc = ACG_ESTATE;
     }
     hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work); hipFree(d_keep);
+    return rc;
+}
+
+// ---- the flight table (flight.hip, flights.cpp) -------------------------------------------------------------------------
+extern "C" int acg_flights_enable(acg_ctx* ctx, const acg_flight_config* cfg)
+{
+    if (!ctx || (cfg && !acg_fl_config_ok(cfg))) return ACG_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    if (ctx->flights) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+        acg_fl_destroy(ctx->flights);
+        ctx->flights = nullptr;
+    }
+    if (!cfg) return ACG_OK;
+    if (!acg_fl_create) return fail(ctx, ACG_ESTATE, "flight table: not in this build");
+    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "flight table: context created without ACG_F_REPAIR");
+    if (ctx->cfg.nch > (1 << 20)) return fail(ctx, ACG_EINVAL, "flight table: more than 2^20 channels");
+    const int rc = acg_fl_create(&ctx->flights, cfg);
+    return rc == ACG_OK ? rc : fail(ctx, rc, "flight table: allocation failed");
+}
+
+extern "C" int acg_flight_snapshot(acg_ctx* ctx, acg_flight* out, int max, int* n, int* dropped)
+{
+    if (!ctx || !n || max < 0 || (max > 0 && !out)) return ACG_EINVAL;
+    *n = 0;
+    if (!ctx->flights) return fail(ctx, ACG_ESTATE, "flight table is off");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int rc = acg_fl_snapshot(ctx->flights, ctx->copy_stream, out, max, n, dropped);
+    return rc == ACG_OK ? rc : fail(ctx, rc, rc == ACG_EAGAIN ? "more flights than fit: *n says how many" : "flight snapshot failed");
+}
+
+extern "C" int acg_drain_routes(acg_ctx* ctx, acg_route* out, int max, int* n)
+{
+    if (!ctx || !n || max < 0 || (max > 0 && !out)) return ACG_EINVAL;
+    *n = 0;
+    if (!ctx->flights) return fail(ctx, ACG_ESTATE, "flight table is off");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int rc = acg_fl_drain_routes(ctx->flights, ctx->copy_stream, out, max, n);
+    return rc == ACG_OK ? rc : fail(ctx, rc, rc == ACG_EAGAIN ? "more routes queued than fit: call again" : "route hand-over failed");
+}
+
+extern "C" int acg_selftest_flights(const acg_msg* in, const int* batch, int nbatch, const acg_flight_config* cfg, const acg_msg_filter* f,
+                                    acg_flight* snaps, int snap_cap, int* snap_n, acg_route* routes, int route_cap, int* nroutes, int* dropped)
+{
+    if (nbatch < 0 || !acg_fl_config_ok(cfg) || snap_cap < 0 || route_cap < 0 || !nroutes || (nbatch > 0 && (!batch || !snap_n)) ||
+        (snap_cap > 0 && !snaps) || (route_cap > 0 && !routes))
+        return ACG_EINVAL;
+    AcgLabelFilter d;
+    if (label_filter_dev(f, &d) != ACG_OK) return ACG_EINVAL;
+    size_t total = 0, biggest = 0;
+    for (int b = 0; b < nbatch; ++b) {
+        if (batch[b] < 0) return ACG_EINVAL;
+        total += (size_t)batch[b];
+        biggest = std::max(biggest, (size_t)batch[b]);
+    }
+    if (total > 0 && !in) return ACG_EINVAL;
+    *nroutes = 0;
+    int ndev = 0;
+    if (!acg_fl_create || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
+    AcgFlights* t = nullptr;
+    int rc = acg_fl_create(&t, cfg);
+    if (rc != ACG_OK) return rc;
+    std::vector<AcgMsgRec> h(std::max<size_t>(biggest, 1));
+    AcgMsgRec *d_in = nullptr, *d_out = nullptr;
+    acg_oooi* d_oooi = nullptr;
+    unsigned int* d_work = nullptr;
+    const size_t nwg = biggest / 256 + 1, by = std::max<size_t>(biggest, 1) * sizeof(AcgMsgRec);
+    if (hipMalloc(&d_in, by) != hipSuccess || hipMalloc(&d_out, by) != hipSuccess ||
+        hipMalloc(&d_oooi, std::max<size_t>(biggest, 1) * sizeof(acg_oooi)) != hipSuccess ||
+        hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) != hipSuccess)
+        rc = ACG_ENOMEM;
+    size_t at = 0;
+    int snap_at = 0;
+    for (int b = 0; b < nbatch && rc == ACG_OK; ++b) {
+        const unsigned int n = (unsigned int)batch[b];
+        for (unsigned int i = 0; i < n; ++i) {                    // the public record back into the device's form
+            std::memcpy(&h[i], &in[at + i], sizeof(AcgMsgRec));
+            h[i].valid = 1;
+            h[i].soh_back = (int)(in[at + i].end_sample - in[at + i].soh_sample);
+        }
+        at += n;
+        if (n) {
+            AcgLabelPass pass{&d, d_work, d_out, d_oooi, d_work + nwg, nullptr, nullptr};
+            rc = acg_fl_prepare(t, n, nullptr, &pass.flights);
+            if (rc == ACG_OK && (hipMemcpy(d_in, h.data(), (size_t)n * sizeof(AcgMsgRec), hipMemcpyHostToDevice) != hipSuccess ||
+                                 acg_launch_msg_split(nullptr, 0, 0, n, d_in, nullptr, &pass) != 0))
+                rc = ACG_EHIP;
+        }
+        if (rc == ACG_OK) {
+            rc = acg_fl_snapshot(t, nullptr, snaps + snap_at, snap_cap - snap_at, &snap_n[b], dropped);
+            if (rc == ACG_OK) snap_at += snap_n[b];
+        }
+    }
+    if (rc == ACG_OK) rc = acg_fl_drain_routes(t, nullptr, routes, route_cap, nroutes);
+    hipDeviceSynchronize();
+    hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
+    acg_fl_destroy(t);
     return rc;
 }
 

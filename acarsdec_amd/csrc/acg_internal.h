@@ -82,6 +82,65 @@ struct AcgLabelFilter {
     unsigned int tok[ACG_LBL_MAXTOK];
 };
 
+// ---- the flight table (flight.hip, flights.cpp): addFlight() / routejson() of output.c:361-456 over a call's split records ----
+// One event = one message that reaches addFlight(), extracted by label.hip beside the filter pass (input order)
+struct AcgFlightEv {
+    unsigned long long key;     // addr (7 bytes) | 1 << 63: never 0 (an empty slot)
+    long long soh_sample;
+    long long sec;              // tv = t0 + soh_sample / 12500 s
+    int usec;
+    int chn;
+    unsigned long long fid;     // 7 bytes
+    unsigned char oooi[40];     // acg_oooi: all zero when the decode failed
+    unsigned int e_ok;          // passes -e (routejson() runs only then)
+    unsigned int pad_;
+};
+
+// One slot of the open-addressing table (HBM, resident across calls); snapshot_kernel turns it into an acg_flight
+struct AcgFlightSlot {
+    unsigned long long key;     // 0 = never used
+    unsigned long long seq;     // (pass << 32) | rank of the latest event in its pass: the move-to-front order
+    unsigned long long fid, chm;
+    long long ts_sample, tl_sample, ts_sec, tl_sec;
+    int ts_usec, tl_usec, first_chn, last_chn;
+    int nbm;
+    unsigned int rt;
+    unsigned int touch;         // the pass that last used or claimed the slot (the claim word of an insertion)
+    unsigned int fld[7];        // da sa eta gout gin woff won, 4 chars each (the fifth is always NUL)
+};
+
+struct AcgFlightState {
+    long long G;                // the largest tv_sec any event has carried
+    unsigned int m;             // events of the pass in flight
+    unsigned int nseg;          // ... and its aircraft segments
+    unsigned int nroutes;       // routes queued
+    unsigned int dropped;       // new aircraft that found no slot
+    unsigned int nlive;         // snapshot: live entries
+    unsigned int pad_;
+};
+
+struct AcgRouteRec {
+    unsigned long long order;   // (pass << 32) | rank of the triggering event
+    unsigned char r[56];        // acg_route
+};
+
+struct AcgFlightPass {
+    long long t0_sec;
+    int t0_usec, mdly;
+    unsigned int pass;          // 1, 2, ...: this pass
+    unsigned int cap;           // table slots (a power of two)
+    AcgFlightSlot* slots;
+    AcgFlightState* st;
+    AcgRouteRec* routes;
+    unsigned int route_cap;
+    // per-pass work space, each for at least the pass's n records
+    AcgFlightEv* ev;
+    unsigned long long *key1, *key1s, *key2, *key2s;
+    unsigned int *idx1, *idx1s, *rank2, *rank2s;
+    long long* pmax;
+    uint2* segs;
+};
+
 struct FirArgs {
     const uint8_t* iq;          // [nstreams] rows
     size_t pitch;               // bytes between stream rows (multiple of 16)
@@ -190,11 +249,19 @@ struct AcgLabelPass {
     void* oooi;                 // acg_oooi[]: their labels decoded
     unsigned int* total;        // how many were kept
     unsigned char* keep_out;    // or null: the decision per input record
+    const AcgFlightPass* flights;   // or null: flight.hip's pass over the same n records follows
 };
 int acg_launch_msg_split(const AcgFrameRec* frames, unsigned int cap, unsigned int first, unsigned int n, AcgMsgRec* out, void* stream,
                          const AcgLabelPass* labels = nullptr);
 // label.hip: filter, label decoding and compaction of n split records (reached through acg_launch_msg_split)
 int acg_launch_msg_labels(const AcgMsgRec* recs, unsigned int n, const AcgLabelPass* p, void* stream);
+// label.hip: the events of n records (filter f: -A / -b decide, -e is only noted), compacted, with the keys of the time sort
+int acg_launch_flight_extract(const AcgMsgRec* recs, unsigned int n, const AcgLabelFilter* f, const AcgFlightPass* p, void* stream);
+// flight.hip: extraction, ordering, segment walk and table update for n records
+int acg_launch_flight_pass(const AcgMsgRec* recs, unsigned int n, const AcgLabelFilter* f, const AcgFlightPass* p, void* stream);
+// flight.hip: the live entries, latest update first, as acg_flight records in out[cap]; st->nlive = how many
+int acg_launch_flight_snapshot(const AcgFlightPass* p, unsigned long long* skey, unsigned long long* skey_s, unsigned int* sval,
+                               unsigned int* sval_s, void* out, void* stream);
 int acg_launch_sincos_selftest(const double* x, double* s, double* c, int n, const double* sctab, void* stream);
 int acg_launch_div2_selftest(const double* n0, const double* n1, const double* d, double* out, int n, void* stream);
 int acg_launch_synth_iq(uint8_t* iq, size_t pitch, int nrows, int nout, int decim, const float* env,

@@ -1,0 +1,23 @@
+// flights.h -- the flight table's host object (flights.cpp), shared by acg_api.cpp's entry points and the self test.
+// The functions are WEAK references: the host runtime (acg_api.cpp) is also linked without the device units and without
+// flights.cpp (the sanitizer build of tests/test_host_logic.py, which stubs the launchers it knows); there the table is simply
+// absent, acg_flights_enable says ACG_ESTATE and nothing else is reachable.  flights.cpp includes this header too, so its
+// definitions are emitted weak as well: intended and harmless, there is one definition of each in the library.
+#pragma once
+#include "acarsdec_amd.h"
+#include "acg_internal.h"
+
+struct AcgFlights;
+#define ACG_FL_WEAK __attribute__((weak))
+static inline int acg_fl_config_ok(const acg_flight_config* cfg)
+{
+    return cfg && cfg->mdly >= 1 && cfg->max_flights >= 1 && cfg->max_flights <= (1 << 24) && cfg->t0_usec >= 0 && cfg->t0_usec <= 999999;
+}
+ACG_FL_WEAK int acg_fl_create(AcgFlights** out, const acg_flight_config* cfg);     // an empty table on the current device
+ACG_FL_WEAK void acg_fl_destroy(AcgFlights* t);
+ACG_FL_WEAK int acg_fl_reset(AcgFlights* t);                                       // empties table, counters and pending routes (synchronises)
+// before a pass over n records on `stream`: grows the work space and the route queue, numbers the pass; *pass goes to
+// AcgLabelPass::flights
+ACG_FL_WEAK int acg_fl_prepare(AcgFlights* t, unsigned int n, void* stream, const AcgFlightPass** pass);
+ACG_FL_WEAK int acg_fl_snapshot(AcgFlights* t, void* stream, acg_flight* out, int max, int* n, int* dropped);
+ACG_FL_WEAK int acg_fl_drain_routes(AcgFlights* t, void* stream, acg_route* out, int max, int* n);

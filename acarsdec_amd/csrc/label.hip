@@ -8,6 +8,8 @@
 //                           a ballot per wave, copies them and their decoded labels to base + rank, and the last workgroup
 //                           publishes the total.  The decision is the same function in both kernels: nothing is stored between.
 // Deterministic: positions follow the input order whatever order the workgroups run in.
+// With the flight table on (acg_flights_enable) a third launch, flight_extract_kernel, turns the same records into the events
+// of flight.hip's pass, which follows on the same stream.
 //
 // The decoder is TABLE-DRIVEN: per label a list of guards (bytes at an offset equal one of at most two strings) and a list of
 // copies (field <- 4 bytes at an offset), applied in order (label 44 writes eta twice: the later copy wins).  Success = every
@@ -108,7 +110,8 @@ __device__ __forceinline__ Txt rec_txt(const AcgMsgRec* r)
 }
 
 // output.c:537-540, 650 (and outputmsg()'s callers: blocks the repair dropped never get there)
-__device__ __forceinline__ bool msg_keep(const AcgMsgRec* r, const AcgLabelFilter& f)
+// -A and -b: what decides whether a block reaches addFlight() (output.c:537-540)
+__device__ __forceinline__ bool msg_keep_ab(const AcgMsgRec* r, const AcgLabelFilter& f)
 {
     if (!r->valid) return false;
     if ((f.flags & ACG_MSGF_DOWNLINK_ONLY) && !r->down) return false;
@@ -120,8 +123,19 @@ __device__ __forceinline__ bool msg_keep(const AcgMsgRec* r, const AcgLabelFilte
         for (int i = 0; i < f.nlabels; ++i) hit |= (l0 != 0) & (f.tok[i] == key);
         if (!hit) return false;
     }
-    if ((f.flags & ACG_MSGF_SKIP_EMPTY) && rec_txt(r)(0) == 0) return false;
     return true;
+}
+
+// -e (output.c:650)
+__device__ __forceinline__ bool msg_keep_e(const AcgMsgRec* r, const AcgLabelFilter& f)
+{
+    return !((f.flags & ACG_MSGF_SKIP_EMPTY) && rec_txt(r)(0) == 0);
+}
+
+// output.c:537-540, 650 (and outputmsg()'s callers: blocks the repair dropped never get there)
+__device__ __forceinline__ bool msg_keep(const AcgMsgRec* r, const AcgLabelFilter& f)
+{
+    return msg_keep_ab(r, f) && msg_keep_e(r, f);
 }
 
 __device__ __forceinline__ int find_byte(const Txt& t, int from, unsigned char c)   // strchr: stops at the first NUL
@@ -241,6 +255,55 @@ __global__ __launch_bounds__(LBL_WG) void msg_compact_kernel(const AcgMsgRec* re
     }
 }
 
+// The flight table's event extraction (flight.hip does the rest): a thread per record.  A record reaches addFlight() when it
+// passed -A / -b and is a downlink with bs != 0x03 (output.c:545-567,647); -e is tested after addFlight() and only noted here.
+// The events are compacted as they are found (a counter, one atomic per wave; their order does not matter: the time sort's keys
+// (end_sample, chn) are distinct).  tv = t0 + soh_sample / 12500 s in integers: a sample is exactly 80 us.
+__global__ __launch_bounds__(LBL_WG) void flight_extract_kernel(const AcgMsgRec* recs, unsigned int n, AcgLabelFilter f, AcgFlightPass p)
+{
+    const unsigned int i = blockIdx.x * LBL_WG + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const AcgMsgRec* r = recs + i;
+    const bool ev = i < n && msg_keep_ab(r, f) && r->down && r->bs != 0x03;
+    const unsigned long long m = __ballot(ev);
+    if (!m) return;
+    unsigned int base = 0;
+    if (lane == 0) base = atomicAdd(&p.st->m, (unsigned int)__popcll(m));
+    base = (unsigned int)__shfl((int)base, 0);
+    if (!ev) return;
+    const unsigned int at = base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+    AcgFlightEv* e = p.ev + at;
+    unsigned long long a = 0;
+    for (int b = 0; b < 7; ++b) a |= (unsigned long long)(unsigned char)r->addr[b] << (8 * b);
+    for (int b = 1; b < 7; ++b)                                          // a C string: nothing behind its NUL counts
+        if (((a >> (8 * (b - 1))) & 0xff) == 0) a &= (1ull << (8 * b)) - 1ull;
+    unsigned long long fid = 0;
+    for (int b = 0; b < 7; ++b) fid |= (unsigned long long)(unsigned char)r->fid[b] << (8 * b);
+    for (int b = 1; b < 7; ++b)
+        if (((fid >> (8 * (b - 1))) & 0xff) == 0) fid &= (1ull << (8 * b)) - 1ull;
+    const long long soh = r->end_sample - (long long)r->soh_back;
+    const long long us = (long long)p.t0_usec + soh * 80ll;
+    long long q = us / 1000000ll, rem = us % 1000000ll;
+    if (rem < 0) { rem += 1000000ll; --q; }
+    e->key = a | (1ull << 63);
+    e->soh_sample = soh;
+    e->sec = p.t0_sec + q;
+    e->usec = (int)rem;
+    e->chn = r->chn;
+    e->fid = fid;
+    decode_label(r, e->oooi);
+    e->e_ok = msg_keep_e(r, f) ? 1u : 0u;
+    e->pad_ = 0u;
+    p.key1[at] = (((unsigned long long)r->end_sample & ((1ull << 43) - 1ull)) << 20) | ((unsigned long long)(unsigned int)r->chn & 0xfffffull);
+    p.idx1[at] = at;
+}
+
+extern "C" int acg_launch_flight_extract(const AcgMsgRec* recs, unsigned int n, const AcgLabelFilter* f, const AcgFlightPass* p, void* stream)
+{
+    hipLaunchKernelGGL(flight_extract_kernel, dim3((n + LBL_WG - 1) / LBL_WG), dim3(LBL_WG), 0, (hipStream_t)stream, recs, n, *f, *p);
+    return (int)hipGetLastError();
+}
+
 extern "C" int acg_launch_msg_labels(const AcgMsgRec* recs, unsigned int n, const AcgLabelPass* p, void* stream)
 {
     if (n == 0) return 0;
@@ -248,5 +311,7 @@ extern "C" int acg_launch_msg_labels(const AcgMsgRec* recs, unsigned int n, cons
     hipLaunchKernelGGL(msg_keep_count_kernel, dim3(g), dim3(LBL_WG), 0, (hipStream_t)stream, recs, n, *p->f, p->wg_count);
     hipLaunchKernelGGL(msg_compact_kernel, dim3(g), dim3(LBL_WG), 0, (hipStream_t)stream, recs, n, *p->f, (const unsigned int*)p->wg_count,
                        p->kept, (acg_oooi*)p->oooi, p->total, p->keep_out);
-    return (int)hipGetLastError();
+    const int e = (int)hipGetLastError();
+    if (e || !p->flights) return e;
+    return acg_launch_flight_pass(recs, n, p->f, p->flights, stream);
 }

@@ -294,6 +294,47 @@ class Decoder:
             if rc == K.OK:
                 return out
 
+    # ---- the flight table (acg_flights_enable, acg_flight_snapshot, acg_drain_routes) --------------------------------------
+    def enable_flights(self, t0=0.0, mdly=600, max_flights=4096):
+        """addFlight() / routejson() (output.c:361-456) on the device for every message entry point from now on.  t0: wall clock
+        of the first sample since reset, seconds (a float) or (sec, usec); mdly: the CLI's -t; max_flights: capacity (rounded up
+        to a power of two).  The table starts empty."""
+        sec, usec = t0 if isinstance(t0, tuple) else (int(t0 // 1), int(round((t0 - t0 // 1) * 1e6)))
+        if usec >= 1000000:
+            sec, usec = sec + 1, usec - 1000000
+        cfg = K.FlightConfig(int(sec), int(usec), int(mdly), int(max_flights))
+        self._chk(self.L.acg_flights_enable(self.ctx, C.byref(cfg)))
+        self.flights_dropped = 0
+
+    def disable_flights(self):
+        self._chk(self.L.acg_flights_enable(self.ctx, None))
+
+    def flights(self):
+        """The live entries as a list of K.Flight, latest update first (printmonitor()'s order); self.flights_dropped = new
+        aircraft that found no slot since enable / reset."""
+        cap = getattr(self, "_flbuf_cap", 0) or 256
+        while True:
+            if getattr(self, "_flbuf_cap", 0) < cap:
+                self._flbuf = (K.Flight * cap)()
+                self._flbuf_cap = cap
+            n, dropped = C.c_int(0), C.c_int(0)
+            rc = self._chk(self.L.acg_flight_snapshot(self.ctx, self._flbuf, self._flbuf_cap, C.byref(n), C.byref(dropped)), allow=(K.EAGAIN,))
+            if rc == K.OK:
+                self.flights_dropped = dropped.value
+                return [K.Flight.from_buffer_copy(self._flbuf[i]) for i in range(n.value)]
+            cap = max(n.value, 2 * cap)
+
+    def drain_routes(self, max_routes=1024):
+        """The route records emitted so far (K.Route), in the order of their triggering messages."""
+        buf = (K.Route * max(1, int(max_routes)))()
+        out = []
+        while True:
+            n = C.c_int(0)
+            rc = self._chk(self.L.acg_drain_routes(self.ctx, buf, len(buf), C.byref(n)), allow=(K.EAGAIN,))
+            out += [K.Route.from_buffer_copy(buf[i]) for i in range(n.value)]
+            if rc == K.OK:
+                return out
+
     def bits(self, ch):
         vo = np.zeros(self.bit_cap, dtype=np.float32)
         lvl = np.zeros(self.bit_cap, dtype=np.float32)
@@ -365,6 +406,31 @@ def oooi_json(msg, oooi):
         v = getattr(oooi, field)                      # (ctypes c_char arrays read up to the first NUL)
         if v:
             out[key] = v.decode("latin1")
+    return out
+
+
+def monitor_rows(flights, nbch):
+    """printmonitor()'s rows (output.c:471-478) for a snapshot, without the clock column: the text before the time of the first
+    message and the text after it, joined by one blank.  nbch: the channels the mask shows (the reference's nbch <= 16)."""
+    rows = []
+    for f in flights:
+        s = " %-8s %-7s %3d " % (f.addr.decode("latin1"), f.fid.decode("latin1"), f.nbm)
+        s += "".join("x" if (f.chm >> i) & 1 else "." for i in range(nbch)) + " " * max(0, 16 - nbch)
+        s += " "
+        for v in (f.sa, f.da, f.eta):
+            s += (" %4s " % v.decode("latin1")) if v else "      "
+        rows.append(s)
+    return rows
+
+
+def route_json(route, station=None):
+    """routejson()'s object (output.c:442-447) for a K.Route, keys in the reference's order"""
+    out = {"timestamp": route.sec + route.usec / 1e6}
+    if station:
+        out["station_id"] = station
+    out["flight"] = route.fid.decode("latin1")
+    out["depa"] = route.sa.decode("latin1")
+    out["dsta"] = route.da.decode("latin1")
     return out
 
 

@@ -299,6 +299,76 @@ typedef struct {
  * kept cross to the host. */
 int  acg_drain_msgs_oooi(acg_ctx *ctx, acg_msg *out, acg_oooi *oooi, int max_msgs, int *nmsgs);
 int  acg_collect_msgs_oooi(acg_ctx *ctx, int lag, acg_msg *out, acg_oooi *oooi, int max_msgs, int *nmsgs);
+/* ---- the flight table: addFlight() / routejson() (output.c:361-456), what -o 3 and -o 5 print from ---------------------------
+ * Off by default; with it off every entry point launches, copies and returns exactly what it does without this section.
+ * When enabled, every message entry point (acg_drain_msgs, acg_collect_msgs and the _oooi pair) takes the blocks it consumes
+ * through addFlight() on the device, before the -e filter drops anything, in the same host round trip as the label pass; the
+ * records those calls hand out are byte-identical with and without the table.
+ *   which messages   those that passed -A / -b and are downlinks with bs != 0x03 (output.c:545-567,647).  -e is tested AFTER
+ *                    addFlight(), as in the reference; a message that skips addFlight() never emits a route (the reference
+ *                    reads an uninitialised pointer there).
+ *   time             tv = t0 + soh_sample / 12500 s (the epoch rule of acg_frame), in integer arithmetic.
+ *   ORDER            within one drain / collect call the messages are applied in ascending (end_sample, chn); across calls,
+ *                    call order holds.  Every channel of a context advances by the same samples per process call, so this is
+ *                    global real-time order as long as no call returns ACG_EAGAIN.  A call that does return ACG_EAGAIN has
+ *                    consumed an arbitrary oldest part of the block queue: the rule then still holds per call, not globally.
+ *   expiry           an entry whose last message is more than mdly seconds older than the newest message second seen so far
+ *                    is gone (output.c:407-423; the CLI's -t, default 600); its aircraft starts anew with its next message.
+ * One table per context: a host that spreads its channels over several devices merges the tables itself. */
+typedef struct {
+	long long t0_sec;             /* wall clock of the channels' first sample since acg_reset */
+	int t0_usec;                  /* 0 .. 999999 */
+	int mdly;                     /* -t: seconds without a message after which a flight is forgotten, >= 1 */
+	int max_flights;              /* capacity, >= 1 (rounded up to a power of two) */
+} acg_flight_config;
+
+/* One entry of the table (flight_t, output.c:345-358).  Every byte is defined (strings are NUL padded). */
+typedef struct {
+	char addr[8];
+	char fid[7];                  /* of the latest message; may be empty */
+	char rt;                      /* 1 = this entry has emitted its route record */
+	int nbm;                      /* messages */
+	int first_chn, last_chn;      /* channel of the first and of the latest message */
+	int reserved1;                /* 0 */
+	unsigned long long chm;       /* bit (chn % 64) set for every channel heard on: the reference's mask for its <= 16 channels */
+	long long ts_sample, tl_sample;   /* soh_sample of the first and of the latest message */
+	long long ts_sec, tl_sec;     /* ... and as wall clock, from t0 */
+	int ts_usec, tl_usec;
+	char da[5], sa[5], eta[5], gout[5], gin[5], woff[5], won[5];   /* as in acg_oooi: per field the last non-empty value */
+	char reserved2[5];            /* 0 */
+} acg_flight;
+
+/* One route record (routejson(), output.c:428-456): emitted by the first message of an entry that passed -e as well and has a
+ * flight id while departure and destination are known; once per entry.  Every byte is defined. */
+typedef struct {
+	long long soh_sample;         /* of the triggering message */
+	long long sec;                /* its tv */
+	int usec;
+	int chn;
+	char fid[7];
+	char sa[5];                   /* "depa" */
+	char da[5];                   /* "dsta" */
+	char addr[8];
+	char reserved[7];             /* 0 */
+} acg_route;
+
+/* Switches the table on (cfg) or off and frees it (NULL).  Enabling an enabled table replaces it by an empty one.
+ * ACG_EINVAL: mdly < 1, max_flights < 1, t0_usec outside 0..999999; ACG_ESTATE: context without ACG_F_REPAIR.
+ * acg_reset() empties the table and the pending routes (the sample clock restarts there). */
+int  acg_flights_enable(acg_ctx *ctx, const acg_flight_config *cfg);
+/* The live entries in printmonitor()'s order (output.c:467-481): latest update first (the order is total).  ACG_EAGAIN: max is
+ * too small, *n is the number needed.  *dropped (may be NULL) counts, since enable / reset, every (call, aircraft) pair in which an
+ * aircraft that is not in the table had messages and found no slot -- an aircraft that stays unplaced over three calls counts
+ * three times.  Its messages are still delivered, only the table update is skipped.  A slot is free when it was never used or its
+ * entry has expired; an aircraft looks for one within 128 slots of its place, so a table filled to the last slots can drop an
+ * aircraft before it is completely full (size max_flights with room to spare), and when a call brings more new aircraft than
+ * there are free slots, which of them get the slots is not specified.  Waits for the passes issued so far; consumes nothing. */
+int  acg_flight_snapshot(acg_ctx *ctx, acg_flight *out, int max, int *n, int *dropped);
+/* The route records emitted so far, in the order of their triggering messages.  ACG_EAGAIN: more are queued than fit, call again.
+ * Routes stay queued until they are drained or the table is reset or switched off: a host that enables the table for the monitor
+ * alone still drains them now and then, or the queue grows by one record per route emitted. */
+int  acg_drain_routes(acg_ctx *ctx, acg_route *out, int max, int *n);
+
 /* Per-bit records of the LAST process call for one channel (needs ACG_F_BITLOG):
  * vo = the value putbit() receives (msk.c:122-126), lvl = cabsf(v) (msk.c:110). */
 int  acg_read_bits(acg_ctx *ctx, int ch, float *vo, float *lvl, int max_bits, int *nbits);

@@ -71,6 +71,14 @@ int  acg_selftest_div2(const double *n0_host, const double *n1_host, const doubl
  * byte for byte and in order, ACG_EINVAL for a bad filter or n < 0. */
 int  acg_selftest_msg_labels(const acg_msg *in, int n, const acg_msg_filter *f, unsigned char *keep, acg_oooi *oooi);
 
+/* diagnostics: the flight table (flight.hip) on caller-supplied records, without a demodulator.  in holds sum(batch[0..nbatch))
+ * records as acg_drain_msgs hands them out; batch b is taken through one pass (filter f, NULL = none; order (end_sample, chn)
+ * within the batch) of a table made from cfg.  After batch b, snap_n[b] entries of the snapshot are appended to snaps (snap_cap
+ * records in all); the routes of all batches go to routes (route_cap records), *nroutes of them; *dropped as acg_flight_snapshot.
+ * ACG_EAGAIN: snaps or routes too small; ACG_ENODEV: no GPU. */
+int  acg_selftest_flights(const acg_msg *in, const int *batch, int nbatch, const acg_flight_config *cfg, const acg_msg_filter *f,
+			  acg_flight *snaps, int snap_cap, int *snap_n, acg_route *routes, int route_cap, int *nroutes, int *dropped);
+
 /* Test hook (the block ring across the wrap of its 32-bit counters): right after acg_reset, with nothing queued,
  * sets the device's block counter, the repair pass's mark and the host's consumer mark to `value`, as if that many blocks had
  * been produced and consumed already.  ACG_ESTATE if calls have been issued since the reset. */
