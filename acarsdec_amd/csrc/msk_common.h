@@ -195,14 +195,31 @@ __device__ __forceinline__ void sincos_2pi(double x, double* sn, double* cs)
 // of instructions it issues.  Error <= 2.1 ulp (the table entry's and the last addition's rounding dominate)
 // where sincos_2pi has < 1; what the demodulator keeps is (float)(in * cos), (float)(in * -sin) (msk.c:90), and on 4e7 random
 // phases those are identical to glibc cexp's for both (tests/sincos_model.c: the same operations on the CPU, in the CPU suite).
+// (in two parts, so that a caller can issue the table read early and run the series behind other work: msk_lean.hip)
+__device__ __forceinline__ void sincos_tab_entry(double x, const double* __restrict__ tab, double* rr, double* cj, double* sj);
+__device__ __forceinline__ void sincos_tab_rotate(double r, double cj, double sj, double* sn, double* cs);
+
 __device__ __forceinline__ void sincos_tab(double x, const double* __restrict__ tab /* LDS, [128][2] */, double* sn, double* cs)
+{
+    double r, cj, sj;
+    sincos_tab_entry(x, tab, &r, &cj, &sj);
+    sincos_tab_rotate(r, cj, sj, sn, cs);
+}
+
+__device__ __forceinline__ void sincos_tab_entry(double x, const double* __restrict__ tab /* LDS, [128][2] */, double* rr, double* cj, double* sj)
 {
     const double kd = __builtin_rint(x * (6.36619772367581382433e-01 * 32.0));   // x * 128 / (2 pi)
     const int q = (int)kd;
     double r = __builtin_fma(-kd, 1.57079632673412561417e+00 / 32.0, x);        // 2 pi / 128, high 33 bits (exact products: kd <= 128)
     r = __builtin_fma(-kd, 6.07710050650619224932e-11 / 32.0, r);               // tail
     const double2 e = *(const double2*)(tab + 2 * (q & (ACG_SINCOS_N - 1)));
-    const double cj = e.x, sj = e.y;
+    *rr = r;
+    *cj = e.x;
+    *sj = e.y;
+}
+
+__device__ __forceinline__ void sincos_tab_rotate(double r, double cj, double sj, double* sn, double* cs)
+{
     const double z = r * r;
 #ifdef ACG_MSK_AB_FMA3
     // A/B build: the Horner steps as three-address v_fma_f64 with the constants as scalar / resident vector operands (left to the

@@ -16,9 +16,24 @@
 // msk.hip does it (framing inline, between the bit decision and the loop filter, msk.c:122-130).  Same operations in the
 // same order per channel as msk.hip and the reference; tests compare state, blocks and text of both kernels bit for bit.
 //
-// Used for launches without a bit log (ACG_F_BITLOG keeps msk.hip's kernel, whose per-bit records need the polarity at
-// each bit), 16-byte aligned dm rows, len % 32 == 0, 4 or 8 lanes per channel; ACG_MSK_NOLEAN=1 (tuning table) keeps
-// msk.hip's kernel for same-process A/B.
+// Used for every in_callback-shaped launch, with or without a bit log (with ACG_F_BITLOG the segment's per-bit records are stored
+// under the polarity of MskS + k and turned on the rare branch that finds a ~SYN behind them): 16-byte aligned dm rows,
+// len % 32 == 0, not the precise-mixer mode, 4 or 8 lanes per channel (ACG_MSK_LEAN4=0 keeps msk.hip's kernel for 4);
+// ACG_MSK_NOLEAN=1 (tuning table) keeps msk.hip's kernel for same-process A/B.
+//
+// Issue order of a period (round 7).  One wave per SIMD runs this loop, so an LDS round trip that the period's own instructions do
+// not cover is paid in full on the chain that sets the bit rate.  front() therefore issues, pinned with two sched_barriers:
+//   sin/cos table address and read -> tap phase o -> h[o + 12 j] and the five old ring entries (reads) | the mixer's series and
+//   rotation -> ring write -> the six newest ring entries (reads) | the five old taps' arithmetic -> wave-wide test -> decide(),
+//   which only consumes what front() read,
+// and "every lane fired, the segment goes on" is laid out as the fall-through.  One wave's LDS operations execute in order, so the
+// newest-tap reads see the ring write in front of them; every wait is a counted one that leaves the younger reads in flight
+// (which needs every scalar load retired before the loop: see where the epilogue's arguments are loaded).
+// Same operations on the same operands as before.  Each step has a switch that restores the order before it, so that
+// profiles/probe/build_ab.py can time both from one tree: ACG_LEAN_AB_TAPS0 (newest-tap reads in decide()), ACG_LEAN_AB_PIN0 (no
+// barrier in front of the mixer), ACG_LEAN_AB_TAB0 (table read inside the mixer), ACG_LEAN_AB_BRS0 (the compiler's block order).
+// Two more steps were measured and not taken (1 / s started where df is set; the branch hint on `quick` as well): DESIGN 4.
+// tests/test_lean_issue_order.py pins the order in the assembly.
 #include <hip/hip_runtime.h>
 #include "acg_internal.h"
 
@@ -139,8 +154,17 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
     __syncthreads();
 
     if (a.high_prio) __builtin_amdgcn_s_setprio(3);
+    // every kernel argument the epilogue needs is loaded HERE: a scalar load still pending when the loop starts makes the compiler
+    // wait with a zero count inside the segment's first period (scalar loads return out of order), behind that period's h[] reads
+    asm volatile("" :: "s"(a.snap), "s"(a.done_ctr));
 
     typedef float f2v __attribute__((ext_vector_type(2)));
+    // Block order: "the segment goes on" is laid out as the fall-through (ACG_LEAN_AB_BRS0: the compiler's own order, in which it jumps)
+#ifdef ACG_LEAN_AB_BRS0
+#define LEAN_UNLIKELY(c) (c)
+#else
+#define LEAN_UNLIKELY(c) __builtin_expect(!!(c), 0)
+#endif
 #define MSK_TAP(j, x) (f2v{(j & 1) ? hv2[j / 2].y : hv2[j / 2].x, (j & 1) ? hv2[j / 2].y : hv2[j / 2].x} * x)
 
     // what a period's front part (VCO / clock steps, mixer, the five oldest filter taps) hands to its bit decision
@@ -149,6 +173,9 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
     float clk_f;
     f2v hv2[(FLEN + 1) / 2];
     f2v acc;
+#ifndef ACG_LEAN_AB_TAPS0
+    float2 xs[FLEN - 5];                           // the six newest taps' ring entries, read by front() right behind its ring write
+#endif
 
     // ---- front part of a bit period: msk.hip phases A, C0, B, operation for operation
     auto front = [&]() {
@@ -219,6 +246,12 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
         unsigned int idx_n = idx + (unsigned int)cnt;
         if (idx_n >= FLEN) idx_n -= FLEN;
         clk_f = fired ? (float)((double)L.clk - K_3PI2) : L.clk;           // msk.c:100
+#ifndef ACG_LEAN_AB_TAB0
+        // the mixer's table entries first: kd, q, the LDS address and the read, so that the read's latency runs under the tap phase
+        double mr[SPL], mcj[SPL], msj[SPL];
+#pragma unroll
+        for (int j = 0; j < SPL; ++j) sincos_tab_entry(myp[j], lds.sc, &mr[j], &mcj[j], &msj[j]);
+#endif
         int o = (int)(MFLTOVER * (div1_rcp((double)clk_f, s) + 0.5));      // msk.c:103
         if (o > MFLTOVER) o = MFLTOVER;
         if (o < 0) o = 0;
@@ -245,11 +278,19 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
 #pragma unroll
             for (int j = 0; j < 5; ++j) xo[j] = rp0[j * CPW];
         }
+#ifndef ACG_LEAN_AB_PIN0
+        // the tap phase and the h[] / old-ring reads stay in FRONT of the mixer: their LDS latency runs under its sin/cos series
+        __builtin_amdgcn_sched_barrier(0);
+#endif
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
             const int u = g + j * LPC;
             double sn, cs;
+#ifdef ACG_LEAN_AB_TAB0
             sincos_tab(myp[j], lds.sc, &sn, &cs);
+#else
+            sincos_tab_rotate(mr[j], mcj[j], msj[j], &sn, &cs);
+#endif
             const double in = (double)in_cur[j];
             unsigned int k = idx + (unsigned int)u;
             if (k >= FLEN) k -= FLEN;
@@ -260,6 +301,18 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
         }
         n += cnt;
         idx = idx_n;
+#ifndef ACG_LEAN_AB_TAPS0
+        // the six newest taps, read right behind the ring write (one wave's LDS operations execute in order: the reads see the
+        // writes of every lane); the five old taps' arithmetic and the wave-wide test run under their latency
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        {
+            const float2* rp = &ring[idx_n][slot];
+#pragma unroll
+            for (int j = 5; j < FLEN; ++j) xs[j - 5] = rp[j * CPW];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#endif
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
             const f2v x = {xo[j].x, xo[j].y};
@@ -274,10 +327,12 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
     auto decide = [&]() {
         L.clk = clk_f;                                                     // msk.c:100
         {
+#ifdef ACG_LEAN_AB_TAPS0
             const float2* rp = &ring[idx][slot];
             float2 xs[FLEN - 5];
 #pragma unroll
             for (int j = 5; j < FLEN; ++j) xs[j - 5] = rp[j * CPW];
+#endif
 #pragma unroll
             for (int j = 5; j < FLEN; ++j) {
                 const f2v x = {xs[j - 5].x, xs[j - 5].y};
@@ -332,7 +387,7 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
             // through v_cndmask + v_cmp_ne)
             if (__builtin_amdgcn_uicmp((unsigned int)(fired ? lim : 0), (unsigned int)k, 34 /* ugt */) != ~0ull) { tail = true; break; }
 #else
-            if (__builtin_amdgcn_ballot_w64(fired && lim > k) != ~0ull) { tail = true; break; }
+            if (LEAN_UNLIKELY(__builtin_amdgcn_ballot_w64(fired && lim > k) != ~0ull)) { tail = true; break; }
 #endif
             decide();
             // decision + phase detector (msk.c:115-121); S + k is odd where S is odd and k even, ...
