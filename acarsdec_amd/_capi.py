@@ -77,6 +77,15 @@ class Route(C.Structure):
                 ("sa", C.c_char * 5), ("da", C.c_char * 5), ("addr", C.c_char * 8), ("reserved", C.c_char * 7)]
 
 
+JSON_LINE_MAX = 2496
+
+
+class JsonConfig(C.Structure):
+    """acg_json_config: t0 of the sample clock, the station id (-i) and the "app" object of every JSON line"""
+    _fields_ = [("t0_sec", C.c_longlong), ("t0_usec", C.c_int), ("station_id", C.c_char * 33), ("app_name", C.c_char * 17),
+                ("app_ver", C.c_char * 17)]
+
+
 assert C.sizeof(Flight) == 120 and C.sizeof(Route) == 56
 
 BIT_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_float, C.c_float)
@@ -122,6 +131,9 @@ SYMBOLS = {
     "acg_flights_enable": (C.c_int, [C.c_void_p, C.POINTER(FlightConfig)]),
     "acg_flight_snapshot": (C.c_int, [C.c_void_p, C.POINTER(Flight), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "acg_drain_routes": (C.c_int, [C.c_void_p, C.POINTER(Route), C.c_int, C.POINTER(C.c_int)]),
+    "acg_json_enable": (C.c_int, [C.c_void_p, C.POINTER(JsonConfig), C.c_void_p]),
+    "acg_drain_json": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "acg_collect_json": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "acg_read_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "acg_read_bits_all": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acg_bit_capacity": (C.c_int, [C.c_void_p]),
@@ -158,6 +170,9 @@ LAB_SYMBOLS = {
     "acg_selftest_flights": (C.c_int, [C.POINTER(Msg), C.POINTER(C.c_int), C.c_int, C.POINTER(FlightConfig), C.POINTER(MsgFilter),
                                        C.POINTER(Flight), C.c_int, C.POINTER(C.c_int), C.POINTER(Route), C.c_int, C.POINTER(C.c_int),
                                        C.POINTER(C.c_int)]),
+    "acg_selftest_msg_json": (C.c_int, [C.POINTER(Msg), C.c_int, C.POINTER(MsgFilter), C.POINTER(JsonConfig), C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "acg_lab_json_level_guard": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint)]),
     "acg_lab_set_block_counter": (C.c_int, [C.c_void_p, C.c_uint]),
     "acg_lab_block_ring_size": (C.c_uint, [C.c_void_p]),
 }

@@ -216,6 +216,7 @@ struct acg_ctx {
     unsigned int* d_kwork = nullptr;        // [kmsgs_cap / 256 + 1] per-workgroup counts, then the total
     size_t kmsgs_cap = 0;
     AcgFlights* flights = nullptr;          // acg_flights_enable: the flight table (flights.cpp), updated by every message entry point
+    struct AcgJsonState* json = nullptr;    // acg_json_enable: the JSON sink (json.hip): configuration, work space, rendered lines
     unsigned int* d_work = nullptr;     // FIR run dispensers, ACG_DISP_WORDS words per chunk slot
     bool stream_identity = true;        // channel c reads stream c
     unsigned short* d_crctab = nullptr; // [256] + syndromes [1936] (ACG_F_REPAIR)
@@ -290,6 +291,7 @@ extern "C" int acg_device_count(void)
     return n;
 }
 
+static void json_destroy(struct AcgJsonState* st);
 static void free_all(acg_ctx* c)
 {
     if (!c) return;
@@ -300,6 +302,8 @@ static void free_all(acg_ctx* c)
     hipFree(c->d_kmsgs); hipFree(c->d_oooi); hipFree(c->d_kwork); std::free(c->h_oooi);
     if (c->flights) acg_fl_destroy(c->flights);
     c->flights = nullptr;
+    json_destroy(c->json);
+    c->json = nullptr;
     hipFree(c->d_bits); hipFree(c->d_nbits); hipFree(c->d_stage[0]); hipFree(c->d_stage[1]); hipFree(c->d_work); hipFree(c->d_msk_done); std::free(c->h_stage); hipFree(c->d_crctab); hipFree(c->d_rep_upto);
     for (auto& p : c->fir_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& p : c->msk_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
@@ -1334,6 +1338,41 @@ extern "C" int acg_drain_frames(acg_ctx* ctx, acg_frame* out, int max_frames, in
 // ------------------------------------------------------------------------------------------
 // the claimed blocks through the device-side field split (blk.hip msg_split_kernel)
 static_assert(sizeof(AcgMsgRec) == sizeof(acg_msg), "device record and public record must have one layout");
+// the message entry points' staging (fetch_msgs, fetch_json), grown on demand: the split's records, device and host ...
+static int grow_msg_stage(acg_ctx* ctx, unsigned int take)
+{
+    if (take <= ctx->msgs_cap) return ACG_OK;
+    hipFree(ctx->d_msgs);
+    std::free(ctx->h_msgs);
+    ctx->d_msgs = nullptr;
+    ctx->h_msgs = nullptr;
+    ctx->msgs_cap = 0;
+    const size_t want = std::max<size_t>(take, 4096);
+    HIPCHK(ctx, hipMalloc(&ctx->d_msgs, want * sizeof(AcgMsgRec)));
+    ctx->h_msgs = (AcgMsgRec*)std::malloc(want * sizeof(AcgMsgRec));
+    if (!ctx->h_msgs) return fail(ctx, ACG_ENOMEM, "message staging");
+    ctx->msgs_cap = want;
+    return ACG_OK;
+}
+
+// ... and label.hip's output: the kept records, their labels, the per-workgroup counts and the total
+static int grow_label_stage(acg_ctx* ctx, unsigned int take)
+{
+    if (take <= ctx->kmsgs_cap) return ACG_OK;
+    hipFree(ctx->d_kmsgs); hipFree(ctx->d_oooi); hipFree(ctx->d_kwork);
+    std::free(ctx->h_oooi);
+    ctx->d_kmsgs = nullptr; ctx->d_oooi = nullptr; ctx->d_kwork = nullptr; ctx->h_oooi = nullptr;
+    ctx->kmsgs_cap = 0;
+    const size_t want = std::max<size_t>(take, 4096);
+    HIPCHK(ctx, hipMalloc(&ctx->d_kmsgs, want * sizeof(AcgMsgRec)));
+    HIPCHK(ctx, hipMalloc(&ctx->d_oooi, want * sizeof(acg_oooi)));
+    HIPCHK(ctx, hipMalloc(&ctx->d_kwork, (want / 256 + 2) * sizeof(unsigned int)));
+    ctx->h_oooi = (acg_oooi*)std::malloc(want * sizeof(acg_oooi));
+    if (!ctx->h_oooi) return fail(ctx, ACG_ENOMEM, "label staging");
+    ctx->kmsgs_cap = want;
+    return ACG_OK;
+}
+
 static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
 {
     unsigned int upto = 0, pending = 0, take = 0;
@@ -1345,35 +1384,13 @@ static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int m
     // all fit) and consumes exactly those: draining a long queue through a small buffer costs what it hands out, not the
     // square of it, and the staging follows the caller's buffer, not the ring.
     rc = ring_claim(ctx, upto, max_msgs, &pending, &take);
-    if (take > ctx->msgs_cap) {
-        hipFree(ctx->d_msgs);
-        std::free(ctx->h_msgs);
-        ctx->d_msgs = nullptr;
-        ctx->h_msgs = nullptr;
-        ctx->msgs_cap = 0;
-        const size_t want = std::max<size_t>(take, 4096);
-        HIPCHK(ctx, hipMalloc(&ctx->d_msgs, want * sizeof(AcgMsgRec)));
-        ctx->h_msgs = (AcgMsgRec*)std::malloc(want * sizeof(AcgMsgRec));
-        if (!ctx->h_msgs) return fail(ctx, ACG_ENOMEM, "message staging");
-        ctx->msgs_cap = want;
-    }
+    if (const int gr = grow_msg_stage(ctx, take)) return gr;
     // label.hip's pass (filters, label decoding, compaction) runs when a filter is set, the labels are asked for or the flight
     // table is on (its pass hangs on this one and shares its round trip); without all three the call launches and copies exactly
     // what it did before the pass existed
     const bool labels = oooi != nullptr || ctx->msg_filter_on || ctx->flights != nullptr;
-    if (labels && take > ctx->kmsgs_cap) {
-        hipFree(ctx->d_kmsgs); hipFree(ctx->d_oooi); hipFree(ctx->d_kwork);
-        std::free(ctx->h_oooi);
-        ctx->d_kmsgs = nullptr; ctx->d_oooi = nullptr; ctx->d_kwork = nullptr; ctx->h_oooi = nullptr;
-        ctx->kmsgs_cap = 0;
-        const size_t want = std::max<size_t>(take, 4096);
-        HIPCHK(ctx, hipMalloc(&ctx->d_kmsgs, want * sizeof(AcgMsgRec)));
-        HIPCHK(ctx, hipMalloc(&ctx->d_oooi, want * sizeof(acg_oooi)));
-        HIPCHK(ctx, hipMalloc(&ctx->d_kwork, (want / 256 + 2) * sizeof(unsigned int)));
-        ctx->h_oooi = (acg_oooi*)std::malloc(want * sizeof(acg_oooi));
-        if (!ctx->h_oooi) return fail(ctx, ACG_ENOMEM, "label staging");
-        ctx->kmsgs_cap = want;
-    }
+    if (labels)
+        if (const int gr = grow_label_stage(ctx, take)) return gr;
     unsigned int nrec = take;                                     // records that cross to the host
     if (take) {
         // the split writes every byte of a record (text tail zeroed), so nothing stale crosses the ABI
@@ -1643,6 +1660,292 @@ extern "C" int acg_selftest_flights(const acg_msg* in, const int* batch, int nba
     hipDeviceSynchronize();
     hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
     acg_fl_destroy(t);
+    return rc;
+}
+
+// ---- the JSON sink (json.hip): buildjson()'s lines rendered on the device ---------------------------------------------------
+static_assert(ACG_JS_LINE_MAX == ACG_JSON_LINE_MAX, "line bound");
+struct AcgJsonState {
+    AcgJsonDev* d_cfg = nullptr;            // the constant stretches of a line, escaped by acg_json_enable
+    unsigned char* d_freq = nullptr;        // [nch][8] "%3.3f" tokens
+    unsigned int* d_cnt = nullptr;          // [4]: bytes, lines of the last pass; the level guard
+    size_t cap = 0;                         // records the work space below holds
+    unsigned long long *d_key = nullptr, *d_key_s = nullptr;
+    unsigned int *d_idx = nullptr, *d_idx_s = nullptr, *d_len = nullptr, *d_off = nullptr, *d_wg = nullptr;
+    unsigned char* d_out = nullptr;         // cap * ACG_JSON_LINE_MAX bytes
+};
+
+static void json_free_work(AcgJsonState* st)
+{
+    hipFree(st->d_key); hipFree(st->d_key_s); hipFree(st->d_idx); hipFree(st->d_idx_s); hipFree(st->d_len); hipFree(st->d_off);
+    hipFree(st->d_wg); hipFree(st->d_out);
+    st->d_key = st->d_key_s = nullptr;
+    st->d_idx = st->d_idx_s = st->d_len = st->d_off = st->d_wg = nullptr;
+    st->d_out = nullptr;
+    st->cap = 0;
+}
+
+static void json_destroy(AcgJsonState* st)
+{
+    if (!st) return;
+    json_free_work(st);
+    hipFree(st->d_cfg); hipFree(st->d_freq); hipFree(st->d_cnt);
+    delete st;
+}
+
+// print_string_ptr's escaping (cJSON.c:828-950) of a C string, appended to dst; returns the new length
+static unsigned int json_escape(unsigned char* dst, unsigned int at, const char* s)
+{
+    for (; *s; ++s) {
+        const unsigned char b = (unsigned char)*s;
+        const char* two = b == '"' ? "\\\"" : b == '\\' ? "\\\\" : b == '\b' ? "\\b" : b == '\f' ? "\\f" : b == '\n' ? "\\n" : b == '\r' ? "\\r" :
+                          b == '\t' ? "\\t" : nullptr;
+        if (two) { dst[at++] = (unsigned char)two[0]; dst[at++] = (unsigned char)two[1]; }
+        else if (b < 32) at += (unsigned int)std::snprintf((char*)dst + at, 7, "\\u%04x", b);
+        else dst[at++] = b;
+    }
+    return at;
+}
+
+static unsigned int json_append(unsigned char* dst, unsigned int at, const char* lit)
+{
+    const size_t n = std::strlen(lit);
+    std::memcpy(dst + at, lit, n);
+    return at + (unsigned int)n;
+}
+
+static bool json_config_ok(const acg_json_config* c)
+{
+    return c && c->t0_sec >= 1000000000ll && c->t0_sec < 4000000000ll && c->t0_usec >= 0 && c->t0_usec <= 999999 &&
+           std::memchr(c->station_id, 0, sizeof(c->station_id)) && std::memchr(c->app_name, 0, sizeof(c->app_name)) &&
+           std::memchr(c->app_ver, 0, sizeof(c->app_ver));
+}
+
+// ACG_OK, ACG_ENOMEM or ACG_EHIP; cfg has passed json_config_ok
+static int json_create(AcgJsonState** out, const acg_json_config* cfg, const int* Fr_hz, int nch)
+{
+    AcgJsonDev h;
+    std::memset(&h, 0, sizeof(h));
+    h.t0_sec = cfg->t0_sec;
+    h.t0_usec = cfg->t0_usec;
+    h.nch = nch;
+    if (cfg->station_id[0]) {                                     // output.c:246
+        h.pre_len = json_append(h.pre, 0, ",\"station_id\":\"");
+        h.pre_len = json_escape(h.pre, h.pre_len, cfg->station_id);
+        h.pre_len = json_append(h.pre, h.pre_len, "\"");
+    }
+    h.post_len = json_append(h.post, 0, ",\"app\":{\"name\":\"");
+    h.post_len = json_escape(h.post, h.post_len, cfg->app_name);
+    h.post_len = json_append(h.post, h.post_len, "\",\"ver\":\"");
+    h.post_len = json_escape(h.post, h.post_len, cfg->app_ver);
+    h.post_len = json_append(h.post, h.post_len, "\"}}\n");
+    if (h.pre_len > ACG_JS_PRE_MAX || h.post_len > ACG_JS_POST_MAX) return ACG_EINVAL;      // (cannot happen: 208 and 221)
+    std::vector<unsigned char> freq((size_t)nch * 8, 0);
+    for (int c = 0; c < nch; ++c) {
+        const float f = (float)((Fr_hz ? Fr_hz[c] : 0) / 1000000.0);                        // output.c:232
+        char tmp[8];
+        std::snprintf(tmp, sizeof(tmp), "%3.3f", f);                                        // output.c:248: cut to 7 characters
+        const size_t n = std::strlen(tmp);
+        std::memcpy(&freq[(size_t)c * 8], tmp, n);
+        freq[(size_t)c * 8 + 7] = (unsigned char)n;
+    }
+    AcgJsonState* st = new (std::nothrow) AcgJsonState();
+    if (!st) return ACG_ENOMEM;
+    if (hipMalloc(&st->d_cfg, sizeof(h)) != hipSuccess || hipMalloc(&st->d_freq, freq.size()) != hipSuccess ||
+        hipMalloc(&st->d_cnt, 4 * sizeof(unsigned int)) != hipSuccess) {
+        json_destroy(st);
+        return ACG_ENOMEM;
+    }
+    if (hipMemcpy(st->d_cfg, &h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(st->d_freq, freq.data(), freq.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(st->d_cnt, 0, 4 * sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        json_destroy(st);
+        return ACG_EHIP;
+    }
+    *out = st;
+    return ACG_OK;
+}
+
+// work space and line buffer for n records, grown on demand as d_kmsgs is
+static int json_reserve(AcgJsonState* st, size_t n)
+{
+    if (n <= st->cap) return ACG_OK;
+    json_free_work(st);
+    const size_t want = std::max<size_t>(n, 4096);
+    if (hipMalloc(&st->d_key, want * 8) != hipSuccess || hipMalloc(&st->d_key_s, want * 8) != hipSuccess ||
+        hipMalloc(&st->d_idx, want * 4) != hipSuccess || hipMalloc(&st->d_idx_s, want * 4) != hipSuccess ||
+        hipMalloc(&st->d_len, want * 4) != hipSuccess || hipMalloc(&st->d_off, want * 4) != hipSuccess ||
+        hipMalloc(&st->d_wg, 2 * (want / 256 + 1) * 4) != hipSuccess || hipMalloc(&st->d_out, want * (size_t)ACG_JSON_LINE_MAX) != hipSuccess) {
+        json_free_work(st);
+        return ACG_ENOMEM;
+    }
+    st->cap = want;
+    return ACG_OK;
+}
+
+// the most records one pass takes: their lines' offsets are 32-bit
+static constexpr unsigned int JSON_MAX_TAKE = (1u << 31) / ACG_JSON_LINE_MAX;
+
+static AcgJsonPass json_pass(const AcgJsonState* st, const AcgMsgRec* recs, const void* oooi, const unsigned int* total, unsigned int nmax, bool lvl_from_rec)
+{
+    AcgJsonPass p;
+    std::memset(&p, 0, sizeof(p));
+    p.recs = recs;
+    p.oooi = (const unsigned char*)oooi;
+    p.total = total;
+    p.nmax = nmax;
+    p.cfg = st->d_cfg;
+    p.freq = st->d_freq;
+    p.lvl_from_rec = lvl_from_rec ? 1 : 0;
+    p.key = st->d_key; p.key_s = st->d_key_s;
+    p.idx = st->d_idx; p.idx_s = st->d_idx_s;
+    p.len = st->d_len; p.off = st->d_off;
+    p.wg_sum = st->d_wg; p.wg_cnt = st->d_wg + (st->cap / 256 + 1);
+    p.counters = st->d_cnt;
+    p.out = st->d_out;
+    p.out_cap = (unsigned int)std::min<size_t>(st->cap * (size_t)ACG_JSON_LINE_MAX, 0xffffffffu);
+    return p;
+}
+
+extern "C" int acg_json_enable(acg_ctx* ctx, const acg_json_config* cfg, const int* Fr_hz)
+{
+    if (!ctx) return ACG_EINVAL;
+    if (cfg && !json_config_ok(cfg)) return fail(ctx, ACG_EINVAL, "JSON sink: t0 outside [10^9, 4 * 10^9) s / 0..999999 us, or an unterminated string");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    if (ctx->json) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+        json_destroy(ctx->json);
+        ctx->json = nullptr;
+    }
+    if (!cfg) return ACG_OK;
+    if (!acg_launch_json) return fail(ctx, ACG_ESTATE, "JSON sink: not in this build");
+    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "JSON sink: context created without ACG_F_REPAIR");
+    if (ctx->cfg.nch > (1 << 20)) return fail(ctx, ACG_EINVAL, "JSON sink: more than 2^20 channels");
+    const int rc = json_create(&ctx->json, cfg, Fr_hz, ctx->cfg.nch);
+    return rc == ACG_OK ? rc : fail(ctx, rc, "JSON sink: allocation failed");
+}
+
+// fetch_msgs' sibling: the same claim, split, label pass and flight pass; then json.hip's passes on the same stream, and only
+// the packed lines and two counters cross to the host
+static int fetch_json(acg_ctx* ctx, int lag, char* out, size_t cap, size_t* nbytes, int* nlines)
+{
+    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
+    if (!ctx->json) return fail(ctx, ACG_ESTATE, "JSON sink is off: acg_json_enable first");
+    unsigned int upto = 0, pending = 0, take = 0;
+    bool any = false;
+    int rc = ring_upto(ctx, lag, &upto, &any);
+    if (rc != ACG_OK || !any) return rc;
+    // a block yields at most one line of at most ACG_JSON_LINE_MAX bytes: the oldest cap / ACG_JSON_LINE_MAX blocks always fit
+    rc = ring_claim(ctx, upto, (int)std::min<size_t>(cap / ACG_JSON_LINE_MAX, JSON_MAX_TAKE), &pending, &take);
+    if (!take) return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
+    if (const int gr = grow_msg_stage(ctx, take)) return gr;
+    if (const int gr = grow_label_stage(ctx, take)) return gr;
+    AcgJsonState* js = ctx->json;
+    if (json_reserve(js, take) != ACG_OK) return fail(ctx, ACG_ENOMEM, "JSON sink: work space");
+    unsigned int* d_total = ctx->d_kwork + ctx->kmsgs_cap / 256 + 1;
+    AcgLabelPass pass{&ctx->msg_filter, ctx->d_kwork, ctx->d_kmsgs, ctx->d_oooi, d_total, nullptr, nullptr};
+    if (ctx->flights) {                                           // over exactly the blocks this call consumes, before -e drops any
+        const int fr = acg_fl_prepare(ctx->flights, take, ctx->copy_stream, &pass.flights);
+        if (fr != ACG_OK) return fail(ctx, fr, "flight table: work space");
+    }
+    if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, take, ctx->d_msgs, ctx->copy_stream, &pass) != 0)
+        return fail(ctx, ACG_EHIP, "message split launch failed");
+    const AcgJsonPass jp = json_pass(js, ctx->d_kmsgs, ctx->d_oooi, d_total, take, false);
+    if (acg_launch_json(&jp, ctx->copy_stream) != 0) return fail(ctx, ACG_EHIP, "JSON pass launch failed");
+    unsigned int cnt[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(cnt, js->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->copy_stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    if (cnt[0] > cap || cnt[1] > take || (size_t)cnt[0] > (size_t)take * ACG_JSON_LINE_MAX) return fail(ctx, ACG_EHIP, "JSON pass: counts out of range");
+    if (cnt[0]) {
+        HIPCHK(ctx, hipMemcpyAsync(out, js->d_out, cnt[0], hipMemcpyDeviceToHost, ctx->copy_stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    }
+    ctx->consumed += take;
+    *nbytes = cnt[0];
+    *nlines = (int)cnt[1];
+    return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
+}
+
+extern "C" int acg_collect_json(acg_ctx* ctx, int lag, char* out, size_t cap, size_t* nbytes, int* nlines)
+{
+    if (!ctx || !out || !nbytes || !nlines || lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
+    *nbytes = 0;
+    *nlines = 0;
+    if (cap < ACG_JSON_LINE_MAX) return fail(ctx, ACG_EINVAL, "JSON sink: the buffer holds less than one line (ACG_JSON_LINE_MAX)");
+    return fetch_json(ctx, lag, out, cap, nbytes, nlines);
+}
+
+extern "C" int acg_drain_json(acg_ctx* ctx, char* out, size_t cap, size_t* nbytes, int* nlines)
+{
+    if (!ctx || !out || !nbytes || !nlines) return ACG_EINVAL;
+    *nbytes = 0;
+    *nlines = 0;
+    if (cap < ACG_JSON_LINE_MAX) return fail(ctx, ACG_EINVAL, "JSON sink: the buffer holds less than one line (ACG_JSON_LINE_MAX)");
+    return fetch_json(ctx, DRAIN, out, cap, nbytes, nlines);
+}
+
+extern "C" int acg_lab_json_level_guard(acg_ctx* ctx, unsigned int* near_midpoint)
+{
+    if (!ctx || !near_midpoint) return ACG_EINVAL;
+    *near_midpoint = 0;
+    if (!ctx->json) return fail(ctx, ACG_ESTATE, "JSON sink is off");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    HIPCHK(ctx, hipMemcpy(near_midpoint, ctx->json->d_cnt + 2, sizeof(unsigned int), hipMemcpyDeviceToHost));
+    return ACG_OK;
+}
+
+extern "C" int acg_selftest_msg_json(const acg_msg* in, int n, const acg_msg_filter* f, const acg_json_config* cfg, const int* Fr_hz, int nch,
+                                     char* out, size_t cap, size_t* nbytes, int* nlines)
+{
+    if (n < 0 || (n > 0 && !in) || !json_config_ok(cfg) || nch < 1 || nch > (1 << 20) || !nbytes || !nlines || (cap > 0 && !out) ||
+        (unsigned int)n > JSON_MAX_TAKE)
+        return ACG_EINVAL;
+    AcgLabelFilter d;
+    if (label_filter_dev(f, &d) != ACG_OK) return ACG_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (in[i].chn < 0 || in[i].chn >= nch || in[i].end_bit < 0 || in[i].end_bit >= (1ll << 44)) return ACG_EINVAL;
+    *nbytes = 0;
+    *nlines = 0;
+    if (n == 0) return ACG_OK;
+    int ndev = 0;
+    if (!acg_launch_json || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
+    std::vector<AcgMsgRec> h((size_t)n);
+    for (int i = 0; i < n; ++i) {                                  // the public record back into the device's form
+        std::memcpy(&h[i], &in[i], sizeof(AcgMsgRec));
+        h[i].valid = in[i].reserved2 ? 0 : 1;
+        h[i].soh_back = (int)(in[i].end_sample - in[i].soh_sample);
+    }
+    AcgJsonState* st = nullptr;
+    int rc = json_create(&st, cfg, Fr_hz, nch);
+    if (rc != ACG_OK) return rc;
+    rc = json_reserve(st, (size_t)n);
+    const size_t by = (size_t)n * sizeof(AcgMsgRec), nwg = (size_t)n / 256 + 1;
+    AcgMsgRec *d_in = nullptr, *d_out = nullptr;
+    acg_oooi* d_oooi = nullptr;
+    unsigned int* d_work = nullptr;
+    if (rc == ACG_OK && (hipMalloc(&d_in, by) != hipSuccess || hipMalloc(&d_out, by) != hipSuccess ||
+                         hipMalloc(&d_oooi, (size_t)n * sizeof(acg_oooi)) != hipSuccess || hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) != hipSuccess))
+        rc = ACG_ENOMEM;
+    if (rc == ACG_OK) {
+        const AcgLabelPass pass{&d, d_work, d_out, d_oooi, d_work + nwg, nullptr, nullptr};
+        const AcgJsonPass jp = json_pass(st, d_out, d_oooi, d_work + nwg, (unsigned int)n, true);
+        unsigned int cnt[2] = {0, 0};
+        if (hipMemcpy(d_in, h.data(), by, hipMemcpyHostToDevice) != hipSuccess ||
+            acg_launch_msg_split(nullptr, 0, 0, (unsigned int)n, d_in, nullptr, &pass) != 0 || acg_launch_json(&jp, nullptr) != 0 ||
+            hipMemcpy(cnt, st->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess || cnt[1] > (unsigned int)n ||
+            (size_t)cnt[0] > (size_t)n * ACG_JSON_LINE_MAX)
+            rc = ACG_EHIP;
+        if (rc == ACG_OK) {
+            *nbytes = cnt[0];
+            *nlines = (int)cnt[1];
+            if (cnt[0] > cap) rc = ACG_EAGAIN;
+            else if (cnt[0] && hipMemcpy(out, st->d_out, cnt[0], hipMemcpyDeviceToHost) != hipSuccess) rc = ACG_EHIP;
+        }
+    }
+    hipDeviceSynchronize();
+    hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
+    json_destroy(st);
     return rc;
 }
 

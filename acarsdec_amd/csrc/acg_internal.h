@@ -141,6 +141,37 @@ struct AcgFlightPass {
     uint2* segs;
 };
 
+// ---- the JSON line renderer (json.hip): buildjson() + cJSON_PrintPreallocated (output.c:227-324) over a call's kept records ----
+#define ACG_JS_LINE_MAX 2496    // == ACG_JSON_LINE_MAX of the public header (derived there)
+#define ACG_JS_PRE_MAX 224      // ,"station_id":"<escaped>"            (15 + 32 * 6 + 1 = 208)
+#define ACG_JS_POST_MAX 224     // ,"app":{"name":"..","ver":".."}}\n    (16 + 96 + 9 + 96 + 3 + 1 = 221)
+// What acg_json_enable renders once on the host: the two constant stretches of every line, already escaped
+struct AcgJsonDev {
+    long long t0_sec;
+    int t0_usec;
+    int nch;                    // freq tokens
+    unsigned int pre_len, post_len;
+    unsigned char pre[ACG_JS_PRE_MAX];
+    unsigned char post[ACG_JS_POST_MAX];
+};
+
+struct AcgJsonPass {
+    const AcgMsgRec* recs;      // label.hip's kept records ...
+    const unsigned char* oooi;  // ... their acg_oooi ...
+    const unsigned int* total;  // ... and how many (a device word: the host does not know it when it launches)
+    unsigned int nmax;          // >= *total: what the grids and the work space are sized for
+    const AcgJsonDev* cfg;
+    const unsigned char* freq;  // [cfg->nch][8]: the "%3.3f" token of the channel (<= 7 chars), its length in byte 7
+    int lvl_from_rec;           // lab entry: the level is the record's lvl, not 10 log10(lvlsum / bitcount)
+    unsigned long long *key, *key_s;    // (chn, end_bit) and the sorted keys
+    unsigned int *idx, *idx_s;          // record index, and in sorted order
+    unsigned int *len, *off;            // per sorted rank: line length, byte offset
+    unsigned int *wg_sum, *wg_cnt;      // per 256 ranks: bytes, lines
+    unsigned int* counters;     // [0] bytes, [1] lines of this pass; [2] level guard (accumulates); [3] unused
+    unsigned char* out;         // nmax * ACG_JS_LINE_MAX bytes, 16-byte aligned
+    unsigned int out_cap;
+};
+
 struct FirArgs {
     const uint8_t* iq;          // [nstreams] rows
     size_t pitch;               // bytes between stream rows (multiple of 16)
@@ -262,6 +293,14 @@ int acg_launch_flight_pass(const AcgMsgRec* recs, unsigned int n, const AcgLabel
 // flight.hip: the live entries, latest update first, as acg_flight records in out[cap]; st->nlive = how many
 int acg_launch_flight_snapshot(const AcgFlightPass* p, unsigned long long* skey, unsigned long long* skey_s, unsigned int* sval,
                                unsigned int* sval_s, void* out, void* stream);
+// flight.hip: the pass's stable radix sort of (64-bit key, 32-bit value) pairs by one workgroup, for other passes: n = *n_ptr
+// (a device word) or n_fixed; the result lies in (kb, vb)
+int acg_launch_sort_pairs(unsigned long long* ka, unsigned int* va, unsigned long long* kb, unsigned int* vb, const unsigned int* n_ptr,
+                          unsigned int n_fixed, void* stream);
+// json.hip: order, measure, scan and render the kept records of one label pass into p->out; p->counters says how much.
+// A WEAK reference, as flights.h's: the host runtime is also linked without the device units (the sanitizer build of
+// tests/test_host_logic.py, which stubs the launchers it knows); there the JSON sink is absent and acg_json_enable says ACG_ESTATE.
+__attribute__((weak)) int acg_launch_json(const AcgJsonPass* p, void* stream);
 int acg_launch_sincos_selftest(const double* x, double* s, double* c, int n, const double* sctab, void* stream);
 int acg_launch_div2_selftest(const double* n0, const double* n1, const double* d, double* out, int n, void* stream);
 int acg_launch_synth_iq(uint8_t* iq, size_t pitch, int nrows, int nout, int decim, const float* env,

@@ -436,6 +436,13 @@ extern "C" int acg_launch_flight_pass(const AcgMsgRec* recs, unsigned int n, con
     return (int)hipGetLastError();
 }
 
+extern "C" int acg_launch_sort_pairs(unsigned long long* ka, unsigned int* va, unsigned long long* kb, unsigned int* vb, const unsigned int* n_ptr,
+                                     unsigned int n_fixed, void* stream)
+{
+    hipLaunchKernelGGL(flight_sort_kernel, dim3(1), dim3(RS_WG), 0, (hipStream_t)stream, ka, va, kb, vb, n_ptr, n_fixed);
+    return (int)hipGetLastError();
+}
+
 // ---- the snapshot: printmonitor()'s walk from the list head (output.c:467-481) = the live entries, latest update first
 __global__ __launch_bounds__(FL_WG) void flight_snapkeys_kernel(AcgFlightPass p, unsigned long long* skey, unsigned int* sval)
 {

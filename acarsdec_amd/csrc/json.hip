@@ -1,0 +1,371 @@
+// json.hip -- the last step of outputmsg() for the batch sink: buildjson() + cJSON_PrintPreallocated(.., fmt = 0)
+// (output.c:227-324, cJSON.c print_object / print_string_ptr / print_number) for the build without libacars, over the records
+// label.hip kept and compacted for one drain / collect.  What leaves is what `-o 4` prints: one JSON object per message, each
+// ended by '\n', packed back to back in (chn, end_bit) order; the host copies bytes and two counters, no records.
+//
+// The passes, all on the stream of the label pass they hang on:
+//   json_keys_kernel     a thread per kept record: the sort key (chn << 44 | end_bit) and the record's index;
+//   flight_sort_kernel   flight.hip's one-workgroup radix sort (acg_launch_sort_pairs) puts them in (chn, end_bit) order;
+//   json_measure_kernel  one WAVE per record: the line's length.  The escape class of every string byte is decided by the lanes
+//                        in parallel (the text: four rounds of 64 lanes), a C string's end is a ballot and a find-first, the
+//                        length is popcounts;
+//   json_sum_kernel / json_offsets_kernel   the exclusive scan of the lengths in sorted order (label.hip's two-launch count /
+//                        base scheme): every line's byte offset, the pass's bytes and lines;
+//   json_render_kernel   one wave per record: the line assembled in a per-wave LDS row, then stored to its packed offset.
+//
+// A string byte's place in the line is its index + the two-character escapes before it + 5 x the \u00xx escapes before it: two
+// ballots and two popcounts, never a lane walking the text.  Numbers are integer arithmetic (json_num.h): lane j computes the
+// j-th character of a token.  Measure and render run the SAME function (json_line<false / true>): the length a line was given
+// room for is the length it is rendered with.
+//
+// THE SEAM.  Lines are packed without padding, so two neighbouring lines share a 16-byte chunk where they meet, and another
+// wave writes the neighbour.  No chunk is ever read back and merged: the row holds the line at the same offset mod 16 as its
+// place in the output, a line's first bytes up to the next 16-byte boundary and its last bytes behind the last one leave as
+// BYTE stores, and only chunks that lie wholly inside the line leave as 16-byte stores (LDS 16-byte reads, both sides aligned).
+//
+// No scratch (no indexed private array: a record's fields are read out of LDS, digits are computed, not stored), no per-byte
+// global traffic (a record comes in as 80 + 10 dword loads, the constant stretches as dwords, a line leaves as 16-byte stores and < 30 byte stores), two
+// independent waves per workgroup (2 x 2 944 B of LDS): these passes run beside a down-converter that saturates HBM.
+#include <hip/hip_runtime.h>
+#include "acg_internal.h"
+#include "acarsdec_amd.h"
+#include "json_num.h"
+
+#define JS_WAVES 2
+#define JS_ROW (ACG_JS_LINE_MAX + 16)       // the line at offset (its output offset mod 16)
+#define JS_REC 384                          // the record (320 B) and its acg_oooi (40 B)
+#define JS_WG 256
+
+static_assert(ACG_JS_LINE_MAX == ACG_JSON_LINE_MAX && ACG_JS_LINE_MAX % 64 == 0, "line bound");
+static_assert(sizeof(AcgMsgRec) == 320 && sizeof(acg_oooi) == 40 && sizeof(AcgMsgRec) + sizeof(acg_oooi) <= JS_REC, "record layout");
+
+// a literal of at most 16 characters as two immediates: lane j takes byte j, nothing is loaded
+struct JsLit {
+    unsigned long long lo, hi;
+    unsigned int n;
+};
+
+constexpr JsLit js_lit(const char* s)
+{
+    JsLit l{0, 0, 0};
+    for (; s[l.n]; ++l.n) {
+        if (l.n < 8) l.lo |= (unsigned long long)(unsigned char)s[l.n] << (8 * l.n);
+        else l.hi |= (unsigned long long)(unsigned char)s[l.n] << (8 * (l.n - 8));
+    }
+    return l;
+}
+
+template <bool W>
+__device__ __forceinline__ void js_st(unsigned char* row, unsigned int p, unsigned char v)
+{
+    if (W && p < (unsigned int)ACG_JS_LINE_MAX) row[p] = v;       // (the bound holds by construction; this keeps a bug inside the row)
+}
+
+template <bool W>
+__device__ __forceinline__ unsigned int put_lit(unsigned char* row, unsigned int pos, const JsLit l, int lane)
+{
+    if (W && (unsigned int)lane < l.n) js_st<W>(row, pos + lane, (unsigned char)((lane < 8 ? l.lo : l.hi) >> (8 * (lane & 7))));
+    return pos + l.n;
+}
+#define PUT_LIT(s) do { constexpr JsLit l_ = js_lit(s); static_assert(sizeof(s) - 1 <= 16, "literal"); pos = put_lit<W>(row, pos, l_, lane); } while (0)
+
+// n bytes that are already escaped (the station and app stretches), 4-byte aligned: a dword load per lane, not a load per byte
+template <bool W>
+__device__ __forceinline__ unsigned int put_words(unsigned char* row, unsigned int pos, const unsigned char* src, unsigned int n, int lane)
+{
+    if (W)
+        for (unsigned int i = 4u * lane; i < n; i += 256) {
+            const unsigned int w = *(const unsigned int*)(src + i);
+#pragma unroll
+            for (unsigned int k = 0; k < 4; ++k)
+                if (i + k < n) js_st<W>(row, pos + i + k, (unsigned char)(w >> (8 * k)));
+        }
+    return pos + n;
+}
+
+template <bool W>
+__device__ __forceinline__ unsigned int put_tok(unsigned char* row, unsigned int pos, const JnTok& t, int lane)
+{
+    if (W && lane < t.len) js_st<W>(row, pos + lane, jn_char(t, lane));
+    return pos + (unsigned int)t.len;
+}
+
+// print_string_ptr's classes (cJSON.c:858-877)
+__device__ __forceinline__ bool js_two(unsigned int b)
+{
+    return b == '"' || b == '\\' || b == '\b' || b == '\f' || b == '\n' || b == '\r' || b == '\t';
+}
+
+// one lane's byte, escaped, at p
+template <bool W>
+__device__ __forceinline__ void put_escaped(unsigned char* row, unsigned int p, unsigned int b, bool two, bool six)
+{
+    if (!W) return;
+    if (two) {
+        js_st<W>(row, p, '\\');
+        js_st<W>(row, p + 1, (unsigned char)(b == '\b' ? 'b' : b == '\f' ? 'f' : b == '\n' ? 'n' : b == '\r' ? 'r' : b == '\t' ? 't' : b));
+    } else if (six) {                                              // sprintf("u%04x"): lower-case hex, b < 32
+        js_st<W>(row, p, '\\');
+        js_st<W>(row, p + 1, 'u');
+        js_st<W>(row, p + 2, '0');
+        js_st<W>(row, p + 3, '0');
+        js_st<W>(row, p + 4, (unsigned char)('0' + (b >> 4)));
+        const unsigned int lo = b & 15u;
+        js_st<W>(row, p + 5, (unsigned char)(lo < 10 ? '0' + lo : 'a' + lo - 10));
+    } else {
+        js_st<W>(row, p, (unsigned char)b);
+    }
+}
+
+// up to 64 bytes of a string whose lane's byte is b (0 = at or behind its end): `live` lanes are those before the first NUL.
+// Returns the escaped length; *more = no NUL among the 64 (the string goes on in the next round).
+template <bool W>
+__device__ __forceinline__ unsigned int put_round(unsigned char* row, unsigned int pos, unsigned int b, int lane, bool* more)
+{
+    const unsigned long long nul = __ballot(b == 0);
+    const int n = nul ? __ffsll((unsigned long long)nul) - 1 : 64;
+    const bool live = lane < n;
+    const bool two = live && js_two(b), six = live && b < 32u && !two;
+    const unsigned long long m2 = __ballot(two), m6 = __ballot(six), below = (1ull << lane) - 1ull;
+    if (live) put_escaped<W>(row, pos + (unsigned int)lane + (unsigned int)__popcll(m2 & below) + 5u * (unsigned int)__popcll(m6 & below), b, two, six);
+    *more = n == 64;
+    return (unsigned int)n + (unsigned int)__popcll(m2) + 5u * (unsigned int)__popcll(m6);
+}
+
+// "<C string at s, at most maxlen < 64 bytes>" escaped as print_string_ptr does
+template <bool W>
+__device__ __forceinline__ unsigned int put_str(unsigned char* row, unsigned int pos, const unsigned char* s, int maxlen, int lane)
+{
+    const unsigned int b = lane < maxlen ? s[lane] : 0u;
+    bool more;
+    if (lane == 0) js_st<W>(row, pos, '"');
+    const unsigned int n = put_round<W>(row, pos + 1, b, lane, &more);
+    if (lane == 0) js_st<W>(row, pos + 1 + n, '"');
+    return pos + n + 2;
+}
+
+// One line.  R: the record and, at R + 320, its acg_oooi (LDS); row: where the line's first byte goes (W) or unused.
+template <bool W>
+__device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsigned char* row, const AcgJsonPass& p, int lane, bool* near_mid)
+{
+    const AcgMsgRec* r = (const AcgMsgRec*)R;
+    const AcgJsonDev* cfg = p.cfg;
+    unsigned int pos = 0;
+    // ---- "timestamp": tv = t0 + soh_sample / 12500 s in integers (a sample is exactly 80 us), as flight_extract_kernel
+    const long long soh = r->end_sample - (long long)r->soh_back;
+    const long long us = (long long)cfg->t0_usec + soh * 80ll;
+    long long q = us / 1000000ll, rem = us % 1000000ll;
+    if (rem < 0) { rem += 1000000ll; --q; }
+    PUT_LIT("{\"timestamp\":");
+    pos = put_tok<W>(row, pos, jn_timestamp(cfg->t0_sec + q, (int)rem), lane);
+    pos = put_words<W>(row, pos, cfg->pre, cfg->pre_len, lane);                   // ,"station_id":".." or nothing
+    const int chn = r->chn;
+    PUT_LIT(",\"channel\":");
+    pos = put_tok<W>(row, pos, jn_int(chn), lane);
+    PUT_LIT(",\"freq\":");
+    if ((unsigned int)chn < (unsigned int)cfg->nch) {
+        const unsigned long long ft = ((const unsigned long long*)p.freq)[chn];    // 7 characters and their count: one load
+        const unsigned int fn = (unsigned int)(ft >> 56) & 7u;
+        if (W && (unsigned int)lane < fn) js_st<W>(row, pos + lane, (unsigned char)(ft >> (8 * lane)));
+        pos += fn;
+    } else {
+        PUT_LIT("0.000");
+    }
+    // ---- "level": the float of acars.c:351, then "%2.1f" cut to 7 characters (json_num.h)
+    float lvl = r->lvl;
+    *near_mid = false;
+    if (!p.lvl_from_rec) {
+        const double d = 10.0 * log10(r->lvlsum / (double)r->bitcount);
+        lvl = (float)d;
+        // the one inexact step: another log10 may land on the other side of a float rounding boundary when d lies next to one.
+        // A float midpoint is a double whose low 29 mantissa bits are 1 << 28 (normal floats).
+        const long long low = (long long)((unsigned long long)__double_as_longlong(d) & ((1ull << 29) - 1ull)) - (1ll << 28);
+        *near_mid = d == d && d - d == 0.0 && (low < 0 ? -low : low) <= 8;
+    }
+    PUT_LIT(",\"level\":");
+    pos = put_tok<W>(row, pos, jn_level(lvl), lane);
+    PUT_LIT(",\"error\":");
+    pos = put_tok<W>(row, pos, jn_int(r->err), lane);
+    PUT_LIT(",\"mode\":");
+    pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, mode), 1, lane);           // "%c": a NUL gives ""
+    PUT_LIT(",\"label\":");
+    pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, label), 2, lane);
+    const char bid = r->bid;
+    if (bid) {
+        PUT_LIT(",\"block_id\":");
+        pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, bid), 1, lane);
+        if (r->ack == '!') {
+            PUT_LIT(",\"ack\":false");
+        } else {
+            PUT_LIT(",\"ack\":");
+            pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, ack), 1, lane);
+        }
+        PUT_LIT(",\"tail\":");
+        pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, addr), 7, lane);
+        if (bid >= '0' && bid <= '9') {                                          // IS_DOWNLINK_BLK, output.c:31,269
+            PUT_LIT(",\"flight\":");
+            pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, fid), 6, lane);
+            PUT_LIT(",\"msgno\":");
+            pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, no), 4, lane);
+        }
+    }
+    // ---- "text": a C string within txt_len bytes, four rounds of 64 lanes
+    int tl = r->txt_len;
+    tl = tl < 0 ? 0 : tl > ACG_MSG_TXT ? ACG_MSG_TXT : tl;
+    const unsigned char* txt = R + offsetof(AcgMsgRec, txt);
+    if (tl > 0 && txt[0]) {
+        PUT_LIT(",\"text\":\"");
+        for (int rd = 0; rd < 4; ++rd) {
+            const int i = 64 * rd + lane;
+            const unsigned int b = i < tl ? txt[i] : 0u;
+            bool more;
+            pos += put_round<W>(row, pos, b, lane, &more);
+            if (!more) break;                                                    // (wave-uniform)
+        }
+        PUT_LIT("\"");
+    }
+    if (r->be == 0x17) PUT_LIT(",\"end\":true");
+    // ---- the OOOI keys in buildjson's order (output.c:280-295): sa da eta gout gin woff won of {da sa eta gout gin woff won}
+    const unsigned char* O = R + sizeof(AcgMsgRec);
+    if (O[35]) {
+        if (O[5]) { PUT_LIT(",\"depa\":"); pos = put_str<W>(row, pos, O + 5, 4, lane); }
+        if (O[0]) { PUT_LIT(",\"dsta\":"); pos = put_str<W>(row, pos, O + 0, 4, lane); }
+        if (O[10]) { PUT_LIT(",\"eta\":"); pos = put_str<W>(row, pos, O + 10, 4, lane); }
+        if (O[15]) { PUT_LIT(",\"gtout\":"); pos = put_str<W>(row, pos, O + 15, 4, lane); }
+        if (O[20]) { PUT_LIT(",\"gtin\":"); pos = put_str<W>(row, pos, O + 20, 4, lane); }
+        if (O[25]) { PUT_LIT(",\"wloff\":"); pos = put_str<W>(row, pos, O + 25, 4, lane); }
+        if (O[30]) { PUT_LIT(",\"wlin\":"); pos = put_str<W>(row, pos, O + 30, 4, lane); }
+    }
+    pos = put_words<W>(row, pos, cfg->post, cfg->post_len, lane);                 // ,"app":{"name":"..","ver":".."}}\n
+    return pos;
+}
+
+// the record of sorted rank r and its acg_oooi into the wave's LDS: 80 + 10 dwords
+__device__ __forceinline__ void js_load(unsigned char* R, const AcgJsonPass& p, unsigned int idx, int lane)
+{
+    const unsigned int* src = (const unsigned int*)(p.recs + idx);
+    unsigned int* dst = (unsigned int*)R;
+    dst[lane] = src[lane];
+    if (lane < 16) dst[64 + lane] = src[64 + lane];
+    if (lane < 10) dst[80 + lane] = ((const unsigned int*)(p.oooi + (size_t)idx * sizeof(acg_oooi)))[lane];
+    // (LDS operations of one wave execute in order; the fence keeps the compiler from moving them across each other)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__global__ __launch_bounds__(JS_WG) void json_keys_kernel(AcgJsonPass p)
+{
+    const unsigned int i = blockIdx.x * JS_WG + threadIdx.x;
+    if (i >= p.nmax || i >= *p.total) return;
+    const AcgMsgRec* r = p.recs + i;
+    // records the block repair dropped (none passes label.hip's filter) would sort last and render nothing
+    p.key[i] = r->valid ? (((unsigned long long)(unsigned int)r->chn & 0xfffffull) << 44) | ((unsigned long long)r->end_bit & ((1ull << 44) - 1ull)) : ~0ull;
+    p.idx[i] = i;
+}
+
+__global__ __launch_bounds__(64 * JS_WAVES) void json_measure_kernel(AcgJsonPass p)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char recs[JS_WAVES][JS_REC];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned int r = blockIdx.x * JS_WAVES + wv;                           // wave-uniform
+    if (r >= p.nmax || r >= *p.total) return;
+    if (p.key_s[r] == ~0ull) {
+        if (lane == 0) p.len[r] = 0;
+        return;
+    }
+    js_load(recs[wv], p, p.idx_s[r], lane);
+    bool nm;
+    const unsigned int n = json_line<false>(recs[wv], nullptr, p, lane, &nm);
+    if (lane == 0) p.len[r] = n > (unsigned int)ACG_JS_LINE_MAX ? (unsigned int)ACG_JS_LINE_MAX : n;
+}
+
+__global__ __launch_bounds__(JS_WG) void json_sum_kernel(AcgJsonPass p)
+{
+    __shared__ unsigned int sum_s;
+    if (threadIdx.x == 0) sum_s = 0;
+    __syncthreads();
+    const unsigned int i = blockIdx.x * JS_WG + threadIdx.x;
+    const unsigned int v = (i < p.nmax && i < *p.total) ? p.len[i] : 0u;
+    if (v) atomicAdd(&sum_s, v);
+    const int c = __syncthreads_count(v != 0);
+    if (threadIdx.x == 0) {
+        p.wg_sum[blockIdx.x] = sum_s;
+        p.wg_cnt[blockIdx.x] = (unsigned int)c;
+    }
+}
+
+__global__ __launch_bounds__(JS_WG) void json_offsets_kernel(AcgJsonPass p)
+{
+    __shared__ unsigned int base_s, cnt_s;
+    __shared__ unsigned int wave_n[JS_WG / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0) { base_s = 0; cnt_s = 0; }
+    __syncthreads();
+    unsigned int s = 0, c = 0;
+    for (unsigned int j = threadIdx.x; j < blockIdx.x; j += JS_WG) { s += p.wg_sum[j]; c += p.wg_cnt[j]; }
+    if (s) atomicAdd(&base_s, s);
+    if (c) atomicAdd(&cnt_s, c);
+    const unsigned int i = blockIdx.x * JS_WG + threadIdx.x;
+    const unsigned int v = (i < p.nmax && i < *p.total) ? p.len[i] : 0u;
+    unsigned int incl = v;                                                       // inclusive scan within the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned int o = (unsigned int)__shfl((int)incl, lane >= off ? lane - off : lane);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) wave_n[wv] = incl;
+    __syncthreads();
+    unsigned int before = base_s;
+    for (int w = 0; w < wv; ++w) before += wave_n[w];
+    if (i < p.nmax) p.off[i] = before + incl - v;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        unsigned int t = base_s;
+        for (int w = 0; w < JS_WG / 64; ++w) t += wave_n[w];
+        p.counters[0] = t;
+        p.counters[1] = cnt_s + p.wg_cnt[blockIdx.x];
+    }
+}
+
+__global__ __launch_bounds__(64 * JS_WAVES) void json_render_kernel(AcgJsonPass p)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char recs[JS_WAVES][JS_REC];
+    __shared__ __attribute__((aligned(16))) unsigned char rows[JS_WAVES][JS_ROW];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned int r = blockIdx.x * JS_WAVES + wv;                           // wave-uniform
+    if (r >= p.nmax || r >= *p.total) return;
+    const unsigned int len = p.len[r], off = p.off[r];
+    if (len == 0 || len > (unsigned int)ACG_JS_LINE_MAX || off > p.out_cap || len > p.out_cap - off) return;
+    js_load(recs[wv], p, p.idx_s[r], lane);
+    const unsigned int a = off & 15u;                                            // the row mirrors the output's alignment
+    bool near_mid;
+    const unsigned int n = json_line<true>(recs[wv], rows[wv] + a, p, lane, &near_mid);
+    if (n != len) return;                                                        // (cannot happen: one function measures and renders)
+    if (near_mid && lane == 0) atomicAdd(&p.counters[2], 1u);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // ---- out.  Row byte x <-> output byte (off - a) + x, the line is row[a, a + len); chunk c = row[16 c, 16 c + 16)
+    const unsigned char* row = rows[wv];
+    unsigned char* dst = p.out + (off - a);                                      // 16-byte aligned
+    const unsigned int end = a + len;
+    const unsigned int c0 = (a + 15u) >> 4, c1 = end >> 4;                       // whole chunks: [c0, c1)
+    const unsigned int head_end = c1 > c0 ? 16u * c0 : end;                      // no whole chunk: everything leaves as bytes
+    const unsigned int tail_beg = c1 > c0 ? 16u * c1 : end;
+    for (unsigned int x = a + lane; x < head_end; x += 64) dst[x] = row[x];      // (< 16 bytes, or < 31 when no chunk is whole)
+    for (unsigned int x = tail_beg + lane; x < end; x += 64) dst[x] = row[x];
+    for (unsigned int c = c0 + lane; c < c1; c += 64) ((uint4*)dst)[c] = ((const uint4*)row)[c];
+}
+
+extern "C" int acg_launch_json(const AcgJsonPass* p, void* stream)
+{
+    if (p->nmax == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned int g = (p->nmax + JS_WG - 1) / JS_WG, gw = (p->nmax + JS_WAVES - 1) / JS_WAVES;
+    hipLaunchKernelGGL(json_keys_kernel, dim3(g), dim3(JS_WG), 0, s, *p);
+    int e = acg_launch_sort_pairs(p->key, p->idx, p->key_s, p->idx_s, p->total, 0u, stream);
+    if (e) return e;
+    hipLaunchKernelGGL(json_measure_kernel, dim3(gw), dim3(64 * JS_WAVES), 0, s, *p);
+    hipLaunchKernelGGL(json_sum_kernel, dim3(g), dim3(JS_WG), 0, s, *p);
+    hipLaunchKernelGGL(json_offsets_kernel, dim3(g), dim3(JS_WG), 0, s, *p);
+    hipLaunchKernelGGL(json_render_kernel, dim3(gw), dim3(64 * JS_WAVES), 0, s, *p);
+    return (int)hipGetLastError();
+}

@@ -335,6 +335,49 @@ class Decoder:
             if rc == K.OK:
                 return out
 
+    # ---- the JSON sink (acg_json_enable, acg_drain_json, acg_collect_json) -------------------------------------------------
+    def enable_json(self, t0, station_id="", app_name="acarsdec", app_ver="", freqs_hz=None):
+        """buildjson()'s lines (output.c:227-324, what -o 4 prints) rendered on the device from now on.  t0: wall clock of the
+        first sample since reset, (sec, usec) or seconds as a float, 10^9 <= sec < 4 * 10^9; station_id: the CLI's -i ("" = no
+        key); app_name / app_ver: the "app" object; freqs_hz: the channels' frequencies in Hz (None = 0, "0.000")."""
+        cfg = json_config(t0, station_id, app_name, app_ver)
+        fr = None
+        if freqs_hz is not None:
+            fr = np.ascontiguousarray(freqs_hz, dtype=np.int32)
+            assert fr.size == self.nch
+        self._chk(self.L.acg_json_enable(self.ctx, C.byref(cfg), fr.ctypes.data if fr is not None else None))
+
+    def disable_json(self):
+        self._chk(self.L.acg_json_enable(self.ctx, None, None))
+
+    def _json_call(self, fn, max_lines, *lead):
+        cap = max(1, int(max_lines)) * K.JSON_LINE_MAX
+        if getattr(self, "_jbuf_cap", 0) < cap:
+            self._jbuf = C.create_string_buffer(cap)
+            self._jbuf_cap = cap
+        out = []
+        while True:
+            nb, nl = C.c_size_t(0), C.c_int(0)
+            rc = self._chk(fn(self.ctx, *lead, self._jbuf, self._jbuf_cap, C.byref(nb), C.byref(nl)), allow=(K.EAGAIN,))
+            out.append(C.string_at(self._jbuf, nb.value))
+            if rc == K.OK:
+                return b"".join(out)
+
+    def drain_json(self, max_lines=4096):
+        """The JSON lines of every block completed since the last drain (needs repair=True and enable_json), as bytes: one object
+        per kept message, each ended by a newline, in (chn, end_bit) order per C call; loops while the C side says ACG_EAGAIN."""
+        return self._json_call(self.L.acg_drain_json, max_lines)
+
+    def collect_json(self, lag=1, max_lines=4096):
+        """Streaming variant (acg_collect_json): the lines of all calls but the `lag` newest"""
+        return self._json_call(self.L.acg_collect_json, max_lines, lag)
+
+    def json_level_guard(self):
+        """lines rendered since enable_json whose level lay within 8 ulp of a float rounding boundary (acg_lab_json_level_guard)"""
+        n = C.c_uint(0)
+        self._chk(self.L.acg_lab_json_level_guard(self.ctx, C.byref(n)))
+        return n.value
+
     def bits(self, ch):
         vo = np.zeros(self.bit_cap, dtype=np.float32)
         lvl = np.zeros(self.bit_cap, dtype=np.float32)
@@ -389,6 +432,18 @@ def make_msg_filter(downlink_only=False, skip_empty=False, labels=None, lib=None
         for i, l in enumerate(labels):
             f.labels[i].value = l[:3]
     return f
+
+
+def json_config(t0, station_id="", app_name="acarsdec", app_ver=""):
+    """K.JsonConfig for acg_json_enable / acg_selftest_msg_json; t0 = (sec, usec) or seconds as a float"""
+    sec, usec = t0 if isinstance(t0, tuple) else (int(t0 // 1), int(round((t0 - t0 // 1) * 1e6)))
+    if usec >= 1000000:
+        sec, usec = sec + 1, usec - 1000000
+    enc = lambda v: v.encode("latin1") if isinstance(v, str) else bytes(v)
+    station_id, app_name, app_ver = enc(station_id), enc(app_name), enc(app_ver)
+    if len(station_id) > 32 or len(app_name) > 16 or len(app_ver) > 16:
+        raise ValueError("station_id holds 32 characters, app_name and app_ver 16")
+    return K.JsonConfig(int(sec), int(usec), station_id, app_name, app_ver)
 
 
 # oooi_t field -> the reference JSON's key (output.c:280-295, in the order buildjson adds them)

@@ -369,6 +369,49 @@ int  acg_flight_snapshot(acg_ctx *ctx, acg_flight *out, int max, int *n, int *dr
  * alone still drains them now and then, or the queue grows by one record per route emitted. */
 int  acg_drain_routes(acg_ctx *ctx, acg_route *out, int max, int *n);
 
+/* ---- the JSON sink: buildjson() (output.c:227-324), what -o 4 prints, -j sends and the MQTT sink publishes ------------------
+ * Off by default; with it off every entry point launches, copies and returns exactly what it does without this section.
+ * acg_drain_json / acg_collect_json are message entry points like acg_drain_msgs / acg_collect_msgs (ACG_F_REPAIR, the filters
+ * of acg_set_msg_filter, the flight table when it is on, blocks the repair dropped yield nothing), but what they hand out is
+ * TEXT rendered on the device: one JSON object per kept message, each ended by '\n', packed back to back in `out`, in
+ * (chn, end_bit) order within the call -- byte for byte what the reference built without libacars prints through
+ * cJSON_PrintPreallocated(.., fmt = 0), time stamps included.  *nbytes bytes, *nlines lines; out is not NUL terminated.
+ * A call looks at the oldest cap / ACG_JSON_LINE_MAX queued blocks only and consumes exactly those; more queued: ACG_EAGAIN
+ * (call again, nothing is lost).  ACG_EINVAL: cap < ACG_JSON_LINE_MAX; ACG_ESTATE: no ACG_F_REPAIR, or acg_json_enable has
+ * not been called.
+ *
+ * ACG_JSON_LINE_MAX, the longest line, every string byte a control character that costs 6 ("\u00xx"), key by key:
+ *   {"timestamp":            13 + 18   ten integer digits, the point, seven fraction digits ("%1.17g")
+ *   ,"station_id":".."       15 + 32 * 6 + 1 = 208
+ *   ,"channel":              11 + 11   (an int)
+ *   ,"freq":                  8 + 7    ,"level":  9 + 7    (both cut to 7 characters by the reference's 8-byte buffer)
+ *   ,"error":                 9 + 11
+ *   ,"mode":".."              9 + 6 + 1       ,"label":".."   10 + 2 * 6 + 1    ,"block_id":".."  13 + 6 + 1
+ *   ,"ack":".."               8 + 6 + 1       ,"tail":".."     9 + 7 * 6 + 1
+ *   ,"flight":".."           11 + 6 * 6 + 1   ,"msgno":".."   10 + 4 * 6 + 1
+ *   ,"text":".."              9 + 242 * 6 + 1 = 1462
+ *   ,"end":true              11
+ *   ,"depa":".." ,"dsta":".." ,"eta":".." ,"gtout":".." ,"gtin":".." ,"wloff":".." ,"wlin":".."     64 + 7 * (4 * 6 + 1) = 239
+ *   ,"app":{"name":"..","ver":".."}}    16 + 16 * 6 + 9 + 16 * 6 + 3 = 220,    '\n'  1
+ * = 2454, rounded up to a multiple of 64. */
+#define ACG_JSON_LINE_MAX  2496
+typedef struct {
+	long long t0_sec;             /* the epoch rule of acg_frame: tv = t0 + soh_sample / 12500 s, in integers */
+	int t0_usec;                  /* 0 .. 999999 */
+	char station_id[33];          /* idstation (-i); "" = the key is absent (output.c:246) */
+	char app_name[17], app_ver[17];   /* "app":{"name":..,"ver":..}: the reference's are "acarsdec" and its ACARSDEC_VERSION */
+} acg_json_config;
+/* Switches the JSON sink on (cfg) or off and frees it (NULL).  Fr_hz: the channels' frequencies in Hz ([nch]; NULL = all 0, what
+ * a reference built without an SDR front end prints): "freq" is snprintf(8 bytes, "%3.3f", (float)(Fr / 1000000.0)), rendered
+ * here once per channel (output.c:232,248).  The three strings are escaped once, like every string of a line.
+ * "timestamp" is print_number's text (cJSON.c:475-506: "%1.15g", or "%1.17g" when that does not parse back) of
+ * (double)tv_sec + (double)tv_usec / 1e6, exact for 10^9 <= tv_sec < 9999999998 (September 2001 .. the year 2286); outside, the
+ * token is the integer second (well formed, not the reference's digits).  ACG_EINVAL: t0_sec outside [10^9, 4 * 10^9), t0_usec
+ * outside 0..999999, an unterminated string; ACG_ESTATE: context without ACG_F_REPAIR.  acg_reset keeps the configuration. */
+int  acg_json_enable(acg_ctx *ctx, const acg_json_config *cfg, const int *Fr_hz);
+int  acg_drain_json(acg_ctx *ctx, char *out, size_t cap, size_t *nbytes, int *nlines);
+int  acg_collect_json(acg_ctx *ctx, int lag, char *out, size_t cap, size_t *nbytes, int *nlines);
+
 /* Per-bit records of the LAST process call for one channel (needs ACG_F_BITLOG):
  * vo = the value putbit() receives (msk.c:122-126), lvl = cabsf(v) (msk.c:110). */
 int  acg_read_bits(acg_ctx *ctx, int ch, float *vo, float *lvl, int max_bits, int *nbits);

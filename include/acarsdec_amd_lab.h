@@ -79,6 +79,21 @@ int  acg_selftest_msg_labels(const acg_msg *in, int n, const acg_msg_filter *f, 
 int  acg_selftest_flights(const acg_msg *in, const int *batch, int nbatch, const acg_flight_config *cfg, const acg_msg_filter *f,
 			  acg_flight *snaps, int snap_cap, int *snap_n, acg_route *routes, int route_cap, int *nroutes, int *dropped);
 
+/* diagnostics: the JSON sink's passes (label.hip's filter and compaction, then json.hip's order / measure / scan / render) on n
+ * caller-supplied records, taken as acg_drain_msgs hands them out, without a demodulator: the lines of the records the filter f
+ * (NULL = none) keeps, in (chn, end_bit) order (equal keys: input order), packed into out; *nbytes, *nlines as acg_drain_json.
+ *   level        this entry has no lvlsum / bitcount: "level" is "%2.1f" of in[i].lvl as it stands (the device's log10 is not run);
+ *   time         tv = cfg->t0 + in[i].soh_sample / 12500 s;
+ *   dropped      in[i].reserved2 != 0 marks a record the block repair dropped: it yields nothing;
+ *   freq         Fr_hz[nch] (NULL = 0); ACG_EINVAL unless 0 <= in[i].chn < nch <= 2^20 and 0 <= in[i].end_bit < 2^44.
+ * ACG_EAGAIN: cap < the bytes needed (*nbytes says how many; out is untouched); ACG_ENODEV: no GPU. */
+int  acg_selftest_msg_json(const acg_msg *in, int n, const acg_msg_filter *f, const acg_json_config *cfg, const int *Fr_hz, int nch,
+			   char *out, size_t cap, size_t *nbytes, int *nlines);
+/* diagnostics: how many lines acg_drain_json / acg_collect_json have rendered since acg_json_enable whose level, as the double
+ * 10 log10(lvlsum / bitcount), lay within 8 ulp of the midpoint of two floats -- the only lines whose "level" could differ from
+ * a host's that narrows glibc's log10 */
+int  acg_lab_json_level_guard(acg_ctx *ctx, unsigned int *near_midpoint);
+
 /* Test hook (the block ring across the wrap of its 32-bit counters): right after acg_reset, with nothing queued,
  * sets the device's block counter, the repair pass's mark and the host's consumer mark to `value`, as if that many blocks had
  * been produced and consumed already.  ACG_ESTATE if calls have been issued since the reset. */
