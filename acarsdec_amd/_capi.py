@@ -86,6 +86,13 @@ class JsonConfig(C.Structure):
                 ("app_ver", C.c_char * 17)]
 
 
+class LaunchShape(C.Structure):
+    """acg_lab_launch_shape: the down-converter launch the library makes for one launch of nblocks callbacks"""
+    _fields_ = [("kernel", C.c_int), ("stages", C.c_int), ("cpr", C.c_int), ("ncu", C.c_int), ("device_cus", C.c_int),
+                ("chunk_blocks", C.c_int), ("units", C.c_uint), ("runs_per_unit", C.c_uint), ("tiles_per_run", C.c_uint),
+                ("runs", C.c_uint), ("wave_slots", C.c_uint), ("workgroups", C.c_uint), ("waves", C.c_uint)]
+
+
 assert C.sizeof(Flight) == 120 and C.sizeof(Route) == 56
 
 BIT_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_float, C.c_float)
@@ -175,6 +182,7 @@ LAB_SYMBOLS = {
     "acg_lab_json_level_guard": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint)]),
     "acg_lab_set_block_counter": (C.c_int, [C.c_void_p, C.c_uint]),
     "acg_lab_block_ring_size": (C.c_uint, [C.c_void_p]),
+    "acg_lab_fir_launch_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(LaunchShape)]),
 }
 # declared in acarsdec_amd_lab.h, present in the stamp build only (-DACG_MSK_STAMP)
 STAMP_SYMBOLS = ("acg_msk_stamp_read", "acg_msk_lanes_per_channel")

@@ -17,6 +17,7 @@
 
 #include "acarsdec_amd.h"
 #include "acarsdec_amd_lab.h"
+#include "fir_mm_plan.h"
 #include "acg_internal.h"
 #include "flights.h"
 
@@ -740,78 +741,89 @@ static FirArgs u8_args(const acg_ctx* c, const uint8_t* iq_dev, size_t pitch)
     return a;
 }
 
+// Which u8 I/Q down-converter kernel takes the launch a (nwin, ncu set by the caller) on this context; fills in the arguments that
+// kernel needs.  Changes nothing in the context: launch_fir_u8 launches what this says, acg_lab_fir_launch_shape reports it.
+enum FirU8Kernel { FIR_U8_GENERIC, FIR_U8_DIRECT, FIR_U8_SHARED, FIR_U8_MM, FIR_U8_MM1 };
+static FirU8Kernel fir_u8_kernel(const acg_ctx* c, FirArgs& a)
+{
+    const acg_config& g = c->cfg;
+    a.nseg = 1;
+    // verification mode: rtl.c:335-353 in the reference's own order of operations (fir.hip, fir_u8_generic_kernel)
+    if (c->exact_fir || !c->tile_path) return FIR_U8_GENERIC;
+    a.cpr = a.row_bytes / 16;
+    a.row_stride = (a.cpr & 1) ? a.row_bytes : a.row_bytes + 16;
+    a.cpr_magic = ((1u << 20) + (unsigned int)a.cpr - 1) / (unsigned int)a.cpr;
+    const int ntile = a.nwin / ACG_TILE_WIN;
+    int nseg = (4096 + g.nch - 1) / g.nch;          // aim at >= ~4096 workgroups
+    nseg = std::max(1, std::min(nseg, ntile));
+    a.nseg = nseg;
+    a.groups = c->d_groups;
+    a.group_ch = c->d_group_ch;
+    a.ngroups = c->ngroups;
+    a.gtaps = c->d_gtaps;
+    a.mm_img = c->d_mm_img;
+    a.mm_chan = c->d_mm_chan;
+    // one stream per channel: the exact contraction with K = 1 takes the arithmetic off the vector pipe (fir_u8_mm1_kernel)
+    if (c->ngroups == 0 && acg_tune_get("ACG_FIR_MM1", ACG_FIR_MM1_DEFAULT) && acg_fir_mm1_image_bytes(g.decim, 1) != 0) {
+        // (its images are made at the first launch that wants them, launch_fir_u8: whether the kernel takes the shape does not
+        //  depend on where they lie)
+        FirArgs t = a;
+        t.mm_img = c->d_mm1_img ? c->d_mm1_img : (const void*)c->d_taps;
+        t.mm_chan = c->d_mm_chan ? c->d_mm_chan : (const void*)c->d_taps;
+        if (acg_fir_mm1_takes(&t)) return FIR_U8_MM1;
+    }
+    // several channels per stream: the contraction goes to the matrix pipe (fir_mm.hip) where it takes the shape
+    // (rtlMult 160 / 192 / 200, whole tiles), else to the vector-pipe kernel
+    if (c->ngroups > 0 && acg_tune_get("ACG_FIR_MM", 1) && acg_fir_mm_takes(&a)) return FIR_U8_MM;
+    return c->ngroups > 0 ? FIR_U8_SHARED : FIR_U8_DIRECT;
+}
+
 // The u8 I/Q down-converter kernel for this context, and the tap images it needs.  Returns what the kernel's launcher
 // returned (a HIP error, 0 = launched), or ACG_EHIP with the text in c->err when a tap image could not be made.
 static int launch_fir_u8(acg_ctx* c, FirArgs& a, hipStream_t s)
 {
     const acg_config& g = c->cfg;
     int e;
-    if (c->exact_fir) {
-        // verification mode: rtl.c:335-353 in the reference's own order of operations (fir.hip, fir_u8_generic_kernel)
-        a.nseg = 1;
-        e = acg_launch_fir_generic(&a, s);
-    } else if (c->tile_path) {
-        a.cpr = a.row_bytes / 16;
-        a.row_stride = (a.cpr & 1) ? a.row_bytes : a.row_bytes + 16;
-        a.cpr_magic = ((1u << 20) + (unsigned int)a.cpr - 1) / (unsigned int)a.cpr;
-        const int ntile = a.nwin / ACG_TILE_WIN;
-        int nseg = (4096 + g.nch - 1) / g.nch;          // aim at >= ~4096 workgroups
-        nseg = std::max(1, std::min(nseg, ntile));
-        a.nseg = nseg;
-        a.groups = c->d_groups;
-        a.group_ch = c->d_group_ch;
-        a.ngroups = c->ngroups;
-        a.gtaps = c->d_gtaps;
-        a.mm_img = c->d_mm_img;
-        a.mm_chan = c->d_mm_chan;
-        // several channels per stream: the contraction goes to the matrix pipe (fir_mm.hip) where it takes the shape
-        // (rtlMult 160 / 192 / 200, whole tiles), else to the vector-pipe kernel below
-        const bool mm = c->ngroups > 0 && acg_tune_get("ACG_FIR_MM", 1) && acg_fir_mm_takes(&a);
-        // one stream per channel: the same exact contraction with K = 1 takes the arithmetic off the vector pipe (fir_u8_mm1_kernel)
-        bool mm1 = false;
-        if (c->ngroups == 0 && acg_tune_get("ACG_FIR_MM1", ACG_FIR_MM1_DEFAULT) && acg_fir_mm1_image_bytes(g.decim, 1) != 0) {
-            if (!c->d_mm1_img) {
-                HIPCHK(c, hipMalloc(&c->d_mm1_img, acg_fir_mm1_image_bytes(g.decim, g.nch)));
-                c->mm1_dirty = true;
-            }
-            if (!c->d_mm_chan) HIPCHK(c, hipMalloc(&c->d_mm_chan, (size_t)g.nch * sizeof(MmChan)));
-            a.mm_img = c->d_mm1_img;
-            a.mm_chan = c->d_mm_chan;
-            mm1 = acg_fir_mm1_takes(&a) != 0;
+    switch (fir_u8_kernel(c, a)) {
+    case FIR_U8_GENERIC:
+        return acg_launch_fir_generic(&a, s);
+    case FIR_U8_MM1:
+        if (!c->d_mm1_img) {
+            HIPCHK(c, hipMalloc(&c->d_mm1_img, acg_fir_mm1_image_bytes(g.decim, g.nch)));
+            c->mm1_dirty = true;
         }
-        if (mm1) {
-            if (c->mm1_dirty) {
-                if ((e = acg_launch_fir_mm1_prep(&a, s)) != 0) {
-                    c->err = std::string("tap digit launch: ") + hipGetErrorString((hipError_t)e);
-                    return ACG_EHIP;
-                }
-                c->mm1_dirty = false;
-            }
-            e = acg_launch_fir_mm1(&a, s);
-        } else if (mm) {
-            if (c->mm_dirty) {
-                if ((e = acg_launch_fir_mm_prep(&a, s)) != 0) {
-                    c->err = std::string("tap digit launch: ") + hipGetErrorString((hipError_t)e);
-                    return ACG_EHIP;
-                }
-                c->mm_dirty = false;
-            }
-            e = acg_launch_fir_mm(&a, s);
-        } else {
-        if (c->ngroups > 0 && c->gtaps_dirty) {          // taps or the stream map changed (both synchronise the device)
-            if ((e = acg_launch_regroup_taps(&a, s)) != 0) {
-                c->err = std::string("tap regroup launch: ") + hipGetErrorString((hipError_t)e);
+        if (!c->d_mm_chan) HIPCHK(c, hipMalloc(&c->d_mm_chan, (size_t)g.nch * sizeof(MmChan)));
+        a.mm_img = c->d_mm1_img;
+        a.mm_chan = c->d_mm_chan;
+        if (c->mm1_dirty) {
+            if ((e = acg_launch_fir_mm1_prep(&a, s)) != 0) {
+                c->err = std::string("tap digit launch: ") + hipGetErrorString((hipError_t)e);
                 return ACG_EHIP;
             }
-            c->gtaps_dirty = false;
+            c->mm1_dirty = false;
         }
-        e = c->ngroups > 0 ? acg_launch_fir_shared(&a, s) : acg_launch_fir(&a, s);
+        return acg_launch_fir_mm1(&a, s);
+    case FIR_U8_MM:
+        if (c->mm_dirty) {
+            if ((e = acg_launch_fir_mm_prep(&a, s)) != 0) {
+                c->err = std::string("tap digit launch: ") + hipGetErrorString((hipError_t)e);
+                return ACG_EHIP;
+            }
+            c->mm_dirty = false;
         }
-    } else {
-        a.nseg = 1;
-        e = acg_launch_fir_generic(&a, s);
+        return acg_launch_fir_mm(&a, s);
+    case FIR_U8_SHARED:
+    case FIR_U8_DIRECT:
+        break;
     }
-    return e;
+    if (c->ngroups > 0 && c->gtaps_dirty) {          // taps or the stream map changed (both synchronise the device)
+        if ((e = acg_launch_regroup_taps(&a, s)) != 0) {
+            c->err = std::string("tap regroup launch: ") + hipGetErrorString((hipError_t)e);
+            return ACG_EHIP;
+        }
+        c->gtaps_dirty = false;
+    }
+    return c->ngroups > 0 ? acg_launch_fir_shared(&a, s) : acg_launch_fir(&a, s);
 }
 
 // One down-converter launch on stream s: launch(c, a, s) is the format's kernel choice (launch_fir_u8 or acg_launch_fir_fmt),
@@ -2125,6 +2137,37 @@ extern "C" int acg_lab_set_block_counter(acg_ctx* ctx, unsigned int value)
     return ACG_OK;
 }
 extern "C" unsigned int acg_lab_block_ring_size(const acg_ctx* ctx) { return ctx ? ctx->frame_cap : 0u; }
+
+// ---- lab: the down-converter launch of `nblocks` callbacks, as the launcher decides it ---------------------------------------
+extern "C" int acg_lab_fir_launch_shape(acg_ctx* ctx, int nblocks, acg_lab_launch_shape* out)
+{
+    if (!ctx || !out) return ACG_EINVAL;
+    if (nblocks < 1 || nblocks > ctx->cfg.max_blocks) return fail(ctx, ACG_EINVAL, "nblocks out of range");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    std::memset(out, 0, sizeof *out);
+    (void)hipDeviceGetAttribute(&out->device_cus, hipDeviceAttributeMultiprocessorCount, ctx->cfg.device);
+    // the arguments of run_pipeline's launch: the format's, the chunk's window count, the partition's CU count
+    FirArgs a = u8_args(ctx, nullptr, 0);
+    a.nwin = nblocks * ACG_BLOCK;
+    if (ctx->fir_stream) a.ncu = ctx->fir_ncu;
+    out->ncu = a.ncu > 0 ? a.ncu : out->device_cus;
+    out->chunk_blocks = ctx->pipe_blocks;
+    const FirU8Kernel k = fir_u8_kernel(ctx, a);
+    if (k != FIR_U8_MM && k != FIR_U8_MM1) return ACG_OK;
+    const MmPlan p = k == FIR_U8_MM ? acg_fir_mm_plan(&a, out->device_cus) : acg_fir_mm1_plan(&a, out->device_cus);
+    out->kernel = p.kernel;
+    out->stages = p.stages;
+    out->cpr = p.cpr;
+    out->ncu = p.ncu;
+    out->units = p.units;
+    out->runs_per_unit = p.runs_per_unit;
+    out->tiles_per_run = p.tiles_per_run;
+    out->runs = p.runs;
+    out->wave_slots = p.wave_slots;
+    out->workgroups = p.workgroups;
+    out->waves = p.waves;
+    return ACG_OK;
+}
 
 extern "C" int acg_set_timing(acg_ctx* ctx, int mode)
 {

@@ -36,13 +36,13 @@
 #include <map>
 #include <mutex>
 #include "acg_internal.h"
+#include "fir_mm_plan.h"
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef int v16i_t __attribute__((ext_vector_type(16)));
 typedef unsigned int u4m_t __attribute__((ext_vector_type(4)));
 
 extern __shared__ __attribute__((aligned(16))) unsigned char mm_smem[];
-extern "C" int acg_tune_get(const char* name, int dflt);          // measurement / layout switches (acg_api.cpp)
 
 template <int CPR>
 struct FirMM {
@@ -485,27 +485,16 @@ int mm_optin(MmDev* d, const void* kernel, size_t bytes)
 }
 
 template <int CPR, int STAGES>
-int launch_mm(const FirArgs* a, hipStream_t stream)
+int launch_mm(const FirArgs* a, const MmPlan& p, hipStream_t stream)
 {
     typedef FirMM<CPR> F;
     MmDev* d = nullptr;
     if (int e = mm_device(&d)) return e;
-    const int ncu = a->ncu > 0 ? a->ncu : d->num_cu;
-    const unsigned int nwaves = (unsigned int)ncu * (STAGES == 1 ? 8u : 4u);
-    const unsigned int ntile = (unsigned int)a->nwin / F::WIN;
-    // ~4 runs per wave where the launch is large enough, at least two tiles per run (a run pays one tile of load latency
-    // and 26 KiB of digits from L2)
-    unsigned int rpg = 1;
-    while (rpg * 2 * (unsigned int)a->ngroups <= 4 * nwaves && ntile % (rpg * 2) == 0 && ntile / (rpg * 2) >= 2) rpg *= 2;
     FirArgs b = *a;
-    b.run_pairs = (int)(ntile / rpg);
-    const unsigned long long nrun = (unsigned long long)a->ngroups * rpg;
-    const unsigned int need = (unsigned int)((nrun + 3) / 4);
-    const unsigned int blocks = (unsigned int)ncu * (STAGES == 1 ? 2u : 1u);
-    const unsigned int grid = need < blocks ? need : blocks;
+    b.run_pairs = (int)p.tiles_per_run;
     const size_t lds = (size_t)4 * F::WAVE_LDS;
     if (int e = mm_optin(d, (const void*)fir_u8_mm_kernel<CPR, STAGES>, lds)) return e;
-    hipLaunchKernelGGL((fir_u8_mm_kernel<CPR, STAGES>), dim3(grid), dim3(256), lds, stream, b, a->iq, (const u4m_t*)a->mm_img,
+    hipLaunchKernelGGL((fir_u8_mm_kernel<CPR, STAGES>), dim3(p.workgroups), dim3(256), lds, stream, b, a->iq, (const u4m_t*)a->mm_img,
                        (const MmChan*)a->mm_chan, a->groups, a->group_ch, a->dm);
     return (int)hipGetLastError();
 }
@@ -545,12 +534,13 @@ extern "C" int acg_launch_fir_mm_prep(const FirArgs* a, void* stream)
 extern "C" int acg_launch_fir_mm(const FirArgs* a, void* stream)
 {
     if (!acg_fir_mm_takes(a)) return (int)hipErrorInvalidValue;
-    // beside the demodulator on the same CUs: one wave per SIMD with two tiles in flight (see the kernel's comment)
-    const int stages = acg_tune_get("ACG_FIR_MM_STAGES", a->shares_cus ? 2 : 1) == 2 ? 2 : 1;
-    switch (a->decim / 8) {
-    case 20: return stages == 2 ? launch_mm<20, 2>(a, (hipStream_t)stream) : launch_mm<20, 1>(a, (hipStream_t)stream);
-    case 24: return stages == 2 ? launch_mm<24, 2>(a, (hipStream_t)stream) : launch_mm<24, 1>(a, (hipStream_t)stream);
-    case 25: return stages == 2 ? launch_mm<25, 2>(a, (hipStream_t)stream) : launch_mm<25, 1>(a, (hipStream_t)stream);
+    MmDev* d = nullptr;
+    if (int e = mm_device(&d)) return e;
+    const MmPlan p = acg_fir_mm_plan(a, d->num_cu);
+    switch (p.cpr) {
+    case 20: return p.stages == 2 ? launch_mm<20, 2>(a, p, (hipStream_t)stream) : launch_mm<20, 1>(a, p, (hipStream_t)stream);
+    case 24: return p.stages == 2 ? launch_mm<24, 2>(a, p, (hipStream_t)stream) : launch_mm<24, 1>(a, p, (hipStream_t)stream);
+    case 25: return p.stages == 2 ? launch_mm<25, 2>(a, p, (hipStream_t)stream) : launch_mm<25, 1>(a, p, (hipStream_t)stream);
     }
     return (int)hipErrorInvalidValue;
 }
@@ -558,29 +548,16 @@ extern "C" int acg_launch_fir_mm(const FirArgs* a, void* stream)
 // ---- one stream per channel (fir_u8_mm1_kernel) ---------------------------------------------------------------------------
 namespace {
 template <int CPR>
-int launch_mm1(const FirArgs* a, hipStream_t stream)
+int launch_mm1(const FirArgs* a, const MmPlan& p, hipStream_t stream)
 {
     typedef FirMM<CPR> F;
     MmDev* d = nullptr;
     if (int e = mm_device(&d)) return e;
-    const int ncu = a->ncu > 0 ? a->ncu : d->num_cu;
-    // 13.2 KiB of LDS and 160 VGPRs per wave: twelve fit a CU that the demodulator does not share (<= 2048 channels: measured
-    // 8 / 10 / 12 waves 2.30 / 2.33 / 2.46 M channel*Msps at 2048 channels); beside the demodulator's workgroups (15.4 KiB each: two
-    // per CU up to 4096 channels, four from 8192) nine or seven (profiles/r06_mm1_waves_ab_*.json)
-    int per_cu = !a->shares_cus ? 12 : a->nch >= 8192 ? 7 : 9;
-    per_cu = acg_tune_get("ACG_FIR_MM1_WAVES", per_cu);
-    if (per_cu < 1 || per_cu > 12) per_cu = 8;
-    const unsigned int nwaves = (unsigned int)ncu * (unsigned int)per_cu;
-    const unsigned int ntile = (unsigned int)a->nwin / F::WIN;
-    unsigned int rpc = 1;                                            // ~4 runs per wave, at least 8 tiles per run
-    while (rpc * 2 * (unsigned int)a->nch <= 4 * nwaves && ntile % (rpc * 2) == 0 && ntile / (rpc * 2) >= 8) rpc *= 2;
     FirArgs b = *a;
-    b.run_pairs = (int)(ntile / rpc);
-    const unsigned long long nrun = (unsigned long long)a->nch * rpc;
-    const unsigned int grid = nrun < nwaves ? (unsigned int)nrun : nwaves;
+    b.run_pairs = (int)p.tiles_per_run;
     const size_t lds = (size_t)F::WAVE_LDS;
     if (int e = mm_optin(d, (const void*)fir_u8_mm1_kernel<CPR>, lds)) return e;
-    hipLaunchKernelGGL(fir_u8_mm1_kernel<CPR>, dim3(grid), dim3(64), lds, stream, b, a->iq, (const u4m_t*)a->mm_img,
+    hipLaunchKernelGGL(fir_u8_mm1_kernel<CPR>, dim3(p.workgroups), dim3(64), lds, stream, b, a->iq, (const u4m_t*)a->mm_img,
                        (const MmChan*)a->mm_chan, a->stream_of, a->dm);
     return (int)hipGetLastError();
 }
@@ -619,10 +596,13 @@ extern "C" int acg_launch_fir_mm1_prep(const FirArgs* a, void* stream)
 extern "C" int acg_launch_fir_mm1(const FirArgs* a, void* stream)
 {
     if (!acg_fir_mm1_takes(a)) return (int)hipErrorInvalidValue;
-    switch (a->decim / 8) {
-    case 20: return launch_mm1<20>(a, (hipStream_t)stream);
-    case 24: return launch_mm1<24>(a, (hipStream_t)stream);
-    case 25: return launch_mm1<25>(a, (hipStream_t)stream);
+    MmDev* d = nullptr;
+    if (int e = mm_device(&d)) return e;
+    const MmPlan p = acg_fir_mm1_plan(a, d->num_cu);
+    switch (p.cpr) {
+    case 20: return launch_mm1<20>(a, p, (hipStream_t)stream);
+    case 24: return launch_mm1<24>(a, p, (hipStream_t)stream);
+    case 25: return launch_mm1<25>(a, p, (hipStream_t)stream);
     }
     return (int)hipErrorInvalidValue;
 }

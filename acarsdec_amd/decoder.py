@@ -180,6 +180,13 @@ class Decoder:
         self._chk(self.L.acg_placement_trial_samples(self.ctx, fmt, dev_tensor.data_ptr(), pitch, plane, nblocks, repeats, stream, C.byref(ms)))
         return ms.value
 
+    def launch_shape(self, nblocks):
+        """The down-converter launch the library makes for one launch of nblocks callbacks (acg_lab_fir_launch_shape), as a
+        K.LaunchShape: kernel (0 vector pipe, 1 fir_u8_mm_kernel, 2 fir_u8_mm1_kernel), stages, runs, tiles_per_run, waves ..."""
+        s = K.LaunchShape()
+        self._chk(self.L.acg_lab_fir_launch_shape(self.ctx, int(nblocks), C.byref(s)))
+        return s
+
     def demod_msk(self, dm):
         """demodMSK() for all channels from 12.5 kHz samples: dm float32 [nch, len]."""
         dm = np.ascontiguousarray(dm, dtype=np.float32)

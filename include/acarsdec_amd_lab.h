@@ -101,6 +101,28 @@ int  acg_lab_set_block_counter(acg_ctx *ctx, unsigned int value);
 /* length of the block ring (a power of two) */
 unsigned int acg_lab_block_ring_size(const acg_ctx *ctx);
 
+/* diagnostics: the down-converter launch the library makes for ONE launch of `nblocks` callbacks of u8 I/Q on this context, as the
+ * launcher itself decides it (the same function sizes the launch): which kernel, how the input is cut into dispensed runs, the
+ * grid.  A call of acg_process_iq_u8_* is one such launch per pipeline chunk (chunk_blocks callbacks; 0 = the whole call).  Reads
+ * the tuning switches as a launch at this moment would; launches nothing.  ACG_EINVAL: nblocks outside 1..max_blocks. */
+typedef struct acg_lab_launch_shape {
+	int kernel;			/* 0 a vector-pipe kernel (nothing below but ncu, device_cus, chunk_blocks is set),
+					   1 fir_u8_mm_kernel<cpr, stages>, 2 fir_u8_mm1_kernel<cpr> */
+	int stages;			/* tiles in flight per wave */
+	int cpr;			/* decim / 8 */
+	int ncu;			/* CUs the launch is sized for (the down-converter's side of a CU partition) */
+	int device_cus;			/* CUs of the device */
+	int chunk_blocks;		/* the context's pipeline chunk in callbacks, 0 = whole calls */
+	unsigned int units;		/* channel groups (kernel 1) or channels (kernel 2) */
+	unsigned int runs_per_unit;
+	unsigned int tiles_per_run;	/* 32-window tiles per dispensed run */
+	unsigned int runs;		/* units * runs_per_unit */
+	unsigned int wave_slots;	/* resident waves the run length was sized for; fewer runs than this: the grid is cut */
+	unsigned int workgroups;	/* the grid */
+	unsigned int waves;		/* waves launched: runs beyond these are handed out by ticket */
+} acg_lab_launch_shape;
+int  acg_lab_fir_launch_shape(acg_ctx *ctx, int nblocks, acg_lab_launch_shape *out);
+
 /* only in the stamp build (libacarsdec_amd_stamp.so, -DACG_MSK_STAMP): phase cycle sums of the LAST demodulator launch,
  * [waves][10], and the lanes per channel of the context's demodulator */
 int  acg_msk_stamp_read(acg_ctx *ctx, unsigned long long *out, int nwaves);

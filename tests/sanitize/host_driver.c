@@ -126,6 +126,10 @@ int main(void)
 		CHECK(acg_get_state_n(NULL, 0, 1, &st) == ACG_EINVAL && acg_set_state_n(NULL, 0, 1, &st) == ACG_EINVAL);
 		CHECK(acg_read_dm_n(NULL, 0, 1, buf, 4, 4) == ACG_EINVAL);
 		CHECK(acg_lab_set_block_counter(NULL, 1u) == ACG_EINVAL && acg_lab_block_ring_size(NULL) == 0u);
+		{
+			acg_lab_launch_shape shape;
+			CHECK(acg_lab_fir_launch_shape(NULL, 1, &shape) == ACG_EINVAL);
+		}
 		CHECK(acg_replay_bits(NULL, NULL, NULL) == ACG_EINVAL);
 		CHECK(acg_get_timing(NULL, &ms, &n, &ms, &n) == ACG_EINVAL && acg_set_timing(NULL, 1) == ACG_EINVAL);
 		CHECK(acg_fill_random_u8_dev(NULL, 16, 1, 16, 1, NULL) == ACG_EINVAL);

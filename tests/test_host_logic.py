@@ -13,6 +13,7 @@ import pytest
 from conftest import ROOT, has_gpu
 from acarsdec_amd import _capi as K, decoder as D, synth as S
 from oracle import oracle as O
+import mm_model
 
 
 def header_symbols(header="acarsdec_amd.h"):
@@ -530,16 +531,12 @@ def test_matrix_pipe_digit_arithmetic_is_exact():
         w[:ntaps, 0] = (np.cos(ph) * win / M / 127.5 * shrink).astype(np.float32)
         w[:ntaps, 1] = (np.sin(ph) * win / M / 127.5 * shrink).astype(np.float32)
         mx = float(np.abs(w).max())
-        e = int(np.frexp(np.float32(mx))[1])
-        up = 2.0 ** (30 - e)
-        q = np.rint(w.astype(np.float64) * up).astype(np.int64)
+        k = mm_model.chan_consts(w, M)                   # the restatement lives in tests/mm_model.py, which the device is held to
+        e, q = k.e, k.q
         assert np.abs(q).max() <= 2 ** 30
         # balanced digits: the signed low byte, then an exact shift
-        digs, r = [], q.copy()
-        for p in range(4):
-            d = ((r + 128) % 256) - 128
-            digs.append(d)
-            r = (r - d) // 256
+        digs = mm_model.digits(q)
+        r = q - (digs[0] + 256 * digs[1] + 65536 * digs[2] + (1 << 24) * digs[3])
         assert np.all(r == 0) and all(np.abs(d).max() <= 128 and d.min() >= -128 and d.max() <= 127 for d in digs)
         assert np.array_equal(digs[0] + 256 * digs[1] + 65536 * digs[2] + (1 << 24) * digs[3], q)
         nwin = 64
@@ -560,8 +557,9 @@ def test_matrix_pipe_digit_arithmetic_is_exact():
             D = hi.astype(np.float64) * 65536.0 + lo.astype(np.float64)
             assert np.array_equal(D.astype(np.int64), hi * 65536 + lo)              # exact in f64
             sums[name] = D
-        scale = 2.0 ** (e - 30)
-        c = 128.0 - float(np.float32(127.37))
+        scale = k.scale
+        c = mm_model.DC
+        assert scale == 2.0 ** (e - 30) and c == 128.0 - float(np.float32(127.37))
         sr, si = int(q[:, 0].sum()), int(q[:, 1].sum())
         re = sums["re"] * scale + c * (sr - si) * scale
         im = sums["im"] * scale + c * (sr + si) * scale
@@ -575,8 +573,8 @@ def test_matrix_pipe_digit_arithmetic_is_exact():
 
 def test_matrix_pipe_kernels_isa():
     """fir_mm.hip compiled with the product's flags: no scratch access anywhere; per 32-window tile the shared-stream kernel issues
-    two v_mfma_i32_32x32x32_i8 per 32-byte k-step (2 x 13 at rtlMult 200: one tile's worth, straight-line) and the one-stream kernel
-    one; the one-tile variant stays inside 256 VGPRs (two waves per SIMD), the two-tile variant leaves room for a demodulator wave
+    two v_mfma_i32_32x32x32_i8 per 32-byte k-step (2 x 13 at rtlMult 200: one tile's worth, straight-line; the two-tile variant
+    carries the tile body once per register stage: 4 x 13) and the one-stream kernel one; the one-tile variant stays inside 256 VGPRs (two waves per SIMD), the two-tile variant leaves room for a demodulator wave
     (<= 512 - 136), the one-stream kernel fits three waves per SIMD."""
     import re
     import shutil
@@ -600,7 +598,9 @@ def test_matrix_pipe_kernels_isa():
         else:
             assert 256 < n <= 512 - 136, (name, n)
     for cpr, ks in ((20, 10), (24, 12), (25, 13)):
-        for name, per in (("_Z16fir_u8_mm_kernelILi%dELi1EE" % cpr, 2 * ks), ("_Z17fir_u8_mm1_kernelILi%dEE" % cpr, ks)):
+        # (the two-tile variant holds the tile body twice, once per register stage: 2 x 2 KS)
+        for name, per in (("_Z16fir_u8_mm_kernelILi%dELi1EE" % cpr, 2 * ks), ("_Z16fir_u8_mm_kernelILi%dELi2EE" % cpr, 4 * ks),
+                          ("_Z17fir_u8_mm1_kernelILi%dEE" % cpr, ks)):
             start = next(k for k, l in enumerate(asm.splitlines()) if l.startswith(name) and ": ; @" in l)
             body = asm.splitlines()[start:]
             body = body[:next(k for k, l in enumerate(body) if "s_endpgm" in l)]
