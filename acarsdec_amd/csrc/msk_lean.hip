@@ -34,6 +34,22 @@
 // barrier in front of the mixer), ACG_LEAN_AB_TAB0 (table read inside the mixer), ACG_LEAN_AB_BRS0 (the compiler's block order).
 // Two more steps were measured and not taken (1 / s started where df is set; the branch hint on `quick` as well): DESIGN 4.
 // tests/test_lean_issue_order.py pins the order in the assembly.
+//
+// The front of a period (round 8).  A period takes up to six samples, each a VCO phase step (add, compare with 2 pi, select, fma) and
+// a clock step (widen, add, narrow); the two chains only share the step s.  The compiler's order ran them one behind the other:
+// clock steps 1-4, the test on `quick`, then phase steps 2-6 and clock steps 5 and 6 under the branch (machine sinking moves what is
+// only used there), the sixth clock step in an exec-save block of its own, and behind the join the twelve selects with which a lane
+// picks its own sample's phase.  front() now computes all six steps of both chains in ONE block in front of the test, side by side:
+// steps 5 and 6 uncommitted (for a lane that is not `quick`, has fired or has no sample left they are arithmetic on registers whose
+// result is dropped), the lane's pick issued behind the step that produces it, and the guarded block left with the commits (cnt, p,
+// L.clk, fired: the same compares on the same values).  What keeps steps 1-4 in front of the branch is that steps 5 and 6 and the
+// picks use them there; steps 5 and 6 are held by an empty asm volatile each (LEAN_HOLD_STEP), without which the sixth sinks again.
+// Same operations on the same operands; a pick that a lane does not need (sample u >= cnt) goes to the ring's spare row as before.
+// Switches: ACG_LEAN_AB_SPEC0 (steps 5 and 6 under the branch), ACG_LEAN_AB_PICK0 (the picks in the guarded block), ACG_LEAN_AB_VCO0
+// (with both of those: no hold on steps 1-4 either, which is the order before round 8 and the parent commit's assembly),
+// ACG_LEAN_AB_HOLDS (which steps carry a hold).  Measured and not taken: a hold behind every step (1 % slower than holds on 5 and 6
+// only), the six newest taps as plain f32 (4 % slower), and the one-sample case by selects too; DESIGN 4.
+// tests/test_lean_chain_layout.py pins the placement in the assembly.
 #include <hip/hip_runtime.h>
 #include "acg_internal.h"
 
@@ -165,6 +181,21 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
 #else
 #define LEAN_UNLIKELY(c) __builtin_expect(!!(c), 0)
 #endif
+// holds a VCO / clock step where the source has it: an empty statement that the compiler must take to read and write the step's
+// phase and clock and the lane's pick (nothing is issued for it), so that neither sinking nor the scheduler carries the step past
+// it.  ACG_LEAN_AB_HOLDS (A/B builds): bit 0 = behind each of steps 1-4, bit 1 = behind steps 5 and 6, bit 2 = the pick is named too
+#ifndef ACG_LEAN_AB_HOLDS
+#ifdef ACG_LEAN_AB_SPEC0
+#define ACG_LEAN_AB_HOLDS 7                        /* (steps 5 and 6 under the branch: only a hold keeps steps 2-4 in front of it) */
+#else
+#define ACG_LEAN_AB_HOLDS 6
+#endif
+#endif
+#if defined(ACG_LEAN_AB_PICK0) || !(ACG_LEAN_AB_HOLDS & 4)
+#define LEAN_HOLD_STEP(pv, cv, mv) asm volatile("" : "+v"(pv), "+v"(cv))
+#else
+#define LEAN_HOLD_STEP(pv, cv, mv) asm volatile("" : "+v"(pv), "+v"(cv), "+v"(mv))
+#endif
 #define MSK_TAP(j, x) (f2v{(j & 1) ? hv2[j / 2].y : hv2[j / 2].x, (j & 1) ? hv2[j / 2].y : hv2[j / 2].x} * x)
 
     // what a period's front part (VCO / clock steps, mixer, the five oldest filter taps) hands to its bit decision
@@ -201,12 +232,57 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
             p4 = wrap_2pi(p4);
             c4 = (float)((double)c4 + s);
             pq[u] = p4;
+#if !defined(ACG_LEAN_AB_VCO0) && (ACG_LEAN_AB_HOLDS & 1)
+            // (only where steps 5 and 6 are under the branch: there machine sinking moves the phase step after them otherwise)
+            LEAN_HOLD_STEP(p4, c4, myp[(u > 0 ? u - 1 : 0) / LPC]);
+#endif
+#ifndef ACG_LEAN_AB_PICK0
+            // (a lane that is not `quick` or has no sample left mixes these into the ring's spare row, except its first sample,
+            // whose phase is this one: the one-sample branch below computes the same p + s)
+            if ((u % LPC) == g) myp[u / LPC] = p4;
+#endif
         }
         const bool quick = (s > 0) && !((double)c4 >= thr) && (n + 6 <= len);
+#ifndef ACG_LEAN_AB_SPEC0
+        // steps 5 and 6 of both chains in the same block, uncommitted: the guarded block below only selects
+        double p5 = p4 + s;                                                // msk.c:82-83
+        p5 = wrap_2pi(p5);
+        float c5 = (float)((double)c4 + s);                          // msk.c:95
+#if ACG_LEAN_AB_HOLDS & 2
+        LEAN_HOLD_STEP(p5, c5, myp[3 / LPC]);
+#endif
+        const bool fired5 = (double)c5 >= thr;
+#ifndef ACG_LEAN_AB_PICK0
+        if ((4 % LPC) == g) myp[4 / LPC] = p5;
+#endif
+        double p6 = p5 + s;
+        p6 = wrap_2pi(p6);
+        float c6 = (float)((double)c5 + s);
+#if ACG_LEAN_AB_HOLDS & 2
+        LEAN_HOLD_STEP(p6, c6, myp[4 / LPC]);
+#endif
+        const bool fired6 = (double)c6 >= thr;
+#ifndef ACG_LEAN_AB_PICK0
+        if ((5 % LPC) == g) myp[5 / LPC] = p6;
+#endif
+#endif
         if (n < len && quick) {
+#ifdef ACG_LEAN_AB_PICK0
 #pragma unroll
             for (int u = 0; u < 4; ++u)
                 if ((u % LPC) == g) myp[u / LPC] = pq[u];
+#endif
+#ifndef ACG_LEAN_AB_SPEC0
+#ifdef ACG_LEAN_AB_PICK0
+            if ((4 % LPC) == g) myp[4 / LPC] = p5;
+            if ((5 % LPC) == g) myp[5 / LPC] = p6;
+#endif
+            const bool go = !fired5;
+            p = go ? p6 : p5;
+            L.clk = go ? c6 : c5;
+            cnt = go ? 6 : 5;
+            fired = go ? fired6 : true;
+#else
             p = p4;
             L.clk = c4;
             cnt = 4;
@@ -233,6 +309,7 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
                 }
                 if ((5 % LPC) == g) myp[5 / LPC] = pn;
             }
+#endif
         } else if (n < len) {
             double pn = p + s;
             pn = wrap_2pi(pn);
@@ -241,7 +318,9 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
             L.clk = cn;
             cnt = 1;
             fired = (double)cn >= thr;
+#ifdef ACG_LEAN_AB_PICK0
             if (g == 0) myp[0] = pn;
+#endif
         }
         unsigned int idx_n = idx + (unsigned int)cnt;
         if (idx_n >= FLEN) idx_n -= FLEN;

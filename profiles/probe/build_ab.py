@@ -1,20 +1,25 @@
 """A/B builds of the demodulator for same-box timing: python profiles/probe/build_ab.py NAME[:-DFLAG[,-DFLAG...]] ...
 Each NAME becomes acarsdec_amd/lib/ab/libNAME.so = the product objects with msk.hip recompiled under the given flags
 (a git revision may be given as NAME@REV:flags to take msk.hip from history).  profiles/probe/run_ab.sh times them all
-on one box through ACARSDEC_AMD_LIB.  Measurement aid only; nothing here is loaded by the product."""
+on one box through ACARSDEC_AMD_LIB.  Measurement aid only; nothing here is loaded by the product.
+Switches of msk_lean.hip may be given by their short names: a flag without a leading dash is taken as -DACG_LEAN_AB_<FLAG>
+(round 7: TAPS0, PIN0, TAB0, BRS0; round 8: VCO0, SPEC0, PICK0, TAPSF1), and R07PARENT / R08PARENT stand for every old-order
+switch of that round, the arm whose msk_lean assembly is the parent commit's."""
 import os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 sys.path.insert(0, ROOT)
 from acarsdec_amd import _build as B
 
 MSK_FLAGS = B.MSK_FLAGS                 # the product's recipe (acarsdec_amd/_build.py)
+GROUPS = {"R07PARENT": ["TAPS0", "PIN0", "TAB0", "BRS0"], "R08PARENT": ["VCO0", "SPEC0", "PICK0"]}
 B.build_lib()
 out = os.path.join(B.LIBDIR, "ab")
 os.makedirs(out, exist_ok=True)
 for spec in sys.argv[1:]:
     name, _, flags = spec.partition(":")
     name, _, rev = name.partition("@")
-    flags = [f for f in flags.split(",") if f]
+    flags = [g for f in flags.split(",") if f for g in GROUPS.get(f, [f])]
+    flags = [f if f.startswith(("-", "DROP=")) else "-DACG_LEAN_AB_" + f for f in flags]
     drop = [f[5:] for f in flags if f.startswith("DROP=")]          # DROP=substr: leave out the product flags containing it
     flags = [f for f in flags if not f.startswith("DROP=")]
     base = []
