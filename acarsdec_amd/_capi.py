@@ -182,6 +182,7 @@ LAB_SYMBOLS = {
     "acg_lab_json_level_guard": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint)]),
     "acg_lab_set_block_counter": (C.c_int, [C.c_void_p, C.c_uint]),
     "acg_lab_block_ring_size": (C.c_uint, [C.c_void_p]),
+    "acg_lab_set_stream_counters": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong]),
     "acg_lab_fir_launch_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(LaunchShape)]),
 }
 # declared in acarsdec_amd_lab.h, present in the stamp build only (-DACG_MSK_STAMP)

@@ -2138,6 +2138,26 @@ extern "C" int acg_lab_set_block_counter(acg_ctx* ctx, unsigned int value)
 }
 extern "C" unsigned int acg_lab_block_ring_size(const acg_ctx* ctx) { return ctx ? ctx->frame_cap : 0u; }
 
+// ---- lab: the stream counters after days of uptime (acarsdec_amd_lab.h) -------------------------------------------------
+extern "C" int acg_lab_set_stream_counters(acg_ctx* ctx, int ch0, int n, long long nsamp_total, long long nbit_total)
+{
+    if (!ctx || ch0 < 0 || n < 1 || ch0 + n > ctx->cfg.nch || nsamp_total < 0 || nbit_total < 0) return ACG_EINVAL;
+    if (ctx->call_seq != 0) return fail(ctx, ACG_ESTATE, "acg_lab_set_stream_counters: only right after acg_reset");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    // read-modify-write, as acg_set_state_n: everything but the three counters stays as the device has it
+    std::vector<AcgChan> dv((size_t)n);
+    HIPCHK(ctx, hipMemcpy(dv.data(), ctx->d_st + ch0, (size_t)n * sizeof(AcgChan), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+        AcgChan& d = dv[(size_t)i];
+        d.nsamp_total = nsamp_total;
+        d.nbit_total = nbit_total;
+        d.soh32 = (unsigned int)nsamp_total;
+    }
+    HIPCHK(ctx, hipMemcpy(ctx->d_st + ch0, dv.data(), (size_t)n * sizeof(AcgChan), hipMemcpyHostToDevice));
+    return ACG_OK;
+}
+
 // ---- lab: the down-converter launch of `nblocks` callbacks, as the launcher decides it ---------------------------------------
 extern "C" int acg_lab_fir_launch_shape(acg_ctx* ctx, int nblocks, acg_lab_launch_shape* out)
 {

@@ -187,6 +187,12 @@ class Decoder:
         self._chk(self.L.acg_lab_fir_launch_shape(self.ctx, int(nblocks), C.byref(s)))
         return s
 
+    def set_stream_counters(self, nsamp_total, nbit_total, ch0=0, n=None):
+        """Test hook (acg_lab_set_stream_counters): right after reset, channels ch0 .. ch0+n-1 (default: all from ch0) count their
+        samples and bits from these values on, as after days of uptime."""
+        n = self.nch - ch0 if n is None else n
+        self._chk(self.L.acg_lab_set_stream_counters(self.ctx, int(ch0), int(n), int(nsamp_total), int(nbit_total)))
+
     def demod_msk(self, dm):
         """demodMSK() for all channels from 12.5 kHz samples: dm float32 [nch, len]."""
         dm = np.ascontiguousarray(dm, dtype=np.float32)

@@ -2,7 +2,8 @@
  * acarsdec_amd_lab.h -- measurement and diagnostic entry points of libacarsdec_amd.so.  NOT product API: nothing here has a
  * counterpart in the reference, and a host that decodes ACARS needs none of it.  bench.py, the GPU tests and the probes under
  * profiles/probe/ use it: tuning switches for same-process A/B, timing trials, bandwidth probes, self tests of the device
- * arithmetic, device-side generators of synthetic input, and the test hook that moves the block counters next to their wrap.
+ * arithmetic, device-side generators of synthetic input, and the test hooks that move the block counters next to their wrap and the
+ * stream counters to where days of uptime put them.
  * Everything is exported by the product library as well (bench.py times the product), except where noted.
  */
 #ifndef ACARSDEC_AMD_LAB_H
@@ -100,6 +101,11 @@ int  acg_lab_json_level_guard(acg_ctx *ctx, unsigned int *near_midpoint);
 int  acg_lab_set_block_counter(acg_ctx *ctx, unsigned int value);
 /* length of the block ring (a power of two) */
 unsigned int acg_lab_block_ring_size(const acg_ctx *ctx);
+/* Test hook (the stream counters after days of uptime: 2^31 samples at 12.5 kHz are 47.7 hours): right after acg_reset, sets the
+ * 64-bit sample and bit counters of channels ch0 .. ch0+n-1 to the given values, and their 32-bit SOH stamp to the low word of
+ * nsamp_total, as if that much signal had been demodulated already.  Nothing else changes.  ACG_EINVAL for a channel range
+ * outside the context or a negative value; ACG_ESTATE if calls have been issued since the reset. */
+int  acg_lab_set_stream_counters(acg_ctx *ctx, int ch0, int n, long long nsamp_total, long long nbit_total);
 
 /* diagnostics: the down-converter launch the library makes for ONE launch of `nblocks` callbacks of u8 I/Q on this context, as the
  * launcher itself decides it (the same function sizes the launch): which kernel, how the input is cut into dispensed runs, the

@@ -108,6 +108,13 @@ class Channel:
         self.c.frames_cap = max_frames
         lib().orc_chan_init(C.byref(self.c), chn)
 
+    def preset(self, nsamp_total, nbit_total):
+        """Before the first demod(): count samples and bits from these values on, as after days of uptime (the library's
+        acg_lab_set_stream_counters).  The counters are 64-bit throughout; the blocks of a run from 0 come out shifted."""
+        assert self.c.nsamp_total == 0 and self.c.nbit_total == 0 and nsamp_total >= 0 and nbit_total >= 0
+        self.c.nsamp_total = self.c.cur_sample = self.c.soh_sample = int(nsamp_total)
+        self.c.nbit_total = int(nbit_total)
+
     def demod(self, dm):
         dm = np.ascontiguousarray(dm, dtype=np.float32)
         lib().orc_demod_msk(C.byref(self.c), dm.ctypes.data, int(dm.size))

@@ -126,6 +126,7 @@ int main(void)
 		CHECK(acg_get_state_n(NULL, 0, 1, &st) == ACG_EINVAL && acg_set_state_n(NULL, 0, 1, &st) == ACG_EINVAL);
 		CHECK(acg_read_dm_n(NULL, 0, 1, buf, 4, 4) == ACG_EINVAL);
 		CHECK(acg_lab_set_block_counter(NULL, 1u) == ACG_EINVAL && acg_lab_block_ring_size(NULL) == 0u);
+		CHECK(acg_lab_set_stream_counters(NULL, 0, 1, 1ll << 32, 1ll << 32) == ACG_EINVAL);
 		{
 			acg_lab_launch_shape shape;
 			CHECK(acg_lab_fir_launch_shape(NULL, 1, &shape) == ACG_EINVAL);
