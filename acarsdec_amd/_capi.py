@@ -80,6 +80,16 @@ class Route(C.Structure):
 JSON_LINE_MAX = 2496
 
 
+TEXT_REC_MAX = 704
+TEXT_ONELINE, TEXT_STD, TEXT_PP, TEXT_SV = 1, 2, 3, 4
+TEXT_F_DATE, TEXT_F_FREQ = 1, 2
+
+
+class TextConfig(C.Structure):
+    """acg_text_config: the format (printoneline / printmsg / Netoutpp / Netoutsv), its flags, t0 of the sample clock, the station id"""
+    _fields_ = [("format", C.c_int), ("flags", C.c_uint), ("t0_sec", C.c_longlong), ("t0_usec", C.c_int), ("station_id", C.c_char * 33)]
+
+
 class JsonConfig(C.Structure):
     """acg_json_config: t0 of the sample clock, the station id (-i) and the "app" object of every JSON line"""
     _fields_ = [("t0_sec", C.c_longlong), ("t0_usec", C.c_int), ("station_id", C.c_char * 33), ("app_name", C.c_char * 17),
@@ -141,6 +151,9 @@ SYMBOLS = {
     "acg_json_enable": (C.c_int, [C.c_void_p, C.POINTER(JsonConfig), C.c_void_p]),
     "acg_drain_json": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "acg_collect_json": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "acg_text_enable": (C.c_int, [C.c_void_p, C.POINTER(TextConfig), C.c_void_p]),
+    "acg_drain_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "acg_collect_text": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "acg_read_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "acg_read_bits_all": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acg_bit_capacity": (C.c_int, [C.c_void_p]),
@@ -180,6 +193,11 @@ LAB_SYMBOLS = {
     "acg_selftest_msg_json": (C.c_int, [C.POINTER(Msg), C.c_int, C.POINTER(MsgFilter), C.POINTER(JsonConfig), C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "acg_lab_json_level_guard": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint)]),
+    "acg_selftest_msg_text": (C.c_int, [C.POINTER(Msg), C.c_int, C.POINTER(MsgFilter), C.POINTER(TextConfig), C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_int)]),
+    "acg_lab_text_level_guard": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint)]),
+    "acg_lab_time_sink_passes": (C.c_int, [C.POINTER(Msg), C.c_int, C.POINTER(JsonConfig), C.POINTER(TextConfig), C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p]),
     "acg_lab_set_block_counter": (C.c_int, [C.c_void_p, C.c_uint]),
     "acg_lab_block_ring_size": (C.c_uint, [C.c_void_p]),
     "acg_lab_set_stream_counters": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong]),

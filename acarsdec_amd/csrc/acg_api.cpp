@@ -217,6 +217,7 @@ struct acg_ctx {
     unsigned int* d_kwork = nullptr;        // [kmsgs_cap / 256 + 1] per-workgroup counts, then the total
     size_t kmsgs_cap = 0;
     AcgFlights* flights = nullptr;          // acg_flights_enable: the flight table (flights.cpp), updated by every message entry point
+    struct AcgTextState* text = nullptr;    // acg_text_enable: the text sink (text.hip), as json
     struct AcgJsonState* json = nullptr;    // acg_json_enable: the JSON sink (json.hip): configuration, work space, rendered lines
     unsigned int* d_work = nullptr;     // FIR run dispensers, ACG_DISP_WORDS words per chunk slot
     bool stream_identity = true;        // channel c reads stream c
@@ -293,6 +294,7 @@ extern "C" int acg_device_count(void)
 }
 
 static void json_destroy(struct AcgJsonState* st);
+static void text_destroy(struct AcgTextState* st);
 static void free_all(acg_ctx* c)
 {
     if (!c) return;
@@ -305,6 +307,8 @@ static void free_all(acg_ctx* c)
     c->flights = nullptr;
     json_destroy(c->json);
     c->json = nullptr;
+    text_destroy(c->text);
+    c->text = nullptr;
     hipFree(c->d_bits); hipFree(c->d_nbits); hipFree(c->d_stage[0]); hipFree(c->d_stage[1]); hipFree(c->d_work); hipFree(c->d_msk_done); std::free(c->h_stage); hipFree(c->d_crctab); hipFree(c->d_rep_upto);
     for (auto& p : c->fir_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& p : c->msk_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
@@ -1677,17 +1681,21 @@ extern "C" int acg_selftest_flights(const acg_msg* in, const int* batch, int nba
 
 // ---- the JSON sink (json.hip): buildjson()'s lines rendered on the device ---------------------------------------------------
 static_assert(ACG_JS_LINE_MAX == ACG_JSON_LINE_MAX, "line bound");
-struct AcgJsonState {
-    AcgJsonDev* d_cfg = nullptr;            // the constant stretches of a line, escaped by acg_json_enable
-    unsigned char* d_freq = nullptr;        // [nch][8] "%3.3f" tokens
-    unsigned int* d_cnt = nullptr;          // [4]: bytes, lines of the last pass; the level guard
+// the work space of a device renderer (json.hip, text.hip): sort keys, lengths, offsets and the rendered bytes
+struct AcgSinkWork {
     size_t cap = 0;                         // records the work space below holds
     unsigned long long *d_key = nullptr, *d_key_s = nullptr;
     unsigned int *d_idx = nullptr, *d_idx_s = nullptr, *d_len = nullptr, *d_off = nullptr, *d_wg = nullptr;
-    unsigned char* d_out = nullptr;         // cap * ACG_JSON_LINE_MAX bytes
+    unsigned char* d_out = nullptr;         // cap * (the longest record) bytes
 };
 
-static void json_free_work(AcgJsonState* st)
+struct AcgJsonState : AcgSinkWork {
+    AcgJsonDev* d_cfg = nullptr;            // the constant stretches of a line, escaped by acg_json_enable
+    unsigned char* d_freq = nullptr;        // [nch][8] "%3.3f" tokens
+    unsigned int* d_cnt = nullptr;          // [4]: bytes, lines of the last pass; the level guard
+};
+
+static void sink_free_work(AcgSinkWork* st)
 {
     hipFree(st->d_key); hipFree(st->d_key_s); hipFree(st->d_idx); hipFree(st->d_idx_s); hipFree(st->d_len); hipFree(st->d_off);
     hipFree(st->d_wg); hipFree(st->d_out);
@@ -1700,7 +1708,7 @@ static void json_free_work(AcgJsonState* st)
 static void json_destroy(AcgJsonState* st)
 {
     if (!st) return;
-    json_free_work(st);
+    sink_free_work(st);
     hipFree(st->d_cfg); hipFree(st->d_freq); hipFree(st->d_cnt);
     delete st;
 }
@@ -1778,17 +1786,17 @@ static int json_create(AcgJsonState** out, const acg_json_config* cfg, const int
     return ACG_OK;
 }
 
-// work space and line buffer for n records, grown on demand as d_kmsgs is
-static int json_reserve(AcgJsonState* st, size_t n)
+// work space and output buffer for n records of at most rec_max bytes, grown on demand as d_kmsgs is
+static int sink_reserve(AcgSinkWork* st, size_t n, size_t rec_max)
 {
     if (n <= st->cap) return ACG_OK;
-    json_free_work(st);
+    sink_free_work(st);
     const size_t want = std::max<size_t>(n, 4096);
     if (hipMalloc(&st->d_key, want * 8) != hipSuccess || hipMalloc(&st->d_key_s, want * 8) != hipSuccess ||
         hipMalloc(&st->d_idx, want * 4) != hipSuccess || hipMalloc(&st->d_idx_s, want * 4) != hipSuccess ||
         hipMalloc(&st->d_len, want * 4) != hipSuccess || hipMalloc(&st->d_off, want * 4) != hipSuccess ||
-        hipMalloc(&st->d_wg, 2 * (want / 256 + 1) * 4) != hipSuccess || hipMalloc(&st->d_out, want * (size_t)ACG_JSON_LINE_MAX) != hipSuccess) {
-        json_free_work(st);
+        hipMalloc(&st->d_wg, 2 * (want / 256 + 1) * 4) != hipSuccess || hipMalloc(&st->d_out, want * rec_max) != hipSuccess) {
+        sink_free_work(st);
         return ACG_ENOMEM;
     }
     st->cap = want;
@@ -1837,31 +1845,57 @@ extern "C" int acg_json_enable(acg_ctx* ctx, const acg_json_config* cfg, const i
     return rc == ACG_OK ? rc : fail(ctx, rc, "JSON sink: allocation failed");
 }
 
+// What fetch_json and fetch_text share with fetch_msgs' labelled path: the claim of the oldest blocks, the staging, the flight
+// table's preparation, and the split + label pass issued on the copy stream.  The renderer's passes hang on that stream next.
+struct SinkClaim {
+    int rc = ACG_OK;                        // what the entry point returns when there is nothing to render
+    int ring_rc = ACG_OK;                   // ring_claim's verdict, for ring_result
+    unsigned int pending = 0, take = 0;
+    unsigned int* d_total = nullptr;        // the label pass's count of kept records (a device word)
+};
+
+// work: the renderer's work space, grown here for the claimed blocks.  true: an error (k->rc says which).  false with k->take == 0: nothing to do, k->rc is the entry point's result.
+static bool sink_claim_and_label(acg_ctx* ctx, int lag, int max_take, AcgSinkWork* work, size_t rec_max, SinkClaim* k)
+{
+    unsigned int upto = 0;
+    bool any = false;
+    k->rc = ring_upto(ctx, lag, &upto, &any);
+    if (k->rc != ACG_OK) return true;
+    if (!any) return false;
+    k->ring_rc = ring_claim(ctx, upto, max_take, &k->pending, &k->take);
+    if (!k->take) {
+        k->rc = ring_result(ctx, k->ring_rc, k->pending, k->take, "more messages queued than fit: call again");
+        return false;
+    }
+    if ((k->rc = grow_msg_stage(ctx, k->take)) != ACG_OK) return true;
+    if ((k->rc = grow_label_stage(ctx, k->take)) != ACG_OK) return true;
+    if (sink_reserve(work, k->take, rec_max) != ACG_OK) { k->rc = fail(ctx, ACG_ENOMEM, "sink: work space"); return true; }
+    k->d_total = ctx->d_kwork + ctx->kmsgs_cap / 256 + 1;
+    AcgLabelPass pass{&ctx->msg_filter, ctx->d_kwork, ctx->d_kmsgs, ctx->d_oooi, k->d_total, nullptr, nullptr};
+    if (ctx->flights) {                                           // over exactly the blocks this call consumes, before -e drops any
+        const int fr = acg_fl_prepare(ctx->flights, k->take, ctx->copy_stream, &pass.flights);
+        if (fr != ACG_OK) { k->rc = fail(ctx, fr, "flight table: work space"); return true; }
+    }
+    if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, k->take, ctx->d_msgs, ctx->copy_stream, &pass) != 0) {
+        k->rc = fail(ctx, ACG_EHIP, "message split launch failed");
+        return true;
+    }
+    return false;
+}
+
 // fetch_msgs' sibling: the same claim, split, label pass and flight pass; then json.hip's passes on the same stream, and only
 // the packed lines and two counters cross to the host
 static int fetch_json(acg_ctx* ctx, int lag, char* out, size_t cap, size_t* nbytes, int* nlines)
 {
     if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
     if (!ctx->json) return fail(ctx, ACG_ESTATE, "JSON sink is off: acg_json_enable first");
-    unsigned int upto = 0, pending = 0, take = 0;
-    bool any = false;
-    int rc = ring_upto(ctx, lag, &upto, &any);
-    if (rc != ACG_OK || !any) return rc;
     // a block yields at most one line of at most ACG_JSON_LINE_MAX bytes: the oldest cap / ACG_JSON_LINE_MAX blocks always fit
-    rc = ring_claim(ctx, upto, (int)std::min<size_t>(cap / ACG_JSON_LINE_MAX, JSON_MAX_TAKE), &pending, &take);
-    if (!take) return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
-    if (const int gr = grow_msg_stage(ctx, take)) return gr;
-    if (const int gr = grow_label_stage(ctx, take)) return gr;
+    SinkClaim k;
+    if (sink_claim_and_label(ctx, lag, (int)std::min<size_t>(cap / ACG_JSON_LINE_MAX, JSON_MAX_TAKE), ctx->json, ACG_JSON_LINE_MAX, &k) || !k.take) return k.rc;
+    const unsigned int pending = k.pending, take = k.take;
+    const int rc = k.ring_rc;
+    unsigned int* d_total = k.d_total;
     AcgJsonState* js = ctx->json;
-    if (json_reserve(js, take) != ACG_OK) return fail(ctx, ACG_ENOMEM, "JSON sink: work space");
-    unsigned int* d_total = ctx->d_kwork + ctx->kmsgs_cap / 256 + 1;
-    AcgLabelPass pass{&ctx->msg_filter, ctx->d_kwork, ctx->d_kmsgs, ctx->d_oooi, d_total, nullptr, nullptr};
-    if (ctx->flights) {                                           // over exactly the blocks this call consumes, before -e drops any
-        const int fr = acg_fl_prepare(ctx->flights, take, ctx->copy_stream, &pass.flights);
-        if (fr != ACG_OK) return fail(ctx, fr, "flight table: work space");
-    }
-    if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, take, ctx->d_msgs, ctx->copy_stream, &pass) != 0)
-        return fail(ctx, ACG_EHIP, "message split launch failed");
     const AcgJsonPass jp = json_pass(js, ctx->d_kmsgs, ctx->d_oooi, d_total, take, false);
     if (acg_launch_json(&jp, ctx->copy_stream) != 0) return fail(ctx, ACG_EHIP, "JSON pass launch failed");
     unsigned int cnt[2] = {0, 0};
@@ -1931,7 +1965,7 @@ extern "C" int acg_selftest_msg_json(const acg_msg* in, int n, const acg_msg_fil
     AcgJsonState* st = nullptr;
     int rc = json_create(&st, cfg, Fr_hz, nch);
     if (rc != ACG_OK) return rc;
-    rc = json_reserve(st, (size_t)n);
+    rc = sink_reserve(st, (size_t)n, ACG_JSON_LINE_MAX);
     const size_t by = (size_t)n * sizeof(AcgMsgRec), nwg = (size_t)n / 256 + 1;
     AcgMsgRec *d_in = nullptr, *d_out = nullptr;
     acg_oooi* d_oooi = nullptr;
@@ -1958,6 +1992,291 @@ extern "C" int acg_selftest_msg_json(const acg_msg* in, int n, const acg_msg_fil
     hipDeviceSynchronize();
     hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
     json_destroy(st);
+    return rc;
+}
+
+// ---- the text sink (text.hip): printoneline(), printmsg(), Netoutpp(), Netoutsv() rendered on the device ---------------------
+static_assert(ACG_TX_REC_MAX == ACG_TEXT_REC_MAX, "record bound");
+struct AcgTextState : AcgSinkWork {
+    AcgTextDev* d_cfg = nullptr;
+    unsigned char* d_freq = nullptr;        // [nch][ACG_TX_FREQ_SLOT] "F:%3.3f " tokens
+    unsigned int* d_cnt = nullptr;          // [4]: bytes, records of the last pass; the level guard
+};
+
+static void text_destroy(AcgTextState* st)
+{
+    if (!st) return;
+    sink_free_work(st);
+    hipFree(st->d_cfg); hipFree(st->d_freq); hipFree(st->d_cnt);
+    delete st;
+}
+
+static bool text_config_ok(const acg_text_config* c)
+{
+    if (!c || c->format < ACG_TEXT_ONELINE || c->format > ACG_TEXT_SV) return false;
+    const unsigned int takes = c->format == ACG_TEXT_ONELINE ? ACG_TEXT_F_DATE : c->format == ACG_TEXT_STD ? (ACG_TEXT_F_DATE | ACG_TEXT_F_FREQ) : 0u;
+    return !(c->flags & ~takes) && c->t0_sec >= 1000000000ll && c->t0_sec < 4000000000ll && c->t0_usec >= 0 && c->t0_usec <= 999999 &&
+           std::memchr(c->station_id, 0, sizeof(c->station_id));
+}
+
+// ACG_OK, ACG_ENOMEM or ACG_EHIP; cfg has passed text_config_ok
+static int text_create(AcgTextState** out, const acg_text_config* cfg, const int* Fr_hz, int nch)
+{
+    AcgTextDev h;
+    std::memset(&h, 0, sizeof(h));
+    h.t0_sec = cfg->t0_sec;
+    h.t0_usec = cfg->t0_usec;
+    h.nch = nch;
+    h.format = cfg->format;
+    h.flags = cfg->flags;
+    char st8[40];
+    h.station_len = (unsigned int)std::snprintf(st8, sizeof(st8), "%8s", cfg->station_id);      // netout.c:131
+    if (h.station_len > sizeof(h.station)) return ACG_EINVAL;                                    // (cannot happen: 32 characters)
+    std::memcpy(h.station, st8, h.station_len);
+    std::vector<unsigned char> freq((size_t)nch * ACG_TX_FREQ_SLOT, 0);
+    for (int c = 0; c < nch; ++c) {
+        char tmp[32];
+        const int n = std::snprintf(tmp, sizeof(tmp), "F:%3.3f ", (Fr_hz ? Fr_hz[c] : 0) / 1000000.0);   // output.c:168-169: a double
+        if (n < 0 || n >= ACG_TX_FREQ_SLOT) return ACG_EINVAL;                                   // (cannot happen: an int's 12 characters)
+        std::memcpy(&freq[(size_t)c * ACG_TX_FREQ_SLOT], tmp, (size_t)n);
+        freq[(size_t)c * ACG_TX_FREQ_SLOT + ACG_TX_FREQ_SLOT - 1] = (unsigned char)n;
+    }
+    AcgTextState* st = new (std::nothrow) AcgTextState();
+    if (!st) return ACG_ENOMEM;
+    if (hipMalloc(&st->d_cfg, sizeof(h)) != hipSuccess || hipMalloc(&st->d_freq, freq.size()) != hipSuccess ||
+        hipMalloc(&st->d_cnt, 4 * sizeof(unsigned int)) != hipSuccess) {
+        text_destroy(st);
+        return ACG_ENOMEM;
+    }
+    if (hipMemcpy(st->d_cfg, &h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(st->d_freq, freq.data(), freq.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(st->d_cnt, 0, 4 * sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        text_destroy(st);
+        return ACG_EHIP;
+    }
+    *out = st;
+    return ACG_OK;
+}
+
+// the most records one pass takes: their offsets are 32-bit
+static constexpr unsigned int TEXT_MAX_TAKE = (1u << 31) / ACG_TEXT_REC_MAX;
+
+static AcgTextPass text_pass(const AcgTextState* st, const AcgMsgRec* recs, const void* oooi, const unsigned int* total, unsigned int nmax, bool lvl_from_rec)
+{
+    AcgTextPass p;
+    std::memset(&p, 0, sizeof(p));
+    p.recs = recs;
+    p.oooi = (const unsigned char*)oooi;
+    p.total = total;
+    p.nmax = nmax;
+    p.cfg = st->d_cfg;
+    p.freq = st->d_freq;
+    p.lvl_from_rec = lvl_from_rec ? 1 : 0;
+    p.key = st->d_key; p.key_s = st->d_key_s;
+    p.idx = st->d_idx; p.idx_s = st->d_idx_s;
+    p.len = st->d_len; p.off = st->d_off;
+    p.wg_sum = st->d_wg; p.wg_cnt = st->d_wg + (st->cap / 256 + 1);
+    p.counters = st->d_cnt;
+    p.out = st->d_out;
+    p.out_cap = (unsigned int)std::min<size_t>(st->cap * (size_t)ACG_TEXT_REC_MAX, 0xffffffffu);
+    return p;
+}
+
+extern "C" int acg_text_enable(acg_ctx* ctx, const acg_text_config* cfg, const int* Fr_hz)
+{
+    if (!ctx) return ACG_EINVAL;
+    if (cfg && !text_config_ok(cfg))
+        return fail(ctx, ACG_EINVAL, "text sink: unknown format, a flag the format does not take, t0 outside [10^9, 4 * 10^9) s / 0..999999 us, or an unterminated station_id");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    if (ctx->text) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+        text_destroy(ctx->text);
+        ctx->text = nullptr;
+    }
+    if (!cfg) return ACG_OK;
+    if (!acg_launch_text) return fail(ctx, ACG_ESTATE, "text sink: not in this build");
+    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "text sink: context created without ACG_F_REPAIR");
+    if (ctx->cfg.nch > (1 << 20)) return fail(ctx, ACG_EINVAL, "text sink: more than 2^20 channels");
+    const int rc = text_create(&ctx->text, cfg, Fr_hz, ctx->cfg.nch);
+    return rc == ACG_OK ? rc : fail(ctx, rc, "text sink: allocation failed");
+}
+
+// fetch_json's sibling: text.hip's passes behind the shared claim / split / label / flight part; the packed records, their
+// offsets and two counters cross to the host
+static int fetch_text(acg_ctx* ctx, int lag, char* out, size_t cap, size_t* nbytes, unsigned int* offs, int max_recs, int* nrecs)
+{
+    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
+    if (!ctx->text) return fail(ctx, ACG_ESTATE, "text sink is off: acg_text_enable first");
+    // a block yields at most one record of at most ACG_TEXT_REC_MAX bytes: the oldest min(max_recs, cap / ACG_TEXT_REC_MAX) always fit
+    const size_t fit = std::min<size_t>(std::min<size_t>(cap / ACG_TEXT_REC_MAX, (size_t)max_recs), TEXT_MAX_TAKE);
+    SinkClaim k;
+    if (sink_claim_and_label(ctx, lag, (int)fit, ctx->text, ACG_TEXT_REC_MAX, &k) || !k.take) return k.rc;
+    AcgTextState* ts = ctx->text;
+    const AcgTextPass tp = text_pass(ts, ctx->d_kmsgs, ctx->d_oooi, k.d_total, k.take, false);
+    if (acg_launch_text(&tp, ctx->copy_stream) != 0) return fail(ctx, ACG_EHIP, "text pass launch failed");
+    unsigned int cnt[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(cnt, ts->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->copy_stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    if (cnt[0] > cap || cnt[1] > k.take || (size_t)cnt[0] > (size_t)k.take * ACG_TEXT_REC_MAX) return fail(ctx, ACG_EHIP, "text pass: counts out of range");
+    if (cnt[1]) {                                                 // (kept records sort in front of dropped ones: the first cnt[1] offsets)
+        HIPCHK(ctx, hipMemcpyAsync(out, ts->d_out, cnt[0], hipMemcpyDeviceToHost, ctx->copy_stream));
+        HIPCHK(ctx, hipMemcpyAsync(offs, ts->d_off, (size_t)cnt[1] * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->copy_stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    }
+    offs[cnt[1]] = cnt[0];
+    ctx->consumed += k.take;
+    *nbytes = cnt[0];
+    *nrecs = (int)cnt[1];
+    return ring_result(ctx, k.ring_rc, k.pending, k.take, "more messages queued than fit: call again");
+}
+
+static int text_args(acg_ctx* ctx, char* out, size_t cap, size_t* nbytes, unsigned int* offs, int max_recs, int* nrecs)
+{
+    if (!ctx || !out || !nbytes || !offs || !nrecs) return ACG_EINVAL;
+    *nbytes = 0;
+    *nrecs = 0;
+    offs[0] = 0;
+    if (cap < ACG_TEXT_REC_MAX || max_recs < 1) return fail(ctx, ACG_EINVAL, "text sink: the buffer holds less than one record (ACG_TEXT_REC_MAX), or max_recs < 1");
+    return ACG_OK;
+}
+
+extern "C" int acg_collect_text(acg_ctx* ctx, int lag, char* out, size_t cap, size_t* nbytes, unsigned int* offs, int max_recs, int* nrecs)
+{
+    if (lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
+    if (const int rc = text_args(ctx, out, cap, nbytes, offs, max_recs, nrecs)) return rc;
+    return fetch_text(ctx, lag, out, cap, nbytes, offs, max_recs, nrecs);
+}
+
+extern "C" int acg_drain_text(acg_ctx* ctx, char* out, size_t cap, size_t* nbytes, unsigned int* offs, int max_recs, int* nrecs)
+{
+    if (const int rc = text_args(ctx, out, cap, nbytes, offs, max_recs, nrecs)) return rc;
+    return fetch_text(ctx, DRAIN, out, cap, nbytes, offs, max_recs, nrecs);
+}
+
+extern "C" int acg_lab_text_level_guard(acg_ctx* ctx, unsigned int* near_midpoint)
+{
+    if (!ctx || !near_midpoint) return ACG_EINVAL;
+    *near_midpoint = 0;
+    if (!ctx->text) return fail(ctx, ACG_ESTATE, "text sink is off");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    HIPCHK(ctx, hipMemcpy(near_midpoint, ctx->text->d_cnt + 2, sizeof(unsigned int), hipMemcpyDeviceToHost));
+    return ACG_OK;
+}
+
+extern "C" int acg_selftest_msg_text(const acg_msg* in, int n, const acg_msg_filter* f, const acg_text_config* cfg, const int* Fr_hz, int nch,
+                                     char* out, size_t cap, size_t* nbytes, unsigned int* offs, int* nrecs)
+{
+    if (n < 0 || (n > 0 && !in) || !text_config_ok(cfg) || nch < 1 || nch > (1 << 20) || !nbytes || !nrecs || !offs || (cap > 0 && !out) ||
+        (unsigned int)n > TEXT_MAX_TAKE)
+        return ACG_EINVAL;
+    AcgLabelFilter d;
+    if (label_filter_dev(f, &d) != ACG_OK) return ACG_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (in[i].chn < 0 || in[i].chn >= nch || in[i].end_bit < 0 || in[i].end_bit >= (1ll << 44)) return ACG_EINVAL;
+    *nbytes = 0;
+    *nrecs = 0;
+    if (n == 0) { offs[0] = 0; return ACG_OK; }
+    int ndev = 0;
+    if (!acg_launch_text || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
+    std::vector<AcgMsgRec> h((size_t)n);
+    for (int i = 0; i < n; ++i) {                                  // the public record back into the device's form
+        std::memcpy(&h[i], &in[i], sizeof(AcgMsgRec));
+        h[i].valid = in[i].reserved2 ? 0 : 1;
+        h[i].soh_back = (int)(in[i].end_sample - in[i].soh_sample);
+    }
+    AcgTextState* st = nullptr;
+    int rc = text_create(&st, cfg, Fr_hz, nch);
+    if (rc != ACG_OK) return rc;
+    rc = sink_reserve(st, (size_t)n, ACG_TEXT_REC_MAX);
+    const size_t by = (size_t)n * sizeof(AcgMsgRec), nwg = (size_t)n / 256 + 1;
+    AcgMsgRec *d_in = nullptr, *d_out = nullptr;
+    acg_oooi* d_oooi = nullptr;
+    unsigned int* d_work = nullptr;
+    if (rc == ACG_OK && (hipMalloc(&d_in, by) != hipSuccess || hipMalloc(&d_out, by) != hipSuccess ||
+                         hipMalloc(&d_oooi, (size_t)n * sizeof(acg_oooi)) != hipSuccess || hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) != hipSuccess))
+        rc = ACG_ENOMEM;
+    if (rc == ACG_OK) {
+        const AcgLabelPass pass{&d, d_work, d_out, d_oooi, d_work + nwg, nullptr, nullptr};
+        const AcgTextPass tp = text_pass(st, d_out, d_oooi, d_work + nwg, (unsigned int)n, true);
+        unsigned int cnt[2] = {0, 0};
+        if (hipMemcpy(d_in, h.data(), by, hipMemcpyHostToDevice) != hipSuccess ||
+            acg_launch_msg_split(nullptr, 0, 0, (unsigned int)n, d_in, nullptr, &pass) != 0 || acg_launch_text(&tp, nullptr) != 0 ||
+            hipMemcpy(cnt, st->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess || cnt[1] > (unsigned int)n ||
+            (size_t)cnt[0] > (size_t)n * ACG_TEXT_REC_MAX)
+            rc = ACG_EHIP;
+        if (rc == ACG_OK) {
+            *nbytes = cnt[0];
+            *nrecs = (int)cnt[1];
+            if (cnt[0] > cap) rc = ACG_EAGAIN;
+            else if ((cnt[0] && hipMemcpy(out, st->d_out, cnt[0], hipMemcpyDeviceToHost) != hipSuccess) ||
+                     (cnt[1] && hipMemcpy(offs, st->d_off, (size_t)cnt[1] * sizeof(unsigned int), hipMemcpyDeviceToHost) != hipSuccess))
+                rc = ACG_EHIP;
+            else offs[cnt[1]] = cnt[0];
+        }
+    }
+    hipDeviceSynchronize();
+    hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
+    text_destroy(st);
+    return rc;
+}
+
+extern "C" int acg_lab_time_sink_passes(const acg_msg* in, int n, const acg_json_config* jcfg, const acg_text_config* tcfg, int nch, int warmup,
+                                        int reps, float* ms)
+{
+    if (n < 1 || !in || !json_config_ok(jcfg) || !text_config_ok(tcfg) || nch < 1 || nch > (1 << 20) || warmup < 0 || reps < 1 || !ms ||
+        (unsigned int)n > std::min(JSON_MAX_TAKE, TEXT_MAX_TAKE))
+        return ACG_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (in[i].chn < 0 || in[i].chn >= nch || in[i].end_bit < 0 || in[i].end_bit >= (1ll << 44)) return ACG_EINVAL;
+    int ndev = 0;
+    if (!acg_launch_json || !acg_launch_text || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
+    std::vector<AcgMsgRec> h((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        std::memcpy(&h[i], &in[i], sizeof(AcgMsgRec));
+        h[i].valid = in[i].reserved2 ? 0 : 1;
+        h[i].soh_back = (int)(in[i].end_sample - in[i].soh_sample);
+    }
+    AcgJsonState* js = nullptr;
+    AcgTextState* ts = nullptr;
+    AcgLabelFilter none;
+    std::memset(&none, 0, sizeof(none));
+    const size_t by = (size_t)n * sizeof(AcgMsgRec), nwg = (size_t)n / 256 + 1;
+    AcgMsgRec *d_in = nullptr, *d_out = nullptr;
+    acg_oooi* d_oooi = nullptr;
+    unsigned int* d_work = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int rc = json_create(&js, jcfg, nullptr, nch);
+    if (rc == ACG_OK) rc = text_create(&ts, tcfg, nullptr, nch);
+    if (rc == ACG_OK) rc = sink_reserve(js, (size_t)n, ACG_JSON_LINE_MAX);
+    if (rc == ACG_OK) rc = sink_reserve(ts, (size_t)n, ACG_TEXT_REC_MAX);
+    if (rc == ACG_OK && (hipMalloc(&d_in, by) != hipSuccess || hipMalloc(&d_out, by) != hipSuccess ||
+                         hipMalloc(&d_oooi, (size_t)n * sizeof(acg_oooi)) != hipSuccess || hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) != hipSuccess))
+        rc = ACG_ENOMEM;
+    if (rc == ACG_OK && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)) rc = ACG_EHIP;
+    if (rc == ACG_OK) {
+        const AcgLabelPass pass{&none, d_work, d_out, d_oooi, d_work + nwg, nullptr, nullptr};
+        const AcgJsonPass jp = json_pass(js, d_out, d_oooi, d_work + nwg, (unsigned int)n, true);
+        const AcgTextPass tp = text_pass(ts, d_out, d_oooi, d_work + nwg, (unsigned int)n, true);
+        if (hipMemcpy(d_in, h.data(), by, hipMemcpyHostToDevice) != hipSuccess ||
+            acg_launch_msg_split(nullptr, 0, 0, (unsigned int)n, d_in, nullptr, &pass) != 0 || hipDeviceSynchronize() != hipSuccess)
+            rc = ACG_EHIP;
+        for (int r = -warmup; r < reps && rc == ACG_OK; ++r)
+            for (int arm = 0; arm < 2 && rc == ACG_OK; ++arm) {
+                float t = 0.0f;
+                if (hipEventRecord(ev[0], nullptr) != hipSuccess || (arm ? acg_launch_text(&tp, nullptr) : acg_launch_json(&jp, nullptr)) != 0 ||
+                    hipEventRecord(ev[1], nullptr) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess ||
+                    hipEventElapsedTime(&t, ev[0], ev[1]) != hipSuccess)
+                    rc = ACG_EHIP;
+                else if (r >= 0) ms[arm * reps + r] = t;
+            }
+    }
+    hipDeviceSynchronize();
+    if (ev[0]) hipEventDestroy(ev[0]);
+    if (ev[1]) hipEventDestroy(ev[1]);
+    hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
+    json_destroy(js);
+    text_destroy(ts);
     return rc;
 }
 

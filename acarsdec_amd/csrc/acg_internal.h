@@ -172,6 +172,39 @@ struct AcgJsonPass {
     unsigned int out_cap;
 };
 
+// ---- the text renderer (text.hip): printoneline() / printmsg() (output.c:162-224,327-346), Netoutpp() / Netoutsv() (netout.c:101-140)
+#define ACG_TX_REC_MAX 704      // == ACG_TEXT_REC_MAX of the public header (derived there)
+#define ACG_TX_FREQ_SLOT 16     // "F:%3.3f " of a channel: at most 12 characters ("F:-2147.484 "), their count in byte 15
+// What acg_text_enable renders once on the host
+struct AcgTextDev {
+    long long t0_sec;
+    int t0_usec;
+    int nch;                    // freq tokens
+    int format;                 // ACG_TEXT_*
+    unsigned int flags;         // ACG_TEXT_F_*
+    unsigned int station_len;   // SV: "%8s" of the station id, 8 .. 32 characters
+    unsigned int pad_;
+    unsigned char station[32];
+};
+
+// as AcgJsonPass; off[] is the offset table the entry points hand out
+struct AcgTextPass {
+    const AcgMsgRec* recs;
+    const unsigned char* oooi;
+    const unsigned int* total;
+    unsigned int nmax;
+    const AcgTextDev* cfg;
+    const unsigned char* freq;  // [cfg->nch][ACG_TX_FREQ_SLOT]
+    int lvl_from_rec;
+    unsigned long long *key, *key_s;
+    unsigned int *idx, *idx_s;
+    unsigned int *len, *off;
+    unsigned int *wg_sum, *wg_cnt;
+    unsigned int* counters;     // [0] bytes, [1] records of this pass; [2] level guard (accumulates); [3] unused
+    unsigned char* out;         // nmax * ACG_TX_REC_MAX bytes, 16-byte aligned
+    unsigned int out_cap;
+};
+
 struct FirArgs {
     const uint8_t* iq;          // [nstreams] rows
     size_t pitch;               // bytes between stream rows (multiple of 16)
@@ -301,6 +334,8 @@ int acg_launch_sort_pairs(unsigned long long* ka, unsigned int* va, unsigned lon
 // A WEAK reference, as flights.h's: the host runtime is also linked without the device units (the sanitizer build of
 // tests/test_host_logic.py, which stubs the launchers it knows); there the JSON sink is absent and acg_json_enable says ACG_ESTATE.
 __attribute__((weak)) int acg_launch_json(const AcgJsonPass* p, void* stream);
+// text.hip: the same for the text formats (weak for the same reason)
+__attribute__((weak)) int acg_launch_text(const AcgTextPass* p, void* stream);
 int acg_launch_sincos_selftest(const double* x, double* s, double* c, int n, const double* sctab, void* stream);
 int acg_launch_div2_selftest(const double* n0, const double* n1, const double* d, double* out, int n, void* stream);
 int acg_launch_synth_iq(uint8_t* iq, size_t pitch, int nrows, int nout, int decim, const float* env,

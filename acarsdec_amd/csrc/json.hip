@@ -18,42 +18,20 @@
 // j-th character of a token.  Measure and render run the SAME function (json_line<false / true>): the length a line was given
 // room for is the length it is rendered with.
 //
-// THE SEAM.  Lines are packed without padding, so two neighbouring lines share a 16-byte chunk where they meet, and another
-// wave writes the neighbour.  No chunk is ever read back and merged: the row holds the line at the same offset mod 16 as its
-// place in the output, a line's first bytes up to the next 16-byte boundary and its last bytes behind the last one leave as
-// BYTE stores, and only chunks that lie wholly inside the line leave as 16-byte stores (LDS 16-byte reads, both sides aligned).
+// THE SEAM, the scan, the record load and the level's float are shared with the text renderer (text.hip): sink_pack.h.
 //
 // No scratch (no indexed private array: a record's fields are read out of LDS, digits are computed, not stored), no per-byte
 // global traffic (a record comes in as 80 + 10 dword loads, the constant stretches as dwords, a line leaves as 16-byte stores and < 30 byte stores), two
 // independent waves per workgroup (2 x 2 944 B of LDS): these passes run beside a down-converter that saturates HBM.
-#include <hip/hip_runtime.h>
-#include "acg_internal.h"
-#include "acarsdec_amd.h"
+#include "sink_pack.h"
 #include "json_num.h"
 
 #define JS_WAVES 2
 #define JS_ROW (ACG_JS_LINE_MAX + 16)       // the line at offset (its output offset mod 16)
-#define JS_REC 384                          // the record (320 B) and its acg_oooi (40 B)
-#define JS_WG 256
+#define JS_REC PK_REC
+#define JS_WG PK_WG
 
 static_assert(ACG_JS_LINE_MAX == ACG_JSON_LINE_MAX && ACG_JS_LINE_MAX % 64 == 0, "line bound");
-static_assert(sizeof(AcgMsgRec) == 320 && sizeof(acg_oooi) == 40 && sizeof(AcgMsgRec) + sizeof(acg_oooi) <= JS_REC, "record layout");
-
-// a literal of at most 16 characters as two immediates: lane j takes byte j, nothing is loaded
-struct JsLit {
-    unsigned long long lo, hi;
-    unsigned int n;
-};
-
-constexpr JsLit js_lit(const char* s)
-{
-    JsLit l{0, 0, 0};
-    for (; s[l.n]; ++l.n) {
-        if (l.n < 8) l.lo |= (unsigned long long)(unsigned char)s[l.n] << (8 * l.n);
-        else l.hi |= (unsigned long long)(unsigned char)s[l.n] << (8 * (l.n - 8));
-    }
-    return l;
-}
 
 template <bool W>
 __device__ __forceinline__ void js_st(unsigned char* row, unsigned int p, unsigned char v)
@@ -62,12 +40,12 @@ __device__ __forceinline__ void js_st(unsigned char* row, unsigned int p, unsign
 }
 
 template <bool W>
-__device__ __forceinline__ unsigned int put_lit(unsigned char* row, unsigned int pos, const JsLit l, int lane)
+__device__ __forceinline__ unsigned int put_lit(unsigned char* row, unsigned int pos, const PkLit l, int lane)
 {
     if (W && (unsigned int)lane < l.n) js_st<W>(row, pos + lane, (unsigned char)((lane < 8 ? l.lo : l.hi) >> (8 * (lane & 7))));
     return pos + l.n;
 }
-#define PUT_LIT(s) do { constexpr JsLit l_ = js_lit(s); static_assert(sizeof(s) - 1 <= 16, "literal"); pos = put_lit<W>(row, pos, l_, lane); } while (0)
+#define PUT_LIT(s) do { constexpr PkLit l_ = pk_lit(s); static_assert(sizeof(s) - 1 <= 16, "literal"); pos = put_lit<W>(row, pos, l_, lane); } while (0)
 
 // n bytes that are already escaped (the station and app stretches), 4-byte aligned: a dword load per lane, not a load per byte
 template <bool W>
@@ -172,16 +150,7 @@ __device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsign
         PUT_LIT("0.000");
     }
     // ---- "level": the float of acars.c:351, then "%2.1f" cut to 7 characters (json_num.h)
-    float lvl = r->lvl;
-    *near_mid = false;
-    if (!p.lvl_from_rec) {
-        const double d = 10.0 * log10(r->lvlsum / (double)r->bitcount);
-        lvl = (float)d;
-        // the one inexact step: another log10 may land on the other side of a float rounding boundary when d lies next to one.
-        // A float midpoint is a double whose low 29 mantissa bits are 1 << 28 (normal floats).
-        const long long low = (long long)((unsigned long long)__double_as_longlong(d) & ((1ull << 29) - 1ull)) - (1ll << 28);
-        *near_mid = d == d && d - d == 0.0 && (low < 0 ? -low : low) <= 8;
-    }
+    const float lvl = pk_level(r, p.lvl_from_rec, near_mid);
     PUT_LIT(",\"level\":");
     pos = put_tok<W>(row, pos, jn_level(lvl), lane);
     PUT_LIT(",\"error\":");
@@ -240,26 +209,11 @@ __device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsign
     return pos;
 }
 
-// the record of sorted rank r and its acg_oooi into the wave's LDS: 80 + 10 dwords
-__device__ __forceinline__ void js_load(unsigned char* R, const AcgJsonPass& p, unsigned int idx, int lane)
-{
-    const unsigned int* src = (const unsigned int*)(p.recs + idx);
-    unsigned int* dst = (unsigned int*)R;
-    dst[lane] = src[lane];
-    if (lane < 16) dst[64 + lane] = src[64 + lane];
-    if (lane < 10) dst[80 + lane] = ((const unsigned int*)(p.oooi + (size_t)idx * sizeof(acg_oooi)))[lane];
-    // (LDS operations of one wave execute in order; the fence keeps the compiler from moving them across each other)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 __global__ __launch_bounds__(JS_WG) void json_keys_kernel(AcgJsonPass p)
 {
     const unsigned int i = blockIdx.x * JS_WG + threadIdx.x;
     if (i >= p.nmax || i >= *p.total) return;
-    const AcgMsgRec* r = p.recs + i;
-    // records the block repair dropped (none passes label.hip's filter) would sort last and render nothing
-    p.key[i] = r->valid ? (((unsigned long long)(unsigned int)r->chn & 0xfffffull) << 44) | ((unsigned long long)r->end_bit & ((1ull << 44) - 1ull)) : ~0ull;
+    p.key[i] = pk_key(p.recs + i);
     p.idx[i] = i;
 }
 
@@ -273,7 +227,7 @@ __global__ __launch_bounds__(64 * JS_WAVES) void json_measure_kernel(AcgJsonPass
         if (lane == 0) p.len[r] = 0;
         return;
     }
-    js_load(recs[wv], p, p.idx_s[r], lane);
+    pk_load(recs[wv], p.recs, p.oooi, p.idx_s[r], lane);
     bool nm;
     const unsigned int n = json_line<false>(recs[wv], nullptr, p, lane, &nm);
     if (lane == 0) p.len[r] = n > (unsigned int)ACG_JS_LINE_MAX ? (unsigned int)ACG_JS_LINE_MAX : n;
@@ -282,48 +236,14 @@ __global__ __launch_bounds__(64 * JS_WAVES) void json_measure_kernel(AcgJsonPass
 __global__ __launch_bounds__(JS_WG) void json_sum_kernel(AcgJsonPass p)
 {
     __shared__ unsigned int sum_s;
-    if (threadIdx.x == 0) sum_s = 0;
-    __syncthreads();
-    const unsigned int i = blockIdx.x * JS_WG + threadIdx.x;
-    const unsigned int v = (i < p.nmax && i < *p.total) ? p.len[i] : 0u;
-    if (v) atomicAdd(&sum_s, v);
-    const int c = __syncthreads_count(v != 0);
-    if (threadIdx.x == 0) {
-        p.wg_sum[blockIdx.x] = sum_s;
-        p.wg_cnt[blockIdx.x] = (unsigned int)c;
-    }
+    pk_sum(&sum_s, p.len, p.wg_sum, p.wg_cnt, p.nmax, p.total);
 }
 
 __global__ __launch_bounds__(JS_WG) void json_offsets_kernel(AcgJsonPass p)
 {
     __shared__ unsigned int base_s, cnt_s;
     __shared__ unsigned int wave_n[JS_WG / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) { base_s = 0; cnt_s = 0; }
-    __syncthreads();
-    unsigned int s = 0, c = 0;
-    for (unsigned int j = threadIdx.x; j < blockIdx.x; j += JS_WG) { s += p.wg_sum[j]; c += p.wg_cnt[j]; }
-    if (s) atomicAdd(&base_s, s);
-    if (c) atomicAdd(&cnt_s, c);
-    const unsigned int i = blockIdx.x * JS_WG + threadIdx.x;
-    const unsigned int v = (i < p.nmax && i < *p.total) ? p.len[i] : 0u;
-    unsigned int incl = v;                                                       // inclusive scan within the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned int o = (unsigned int)__shfl((int)incl, lane >= off ? lane - off : lane);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) wave_n[wv] = incl;
-    __syncthreads();
-    unsigned int before = base_s;
-    for (int w = 0; w < wv; ++w) before += wave_n[w];
-    if (i < p.nmax) p.off[i] = before + incl - v;
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        unsigned int t = base_s;
-        for (int w = 0; w < JS_WG / 64; ++w) t += wave_n[w];
-        p.counters[0] = t;
-        p.counters[1] = cnt_s + p.wg_cnt[blockIdx.x];
-    }
+    pk_offsets(&base_s, &cnt_s, wave_n, p.len, p.off, p.wg_sum, p.wg_cnt, p.counters, p.nmax, p.total);
 }
 
 __global__ __launch_bounds__(64 * JS_WAVES) void json_render_kernel(AcgJsonPass p)
@@ -335,7 +255,7 @@ __global__ __launch_bounds__(64 * JS_WAVES) void json_render_kernel(AcgJsonPass 
     if (r >= p.nmax || r >= *p.total) return;
     const unsigned int len = p.len[r], off = p.off[r];
     if (len == 0 || len > (unsigned int)ACG_JS_LINE_MAX || off > p.out_cap || len > p.out_cap - off) return;
-    js_load(recs[wv], p, p.idx_s[r], lane);
+    pk_load(recs[wv], p.recs, p.oooi, p.idx_s[r], lane);
     const unsigned int a = off & 15u;                                            // the row mirrors the output's alignment
     bool near_mid;
     const unsigned int n = json_line<true>(recs[wv], rows[wv] + a, p, lane, &near_mid);
@@ -343,16 +263,7 @@ __global__ __launch_bounds__(64 * JS_WAVES) void json_render_kernel(AcgJsonPass 
     if (near_mid && lane == 0) atomicAdd(&p.counters[2], 1u);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    // ---- out.  Row byte x <-> output byte (off - a) + x, the line is row[a, a + len); chunk c = row[16 c, 16 c + 16)
-    const unsigned char* row = rows[wv];
-    unsigned char* dst = p.out + (off - a);                                      // 16-byte aligned
-    const unsigned int end = a + len;
-    const unsigned int c0 = (a + 15u) >> 4, c1 = end >> 4;                       // whole chunks: [c0, c1)
-    const unsigned int head_end = c1 > c0 ? 16u * c0 : end;                      // no whole chunk: everything leaves as bytes
-    const unsigned int tail_beg = c1 > c0 ? 16u * c1 : end;
-    for (unsigned int x = a + lane; x < head_end; x += 64) dst[x] = row[x];      // (< 16 bytes, or < 31 when no chunk is whole)
-    for (unsigned int x = tail_beg + lane; x < end; x += 64) dst[x] = row[x];
-    for (unsigned int c = c0 + lane; c < c1; c += 64) ((uint4*)dst)[c] = ((const uint4*)row)[c];
+    pk_flush_row(rows[wv], p.out, off, len, lane);
 }
 
 extern "C" int acg_launch_json(const AcgJsonPass* p, void* stream)

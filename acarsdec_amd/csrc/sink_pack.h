@@ -1,0 +1,134 @@
+// sink_pack.h -- what the device renderers of the batch sink (json.hip, text.hip) have in common: a record and its acg_oooi into a
+// wave's LDS, the (chn, end_bit) sort key, the level's float and its guard, the two-launch exclusive scan of the record lengths
+// in sorted order, and the seam-safe flush of a wave's LDS row to its packed place in the output.  Device code only; every
+// function is inlined into the kernels of the unit that includes it, so each unit keeps kernels of its own.
+//
+// THE SEAM.  Records are packed without padding, so two neighbours share a 16-byte chunk where they meet, and another wave writes
+// the neighbour.  No chunk is ever read back and merged: the row holds the record at the same offset mod 16 as its place in the
+// output, the first bytes up to the next 16-byte boundary and the last bytes behind the last one leave as BYTE stores, and only
+// chunks that lie wholly inside the record leave as 16-byte stores (LDS 16-byte reads, both sides aligned).
+#pragma once
+#include <hip/hip_runtime.h>
+#include "acg_internal.h"
+#include "acarsdec_amd.h"
+
+#define PK_WG 256                           // threads of the keys / sum / offsets kernels
+#define PK_REC 384                          // the record (320 B) and its acg_oooi (40 B)
+
+static_assert(sizeof(AcgMsgRec) == 320 && sizeof(acg_oooi) == 40 && sizeof(AcgMsgRec) + sizeof(acg_oooi) <= PK_REC, "record layout");
+
+// a literal of at most 16 characters as two immediates: lane j takes byte j, nothing is loaded
+struct PkLit {
+    unsigned long long lo, hi;
+    unsigned int n;
+};
+
+constexpr PkLit pk_lit(const char* s)
+{
+    PkLit l{0, 0, 0};
+    for (; s[l.n]; ++l.n) {
+        if (l.n < 8) l.lo |= (unsigned long long)(unsigned char)s[l.n] << (8 * l.n);
+        else l.hi |= (unsigned long long)(unsigned char)s[l.n] << (8 * (l.n - 8));
+    }
+    return l;
+}
+
+// the record at recs[idx] and its acg_oooi into the wave's LDS: 80 + 10 dwords
+__device__ __forceinline__ void pk_load(unsigned char* R, const AcgMsgRec* recs, const unsigned char* oooi, unsigned int idx, int lane)
+{
+    const unsigned int* src = (const unsigned int*)(recs + idx);
+    unsigned int* dst = (unsigned int*)R;
+    dst[lane] = src[lane];
+    if (lane < 16) dst[64 + lane] = src[64 + lane];
+    if (lane < 10) dst[80 + lane] = ((const unsigned int*)(oooi + (size_t)idx * sizeof(acg_oooi)))[lane];
+    // (LDS operations of one wave execute in order; the fence keeps the compiler from moving them across each other)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// records the block repair dropped (none passes label.hip's filter) would sort last and render nothing
+__device__ __forceinline__ unsigned long long pk_key(const AcgMsgRec* r)
+{
+    return r->valid ? (((unsigned long long)(unsigned int)r->chn & 0xfffffull) << 44) | ((unsigned long long)r->end_bit & ((1ull << 44) - 1ull)) : ~0ull;
+}
+
+// the float of acars.c:351 (or the record's own, lab entries).  *near_mid: the one inexact step -- another log10 may land on the
+// other side of a float rounding boundary when the double lies next to one.  A float midpoint is a double whose low 29 mantissa
+// bits are 1 << 28 (normal floats).
+__device__ __forceinline__ float pk_level(const AcgMsgRec* r, int lvl_from_rec, bool* near_mid)
+{
+    float lvl = r->lvl;
+    *near_mid = false;
+    if (!lvl_from_rec) {
+        const double d = 10.0 * log10(r->lvlsum / (double)r->bitcount);
+        lvl = (float)d;
+        const long long low = (long long)((unsigned long long)__double_as_longlong(d) & ((1ull << 29) - 1ull)) - (1ll << 28);
+        *near_mid = d == d && d - d == 0.0 && (low < 0 ? -low : low) <= 8;
+    }
+    return lvl;
+}
+
+// ---- the exclusive scan of len[] in sorted order (label.hip's two-launch count / base scheme) --------------------------------
+// first launch: per PK_WG ranks, the bytes and the records that have any.  sum_s: one shared word of the workgroup.
+__device__ __forceinline__ void pk_sum(unsigned int* sum_s, const unsigned int* len, unsigned int* wg_sum, unsigned int* wg_cnt, unsigned int nmax,
+                                       const unsigned int* total)
+{
+    if (threadIdx.x == 0) *sum_s = 0;
+    __syncthreads();
+    const unsigned int i = blockIdx.x * PK_WG + threadIdx.x;
+    const unsigned int v = (i < nmax && i < *total) ? len[i] : 0u;
+    if (v) atomicAdd(sum_s, v);
+    const int c = __syncthreads_count(v != 0);
+    if (threadIdx.x == 0) {
+        wg_sum[blockIdx.x] = *sum_s;
+        wg_cnt[blockIdx.x] = (unsigned int)c;
+    }
+}
+
+// second launch: every rank's byte offset; counters[0] = the pass's bytes, counters[1] = its records.  base_s, cnt_s: a shared word
+// each; wave_n: PK_WG / 64 shared words.
+__device__ __forceinline__ void pk_offsets(unsigned int* base_s, unsigned int* cnt_s, unsigned int* wave_n, const unsigned int* len, unsigned int* off, const unsigned int* wg_sum,
+                                           const unsigned int* wg_cnt, unsigned int* counters, unsigned int nmax, const unsigned int* total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0) { *base_s = 0; *cnt_s = 0; }
+    __syncthreads();
+    unsigned int s = 0, c = 0;
+    for (unsigned int j = threadIdx.x; j < blockIdx.x; j += PK_WG) { s += wg_sum[j]; c += wg_cnt[j]; }
+    if (s) atomicAdd(base_s, s);
+    if (c) atomicAdd(cnt_s, c);
+    const unsigned int i = blockIdx.x * PK_WG + threadIdx.x;
+    const unsigned int v = (i < nmax && i < *total) ? len[i] : 0u;
+    unsigned int incl = v;                                                       // inclusive scan within the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned int t = (unsigned int)__shfl((int)incl, lane >= o ? lane - o : lane);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) wave_n[wv] = incl;
+    __syncthreads();
+    unsigned int before = *base_s;
+    for (int w = 0; w < wv; ++w) before += wave_n[w];
+    if (i < nmax) off[i] = before + incl - v;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        unsigned int t = *base_s;
+        for (int w = 0; w < PK_WG / 64; ++w) t += wave_n[w];
+        counters[0] = t;
+        counters[1] = *cnt_s + wg_cnt[blockIdx.x];
+    }
+}
+
+// ---- out.  The wave's row holds the record at row[a, a + len), a = off & 15; row byte x <-> output byte (off - a) + x;
+// chunk c = row[16 c, 16 c + 16).  The caller has fenced the row's LDS writes and checked off + len against the output.
+__device__ __forceinline__ void pk_flush_row(const unsigned char* row, unsigned char* out, unsigned int off, unsigned int len, int lane)
+{
+    const unsigned int a = off & 15u;
+    unsigned char* dst = out + (off - a);                                        // 16-byte aligned
+    const unsigned int end = a + len;
+    const unsigned int c0 = (a + 15u) >> 4, c1 = end >> 4;                       // whole chunks: [c0, c1)
+    const unsigned int head_end = c1 > c0 ? 16u * c0 : end;                      // no whole chunk: everything leaves as bytes
+    const unsigned int tail_beg = c1 > c0 ? 16u * c1 : end;
+    for (unsigned int x = a + lane; x < head_end; x += 64) dst[x] = row[x];      // (< 16 bytes, or < 31 when no chunk is whole)
+    for (unsigned int x = tail_beg + lane; x < end; x += 64) dst[x] = row[x];
+    for (unsigned int c = c0 + lane; c < c1; c += 64) ((uint4*)dst)[c] = ((const uint4*)row)[c];
+}

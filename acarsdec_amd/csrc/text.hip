@@ -1,0 +1,361 @@
+// text.hip -- the reference's per-message TEXT formats for the batch sink, over the records label.hip kept and compacted for one
+// drain / collect, beside json.hip:
+//   ACG_TEXT_ONELINE  printoneline()  output.c:327-346   what -o 1 prints
+//   ACG_TEXT_STD      printmsg()      output.c:162-224   what -o 2 (the default) prints, the build without libacars
+//   ACG_TEXT_PP       Netoutpp()      netout.c:101-120   the planeplotter datagram (-N)
+//   ACG_TEXT_SV       Netoutsv()      netout.c:122-140   the native datagram (-n)
+// What leaves is the records' bytes packed back to back in (chn, end_bit) order and the table of their offsets: a record may hold
+// any byte ("%1c" of a NUL mode, a '\n' inside a text), so there is nothing to split it by.
+//
+// The passes are json.hip's, on the stream of the label pass they hang on: text_keys_kernel + flight.hip's sort, text_measure_kernel
+// (one WAVE per record: its length), text_sum_kernel / text_offsets_kernel (the exclusive scan in sorted order = the offset table),
+// text_render_kernel (one wave per record: the record assembled in a per-wave LDS row, flushed seam-safe).  Scan, flush, record
+// load, sort key and the level's float are shared with json.hip (sink_pack.h).  Measure and render run the SAME function
+// (text_record<false / true>).
+//
+// "%Ns" is a ballot and a find-first (the C string's end) and max(0, N - len) spaces in front; the text is four rounds of 64 lanes,
+// byte i at place i; lane j computes character j of a number or of the date (json_num.h, text_num.h).  No lane walks anything, no
+// scratch (fields are read out of LDS, digits are computed), no per-byte global traffic (a record comes in as 80 + 10 dword
+// loads, the channel's "F:" token as two quadwords, the station as dwords; a record leaves as 16-byte stores and < 30 byte stores).
+#include "sink_pack.h"
+#include "text_num.h"
+
+#define TX_WAVES 2
+#define TX_ROW (ACG_TX_REC_MAX + 16)        // the record at offset (its output offset mod 16)
+
+static_assert(ACG_TX_REC_MAX == ACG_TEXT_REC_MAX && ACG_TX_REC_MAX % 64 == 0, "record bound");
+
+// characters [from, from + 16) of a literal
+constexpr PkLit tx_lit_part(const char* s, unsigned int from)
+{
+    unsigned int n = 0;
+    while (s[n]) ++n;
+    char part[17] = {};
+    for (unsigned int i = 0; i < 16 && from + i < n; ++i) part[i] = s[from + i];
+    return pk_lit(part);
+}
+
+template <bool W>
+__device__ __forceinline__ void tx_st(unsigned char* row, unsigned int p, unsigned char v)
+{
+    if (W && p < (unsigned int)ACG_TX_REC_MAX) row[p] = v;        // (the bound holds by construction; this keeps a bug inside the row)
+}
+
+template <bool W>
+__device__ __forceinline__ unsigned int tx_lit(unsigned char* row, unsigned int pos, const PkLit l, int lane)
+{
+    if (W && (unsigned int)lane < l.n) tx_st<W>(row, pos + lane, (unsigned char)((lane < 8 ? l.lo : l.hi) >> (8 * (lane & 7))));
+    return pos + l.n;
+}
+// a literal of at most 32 characters
+#define TX_LIT(s) do { static_assert(sizeof(s) - 1 <= 32, "literal"); constexpr PkLit a_ = tx_lit_part(s, 0); pos = tx_lit<W>(row, pos, a_, lane); \
+                       if (sizeof(s) - 1 > 16) { constexpr PkLit b_ = tx_lit_part(s, 16); pos = tx_lit<W>(row, pos, b_, lane); } } while (0)
+
+// one and two characters
+template <bool W>
+__device__ __forceinline__ unsigned int tx_ch(unsigned char* row, unsigned int pos, unsigned int c, int lane)
+{
+    if (W && lane == 0) tx_st<W>(row, pos, (unsigned char)c);
+    return pos + 1;
+}
+
+template <bool W>
+__device__ __forceinline__ unsigned int tx_ch2(unsigned char* row, unsigned int pos, unsigned int c0, unsigned int c1, int lane)
+{
+    if (W && lane < 2) tx_st<W>(row, pos + lane, (unsigned char)(lane ? c1 : c0));
+    return pos + 2;
+}
+
+template <bool W>
+__device__ __forceinline__ unsigned int tx_fill(unsigned char* row, unsigned int pos, unsigned char c, unsigned int n, int lane)
+{
+    if (W && (unsigned int)lane < n) tx_st<W>(row, pos + lane, c);
+    return pos + n;
+}
+
+template <bool W>
+__device__ __forceinline__ unsigned int tx_tok(unsigned char* row, unsigned int pos, const JnTok& t, int lane)
+{
+    if (W && lane < t.len) tx_st<W>(row, pos + lane, jn_char(t, lane));
+    return pos + (unsigned int)t.len;
+}
+
+// the first n characters of printdate()'s text
+template <bool W>
+__device__ __forceinline__ unsigned int tx_date(unsigned char* row, unsigned int pos, const TnDate& d, int n, int lane)
+{
+    if (W && lane < n) tx_st<W>(row, pos + lane, tn_date_char(d, lane));
+    return pos + (unsigned int)n;
+}
+
+template <bool W>
+__device__ __forceinline__ unsigned int tx_level(unsigned char* row, unsigned int pos, float lvl, int lane)
+{
+    const TnLevel l = tn_level(lvl);
+    if (W && lane < l.len) tx_st<W>(row, pos + lane, tn_level_char(l, lane));
+    return pos + (unsigned int)l.len;
+}
+
+// "%<width>s" of the C string at s (at most maxlen < 64 bytes): right-justified to at least width, never cut
+template <bool W>
+__device__ __forceinline__ unsigned int tx_str(unsigned char* row, unsigned int pos, const unsigned char* s, int maxlen, int width, int lane)
+{
+    const unsigned int b = lane < maxlen ? s[lane] : 0u;
+    const unsigned long long nul = __ballot(b == 0);              // (never 0: maxlen < 64)
+    const int n = __ffsll((unsigned long long)nul) - 1;
+    const int pad = width > n ? width - n : 0;
+    if (W) {
+        if (lane < pad) tx_st<W>(row, pos + lane, ' ');
+        if (lane < n) tx_st<W>(row, pos + pad + lane, (unsigned char)b);
+    }
+    return pos + (unsigned int)(pad + n);
+}
+
+// the C string within the first `limit` bytes of the text, byte i at place i; subst: '\n' and '\r' become a space
+template <bool W>
+__device__ __forceinline__ unsigned int tx_text(unsigned char* row, unsigned int pos, const unsigned char* txt, int limit, bool subst, int lane)
+{
+    for (int rd = 0; rd < 4; ++rd) {
+        const int i = 64 * rd + lane;
+        unsigned int b = i < limit ? txt[i] : 0u;
+        const unsigned long long nul = __ballot(b == 0);
+        const int n = nul ? __ffsll((unsigned long long)nul) - 1 : 64;
+        if (subst && (b == '\n' || b == '\r')) b = ' ';
+        if (W && lane < n) tx_st<W>(row, pos + lane, (unsigned char)b);
+        pos += (unsigned int)n;
+        if (n < 64) break;                                         // (wave-uniform)
+    }
+    return pos;
+}
+
+// n <= 32 bytes the host prepared (SV's station), 4-byte aligned: a dword load per lane
+template <bool W>
+__device__ __forceinline__ unsigned int tx_words(unsigned char* row, unsigned int pos, const unsigned char* src, unsigned int n, int lane)
+{
+    if (W && 4u * lane < n) {
+        const unsigned int w = *(const unsigned int*)(src + 4u * lane);
+#pragma unroll
+        for (unsigned int k = 0; k < 4; ++k)
+            if (4u * lane + k < n) tx_st<W>(row, pos + 4u * lane + k, (unsigned char)(w >> (8 * k)));
+    }
+    return pos + n;
+}
+
+// " <label line> : <field>\n" of printmsg()'s OOOI part
+#define TX_OOOI(at, s) do { if (O[at]) { TX_LIT(s); pos = tx_str<W>(row, pos, O + at, 4, 0, lane); pos = tx_ch<W>(row, pos, '\n', lane); } } while (0)
+
+// One record.  R: the message and, at R + 320, its acg_oooi (LDS); row: where the record's first byte goes (W) or unused.
+template <bool W>
+__device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsigned char* row, const AcgTextPass& p, int lane, bool* near_mid)
+{
+    const AcgMsgRec* r = (const AcgMsgRec*)R;
+    const AcgTextDev* cfg = p.cfg;
+    const int format = cfg->format;                               // (wave-uniform, as everything read from cfg and R)
+    const unsigned int flags = cfg->flags;
+    unsigned int pos = 0;
+    // ---- tv = t0 + soh_sample / 12500 s in integers (a sample is exactly 80 us), as json.hip
+    const long long soh = r->end_sample - (long long)r->soh_back;
+    const long long us = (long long)cfg->t0_usec + soh * 80ll;
+    long long q = us / 1000000ll, rem = us % 1000000ll;
+    if (rem < 0) { rem += 1000000ll; --q; }
+    const TnDate date = tn_date(cfg->t0_sec + q, (int)rem);
+    const int chn = r->chn;
+    *near_mid = false;
+    const float lvl = format == ACG_TEXT_PP ? 0.0f : pk_level(r, p.lvl_from_rec, near_mid);
+    int tl = r->txt_len;
+    tl = tl < 0 ? 0 : tl > ACG_MSG_TXT ? ACG_MSG_TXT : tl;
+    const unsigned char* txt = R + offsetof(AcgMsgRec, txt);
+    const unsigned int mode = (unsigned char)r->mode, ack = (unsigned char)r->ack, bid = (unsigned char)r->bid;
+    const unsigned char *addr = R + offsetof(AcgMsgRec, addr), *label = R + offsetof(AcgMsgRec, label), *no = R + offsetof(AcgMsgRec, no),
+                        *fid = R + offsetof(AcgMsgRec, fid);
+
+    if (format == ACG_TEXT_ONELINE) {                             // output.c:338-344
+        pos = tx_ch<W>(row, pos, '#', lane);
+        pos = tx_tok<W>(row, pos, jn_int((long long)chn + 1), lane);
+        TX_LIT(" (L:");
+        pos = tx_level<W>(row, pos, lvl, lane);
+        TX_LIT(" E:");
+        pos = tx_tok<W>(row, pos, jn_int(r->err), lane);
+        TX_LIT(") ");
+        if (flags & ACG_TEXT_F_DATE) pos = tx_date<W>(row, pos, date, TN_DATE_LEN, lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        pos = tx_str<W>(row, pos, addr, 7, 7, lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        pos = tx_str<W>(row, pos, fid, 6, 6, lane);
+        pos = tx_ch2<W>(row, pos, ' ', mode, lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        pos = tx_str<W>(row, pos, label, 2, 2, lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        pos = tx_str<W>(row, pos, no, 4, 4, lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        pos = tx_text<W>(row, pos, txt, tl < 59 ? tl : 59, true, lane);          // strncpy(txt, msg->txt, 59)
+        pos = tx_ch<W>(row, pos, '\n', lane);
+        return pos;
+    }
+    if (format == ACG_TEXT_STD) {                                 // output.c:166-215
+        TX_LIT("\n[#");
+        pos = tx_tok<W>(row, pos, jn_int((long long)chn + 1), lane);
+        TX_LIT(" (");
+        if (flags & ACG_TEXT_F_FREQ) {
+            if ((unsigned int)chn < (unsigned int)cfg->nch) {
+                const unsigned long long* ft = (const unsigned long long*)(p.freq + (size_t)chn * ACG_TX_FREQ_SLOT);
+                const unsigned long long lo = ft[0], hi = ft[1];
+                const unsigned int fn = (unsigned int)(hi >> 56) & 15u;
+                if (W && (unsigned int)lane < fn) tx_st<W>(row, pos + lane, (unsigned char)((lane < 8 ? lo : hi) >> (8 * (lane & 7))));
+                pos += fn;
+            } else {                                              // (no caller gets here: the entry points keep chn < nch.  It only
+                TX_LIT("F:0.000 ");                               //  keeps the token table's load in bounds and the record well formed)
+            }
+        }
+        TX_LIT("L:");
+        pos = tx_level<W>(row, pos, lvl, lane);
+        TX_LIT(" E:");
+        pos = tx_tok<W>(row, pos, jn_int(r->err), lane);
+        TX_LIT(") ");
+        if (flags & ACG_TEXT_F_DATE) pos = tx_date<W>(row, pos, date, TN_DATE_LEN, lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        pos = tx_fill<W>(row, pos, '-', 32, lane);
+        TX_LIT("\nMode : ");
+        pos = tx_ch<W>(row, pos, mode, lane);
+        TX_LIT(" Label : ");
+        pos = tx_str<W>(row, pos, label, 2, 2, lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        if (bid) {
+            TX_LIT("Id : ");
+            pos = tx_ch2<W>(row, pos, bid, ' ', lane);
+            if (ack == '!') {
+                TX_LIT("Nak\n");
+            } else {
+                TX_LIT("Ack : ");
+                pos = tx_ch2<W>(row, pos, ack, '\n', lane);
+            }
+            TX_LIT("Aircraft reg: ");
+            pos = tx_str<W>(row, pos, addr, 7, 0, lane);
+            pos = tx_ch<W>(row, pos, ' ', lane);
+            if (bid >= '0' && bid <= '9') {                       // IS_DOWNLINK_BLK, output.c:31,185
+                TX_LIT("Flight id: ");
+                pos = tx_str<W>(row, pos, fid, 6, 0, lane);
+                TX_LIT("\nNo: ");
+                pos = tx_str<W>(row, pos, no, 4, 4, lane);
+            }
+        }
+        pos = tx_ch<W>(row, pos, '\n', lane);
+        if (tl > 0 && txt[0]) {
+            pos = tx_text<W>(row, pos, txt, tl, false, lane);
+            pos = tx_ch<W>(row, pos, '\n', lane);
+        }
+        if (r->be == 0x17) TX_LIT("ETB\n");
+        const unsigned char* O = R + sizeof(AcgMsgRec);          // oooi_t: da sa eta gout gin woff won, then `decoded`
+        if (O[35]) {
+            pos = tx_fill<W>(row, pos, '#', 26, lane);
+            pos = tx_ch<W>(row, pos, '\n', lane);
+            TX_OOOI(0, "Destination Airport : ");
+            TX_OOOI(5, "Departure Airport : ");
+            TX_OOOI(10, "Estimation Time of Arrival : ");
+            TX_OOOI(15, "Gate out Time : ");
+            TX_OOOI(20, "Gate in Time : ");
+            TX_OOOI(25, "Wheels off Tme : ");
+            TX_OOOI(30, "Wheels on Time : ");
+        }
+        return pos;
+    }
+    // ---- the two datagrams: "<head>%1c %7s %1c %2s %1c %4s %6s %s" (netout.c:112-114,131-135)
+    if (format == ACG_TEXT_SV) {
+        pos = tx_words<W>(row, pos, cfg->station, cfg->station_len, lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        pos = tx_tok<W>(row, pos, jn_int((long long)chn + 1), lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        pos = tx_date<W>(row, pos, date, TN_DATE_SV_LEN, lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        pos = tx_tok<W>(row, pos, jn_int(r->err), lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+        pos = tx_tok<W>(row, pos, tn_int0(tn_trunc_int(lvl), 3), lane);
+        pos = tx_ch<W>(row, pos, ' ', lane);
+    } else {
+        TX_LIT("AC");
+    }
+    pos = tx_ch2<W>(row, pos, mode, ' ', lane);
+    pos = tx_str<W>(row, pos, addr, 7, 7, lane);
+    pos = tx_ch<W>(row, pos, ' ', lane);
+    pos = tx_ch2<W>(row, pos, ack, ' ', lane);
+    pos = tx_str<W>(row, pos, label, 2, 2, lane);
+    pos = tx_ch<W>(row, pos, ' ', lane);
+    pos = tx_ch2<W>(row, pos, bid ? bid : '.', ' ', lane);
+    pos = tx_str<W>(row, pos, no, 4, 4, lane);
+    pos = tx_ch<W>(row, pos, ' ', lane);
+    pos = tx_str<W>(row, pos, fid, 6, 6, lane);
+    pos = tx_ch<W>(row, pos, ' ', lane);
+    pos = tx_text<W>(row, pos, txt, tl, format == ACG_TEXT_PP, lane);            // Netoutpp substitutes, Netoutsv does not
+    return pos;
+}
+
+__global__ __launch_bounds__(PK_WG) void text_keys_kernel(AcgTextPass p)
+{
+    const unsigned int i = blockIdx.x * PK_WG + threadIdx.x;
+    if (i >= p.nmax || i >= *p.total) return;
+    p.key[i] = pk_key(p.recs + i);
+    p.idx[i] = i;
+}
+
+__global__ __launch_bounds__(64 * TX_WAVES) void text_measure_kernel(AcgTextPass p)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char recs[TX_WAVES][PK_REC];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned int r = blockIdx.x * TX_WAVES + wv;                           // wave-uniform
+    if (r >= p.nmax || r >= *p.total) return;
+    if (p.key_s[r] == ~0ull) {
+        if (lane == 0) p.len[r] = 0;
+        return;
+    }
+    pk_load(recs[wv], p.recs, p.oooi, p.idx_s[r], lane);
+    bool nm;
+    const unsigned int n = text_record<false>(recs[wv], nullptr, p, lane, &nm);
+    if (lane == 0) p.len[r] = n > (unsigned int)ACG_TX_REC_MAX ? (unsigned int)ACG_TX_REC_MAX : n;
+}
+
+__global__ __launch_bounds__(PK_WG) void text_sum_kernel(AcgTextPass p)
+{
+    __shared__ unsigned int sum_s;
+    pk_sum(&sum_s, p.len, p.wg_sum, p.wg_cnt, p.nmax, p.total);
+}
+
+__global__ __launch_bounds__(PK_WG) void text_offsets_kernel(AcgTextPass p)
+{
+    __shared__ unsigned int base_s, cnt_s;
+    __shared__ unsigned int wave_n[PK_WG / 64];
+    pk_offsets(&base_s, &cnt_s, wave_n, p.len, p.off, p.wg_sum, p.wg_cnt, p.counters, p.nmax, p.total);
+}
+
+__global__ __launch_bounds__(64 * TX_WAVES) void text_render_kernel(AcgTextPass p)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char recs[TX_WAVES][PK_REC];
+    __shared__ __attribute__((aligned(16))) unsigned char rows[TX_WAVES][TX_ROW];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned int r = blockIdx.x * TX_WAVES + wv;                           // wave-uniform
+    if (r >= p.nmax || r >= *p.total) return;
+    const unsigned int len = p.len[r], off = p.off[r];
+    if (len == 0 || len > (unsigned int)ACG_TX_REC_MAX || off > p.out_cap || len > p.out_cap - off) return;
+    pk_load(recs[wv], p.recs, p.oooi, p.idx_s[r], lane);
+    bool near_mid;
+    const unsigned int n = text_record<true>(recs[wv], rows[wv] + (off & 15u), p, lane, &near_mid);   // the row mirrors the output's alignment
+    if (n != len) return;                                                        // (cannot happen: one function measures and renders)
+    if (near_mid && lane == 0) atomicAdd(&p.counters[2], 1u);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    pk_flush_row(rows[wv], p.out, off, len, lane);
+}
+
+extern "C" int acg_launch_text(const AcgTextPass* p, void* stream)
+{
+    if (p->nmax == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned int g = (p->nmax + PK_WG - 1) / PK_WG, gw = (p->nmax + TX_WAVES - 1) / TX_WAVES;
+    hipLaunchKernelGGL(text_keys_kernel, dim3(g), dim3(PK_WG), 0, s, *p);
+    int e = acg_launch_sort_pairs(p->key, p->idx, p->key_s, p->idx_s, p->total, 0u, stream);
+    if (e) return e;
+    hipLaunchKernelGGL(text_measure_kernel, dim3(gw), dim3(64 * TX_WAVES), 0, s, *p);
+    hipLaunchKernelGGL(text_sum_kernel, dim3(g), dim3(PK_WG), 0, s, *p);
+    hipLaunchKernelGGL(text_offsets_kernel, dim3(g), dim3(PK_WG), 0, s, *p);
+    hipLaunchKernelGGL(text_render_kernel, dim3(gw), dim3(64 * TX_WAVES), 0, s, *p);
+    return (int)hipGetLastError();
+}

@@ -391,6 +391,52 @@ class Decoder:
         self._chk(self.L.acg_lab_json_level_guard(self.ctx, C.byref(n)))
         return n.value
 
+    # ---- the text sink (acg_text_enable, acg_drain_text, acg_collect_text) -------------------------------------------------
+    def enable_text(self, fmt, t0, date=False, freq=False, station_id="", freqs_hz=None):
+        """The reference's text formats rendered on the device from now on.  fmt: "oneline" (-o 1, printoneline), "std" (-o 2,
+        printmsg), "pp" (-N, Netoutpp) or "sv" (-n, Netoutsv), or K.TEXT_*; date: printdate() is printed (oneline, std); freq:
+        printmsg's "F:" token (std); t0 as for enable_json; station_id: sv's "%8s"; freqs_hz: the channels' frequencies in Hz."""
+        cfg = text_config(fmt, t0, date, freq, station_id)
+        fr = None
+        if freqs_hz is not None:
+            fr = np.ascontiguousarray(freqs_hz, dtype=np.int32)
+            assert fr.size == self.nch
+        self._chk(self.L.acg_text_enable(self.ctx, C.byref(cfg), fr.ctypes.data if fr is not None else None))
+
+    def disable_text(self):
+        self._chk(self.L.acg_text_enable(self.ctx, None, None))
+
+    def _text_call(self, fn, max_recs, *lead):
+        n = max(1, int(max_recs))
+        cap = n * K.TEXT_REC_MAX
+        if getattr(self, "_tbuf_cap", 0) < cap:
+            self._tbuf = C.create_string_buffer(cap)
+            self._toffs = (C.c_uint * (n + 1))()
+            self._tbuf_cap = cap
+        out = []
+        while True:
+            nb, nr = C.c_size_t(0), C.c_int(0)
+            rc = self._chk(fn(self.ctx, *lead, self._tbuf, self._tbuf_cap, C.byref(nb), self._toffs, n, C.byref(nr)), allow=(K.EAGAIN,))
+            blob, offs = C.string_at(self._tbuf, nb.value), self._toffs[:nr.value + 1]
+            out += [blob[offs[i]:offs[i + 1]] for i in range(nr.value)]
+            if rc == K.OK:
+                return out
+
+    def drain_text(self, max_recs=4096):
+        """The text records of every block completed since the last drain (needs repair=True and enable_text): a list of bytes, one
+        per kept message, in (chn, end_bit) order per C call; loops while the C side says ACG_EAGAIN."""
+        return self._text_call(self.L.acg_drain_text, max_recs)
+
+    def collect_text(self, lag=1, max_recs=4096):
+        """Streaming variant (acg_collect_text): the records of all calls but the `lag` newest"""
+        return self._text_call(self.L.acg_collect_text, max_recs, lag)
+
+    def text_level_guard(self):
+        """records rendered since enable_text whose level lay within 8 ulp of a float rounding boundary (acg_lab_text_level_guard)"""
+        n = C.c_uint(0)
+        self._chk(self.L.acg_lab_text_level_guard(self.ctx, C.byref(n)))
+        return n.value
+
     def bits(self, ch):
         vo = np.zeros(self.bit_cap, dtype=np.float32)
         lvl = np.zeros(self.bit_cap, dtype=np.float32)
@@ -457,6 +503,21 @@ def json_config(t0, station_id="", app_name="acarsdec", app_ver=""):
     if len(station_id) > 32 or len(app_name) > 16 or len(app_ver) > 16:
         raise ValueError("station_id holds 32 characters, app_name and app_ver 16")
     return K.JsonConfig(int(sec), int(usec), station_id, app_name, app_ver)
+
+
+TEXT_FORMATS = {"oneline": K.TEXT_ONELINE, "std": K.TEXT_STD, "pp": K.TEXT_PP, "sv": K.TEXT_SV}
+
+
+def text_config(fmt, t0, date=False, freq=False, station_id=""):
+    """K.TextConfig for acg_text_enable / acg_selftest_msg_text; fmt: a name of TEXT_FORMATS or K.TEXT_*; t0 as json_config"""
+    sec, usec = t0 if isinstance(t0, tuple) else (int(t0 // 1), int(round((t0 - t0 // 1) * 1e6)))
+    if usec >= 1000000:
+        sec, usec = sec + 1, usec - 1000000
+    station_id = station_id.encode("latin1") if isinstance(station_id, str) else bytes(station_id)
+    if len(station_id) > 32:
+        raise ValueError("station_id holds 32 characters")
+    flags = (K.TEXT_F_DATE if date else 0) | (K.TEXT_F_FREQ if freq else 0)
+    return K.TextConfig(TEXT_FORMATS.get(fmt, fmt), flags, int(sec), int(usec), station_id)
 
 
 # oooi_t field -> the reference JSON's key (output.c:280-295, in the order buildjson adds them)

@@ -412,6 +412,65 @@ int  acg_json_enable(acg_ctx *ctx, const acg_json_config *cfg, const int *Fr_hz)
 int  acg_drain_json(acg_ctx *ctx, char *out, size_t cap, size_t *nbytes, int *nlines);
 int  acg_collect_json(acg_ctx *ctx, int lag, char *out, size_t cap, size_t *nbytes, int *nlines);
 
+/* ---- the text sink: the reference's other per-message formats, rendered on the device like the JSON sink's lines ------------
+ * Off by default; with it off every entry point launches, copies and returns exactly what it does without this section.
+ *   ACG_TEXT_ONELINE  printoneline() (output.c:327-346): what -o 1 prints, one '\n'-ended line per message;
+ *   ACG_TEXT_STD      printmsg() (output.c:162-224) of the build without libacars: what -o 2 prints, and acarsdec without -o;
+ *                     a record begins with the "\n[#" of its header line;
+ *   ACG_TEXT_PP       the packet Netoutpp() formats for -N (netout.c:101-120), no trailing newline;
+ *   ACG_TEXT_SV       the packet Netoutsv() formats for -n (netout.c:122-140), likewise.
+ * acg_drain_text / acg_collect_text are message entry points like acg_drain_json / acg_collect_json (ACG_F_REPAIR, the filters of
+ * acg_set_msg_filter, the flight table when it is on, blocks the repair dropped yield nothing, (chn, end_bit) order within the
+ * call).  Record i is out[offs[i] .. offs[i + 1]); offs gets *nrecs + 1 entries (offs[*nrecs] == *nbytes), records are packed
+ * back to back, out is not NUL terminated.  A record holds its bytes exactly as the reference's printf writes them, a NUL
+ * ("%1c" of a NUL mode), a '\n' or any other byte included: hence a table and no line count.  (PP, SV: the reference sends
+ * strlen() of its packet, so a datagram ends before the first NUL; a host that wants exactly that sends strnlen(record, length).)
+ * A call looks at the oldest min(max_recs, cap / ACG_TEXT_REC_MAX) queued blocks only and consumes exactly those; more queued:
+ * ACG_EAGAIN (call again, nothing is lost).  ACG_EINVAL: cap < ACG_TEXT_REC_MAX or max_recs < 1; ACG_ESTATE: no ACG_F_REPAIR, or
+ * the sink is not enabled.  The JSON sink may be enabled too; each entry point consumes the blocks it hands out.
+ *
+ * The bytes: "%Ns" right-justifies a C string (it ends at its first NUL) to at least N and never cuts it; "%1c" writes the byte.
+ * printoneline shows the first 59 bytes of the text up to its NUL, '\n' and '\r' as a space; Netoutpp the whole text with the same
+ * substitution and `bid ? bid : '.'`; Netoutsv the text as it is and "%03d" of (int)lvl, toward zero (-7.9: "-07"; a level that
+ * is not finite: the x86 conversion's -2147483648).  "L:%+5.1f" is the float's exact value rounded half-even to one decimal,
+ * sign forced, space padded to 5 ("+inf", "-inf", "+nan", "-nan" as glibc); the level's float has the JSON sink's residual
+ * (the device's log10 against glibc's; acarsdec_amd_lab.h counts the candidates).  The date is printdate()'s
+ * "%02d/%02d/%04d %02d:%02d:%02d.%03ld" of gmtime_r(tv), tv = t0 + soh_sample / 12500 s in integers (SV: without ".%03ld"),
+ * exact from 1970 to the year 9999 (2100 is no leap year); printdate() prints nothing when tv_sec + tv_usec == 0, which
+ * t0_sec >= 10^9 excludes.
+ *
+ * ACG_TEXT_REC_MAX, the longest record of any format -- printmsg()'s, token by token:
+ *   "\n[#" 3 + chn 11 + " (" 2 + "F:%3.3f " 12 ("F:-2147.484 ") + "L:" 2 + level 21 (sign, 18 digits, ".d") + " E:" 3 + err 11 + ") " 2 = 67
+ *   date 23, " " + 32 x '-' + "\n" 34
+ *   "Mode : %1c " 9     "Label : %2s " 11    "Id : %1c " 7      "Ack : %1c\n" 8
+ *   "Aircraft reg: %s " 14 + 7 + 1 = 22      "Flight id: %s\n" 11 + 6 + 1 = 18       "No: %4s" 8       "\n" 1
+ *   the text and "\n" 242 + 1 = 243          "ETB\n" 4          26 x '#' + "\n" 27
+ *   "Destination Airport : %s\n" 22 + 4 + 1 = 27       "Departure Airport : %s\n" 25     "Estimation Time of Arrival : %s\n" 34
+ *   "Gate out Time : %s\n" 21    "Gate in Time : %s\n" 20     "Wheels off Tme : %s\n" 22     "Wheels on Time : %s\n" 22
+ * = 653, rounded up to a multiple of 64.  (Netoutsv's: 32 + 11 + 19 + 11 + 11 + the fields + 242 + 17 separators < 400.) */
+#define ACG_TEXT_ONELINE  1   /* -o 1  printoneline()  output.c:327-346 */
+#define ACG_TEXT_STD      2   /* -o 2  printmsg()      output.c:162-224, the build without libacars */
+#define ACG_TEXT_PP       3   /* -N    Netoutpp()      netout.c:101-120: one datagram per record, no trailing newline */
+#define ACG_TEXT_SV       4   /* -n    Netoutsv()      netout.c:122-140: likewise */
+#define ACG_TEXT_F_DATE   1u  /* printdate() is printed (the reference: inmode != 2); ONELINE and STD only */
+#define ACG_TEXT_F_FREQ   2u  /* the "F:%3.3f " token of printmsg() (the reference: inmode >= 3); STD only */
+#define ACG_TEXT_REC_MAX  704
+typedef struct {
+	int format;                   /* ACG_TEXT_* */
+	unsigned int flags;           /* ACG_TEXT_F_* the format takes */
+	long long t0_sec;             /* the epoch rule of acg_frame: tv = t0 + soh_sample / 12500 s, in integers */
+	int t0_usec;                  /* 0 .. 999999 */
+	char station_id[33];          /* idstation (-i): SV's "%8s" */
+} acg_text_config;
+/* Switches the text sink on (cfg) or off and frees it (NULL).  Fr_hz: the channels' frequencies in Hz ([nch]; NULL = all 0):
+ * "F:%3.3f " is snprintf of the DOUBLE Fr / 1000000.0 (output.c:168-169; not the JSON line's float), rendered here once per
+ * channel, as is SV's padded station.  ACG_EINVAL: an unknown format, a flag the format does not take, t0_sec outside
+ * [10^9, 4 * 10^9), t0_usec outside 0..999999, an unterminated station_id; ACG_ESTATE: context without ACG_F_REPAIR.
+ * acg_reset keeps the configuration. */
+int  acg_text_enable(acg_ctx *ctx, const acg_text_config *cfg, const int *Fr_hz);
+int  acg_drain_text(acg_ctx *ctx, char *out, size_t cap, size_t *nbytes, unsigned int *offs, int max_recs, int *nrecs);
+int  acg_collect_text(acg_ctx *ctx, int lag, char *out, size_t cap, size_t *nbytes, unsigned int *offs, int max_recs, int *nrecs);
+
 /* Per-bit records of the LAST process call for one channel (needs ACG_F_BITLOG):
  * vo = the value putbit() receives (msk.c:122-126), lvl = cabsf(v) (msk.c:110). */
 int  acg_read_bits(acg_ctx *ctx, int ch, float *vo, float *lvl, int max_bits, int *nbits);

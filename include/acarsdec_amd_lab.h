@@ -95,6 +95,23 @@ int  acg_selftest_msg_json(const acg_msg *in, int n, const acg_msg_filter *f, co
  * a host's that narrows glibc's log10 */
 int  acg_lab_json_level_guard(acg_ctx *ctx, unsigned int *near_midpoint);
 
+/* diagnostics: the text sink's passes (label.hip's filter and compaction, then text.hip's order / measure / scan / render) on n
+ * caller-supplied records, exactly as acg_selftest_msg_json takes them (level = in[i].lvl as it stands, time, dropped records,
+ * Fr_hz, the ACG_EINVAL conditions): the records of the messages the filter keeps, in (chn, end_bit) order (equal keys: input
+ * order), packed into out; offs (n + 1 entries of room), *nbytes, *nrecs as acg_drain_text.
+ * ACG_EAGAIN: cap < the bytes needed (*nbytes says how many; out and offs are untouched); ACG_ENODEV: no GPU. */
+int  acg_selftest_msg_text(const acg_msg *in, int n, const acg_msg_filter *f, const acg_text_config *cfg, const int *Fr_hz, int nch,
+			   char *out, size_t cap, size_t *nbytes, unsigned int *offs, int *nrecs);
+/* diagnostics: the same count as acg_lab_json_level_guard (the same rule, sink_pack.h) for the records acg_drain_text /
+ * acg_collect_text have rendered since acg_text_enable (PP records show no level and are not counted) */
+int  acg_lab_text_level_guard(acg_ctx *ctx, unsigned int *near_midpoint);
+/* measurement: the device time of json.hip's passes and of text.hip's over the SAME n records (taken as the two self tests take
+ * them, no filter), the label pass run once before; HIP events around each renderer's launches, `warmup` unrecorded rounds and
+ * `reps` recorded ones, the two arms alternated within every round: ms[0 .. reps) = the JSON passes, ms[reps .. 2 reps) = the text
+ * passes, milliseconds.  ACG_ENODEV: no GPU. */
+int  acg_lab_time_sink_passes(const acg_msg *in, int n, const acg_json_config *jcfg, const acg_text_config *tcfg, int nch, int warmup, int reps,
+			      float *ms);
+
 /* Test hook (the block ring across the wrap of its 32-bit counters): right after acg_reset, with nothing queued,
  * sets the device's block counter, the repair pass's mark and the host's consumer mark to `value`, as if that many blocks had
  * been produced and consumed already.  ACG_ESTATE if calls have been issued since the reset. */
