@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -217,8 +218,8 @@ struct acg_ctx {
     unsigned int* d_kwork = nullptr;        // [kmsgs_cap / 256 + 1] per-workgroup counts, then the total
     size_t kmsgs_cap = 0;
     AcgFlights* flights = nullptr;          // acg_flights_enable: the flight table (flights.cpp), updated by every message entry point
-    struct AcgTextState* text = nullptr;    // acg_text_enable: the text sink (text.hip), as json
-    struct AcgJsonState* json = nullptr;    // acg_json_enable: the JSON sink (json.hip): configuration, work space, rendered lines
+    struct AcgSinkState* text = nullptr;    // acg_text_enable: the text sink (text.hip), as json
+    struct AcgSinkState* json = nullptr;    // acg_json_enable: the JSON sink (json.hip): configuration, work space, rendered lines
     unsigned int* d_work = nullptr;     // FIR run dispensers, ACG_DISP_WORDS words per chunk slot
     bool stream_identity = true;        // channel c reads stream c
     unsigned short* d_crctab = nullptr; // [256] + syndromes [1936] (ACG_F_REPAIR)
@@ -293,8 +294,7 @@ extern "C" int acg_device_count(void)
     return n;
 }
 
-static void json_destroy(struct AcgJsonState* st);
-static void text_destroy(struct AcgTextState* st);
+static void sink_destroy(struct AcgSinkState* st);
 static void free_all(acg_ctx* c)
 {
     if (!c) return;
@@ -305,9 +305,9 @@ static void free_all(acg_ctx* c)
     hipFree(c->d_kmsgs); hipFree(c->d_oooi); hipFree(c->d_kwork); std::free(c->h_oooi);
     if (c->flights) acg_fl_destroy(c->flights);
     c->flights = nullptr;
-    json_destroy(c->json);
+    sink_destroy(c->json);
     c->json = nullptr;
-    text_destroy(c->text);
+    sink_destroy(c->text);
     c->text = nullptr;
     hipFree(c->d_bits); hipFree(c->d_nbits); hipFree(c->d_stage[0]); hipFree(c->d_stage[1]); hipFree(c->d_work); hipFree(c->d_msk_done); std::free(c->h_stage); hipFree(c->d_crctab); hipFree(c->d_rep_upto);
     for (auto& p : c->fir_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
@@ -1354,7 +1354,7 @@ extern "C" int acg_drain_frames(acg_ctx* ctx, acg_frame* out, int max_frames, in
 // ------------------------------------------------------------------------------------------
 // the claimed blocks through the device-side field split (blk.hip msg_split_kernel)
 static_assert(sizeof(AcgMsgRec) == sizeof(acg_msg), "device record and public record must have one layout");
-// the message entry points' staging (fetch_msgs, fetch_json), grown on demand: the split's records, device and host ...
+// the message entry points' staging (fetch_msgs, sink_fetch), grown on demand: the split's records, device and host ...
 static int grow_msg_stage(acg_ctx* ctx, unsigned int take)
 {
     if (take <= ctx->msgs_cap) return ACG_OK;
@@ -1389,6 +1389,22 @@ static int grow_label_stage(acg_ctx* ctx, unsigned int take)
     return ACG_OK;
 }
 
+// The split of the `take` oldest blocks into d_msgs on the copy stream (it writes every byte of a record, text tail zeroed, so
+// nothing stale crosses the ABI); with `labels`, label.hip's pass behind it into d_kmsgs / d_oooi (the caller has grown the label
+// stage) and, the flight table on, its pass.  *d_total: the label pass's count of kept records, a device word.
+static int launch_split(acg_ctx* ctx, unsigned int take, bool labels, unsigned int** d_total)
+{
+    *d_total = ctx->d_kwork + ctx->kmsgs_cap / 256 + 1;
+    AcgLabelPass pass{&ctx->msg_filter, ctx->d_kwork, ctx->d_kmsgs, ctx->d_oooi, *d_total, nullptr, nullptr};
+    if (ctx->flights) {                                           // over exactly the blocks this call consumes, before -e drops any
+        const int fr = acg_fl_prepare(ctx->flights, take, ctx->copy_stream, &pass.flights);
+        if (fr != ACG_OK) return fail(ctx, fr, "flight table: work space");
+    }
+    if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, take, ctx->d_msgs, ctx->copy_stream, labels ? &pass : nullptr) != 0)
+        return fail(ctx, ACG_EHIP, "message split launch failed");
+    return ACG_OK;
+}
+
 static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
 {
     unsigned int upto = 0, pending = 0, take = 0;
@@ -1409,15 +1425,8 @@ static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int m
         if (const int gr = grow_label_stage(ctx, take)) return gr;
     unsigned int nrec = take;                                     // records that cross to the host
     if (take) {
-        // the split writes every byte of a record (text tail zeroed), so nothing stale crosses the ABI
-        unsigned int* d_total = ctx->d_kwork + ctx->kmsgs_cap / 256 + 1;
-        AcgLabelPass pass{&ctx->msg_filter, ctx->d_kwork, ctx->d_kmsgs, ctx->d_oooi, d_total, nullptr, nullptr};
-        if (ctx->flights) {                                       // over exactly the blocks this call consumes, before -e drops any
-            const int fr = acg_fl_prepare(ctx->flights, take, ctx->copy_stream, &pass.flights);
-            if (fr != ACG_OK) return fail(ctx, fr, "flight table: work space");
-        }
-        if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, take, ctx->d_msgs, ctx->copy_stream, labels ? &pass : nullptr) != 0)
-            return fail(ctx, ACG_EHIP, "message split launch failed");
+        unsigned int* d_total = nullptr;
+        if (const int lr = launch_split(ctx, take, labels, &d_total)) return lr;
         if (labels) {
             HIPCHK(ctx, hipMemcpyAsync(&nrec, d_total, sizeof(nrec), hipMemcpyDeviceToHost, ctx->copy_stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
@@ -1483,6 +1492,48 @@ extern "C" int acg_drain_msgs_oooi(acg_ctx* ctx, acg_msg* out, acg_oooi* oooi, i
     return fetch_msgs(ctx, DRAIN, out, oooi ? oooi : &none, max_msgs, nmsgs);
 }
 
+// ---- what the lab entries below share: public records turned back into the device's form, staged, and label.hip's pass over them
+// with no ring (the split has nothing to split) on the null stream.  Holds at most `cap` records per pass.
+struct LabStage {
+    const size_t nwg;                       // d_work: nwg per-workgroup counts, then the total
+    std::vector<AcgMsgRec> h;
+    AcgMsgRec *d_in = nullptr, *d_out = nullptr;    // the records staged; the records kept
+    acg_oooi* d_oooi = nullptr;
+    unsigned int* d_work = nullptr;
+    bool allocated;
+
+    explicit LabStage(size_t cap) : nwg(cap / 256 + 1), h(std::max<size_t>(cap, 1))
+    {
+        allocated = hipMalloc(&d_in, h.size() * sizeof(AcgMsgRec)) == hipSuccess && hipMalloc(&d_out, h.size() * sizeof(AcgMsgRec)) == hipSuccess &&
+                    hipMalloc(&d_oooi, h.size() * sizeof(acg_oooi)) == hipSuccess && hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) == hipSuccess;
+    }
+    LabStage(const LabStage&) = delete;
+    ~LabStage()
+    {
+        hipDeviceSynchronize();
+        hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
+    }
+    bool ok() const { return allocated; }
+    unsigned int* d_total() const { return d_work + nwg; }
+    // h[0, n): `valid` is 1, or with from_reserved2 what the sink handed out in acg_msg's reserved2; soh_back is as given, or with
+    // fill_soh_back the distance the public record's two sample counts span
+    void stage(const acg_msg* in, unsigned int n, bool from_reserved2, bool fill_soh_back)
+    {
+        for (unsigned int i = 0; i < n; ++i) {
+            std::memcpy(&h[i], &in[i], sizeof(AcgMsgRec));
+            h[i].valid = from_reserved2 && in[i].reserved2 ? 0 : 1;
+            if (fill_soh_back) h[i].soh_back = (int)(in[i].end_sample - in[i].soh_sample);
+        }
+    }
+    // h[0, n) to the device and the label pass over them; 0, or anything else for a HIP error
+    int label(unsigned int n, const AcgLabelFilter* f, unsigned char* d_keep = nullptr, const AcgFlightPass* flights = nullptr)
+    {
+        const AcgLabelPass pass{f, d_work, d_out, d_oooi, d_total(), d_keep, flights};
+        return hipMemcpy(d_in, h.data(), (size_t)n * sizeof(AcgMsgRec), hipMemcpyHostToDevice) != hipSuccess ||
+               acg_launch_msg_split(nullptr, 0, 0, n, d_in, nullptr, &pass) != 0;
+    }
+};
+
 // ---- the sink's filters (label.c:9-23 build_label_filter, acarsdec.c -A / -b / -e) --------------------------------------
 static_assert(ACG_LBL_MAXTOK == ACG_MSGF_MAXLABELS, "token capacity");
 static_assert(sizeof(acg_oooi) == 40 && offsetof(acg_oooi, decoded) == 35 && offsetof(acg_oooi, won) == 30,
@@ -1543,42 +1594,31 @@ extern "C" int acg_selftest_msg_labels(const acg_msg* in, int n, const acg_msg_f
     if (n == 0) return ACG_OK;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
-    std::vector<AcgMsgRec> h((size_t)n);
-    std::memcpy(h.data(), in, (size_t)n * sizeof(AcgMsgRec));
-    for (auto& r : h) r.valid = 1;                                 // (acg_msg: reserved2) records as the sink hands them out
-    const size_t by = (size_t)n * sizeof(AcgMsgRec);
-    AcgMsgRec *d_in = nullptr, *d_out = nullptr;
-    acg_oooi* d_oooi = nullptr;
-    unsigned int* d_work = nullptr;
+    LabStage lab((size_t)n);
+    lab.stage(in, (unsigned int)n, false, false);                  // soh_back as given: the kept records are compared with these
     unsigned char* d_keep = nullptr;
-    const size_t nwg = (size_t)n / 256 + 1;
     std::vector<AcgMsgRec> kept((size_t)n);
     std::vector<acg_oooi> ko((size_t)n);
     unsigned int total = 0;
     int rc = ACG_EHIP;
-    const bool alloc = hipMalloc(&d_in, by) == hipSuccess && hipMalloc(&d_out, by) == hipSuccess &&
-                       hipMalloc(&d_oooi, (size_t)n * sizeof(acg_oooi)) == hipSuccess &&
-                       hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) == hipSuccess && hipMalloc(&d_keep, (size_t)n) == hipSuccess;
-    const AcgLabelPass pass{&d, d_work, d_out, d_oooi, d_work + nwg, d_keep};
-    if (alloc && hipMemcpy(d_in, h.data(), by, hipMemcpyHostToDevice) == hipSuccess &&
-        acg_launch_msg_split(nullptr, 0, 0, (unsigned int)n, d_in, nullptr, &pass) == 0 &&
-        hipMemcpy(&total, d_work + nwg, sizeof(total), hipMemcpyDeviceToHost) == hipSuccess && total <= (unsigned int)n &&
+    if (lab.ok() && hipMalloc(&d_keep, (size_t)n) == hipSuccess && lab.label((unsigned int)n, &d, d_keep) == 0 &&
+        hipMemcpy(&total, lab.d_total(), sizeof(total), hipMemcpyDeviceToHost) == hipSuccess && total <= (unsigned int)n &&
         hipMemcpy(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
-        hipMemcpy(kept.data(), d_out, (size_t)total * sizeof(AcgMsgRec), hipMemcpyDeviceToHost) == hipSuccess &&
-        hipMemcpy(ko.data(), d_oooi, (size_t)total * sizeof(acg_oooi), hipMemcpyDeviceToHost) == hipSuccess) {
+        hipMemcpy(kept.data(), lab.d_out, (size_t)total * sizeof(AcgMsgRec), hipMemcpyDeviceToHost) == hipSuccess &&
+        hipMemcpy(ko.data(), lab.d_oooi, (size_t)total * sizeof(acg_oooi), hipMemcpyDeviceToHost) == hipSuccess) {
         // the compaction's own check: the kept records, in input order, and nothing else
         rc = ACG_OK;
         unsigned int j = 0;
         for (int i = 0; i < n; ++i) {
             std::memset(&oooi[i], 0, sizeof(acg_oooi));
             if (!keep[i]) continue;
-            if (j >= total || std::memcmp(&kept[j], &h[i], sizeof(AcgMsgRec)) != 0) rc = ACG_ESTATE;
+            if (j >= total || std::memcmp(&kept[j], &lab.h[i], sizeof(AcgMsgRec)) != 0) rc = ACG_ESTATE;
             else oooi[i] = ko[j];
             ++j;
         }
         if (j != total) rc = ACG_ESTATE;
     }
-    hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work); hipFree(d_keep);
+    hipFree(d_keep);
     return rc;
 }
 
@@ -1641,61 +1681,68 @@ extern "C" int acg_selftest_flights(const acg_msg* in, const int* batch, int nba
     AcgFlights* t = nullptr;
     int rc = acg_fl_create(&t, cfg);
     if (rc != ACG_OK) return rc;
-    std::vector<AcgMsgRec> h(std::max<size_t>(biggest, 1));
-    AcgMsgRec *d_in = nullptr, *d_out = nullptr;
-    acg_oooi* d_oooi = nullptr;
-    unsigned int* d_work = nullptr;
-    const size_t nwg = biggest / 256 + 1, by = std::max<size_t>(biggest, 1) * sizeof(AcgMsgRec);
-    if (hipMalloc(&d_in, by) != hipSuccess || hipMalloc(&d_out, by) != hipSuccess ||
-        hipMalloc(&d_oooi, std::max<size_t>(biggest, 1) * sizeof(acg_oooi)) != hipSuccess ||
-        hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) != hipSuccess)
-        rc = ACG_ENOMEM;
-    size_t at = 0;
-    int snap_at = 0;
-    for (int b = 0; b < nbatch && rc == ACG_OK; ++b) {
-        const unsigned int n = (unsigned int)batch[b];
-        for (unsigned int i = 0; i < n; ++i) {                    // the public record back into the device's form
-            std::memcpy(&h[i], &in[at + i], sizeof(AcgMsgRec));
-            h[i].valid = 1;
-            h[i].soh_back = (int)(in[at + i].end_sample - in[at + i].soh_sample);
+    {
+        LabStage lab(biggest);
+        if (!lab.ok()) rc = ACG_ENOMEM;
+        size_t at = 0;
+        int snap_at = 0;
+        for (int b = 0; b < nbatch && rc == ACG_OK; ++b) {
+            const unsigned int n = (unsigned int)batch[b];
+            lab.stage(in + at, n, false, true);
+            at += n;
+            if (n) {
+                const AcgFlightPass* fp = nullptr;
+                rc = acg_fl_prepare(t, n, nullptr, &fp);
+                if (rc == ACG_OK && lab.label(n, &d, nullptr, fp) != 0) rc = ACG_EHIP;
+            }
+            if (rc == ACG_OK) {
+                rc = acg_fl_snapshot(t, nullptr, snaps + snap_at, snap_cap - snap_at, &snap_n[b], dropped);
+                if (rc == ACG_OK) snap_at += snap_n[b];
+            }
         }
-        at += n;
-        if (n) {
-            AcgLabelPass pass{&d, d_work, d_out, d_oooi, d_work + nwg, nullptr, nullptr};
-            rc = acg_fl_prepare(t, n, nullptr, &pass.flights);
-            if (rc == ACG_OK && (hipMemcpy(d_in, h.data(), (size_t)n * sizeof(AcgMsgRec), hipMemcpyHostToDevice) != hipSuccess ||
-                                 acg_launch_msg_split(nullptr, 0, 0, n, d_in, nullptr, &pass) != 0))
-                rc = ACG_EHIP;
-        }
-        if (rc == ACG_OK) {
-            rc = acg_fl_snapshot(t, nullptr, snaps + snap_at, snap_cap - snap_at, &snap_n[b], dropped);
-            if (rc == ACG_OK) snap_at += snap_n[b];
-        }
+        if (rc == ACG_OK) rc = acg_fl_drain_routes(t, nullptr, routes, route_cap, nroutes);
     }
-    if (rc == ACG_OK) rc = acg_fl_drain_routes(t, nullptr, routes, route_cap, nroutes);
-    hipDeviceSynchronize();
-    hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
     acg_fl_destroy(t);
     return rc;
 }
 
-// ---- the JSON sink (json.hip): buildjson()'s lines rendered on the device ---------------------------------------------------
+// ---- the device renderers of the batch sink (json.hip: buildjson()'s lines; text.hip: printoneline(), printmsg(), Netoutpp(),
+// Netoutsv()): one host runtime.  A format supplies its descriptor, the check of its configuration, what it renders once on the
+// host (its AcgJsonDev / AcgTextDev and the channels' frequency tokens) and the argument checks of its entry points.
 static_assert(ACG_JS_LINE_MAX == ACG_JSON_LINE_MAX, "line bound");
-// the work space of a device renderer (json.hip, text.hip): sort keys, lengths, offsets and the rendered bytes
-struct AcgSinkWork {
+static_assert(ACG_TX_REC_MAX == ACG_TEXT_REC_MAX, "record bound");
+
+struct AcgSinkFormat {
+    const char* name;                       // the first word of the shared messages
+    const char* is_off;                     // what a fetch says while the sink is off
+    size_t rec_max;                         // the longest record
+    unsigned int max_take;                  // the most records one pass takes: their offsets are 32-bit
+    int (*launch)(const AcgSinkPass*, void*);   // null: the unit is not in this build
+    bool offsets;                           // the entry points hand out the table of the records' offsets
+};
+static const AcgSinkFormat SINK_JSON = {"JSON", "JSON sink is off: acg_json_enable first", ACG_JSON_LINE_MAX, (1u << 31) / ACG_JSON_LINE_MAX,
+                                        acg_launch_json, false};
+static const AcgSinkFormat SINK_TEXT = {"text", "text sink is off: acg_text_enable first", ACG_TEXT_REC_MAX, (1u << 31) / ACG_TEXT_REC_MAX,
+                                        acg_launch_text, true};
+
+static int sink_fail(acg_ctx* ctx, int code, const AcgSinkFormat* fmt, const char* rest)
+{
+    return fail(ctx, code, (std::string(fmt->name) + rest).c_str());
+}
+
+// a sink: its format, its configuration on the device and its work space (sort keys, lengths, offsets and the rendered bytes)
+struct AcgSinkState {
+    const AcgSinkFormat* fmt = nullptr;
+    void* d_cfg = nullptr;                  // AcgJsonDev / AcgTextDev
+    unsigned char* d_freq = nullptr;        // [nch] frequency tokens: [8] "%3.3f" / [ACG_TX_FREQ_SLOT] "F:%3.3f "
+    unsigned int* d_cnt = nullptr;          // [4]: bytes, records of the last pass; the level guard
     size_t cap = 0;                         // records the work space below holds
     unsigned long long *d_key = nullptr, *d_key_s = nullptr;
     unsigned int *d_idx = nullptr, *d_idx_s = nullptr, *d_len = nullptr, *d_off = nullptr, *d_wg = nullptr;
-    unsigned char* d_out = nullptr;         // cap * (the longest record) bytes
+    unsigned char* d_out = nullptr;         // cap * fmt->rec_max bytes
 };
 
-struct AcgJsonState : AcgSinkWork {
-    AcgJsonDev* d_cfg = nullptr;            // the constant stretches of a line, escaped by acg_json_enable
-    unsigned char* d_freq = nullptr;        // [nch][8] "%3.3f" tokens
-    unsigned int* d_cnt = nullptr;          // [4]: bytes, lines of the last pass; the level guard
-};
-
-static void sink_free_work(AcgSinkWork* st)
+static void sink_free_work(AcgSinkState* st)
 {
     hipFree(st->d_key); hipFree(st->d_key_s); hipFree(st->d_idx); hipFree(st->d_idx_s); hipFree(st->d_len); hipFree(st->d_off);
     hipFree(st->d_wg); hipFree(st->d_out);
@@ -1705,7 +1752,7 @@ static void sink_free_work(AcgSinkWork* st)
     st->cap = 0;
 }
 
-static void json_destroy(AcgJsonState* st)
+static void sink_destroy(AcgSinkState* st)
 {
     if (!st) return;
     sink_free_work(st);
@@ -1713,6 +1760,189 @@ static void json_destroy(AcgJsonState* st)
     delete st;
 }
 
+// what a format renders once on the host
+struct SinkBlob {
+    int rc = ACG_OK;                        // ACG_EINVAL: a stretch does not fit (cannot happen); sink_create hands it on
+    std::vector<unsigned char> cfg, freq;
+};
+
+// ACG_OK, ACG_ENOMEM or ACG_EHIP (or the blob's own verdict)
+static int sink_create(AcgSinkState** out, const AcgSinkFormat* fmt, const SinkBlob& blob)
+{
+    if (blob.rc != ACG_OK) return blob.rc;
+    AcgSinkState* st = new (std::nothrow) AcgSinkState();
+    if (!st) return ACG_ENOMEM;
+    st->fmt = fmt;
+    if (hipMalloc(&st->d_cfg, blob.cfg.size()) != hipSuccess || hipMalloc(&st->d_freq, blob.freq.size()) != hipSuccess ||
+        hipMalloc(&st->d_cnt, 4 * sizeof(unsigned int)) != hipSuccess) {
+        sink_destroy(st);
+        return ACG_ENOMEM;
+    }
+    if (hipMemcpy(st->d_cfg, blob.cfg.data(), blob.cfg.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(st->d_freq, blob.freq.data(), blob.freq.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(st->d_cnt, 0, 4 * sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        sink_destroy(st);
+        return ACG_EHIP;
+    }
+    *out = st;
+    return ACG_OK;
+}
+
+// work space and output buffer for n records, grown on demand as d_kmsgs is
+static int sink_reserve(AcgSinkState* st, size_t n)
+{
+    if (n <= st->cap) return ACG_OK;
+    sink_free_work(st);
+    const size_t want = std::max<size_t>(n, 4096);
+    if (hipMalloc(&st->d_key, want * 8) != hipSuccess || hipMalloc(&st->d_key_s, want * 8) != hipSuccess ||
+        hipMalloc(&st->d_idx, want * 4) != hipSuccess || hipMalloc(&st->d_idx_s, want * 4) != hipSuccess ||
+        hipMalloc(&st->d_len, want * 4) != hipSuccess || hipMalloc(&st->d_off, want * 4) != hipSuccess ||
+        hipMalloc(&st->d_wg, 2 * (want / 256 + 1) * 4) != hipSuccess || hipMalloc(&st->d_out, want * st->fmt->rec_max) != hipSuccess) {
+        sink_free_work(st);
+        return ACG_ENOMEM;
+    }
+    st->cap = want;
+    return ACG_OK;
+}
+
+static AcgSinkPass sink_pass(const AcgSinkState* st, const AcgMsgRec* recs, const void* oooi, const unsigned int* total, unsigned int nmax, bool lvl_from_rec)
+{
+    AcgSinkPass p;
+    std::memset(&p, 0, sizeof(p));
+    p.recs = recs;
+    p.oooi = (const unsigned char*)oooi;
+    p.total = total;
+    p.nmax = nmax;
+    p.cfg = st->d_cfg;
+    p.freq = st->d_freq;
+    p.lvl_from_rec = lvl_from_rec ? 1 : 0;
+    p.key = st->d_key; p.key_s = st->d_key_s;
+    p.idx = st->d_idx; p.idx_s = st->d_idx_s;
+    p.len = st->d_len; p.off = st->d_off;
+    p.wg_sum = st->d_wg; p.wg_cnt = st->d_wg + (st->cap / 256 + 1);
+    p.counters = st->d_cnt;
+    p.out = st->d_out;
+    p.out_cap = (unsigned int)std::min<size_t>(st->cap * st->fmt->rec_max, 0xffffffffu);
+    return p;
+}
+
+// What acg_json_enable and acg_text_enable share, behind the check of their configuration: the old sink leaves behind a stream
+// sync; blob == null leaves the sink off
+static int sink_enable(acg_ctx* ctx, AcgSinkState** slot, const AcgSinkFormat* fmt, const SinkBlob* blob)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    if (*slot) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+        sink_destroy(*slot);
+        *slot = nullptr;
+    }
+    if (!blob) return ACG_OK;
+    if (!fmt->launch) return sink_fail(ctx, ACG_ESTATE, fmt, " sink: not in this build");
+    if (!ctx->d_crctab) return sink_fail(ctx, ACG_ESTATE, fmt, " sink: context created without ACG_F_REPAIR");
+    if (ctx->cfg.nch > (1 << 20)) return sink_fail(ctx, ACG_EINVAL, fmt, " sink: more than 2^20 channels");
+    const int rc = sink_create(slot, fmt, *blob);
+    return rc == ACG_OK ? rc : sink_fail(ctx, rc, fmt, " sink: allocation failed");
+}
+
+// fetch_msgs' sibling: the same claim, split, label pass and flight pass; then the renderer's passes on the same stream, and only
+// the packed records, two counters and (offs != null) the table of the records' offsets cross to the host.  A block yields at
+// most one record of at most rec_max bytes: the oldest min(max_recs, cap / rec_max) always fit.
+static int sink_fetch(acg_ctx* ctx, const AcgSinkFormat* fmt, AcgSinkState* st, int lag, char* out, size_t cap, size_t* nbytes, unsigned int* offs,
+                      int max_recs, int* nrecs)
+{
+    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
+    if (!st) return fail(ctx, ACG_ESTATE, fmt->is_off);
+    const size_t fit = std::min<size_t>(std::min<size_t>(cap / fmt->rec_max, (size_t)max_recs), fmt->max_take);
+    unsigned int upto = 0, pending = 0, take = 0;
+    bool any = false;
+    int rc = ring_upto(ctx, lag, &upto, &any);
+    if (rc != ACG_OK || !any) return rc;
+    rc = ring_claim(ctx, upto, (int)fit, &pending, &take);
+    if (!take) return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
+    if (const int gr = grow_msg_stage(ctx, take)) return gr;
+    if (const int gr = grow_label_stage(ctx, take)) return gr;
+    if (sink_reserve(st, take) != ACG_OK) return fail(ctx, ACG_ENOMEM, "sink: work space");
+    unsigned int* d_total = nullptr;
+    if (const int lr = launch_split(ctx, take, true, &d_total)) return lr;
+    const AcgSinkPass sp = sink_pass(st, ctx->d_kmsgs, ctx->d_oooi, d_total, take, false);
+    if (fmt->launch(&sp, ctx->copy_stream) != 0) return sink_fail(ctx, ACG_EHIP, fmt, " pass launch failed");
+    unsigned int cnt[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(cnt, st->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->copy_stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    if (cnt[0] > cap || cnt[1] > take || (size_t)cnt[0] > (size_t)take * fmt->rec_max) return sink_fail(ctx, ACG_EHIP, fmt, " pass: counts out of range");
+    if (cnt[0]) {                                                 // (kept records sort in front of dropped ones: the first cnt[1] offsets)
+        HIPCHK(ctx, hipMemcpyAsync(out, st->d_out, cnt[0], hipMemcpyDeviceToHost, ctx->copy_stream));
+        if (offs) HIPCHK(ctx, hipMemcpyAsync(offs, st->d_off, (size_t)cnt[1] * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->copy_stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    }
+    if (offs) offs[cnt[1]] = cnt[0];
+    ctx->consumed += take;
+    *nbytes = cnt[0];
+    *nrecs = (int)cnt[1];
+    return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
+}
+
+static int sink_level_guard(acg_ctx* ctx, const AcgSinkFormat* fmt, const AcgSinkState* st, unsigned int* near_midpoint)
+{
+    *near_midpoint = 0;
+    if (!st) return sink_fail(ctx, ACG_ESTATE, fmt, " sink is off");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    HIPCHK(ctx, hipMemcpy(near_midpoint, st->d_cnt + 2, sizeof(unsigned int), hipMemcpyDeviceToHost));
+    return ACG_OK;
+}
+
+// records a lab entry may hand to a renderer
+static bool sink_records_ok(const acg_msg* in, int n, int nch)
+{
+    for (int i = 0; i < n; ++i)
+        if (in[i].chn < 0 || in[i].chn >= nch || in[i].end_bit < 0 || in[i].end_bit >= (1ll << 44)) return false;
+    return true;
+}
+
+// the two sink selftests behind their argument checks: label pass and renderer over n records, no context
+static int sink_selftest(const AcgSinkFormat* fmt, const SinkBlob& blob, const acg_msg* in, int n, const acg_msg_filter* f, int nch, char* out, size_t cap,
+                         size_t* nbytes, unsigned int* offs, int* nrecs)
+{
+    AcgLabelFilter d;
+    if (label_filter_dev(f, &d) != ACG_OK || !sink_records_ok(in, n, nch)) return ACG_EINVAL;
+    *nbytes = 0;
+    *nrecs = 0;
+    if (n == 0) {
+        if (offs) offs[0] = 0;
+        return ACG_OK;
+    }
+    int ndev = 0;
+    if (!fmt->launch || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
+    AcgSinkState* st = nullptr;
+    int rc = sink_create(&st, fmt, blob);
+    if (rc != ACG_OK) return rc;
+    rc = sink_reserve(st, (size_t)n);
+    if (rc == ACG_OK) {
+        LabStage lab((size_t)n);
+        lab.stage(in, (unsigned int)n, true, true);
+        const AcgSinkPass sp = sink_pass(st, lab.d_out, lab.d_oooi, lab.d_total(), (unsigned int)n, true);
+        unsigned int cnt[2] = {0, 0};
+        if (!lab.ok()) rc = ACG_ENOMEM;
+        else if (lab.label((unsigned int)n, &d) != 0 || fmt->launch(&sp, nullptr) != 0 ||
+                 hipMemcpy(cnt, st->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess || cnt[1] > (unsigned int)n ||
+                 (size_t)cnt[0] > (size_t)n * fmt->rec_max)
+            rc = ACG_EHIP;
+        if (rc == ACG_OK) {
+            *nbytes = cnt[0];
+            *nrecs = (int)cnt[1];
+            if (cnt[0] > cap) rc = ACG_EAGAIN;
+            else if ((cnt[0] && hipMemcpy(out, st->d_out, cnt[0], hipMemcpyDeviceToHost) != hipSuccess) ||
+                     (offs && cnt[1] && hipMemcpy(offs, st->d_off, (size_t)cnt[1] * sizeof(unsigned int), hipMemcpyDeviceToHost) != hipSuccess))
+                rc = ACG_EHIP;
+            else if (offs) offs[cnt[1]] = cnt[0];
+        }
+    }
+    sink_destroy(st);
+    return rc;
+}
+
+// ---- the JSON sink: its configuration and entry points ------------------------------------------------------------------------
 // print_string_ptr's escaping (cJSON.c:828-950) of a C string, appended to dst; returns the new length
 static unsigned int json_escape(unsigned char* dst, unsigned int at, const char* s)
 {
@@ -1741,9 +1971,10 @@ static bool json_config_ok(const acg_json_config* c)
            std::memchr(c->app_ver, 0, sizeof(c->app_ver));
 }
 
-// ACG_OK, ACG_ENOMEM or ACG_EHIP; cfg has passed json_config_ok
-static int json_create(AcgJsonState** out, const acg_json_config* cfg, const int* Fr_hz, int nch)
+// the constant stretches of a line, escaped, and the channels' "%3.3f" tokens; cfg has passed json_config_ok
+static SinkBlob json_blob(const acg_json_config* cfg, const int* Fr_hz, int nch)
 {
+    SinkBlob b;
     AcgJsonDev h;
     std::memset(&h, 0, sizeof(h));
     h.t0_sec = cfg->t0_sec;
@@ -1759,258 +1990,67 @@ static int json_create(AcgJsonState** out, const acg_json_config* cfg, const int
     h.post_len = json_append(h.post, h.post_len, "\",\"ver\":\"");
     h.post_len = json_escape(h.post, h.post_len, cfg->app_ver);
     h.post_len = json_append(h.post, h.post_len, "\"}}\n");
-    if (h.pre_len > ACG_JS_PRE_MAX || h.post_len > ACG_JS_POST_MAX) return ACG_EINVAL;      // (cannot happen: 208 and 221)
-    std::vector<unsigned char> freq((size_t)nch * 8, 0);
+    if (h.pre_len > ACG_JS_PRE_MAX || h.post_len > ACG_JS_POST_MAX) b.rc = ACG_EINVAL;      // (cannot happen: 208 and 221)
+    b.cfg.assign((const unsigned char*)&h, (const unsigned char*)&h + sizeof(h));
+    b.freq.assign((size_t)nch * 8, 0);
     for (int c = 0; c < nch; ++c) {
         const float f = (float)((Fr_hz ? Fr_hz[c] : 0) / 1000000.0);                        // output.c:232
         char tmp[8];
         std::snprintf(tmp, sizeof(tmp), "%3.3f", f);                                        // output.c:248: cut to 7 characters
         const size_t n = std::strlen(tmp);
-        std::memcpy(&freq[(size_t)c * 8], tmp, n);
-        freq[(size_t)c * 8 + 7] = (unsigned char)n;
+        std::memcpy(&b.freq[(size_t)c * 8], tmp, n);
+        b.freq[(size_t)c * 8 + 7] = (unsigned char)n;
     }
-    AcgJsonState* st = new (std::nothrow) AcgJsonState();
-    if (!st) return ACG_ENOMEM;
-    if (hipMalloc(&st->d_cfg, sizeof(h)) != hipSuccess || hipMalloc(&st->d_freq, freq.size()) != hipSuccess ||
-        hipMalloc(&st->d_cnt, 4 * sizeof(unsigned int)) != hipSuccess) {
-        json_destroy(st);
-        return ACG_ENOMEM;
-    }
-    if (hipMemcpy(st->d_cfg, &h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(st->d_freq, freq.data(), freq.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(st->d_cnt, 0, 4 * sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        json_destroy(st);
-        return ACG_EHIP;
-    }
-    *out = st;
-    return ACG_OK;
-}
-
-// work space and output buffer for n records of at most rec_max bytes, grown on demand as d_kmsgs is
-static int sink_reserve(AcgSinkWork* st, size_t n, size_t rec_max)
-{
-    if (n <= st->cap) return ACG_OK;
-    sink_free_work(st);
-    const size_t want = std::max<size_t>(n, 4096);
-    if (hipMalloc(&st->d_key, want * 8) != hipSuccess || hipMalloc(&st->d_key_s, want * 8) != hipSuccess ||
-        hipMalloc(&st->d_idx, want * 4) != hipSuccess || hipMalloc(&st->d_idx_s, want * 4) != hipSuccess ||
-        hipMalloc(&st->d_len, want * 4) != hipSuccess || hipMalloc(&st->d_off, want * 4) != hipSuccess ||
-        hipMalloc(&st->d_wg, 2 * (want / 256 + 1) * 4) != hipSuccess || hipMalloc(&st->d_out, want * rec_max) != hipSuccess) {
-        sink_free_work(st);
-        return ACG_ENOMEM;
-    }
-    st->cap = want;
-    return ACG_OK;
-}
-
-// the most records one pass takes: their lines' offsets are 32-bit
-static constexpr unsigned int JSON_MAX_TAKE = (1u << 31) / ACG_JSON_LINE_MAX;
-
-static AcgJsonPass json_pass(const AcgJsonState* st, const AcgMsgRec* recs, const void* oooi, const unsigned int* total, unsigned int nmax, bool lvl_from_rec)
-{
-    AcgJsonPass p;
-    std::memset(&p, 0, sizeof(p));
-    p.recs = recs;
-    p.oooi = (const unsigned char*)oooi;
-    p.total = total;
-    p.nmax = nmax;
-    p.cfg = st->d_cfg;
-    p.freq = st->d_freq;
-    p.lvl_from_rec = lvl_from_rec ? 1 : 0;
-    p.key = st->d_key; p.key_s = st->d_key_s;
-    p.idx = st->d_idx; p.idx_s = st->d_idx_s;
-    p.len = st->d_len; p.off = st->d_off;
-    p.wg_sum = st->d_wg; p.wg_cnt = st->d_wg + (st->cap / 256 + 1);
-    p.counters = st->d_cnt;
-    p.out = st->d_out;
-    p.out_cap = (unsigned int)std::min<size_t>(st->cap * (size_t)ACG_JSON_LINE_MAX, 0xffffffffu);
-    return p;
+    return b;
 }
 
 extern "C" int acg_json_enable(acg_ctx* ctx, const acg_json_config* cfg, const int* Fr_hz)
 {
     if (!ctx) return ACG_EINVAL;
-    if (cfg && !json_config_ok(cfg)) return fail(ctx, ACG_EINVAL, "JSON sink: t0 outside [10^9, 4 * 10^9) s / 0..999999 us, or an unterminated string");
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (ctx->json) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-        json_destroy(ctx->json);
-        ctx->json = nullptr;
-    }
-    if (!cfg) return ACG_OK;
-    if (!acg_launch_json) return fail(ctx, ACG_ESTATE, "JSON sink: not in this build");
-    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "JSON sink: context created without ACG_F_REPAIR");
-    if (ctx->cfg.nch > (1 << 20)) return fail(ctx, ACG_EINVAL, "JSON sink: more than 2^20 channels");
-    const int rc = json_create(&ctx->json, cfg, Fr_hz, ctx->cfg.nch);
-    return rc == ACG_OK ? rc : fail(ctx, rc, "JSON sink: allocation failed");
+    if (!cfg) return sink_enable(ctx, &ctx->json, &SINK_JSON, nullptr);
+    if (!json_config_ok(cfg)) return fail(ctx, ACG_EINVAL, "JSON sink: t0 outside [10^9, 4 * 10^9) s / 0..999999 us, or an unterminated string");
+    const SinkBlob b = json_blob(cfg, Fr_hz, ctx->cfg.nch);
+    return sink_enable(ctx, &ctx->json, &SINK_JSON, &b);
 }
 
-// What fetch_json and fetch_text share with fetch_msgs' labelled path: the claim of the oldest blocks, the staging, the flight
-// table's preparation, and the split + label pass issued on the copy stream.  The renderer's passes hang on that stream next.
-struct SinkClaim {
-    int rc = ACG_OK;                        // what the entry point returns when there is nothing to render
-    int ring_rc = ACG_OK;                   // ring_claim's verdict, for ring_result
-    unsigned int pending = 0, take = 0;
-    unsigned int* d_total = nullptr;        // the label pass's count of kept records (a device word)
-};
-
-// work: the renderer's work space, grown here for the claimed blocks.  true: an error (k->rc says which).  false with k->take == 0: nothing to do, k->rc is the entry point's result.
-static bool sink_claim_and_label(acg_ctx* ctx, int lag, int max_take, AcgSinkWork* work, size_t rec_max, SinkClaim* k)
-{
-    unsigned int upto = 0;
-    bool any = false;
-    k->rc = ring_upto(ctx, lag, &upto, &any);
-    if (k->rc != ACG_OK) return true;
-    if (!any) return false;
-    k->ring_rc = ring_claim(ctx, upto, max_take, &k->pending, &k->take);
-    if (!k->take) {
-        k->rc = ring_result(ctx, k->ring_rc, k->pending, k->take, "more messages queued than fit: call again");
-        return false;
-    }
-    if ((k->rc = grow_msg_stage(ctx, k->take)) != ACG_OK) return true;
-    if ((k->rc = grow_label_stage(ctx, k->take)) != ACG_OK) return true;
-    if (sink_reserve(work, k->take, rec_max) != ACG_OK) { k->rc = fail(ctx, ACG_ENOMEM, "sink: work space"); return true; }
-    k->d_total = ctx->d_kwork + ctx->kmsgs_cap / 256 + 1;
-    AcgLabelPass pass{&ctx->msg_filter, ctx->d_kwork, ctx->d_kmsgs, ctx->d_oooi, k->d_total, nullptr, nullptr};
-    if (ctx->flights) {                                           // over exactly the blocks this call consumes, before -e drops any
-        const int fr = acg_fl_prepare(ctx->flights, k->take, ctx->copy_stream, &pass.flights);
-        if (fr != ACG_OK) { k->rc = fail(ctx, fr, "flight table: work space"); return true; }
-    }
-    if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, k->take, ctx->d_msgs, ctx->copy_stream, &pass) != 0) {
-        k->rc = fail(ctx, ACG_EHIP, "message split launch failed");
-        return true;
-    }
-    return false;
-}
-
-// fetch_msgs' sibling: the same claim, split, label pass and flight pass; then json.hip's passes on the same stream, and only
-// the packed lines and two counters cross to the host
-static int fetch_json(acg_ctx* ctx, int lag, char* out, size_t cap, size_t* nbytes, int* nlines)
-{
-    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
-    if (!ctx->json) return fail(ctx, ACG_ESTATE, "JSON sink is off: acg_json_enable first");
-    // a block yields at most one line of at most ACG_JSON_LINE_MAX bytes: the oldest cap / ACG_JSON_LINE_MAX blocks always fit
-    SinkClaim k;
-    if (sink_claim_and_label(ctx, lag, (int)std::min<size_t>(cap / ACG_JSON_LINE_MAX, JSON_MAX_TAKE), ctx->json, ACG_JSON_LINE_MAX, &k) || !k.take) return k.rc;
-    const unsigned int pending = k.pending, take = k.take;
-    const int rc = k.ring_rc;
-    unsigned int* d_total = k.d_total;
-    AcgJsonState* js = ctx->json;
-    const AcgJsonPass jp = json_pass(js, ctx->d_kmsgs, ctx->d_oooi, d_total, take, false);
-    if (acg_launch_json(&jp, ctx->copy_stream) != 0) return fail(ctx, ACG_EHIP, "JSON pass launch failed");
-    unsigned int cnt[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(cnt, js->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->copy_stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-    if (cnt[0] > cap || cnt[1] > take || (size_t)cnt[0] > (size_t)take * ACG_JSON_LINE_MAX) return fail(ctx, ACG_EHIP, "JSON pass: counts out of range");
-    if (cnt[0]) {
-        HIPCHK(ctx, hipMemcpyAsync(out, js->d_out, cnt[0], hipMemcpyDeviceToHost, ctx->copy_stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-    }
-    ctx->consumed += take;
-    *nbytes = cnt[0];
-    *nlines = (int)cnt[1];
-    return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
-}
-
-extern "C" int acg_collect_json(acg_ctx* ctx, int lag, char* out, size_t cap, size_t* nbytes, int* nlines)
-{
-    if (!ctx || !out || !nbytes || !nlines || lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
-    *nbytes = 0;
-    *nlines = 0;
-    if (cap < ACG_JSON_LINE_MAX) return fail(ctx, ACG_EINVAL, "JSON sink: the buffer holds less than one line (ACG_JSON_LINE_MAX)");
-    return fetch_json(ctx, lag, out, cap, nbytes, nlines);
-}
-
-extern "C" int acg_drain_json(acg_ctx* ctx, char* out, size_t cap, size_t* nbytes, int* nlines)
+static int json_args(acg_ctx* ctx, char* out, size_t cap, size_t* nbytes, int* nlines)
 {
     if (!ctx || !out || !nbytes || !nlines) return ACG_EINVAL;
     *nbytes = 0;
     *nlines = 0;
     if (cap < ACG_JSON_LINE_MAX) return fail(ctx, ACG_EINVAL, "JSON sink: the buffer holds less than one line (ACG_JSON_LINE_MAX)");
-    return fetch_json(ctx, DRAIN, out, cap, nbytes, nlines);
+    return ACG_OK;
+}
+
+extern "C" int acg_collect_json(acg_ctx* ctx, int lag, char* out, size_t cap, size_t* nbytes, int* nlines)
+{
+    if (lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
+    if (const int rc = json_args(ctx, out, cap, nbytes, nlines)) return rc;
+    return sink_fetch(ctx, &SINK_JSON, ctx->json, lag, out, cap, nbytes, nullptr, INT_MAX, nlines);
+}
+
+extern "C" int acg_drain_json(acg_ctx* ctx, char* out, size_t cap, size_t* nbytes, int* nlines)
+{
+    if (const int rc = json_args(ctx, out, cap, nbytes, nlines)) return rc;
+    return sink_fetch(ctx, &SINK_JSON, ctx->json, DRAIN, out, cap, nbytes, nullptr, INT_MAX, nlines);
 }
 
 extern "C" int acg_lab_json_level_guard(acg_ctx* ctx, unsigned int* near_midpoint)
 {
     if (!ctx || !near_midpoint) return ACG_EINVAL;
-    *near_midpoint = 0;
-    if (!ctx->json) return fail(ctx, ACG_ESTATE, "JSON sink is off");
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-    HIPCHK(ctx, hipMemcpy(near_midpoint, ctx->json->d_cnt + 2, sizeof(unsigned int), hipMemcpyDeviceToHost));
-    return ACG_OK;
+    return sink_level_guard(ctx, &SINK_JSON, ctx->json, near_midpoint);
 }
 
 extern "C" int acg_selftest_msg_json(const acg_msg* in, int n, const acg_msg_filter* f, const acg_json_config* cfg, const int* Fr_hz, int nch,
                                      char* out, size_t cap, size_t* nbytes, int* nlines)
 {
     if (n < 0 || (n > 0 && !in) || !json_config_ok(cfg) || nch < 1 || nch > (1 << 20) || !nbytes || !nlines || (cap > 0 && !out) ||
-        (unsigned int)n > JSON_MAX_TAKE)
+        (unsigned int)n > SINK_JSON.max_take)
         return ACG_EINVAL;
-    AcgLabelFilter d;
-    if (label_filter_dev(f, &d) != ACG_OK) return ACG_EINVAL;
-    for (int i = 0; i < n; ++i)
-        if (in[i].chn < 0 || in[i].chn >= nch || in[i].end_bit < 0 || in[i].end_bit >= (1ll << 44)) return ACG_EINVAL;
-    *nbytes = 0;
-    *nlines = 0;
-    if (n == 0) return ACG_OK;
-    int ndev = 0;
-    if (!acg_launch_json || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
-    std::vector<AcgMsgRec> h((size_t)n);
-    for (int i = 0; i < n; ++i) {                                  // the public record back into the device's form
-        std::memcpy(&h[i], &in[i], sizeof(AcgMsgRec));
-        h[i].valid = in[i].reserved2 ? 0 : 1;
-        h[i].soh_back = (int)(in[i].end_sample - in[i].soh_sample);
-    }
-    AcgJsonState* st = nullptr;
-    int rc = json_create(&st, cfg, Fr_hz, nch);
-    if (rc != ACG_OK) return rc;
-    rc = sink_reserve(st, (size_t)n, ACG_JSON_LINE_MAX);
-    const size_t by = (size_t)n * sizeof(AcgMsgRec), nwg = (size_t)n / 256 + 1;
-    AcgMsgRec *d_in = nullptr, *d_out = nullptr;
-    acg_oooi* d_oooi = nullptr;
-    unsigned int* d_work = nullptr;
-    if (rc == ACG_OK && (hipMalloc(&d_in, by) != hipSuccess || hipMalloc(&d_out, by) != hipSuccess ||
-                         hipMalloc(&d_oooi, (size_t)n * sizeof(acg_oooi)) != hipSuccess || hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) != hipSuccess))
-        rc = ACG_ENOMEM;
-    if (rc == ACG_OK) {
-        const AcgLabelPass pass{&d, d_work, d_out, d_oooi, d_work + nwg, nullptr, nullptr};
-        const AcgJsonPass jp = json_pass(st, d_out, d_oooi, d_work + nwg, (unsigned int)n, true);
-        unsigned int cnt[2] = {0, 0};
-        if (hipMemcpy(d_in, h.data(), by, hipMemcpyHostToDevice) != hipSuccess ||
-            acg_launch_msg_split(nullptr, 0, 0, (unsigned int)n, d_in, nullptr, &pass) != 0 || acg_launch_json(&jp, nullptr) != 0 ||
-            hipMemcpy(cnt, st->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess || cnt[1] > (unsigned int)n ||
-            (size_t)cnt[0] > (size_t)n * ACG_JSON_LINE_MAX)
-            rc = ACG_EHIP;
-        if (rc == ACG_OK) {
-            *nbytes = cnt[0];
-            *nlines = (int)cnt[1];
-            if (cnt[0] > cap) rc = ACG_EAGAIN;
-            else if (cnt[0] && hipMemcpy(out, st->d_out, cnt[0], hipMemcpyDeviceToHost) != hipSuccess) rc = ACG_EHIP;
-        }
-    }
-    hipDeviceSynchronize();
-    hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
-    json_destroy(st);
-    return rc;
+    return sink_selftest(&SINK_JSON, json_blob(cfg, Fr_hz, nch), in, n, f, nch, out, cap, nbytes, nullptr, nlines);
 }
 
-// ---- the text sink (text.hip): printoneline(), printmsg(), Netoutpp(), Netoutsv() rendered on the device ---------------------
-static_assert(ACG_TX_REC_MAX == ACG_TEXT_REC_MAX, "record bound");
-struct AcgTextState : AcgSinkWork {
-    AcgTextDev* d_cfg = nullptr;
-    unsigned char* d_freq = nullptr;        // [nch][ACG_TX_FREQ_SLOT] "F:%3.3f " tokens
-    unsigned int* d_cnt = nullptr;          // [4]: bytes, records of the last pass; the level guard
-};
-
-static void text_destroy(AcgTextState* st)
-{
-    if (!st) return;
-    sink_free_work(st);
-    hipFree(st->d_cfg); hipFree(st->d_freq); hipFree(st->d_cnt);
-    delete st;
-}
-
+// ---- the text sink: its configuration and entry points ------------------------------------------------------------------------
 static bool text_config_ok(const acg_text_config* c)
 {
     if (!c || c->format < ACG_TEXT_ONELINE || c->format > ACG_TEXT_SV) return false;
@@ -2019,9 +2059,10 @@ static bool text_config_ok(const acg_text_config* c)
            std::memchr(c->station_id, 0, sizeof(c->station_id));
 }
 
-// ACG_OK, ACG_ENOMEM or ACG_EHIP; cfg has passed text_config_ok
-static int text_create(AcgTextState** out, const acg_text_config* cfg, const int* Fr_hz, int nch)
+// format, flags, SV's station and the channels' "F:%3.3f " tokens; cfg has passed text_config_ok
+static SinkBlob text_blob(const acg_text_config* cfg, const int* Fr_hz, int nch)
 {
+    SinkBlob b;
     AcgTextDev h;
     std::memset(&h, 0, sizeof(h));
     h.t0_sec = cfg->t0_sec;
@@ -2031,103 +2072,28 @@ static int text_create(AcgTextState** out, const acg_text_config* cfg, const int
     h.flags = cfg->flags;
     char st8[40];
     h.station_len = (unsigned int)std::snprintf(st8, sizeof(st8), "%8s", cfg->station_id);      // netout.c:131
-    if (h.station_len > sizeof(h.station)) return ACG_EINVAL;                                    // (cannot happen: 32 characters)
+    if (h.station_len > sizeof(h.station)) { b.rc = ACG_EINVAL; return b; }                      // (cannot happen: 32 characters)
     std::memcpy(h.station, st8, h.station_len);
-    std::vector<unsigned char> freq((size_t)nch * ACG_TX_FREQ_SLOT, 0);
+    b.cfg.assign((const unsigned char*)&h, (const unsigned char*)&h + sizeof(h));
+    b.freq.assign((size_t)nch * ACG_TX_FREQ_SLOT, 0);
     for (int c = 0; c < nch; ++c) {
         char tmp[32];
         const int n = std::snprintf(tmp, sizeof(tmp), "F:%3.3f ", (Fr_hz ? Fr_hz[c] : 0) / 1000000.0);   // output.c:168-169: a double
-        if (n < 0 || n >= ACG_TX_FREQ_SLOT) return ACG_EINVAL;                                   // (cannot happen: an int's 12 characters)
-        std::memcpy(&freq[(size_t)c * ACG_TX_FREQ_SLOT], tmp, (size_t)n);
-        freq[(size_t)c * ACG_TX_FREQ_SLOT + ACG_TX_FREQ_SLOT - 1] = (unsigned char)n;
+        if (n < 0 || n >= ACG_TX_FREQ_SLOT) { b.rc = ACG_EINVAL; return b; }                     // (cannot happen: an int's 12 characters)
+        std::memcpy(&b.freq[(size_t)c * ACG_TX_FREQ_SLOT], tmp, (size_t)n);
+        b.freq[(size_t)c * ACG_TX_FREQ_SLOT + ACG_TX_FREQ_SLOT - 1] = (unsigned char)n;
     }
-    AcgTextState* st = new (std::nothrow) AcgTextState();
-    if (!st) return ACG_ENOMEM;
-    if (hipMalloc(&st->d_cfg, sizeof(h)) != hipSuccess || hipMalloc(&st->d_freq, freq.size()) != hipSuccess ||
-        hipMalloc(&st->d_cnt, 4 * sizeof(unsigned int)) != hipSuccess) {
-        text_destroy(st);
-        return ACG_ENOMEM;
-    }
-    if (hipMemcpy(st->d_cfg, &h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(st->d_freq, freq.data(), freq.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(st->d_cnt, 0, 4 * sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        text_destroy(st);
-        return ACG_EHIP;
-    }
-    *out = st;
-    return ACG_OK;
-}
-
-// the most records one pass takes: their offsets are 32-bit
-static constexpr unsigned int TEXT_MAX_TAKE = (1u << 31) / ACG_TEXT_REC_MAX;
-
-static AcgTextPass text_pass(const AcgTextState* st, const AcgMsgRec* recs, const void* oooi, const unsigned int* total, unsigned int nmax, bool lvl_from_rec)
-{
-    AcgTextPass p;
-    std::memset(&p, 0, sizeof(p));
-    p.recs = recs;
-    p.oooi = (const unsigned char*)oooi;
-    p.total = total;
-    p.nmax = nmax;
-    p.cfg = st->d_cfg;
-    p.freq = st->d_freq;
-    p.lvl_from_rec = lvl_from_rec ? 1 : 0;
-    p.key = st->d_key; p.key_s = st->d_key_s;
-    p.idx = st->d_idx; p.idx_s = st->d_idx_s;
-    p.len = st->d_len; p.off = st->d_off;
-    p.wg_sum = st->d_wg; p.wg_cnt = st->d_wg + (st->cap / 256 + 1);
-    p.counters = st->d_cnt;
-    p.out = st->d_out;
-    p.out_cap = (unsigned int)std::min<size_t>(st->cap * (size_t)ACG_TEXT_REC_MAX, 0xffffffffu);
-    return p;
+    return b;
 }
 
 extern "C" int acg_text_enable(acg_ctx* ctx, const acg_text_config* cfg, const int* Fr_hz)
 {
     if (!ctx) return ACG_EINVAL;
-    if (cfg && !text_config_ok(cfg))
+    if (!cfg) return sink_enable(ctx, &ctx->text, &SINK_TEXT, nullptr);
+    if (!text_config_ok(cfg))
         return fail(ctx, ACG_EINVAL, "text sink: unknown format, a flag the format does not take, t0 outside [10^9, 4 * 10^9) s / 0..999999 us, or an unterminated station_id");
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (ctx->text) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-        text_destroy(ctx->text);
-        ctx->text = nullptr;
-    }
-    if (!cfg) return ACG_OK;
-    if (!acg_launch_text) return fail(ctx, ACG_ESTATE, "text sink: not in this build");
-    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "text sink: context created without ACG_F_REPAIR");
-    if (ctx->cfg.nch > (1 << 20)) return fail(ctx, ACG_EINVAL, "text sink: more than 2^20 channels");
-    const int rc = text_create(&ctx->text, cfg, Fr_hz, ctx->cfg.nch);
-    return rc == ACG_OK ? rc : fail(ctx, rc, "text sink: allocation failed");
-}
-
-// fetch_json's sibling: text.hip's passes behind the shared claim / split / label / flight part; the packed records, their
-// offsets and two counters cross to the host
-static int fetch_text(acg_ctx* ctx, int lag, char* out, size_t cap, size_t* nbytes, unsigned int* offs, int max_recs, int* nrecs)
-{
-    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
-    if (!ctx->text) return fail(ctx, ACG_ESTATE, "text sink is off: acg_text_enable first");
-    // a block yields at most one record of at most ACG_TEXT_REC_MAX bytes: the oldest min(max_recs, cap / ACG_TEXT_REC_MAX) always fit
-    const size_t fit = std::min<size_t>(std::min<size_t>(cap / ACG_TEXT_REC_MAX, (size_t)max_recs), TEXT_MAX_TAKE);
-    SinkClaim k;
-    if (sink_claim_and_label(ctx, lag, (int)fit, ctx->text, ACG_TEXT_REC_MAX, &k) || !k.take) return k.rc;
-    AcgTextState* ts = ctx->text;
-    const AcgTextPass tp = text_pass(ts, ctx->d_kmsgs, ctx->d_oooi, k.d_total, k.take, false);
-    if (acg_launch_text(&tp, ctx->copy_stream) != 0) return fail(ctx, ACG_EHIP, "text pass launch failed");
-    unsigned int cnt[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(cnt, ts->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->copy_stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-    if (cnt[0] > cap || cnt[1] > k.take || (size_t)cnt[0] > (size_t)k.take * ACG_TEXT_REC_MAX) return fail(ctx, ACG_EHIP, "text pass: counts out of range");
-    if (cnt[1]) {                                                 // (kept records sort in front of dropped ones: the first cnt[1] offsets)
-        HIPCHK(ctx, hipMemcpyAsync(out, ts->d_out, cnt[0], hipMemcpyDeviceToHost, ctx->copy_stream));
-        HIPCHK(ctx, hipMemcpyAsync(offs, ts->d_off, (size_t)cnt[1] * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->copy_stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-    }
-    offs[cnt[1]] = cnt[0];
-    ctx->consumed += k.take;
-    *nbytes = cnt[0];
-    *nrecs = (int)cnt[1];
-    return ring_result(ctx, k.ring_rc, k.pending, k.take, "more messages queued than fit: call again");
+    const SinkBlob b = text_blob(cfg, Fr_hz, ctx->cfg.nch);
+    return sink_enable(ctx, &ctx->text, &SINK_TEXT, &b);
 }
 
 static int text_args(acg_ctx* ctx, char* out, size_t cap, size_t* nbytes, unsigned int* offs, int max_recs, int* nrecs)
@@ -2144,139 +2110,67 @@ extern "C" int acg_collect_text(acg_ctx* ctx, int lag, char* out, size_t cap, si
 {
     if (lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
     if (const int rc = text_args(ctx, out, cap, nbytes, offs, max_recs, nrecs)) return rc;
-    return fetch_text(ctx, lag, out, cap, nbytes, offs, max_recs, nrecs);
+    return sink_fetch(ctx, &SINK_TEXT, ctx->text, lag, out, cap, nbytes, offs, max_recs, nrecs);
 }
 
 extern "C" int acg_drain_text(acg_ctx* ctx, char* out, size_t cap, size_t* nbytes, unsigned int* offs, int max_recs, int* nrecs)
 {
     if (const int rc = text_args(ctx, out, cap, nbytes, offs, max_recs, nrecs)) return rc;
-    return fetch_text(ctx, DRAIN, out, cap, nbytes, offs, max_recs, nrecs);
+    return sink_fetch(ctx, &SINK_TEXT, ctx->text, DRAIN, out, cap, nbytes, offs, max_recs, nrecs);
 }
 
 extern "C" int acg_lab_text_level_guard(acg_ctx* ctx, unsigned int* near_midpoint)
 {
     if (!ctx || !near_midpoint) return ACG_EINVAL;
-    *near_midpoint = 0;
-    if (!ctx->text) return fail(ctx, ACG_ESTATE, "text sink is off");
-    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-    HIPCHK(ctx, hipMemcpy(near_midpoint, ctx->text->d_cnt + 2, sizeof(unsigned int), hipMemcpyDeviceToHost));
-    return ACG_OK;
+    return sink_level_guard(ctx, &SINK_TEXT, ctx->text, near_midpoint);
 }
 
 extern "C" int acg_selftest_msg_text(const acg_msg* in, int n, const acg_msg_filter* f, const acg_text_config* cfg, const int* Fr_hz, int nch,
                                      char* out, size_t cap, size_t* nbytes, unsigned int* offs, int* nrecs)
 {
     if (n < 0 || (n > 0 && !in) || !text_config_ok(cfg) || nch < 1 || nch > (1 << 20) || !nbytes || !nrecs || !offs || (cap > 0 && !out) ||
-        (unsigned int)n > TEXT_MAX_TAKE)
+        (unsigned int)n > SINK_TEXT.max_take)
         return ACG_EINVAL;
-    AcgLabelFilter d;
-    if (label_filter_dev(f, &d) != ACG_OK) return ACG_EINVAL;
-    for (int i = 0; i < n; ++i)
-        if (in[i].chn < 0 || in[i].chn >= nch || in[i].end_bit < 0 || in[i].end_bit >= (1ll << 44)) return ACG_EINVAL;
-    *nbytes = 0;
-    *nrecs = 0;
-    if (n == 0) { offs[0] = 0; return ACG_OK; }
-    int ndev = 0;
-    if (!acg_launch_text || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
-    std::vector<AcgMsgRec> h((size_t)n);
-    for (int i = 0; i < n; ++i) {                                  // the public record back into the device's form
-        std::memcpy(&h[i], &in[i], sizeof(AcgMsgRec));
-        h[i].valid = in[i].reserved2 ? 0 : 1;
-        h[i].soh_back = (int)(in[i].end_sample - in[i].soh_sample);
-    }
-    AcgTextState* st = nullptr;
-    int rc = text_create(&st, cfg, Fr_hz, nch);
-    if (rc != ACG_OK) return rc;
-    rc = sink_reserve(st, (size_t)n, ACG_TEXT_REC_MAX);
-    const size_t by = (size_t)n * sizeof(AcgMsgRec), nwg = (size_t)n / 256 + 1;
-    AcgMsgRec *d_in = nullptr, *d_out = nullptr;
-    acg_oooi* d_oooi = nullptr;
-    unsigned int* d_work = nullptr;
-    if (rc == ACG_OK && (hipMalloc(&d_in, by) != hipSuccess || hipMalloc(&d_out, by) != hipSuccess ||
-                         hipMalloc(&d_oooi, (size_t)n * sizeof(acg_oooi)) != hipSuccess || hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) != hipSuccess))
-        rc = ACG_ENOMEM;
-    if (rc == ACG_OK) {
-        const AcgLabelPass pass{&d, d_work, d_out, d_oooi, d_work + nwg, nullptr, nullptr};
-        const AcgTextPass tp = text_pass(st, d_out, d_oooi, d_work + nwg, (unsigned int)n, true);
-        unsigned int cnt[2] = {0, 0};
-        if (hipMemcpy(d_in, h.data(), by, hipMemcpyHostToDevice) != hipSuccess ||
-            acg_launch_msg_split(nullptr, 0, 0, (unsigned int)n, d_in, nullptr, &pass) != 0 || acg_launch_text(&tp, nullptr) != 0 ||
-            hipMemcpy(cnt, st->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess || cnt[1] > (unsigned int)n ||
-            (size_t)cnt[0] > (size_t)n * ACG_TEXT_REC_MAX)
-            rc = ACG_EHIP;
-        if (rc == ACG_OK) {
-            *nbytes = cnt[0];
-            *nrecs = (int)cnt[1];
-            if (cnt[0] > cap) rc = ACG_EAGAIN;
-            else if ((cnt[0] && hipMemcpy(out, st->d_out, cnt[0], hipMemcpyDeviceToHost) != hipSuccess) ||
-                     (cnt[1] && hipMemcpy(offs, st->d_off, (size_t)cnt[1] * sizeof(unsigned int), hipMemcpyDeviceToHost) != hipSuccess))
-                rc = ACG_EHIP;
-            else offs[cnt[1]] = cnt[0];
-        }
-    }
-    hipDeviceSynchronize();
-    hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
-    text_destroy(st);
-    return rc;
+    return sink_selftest(&SINK_TEXT, text_blob(cfg, Fr_hz, nch), in, n, f, nch, out, cap, nbytes, offs, nrecs);
 }
 
 extern "C" int acg_lab_time_sink_passes(const acg_msg* in, int n, const acg_json_config* jcfg, const acg_text_config* tcfg, int nch, int warmup,
                                         int reps, float* ms)
 {
     if (n < 1 || !in || !json_config_ok(jcfg) || !text_config_ok(tcfg) || nch < 1 || nch > (1 << 20) || warmup < 0 || reps < 1 || !ms ||
-        (unsigned int)n > std::min(JSON_MAX_TAKE, TEXT_MAX_TAKE))
+        (unsigned int)n > std::min(SINK_JSON.max_take, SINK_TEXT.max_take) || !sink_records_ok(in, n, nch))
         return ACG_EINVAL;
-    for (int i = 0; i < n; ++i)
-        if (in[i].chn < 0 || in[i].chn >= nch || in[i].end_bit < 0 || in[i].end_bit >= (1ll << 44)) return ACG_EINVAL;
     int ndev = 0;
     if (!acg_launch_json || !acg_launch_text || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
-    std::vector<AcgMsgRec> h((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        std::memcpy(&h[i], &in[i], sizeof(AcgMsgRec));
-        h[i].valid = in[i].reserved2 ? 0 : 1;
-        h[i].soh_back = (int)(in[i].end_sample - in[i].soh_sample);
-    }
-    AcgJsonState* js = nullptr;
-    AcgTextState* ts = nullptr;
+    AcgSinkState* st[2] = {nullptr, nullptr};                      // the arms: JSON, text
     AcgLabelFilter none;
     std::memset(&none, 0, sizeof(none));
-    const size_t by = (size_t)n * sizeof(AcgMsgRec), nwg = (size_t)n / 256 + 1;
-    AcgMsgRec *d_in = nullptr, *d_out = nullptr;
-    acg_oooi* d_oooi = nullptr;
-    unsigned int* d_work = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    int rc = json_create(&js, jcfg, nullptr, nch);
-    if (rc == ACG_OK) rc = text_create(&ts, tcfg, nullptr, nch);
-    if (rc == ACG_OK) rc = sink_reserve(js, (size_t)n, ACG_JSON_LINE_MAX);
-    if (rc == ACG_OK) rc = sink_reserve(ts, (size_t)n, ACG_TEXT_REC_MAX);
-    if (rc == ACG_OK && (hipMalloc(&d_in, by) != hipSuccess || hipMalloc(&d_out, by) != hipSuccess ||
-                         hipMalloc(&d_oooi, (size_t)n * sizeof(acg_oooi)) != hipSuccess || hipMalloc(&d_work, (nwg + 1) * sizeof(unsigned int)) != hipSuccess))
-        rc = ACG_ENOMEM;
-    if (rc == ACG_OK && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)) rc = ACG_EHIP;
+    int rc = sink_create(&st[0], &SINK_JSON, json_blob(jcfg, nullptr, nch));
+    if (rc == ACG_OK) rc = sink_create(&st[1], &SINK_TEXT, text_blob(tcfg, nullptr, nch));
+    if (rc == ACG_OK) rc = sink_reserve(st[0], (size_t)n);
+    if (rc == ACG_OK) rc = sink_reserve(st[1], (size_t)n);
     if (rc == ACG_OK) {
-        const AcgLabelPass pass{&none, d_work, d_out, d_oooi, d_work + nwg, nullptr, nullptr};
-        const AcgJsonPass jp = json_pass(js, d_out, d_oooi, d_work + nwg, (unsigned int)n, true);
-        const AcgTextPass tp = text_pass(ts, d_out, d_oooi, d_work + nwg, (unsigned int)n, true);
-        if (hipMemcpy(d_in, h.data(), by, hipMemcpyHostToDevice) != hipSuccess ||
-            acg_launch_msg_split(nullptr, 0, 0, (unsigned int)n, d_in, nullptr, &pass) != 0 || hipDeviceSynchronize() != hipSuccess)
-            rc = ACG_EHIP;
+        LabStage lab((size_t)n);
+        lab.stage(in, (unsigned int)n, true, true);
+        if (!lab.ok()) rc = ACG_ENOMEM;
+        if (rc == ACG_OK && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)) rc = ACG_EHIP;
+        if (rc == ACG_OK && (lab.label((unsigned int)n, &none) != 0 || hipDeviceSynchronize() != hipSuccess)) rc = ACG_EHIP;
         for (int r = -warmup; r < reps && rc == ACG_OK; ++r)
             for (int arm = 0; arm < 2 && rc == ACG_OK; ++arm) {
+                const AcgSinkPass sp = sink_pass(st[arm], lab.d_out, lab.d_oooi, lab.d_total(), (unsigned int)n, true);
                 float t = 0.0f;
-                if (hipEventRecord(ev[0], nullptr) != hipSuccess || (arm ? acg_launch_text(&tp, nullptr) : acg_launch_json(&jp, nullptr)) != 0 ||
+                if (hipEventRecord(ev[0], nullptr) != hipSuccess || st[arm]->fmt->launch(&sp, nullptr) != 0 ||
                     hipEventRecord(ev[1], nullptr) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess ||
                     hipEventElapsedTime(&t, ev[0], ev[1]) != hipSuccess)
                     rc = ACG_EHIP;
                 else if (r >= 0) ms[arm * reps + r] = t;
             }
     }
-    hipDeviceSynchronize();
     if (ev[0]) hipEventDestroy(ev[0]);
     if (ev[1]) hipEventDestroy(ev[1]);
-    hipFree(d_in); hipFree(d_out); hipFree(d_oooi); hipFree(d_work);
-    json_destroy(js);
-    text_destroy(ts);
+    sink_destroy(st[0]);
+    sink_destroy(st[1]);
     return rc;
 }
 

@@ -155,23 +155,6 @@ struct AcgJsonDev {
     unsigned char post[ACG_JS_POST_MAX];
 };
 
-struct AcgJsonPass {
-    const AcgMsgRec* recs;      // label.hip's kept records ...
-    const unsigned char* oooi;  // ... their acg_oooi ...
-    const unsigned int* total;  // ... and how many (a device word: the host does not know it when it launches)
-    unsigned int nmax;          // >= *total: what the grids and the work space are sized for
-    const AcgJsonDev* cfg;
-    const unsigned char* freq;  // [cfg->nch][8]: the "%3.3f" token of the channel (<= 7 chars), its length in byte 7
-    int lvl_from_rec;           // lab entry: the level is the record's lvl, not 10 log10(lvlsum / bitcount)
-    unsigned long long *key, *key_s;    // (chn, end_bit) and the sorted keys
-    unsigned int *idx, *idx_s;          // record index, and in sorted order
-    unsigned int *len, *off;            // per sorted rank: line length, byte offset
-    unsigned int *wg_sum, *wg_cnt;      // per 256 ranks: bytes, lines
-    unsigned int* counters;     // [0] bytes, [1] lines of this pass; [2] level guard (accumulates); [3] unused
-    unsigned char* out;         // nmax * ACG_JS_LINE_MAX bytes, 16-byte aligned
-    unsigned int out_cap;
-};
-
 // ---- the text renderer (text.hip): printoneline() / printmsg() (output.c:162-224,327-346), Netoutpp() / Netoutsv() (netout.c:101-140)
 #define ACG_TX_REC_MAX 704      // == ACG_TEXT_REC_MAX of the public header (derived there)
 #define ACG_TX_FREQ_SLOT 16     // "F:%3.3f " of a channel: at most 12 characters ("F:-2147.484 "), their count in byte 15
@@ -187,21 +170,21 @@ struct AcgTextDev {
     unsigned char station[32];
 };
 
-// as AcgJsonPass; off[] is the offset table the entry points hand out
-struct AcgTextPass {
-    const AcgMsgRec* recs;
-    const unsigned char* oooi;
-    const unsigned int* total;
-    unsigned int nmax;
-    const AcgTextDev* cfg;
-    const unsigned char* freq;  // [cfg->nch][ACG_TX_FREQ_SLOT]
-    int lvl_from_rec;
-    unsigned long long *key, *key_s;
-    unsigned int *idx, *idx_s;
-    unsigned int *len, *off;
-    unsigned int *wg_sum, *wg_cnt;
+// ---- one pass of a device renderer (json.hip, text.hip; the skeleton: sink_pack.h) over a call's kept records
+struct AcgSinkPass {
+    const AcgMsgRec* recs;      // label.hip's kept records ...
+    const unsigned char* oooi;  // ... their acg_oooi ...
+    const unsigned int* total;  // ... and how many (a device word: the host does not know it when it launches)
+    unsigned int nmax;          // >= *total: what the grids and the work space are sized for
+    const void* cfg;            // the unit's own AcgJsonDev / AcgTextDev
+    const unsigned char* freq;  // the channel's frequency token: [nch][8] "%3.3f" (<= 7 chars, length in byte 7) / [nch][ACG_TX_FREQ_SLOT]
+    int lvl_from_rec;           // lab entry: the level is the record's lvl, not 10 log10(lvlsum / bitcount)
+    unsigned long long *key, *key_s;    // (chn, end_bit) and the sorted keys
+    unsigned int *idx, *idx_s;          // record index, and in sorted order
+    unsigned int *len, *off;            // per sorted rank: record length, byte offset (text: the offset table handed out)
+    unsigned int *wg_sum, *wg_cnt;      // per 256 ranks: bytes, records
     unsigned int* counters;     // [0] bytes, [1] records of this pass; [2] level guard (accumulates); [3] unused
-    unsigned char* out;         // nmax * ACG_TX_REC_MAX bytes, 16-byte aligned
+    unsigned char* out;         // nmax * (the format's record bound) bytes, 16-byte aligned
     unsigned int out_cap;
 };
 
@@ -333,9 +316,9 @@ int acg_launch_sort_pairs(unsigned long long* ka, unsigned int* va, unsigned lon
 // json.hip: order, measure, scan and render the kept records of one label pass into p->out; p->counters says how much.
 // A WEAK reference, as flights.h's: the host runtime is also linked without the device units (the sanitizer build of
 // tests/test_host_logic.py, which stubs the launchers it knows); there the JSON sink is absent and acg_json_enable says ACG_ESTATE.
-__attribute__((weak)) int acg_launch_json(const AcgJsonPass* p, void* stream);
+__attribute__((weak)) int acg_launch_json(const AcgSinkPass* p, void* stream);
 // text.hip: the same for the text formats (weak for the same reason)
-__attribute__((weak)) int acg_launch_text(const AcgTextPass* p, void* stream);
+__attribute__((weak)) int acg_launch_text(const AcgSinkPass* p, void* stream);
 int acg_launch_sincos_selftest(const double* x, double* s, double* c, int n, const double* sctab, void* stream);
 int acg_launch_div2_selftest(const double* n0, const double* n1, const double* d, double* out, int n, void* stream);
 int acg_launch_synth_iq(uint8_t* iq, size_t pitch, int nrows, int nout, int decim, const float* env,

@@ -18,18 +18,14 @@
 // j-th character of a token.  Measure and render run the SAME function (json_line<false / true>): the length a line was given
 // room for is the length it is rendered with.
 //
-// THE SEAM, the scan, the record load and the level's float are shared with the text renderer (text.hip): sink_pack.h.
+// THE SEAM, the scan, the record load, the level's float, the bodies of the keys / measure / render kernels and the launch sequence
+// are shared with the text renderer (text.hip): sink_pack.h.  This unit supplies json_line and keeps its kernels as wrappers.
 //
 // No scratch (no indexed private array: a record's fields are read out of LDS, digits are computed, not stored), no per-byte
 // global traffic (a record comes in as 80 + 10 dword loads, the constant stretches as dwords, a line leaves as 16-byte stores and < 30 byte stores), two
 // independent waves per workgroup (2 x 2 944 B of LDS): these passes run beside a down-converter that saturates HBM.
 #include "sink_pack.h"
 #include "json_num.h"
-
-#define JS_WAVES 2
-#define JS_ROW (ACG_JS_LINE_MAX + 16)       // the line at offset (its output offset mod 16)
-#define JS_REC PK_REC
-#define JS_WG PK_WG
 
 static_assert(ACG_JS_LINE_MAX == ACG_JSON_LINE_MAX && ACG_JS_LINE_MAX % 64 == 0, "line bound");
 
@@ -124,10 +120,10 @@ __device__ __forceinline__ unsigned int put_str(unsigned char* row, unsigned int
 
 // One line.  R: the record and, at R + 320, its acg_oooi (LDS); row: where the line's first byte goes (W) or unused.
 template <bool W>
-__device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsigned char* row, const AcgJsonPass& p, int lane, bool* near_mid)
+__device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsigned char* row, const AcgSinkPass& p, int lane, bool* near_mid)
 {
     const AcgMsgRec* r = (const AcgMsgRec*)R;
-    const AcgJsonDev* cfg = p.cfg;
+    const AcgJsonDev* cfg = (const AcgJsonDev*)p.cfg;
     unsigned int pos = 0;
     // ---- "timestamp": tv = t0 + soh_sample / 12500 s in integers (a sample is exactly 80 us), as flight_extract_kernel
     const long long soh = r->end_sample - (long long)r->soh_back;
@@ -209,74 +205,57 @@ __device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsign
     return pos;
 }
 
-__global__ __launch_bounds__(JS_WG) void json_keys_kernel(AcgJsonPass p)
-{
-    const unsigned int i = blockIdx.x * JS_WG + threadIdx.x;
-    if (i >= p.nmax || i >= *p.total) return;
-    p.key[i] = pk_key(p.recs + i);
-    p.idx[i] = i;
-}
+// what this unit gives the passes' skeleton (sink_pack.h)
+struct JsonFmt {
+    static constexpr unsigned int REC_MAX = ACG_JS_LINE_MAX;
+    template <bool W>
+    static __device__ __forceinline__ unsigned int record(const unsigned char* R, unsigned char* row, const AcgSinkPass& p, int lane, bool* near_mid)
+    {
+        return json_line<W>(R, row, p, lane, near_mid);
+    }
+    static __device__ __forceinline__ unsigned char* row_at(unsigned char (*rows)[REC_MAX + 16], int wv, unsigned int off)
+    {
+        const unsigned int a = off & 15u;                         // the row mirrors the output's alignment (written in this order: sink_pack.h)
+        return rows[wv] + a;
+    }
+};
 
-__global__ __launch_bounds__(64 * JS_WAVES) void json_measure_kernel(AcgJsonPass p)
+// the passes (sink_pack.h): the kernels and their LDS are this unit's own
+__global__ __launch_bounds__(PK_WG) void json_keys_kernel(AcgSinkPass p) { pk_keys(p); }
+
+__global__ __launch_bounds__(64 * PK_WAVES) void json_measure_kernel(AcgSinkPass p)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char recs[JS_WAVES][JS_REC];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned int r = blockIdx.x * JS_WAVES + wv;                           // wave-uniform
-    if (r >= p.nmax || r >= *p.total) return;
+    __shared__ __attribute__((aligned(16))) unsigned char recs[PK_WAVES][PK_REC];
+    const unsigned int r = blockIdx.x * PK_WAVES + (threadIdx.x >> 6);        // wave-uniform
+    if (r >= p.nmax || r >= *p.total) return;                                    // (the early-outs are the kernel's: sink_pack.h, pk_measure)
     if (p.key_s[r] == ~0ull) {
-        if (lane == 0) p.len[r] = 0;
+        if ((threadIdx.x & 63) == 0) p.len[r] = 0;
         return;
     }
-    pk_load(recs[wv], p.recs, p.oooi, p.idx_s[r], lane);
-    bool nm;
-    const unsigned int n = json_line<false>(recs[wv], nullptr, p, lane, &nm);
-    if (lane == 0) p.len[r] = n > (unsigned int)ACG_JS_LINE_MAX ? (unsigned int)ACG_JS_LINE_MAX : n;
+    pk_measure<JsonFmt>(recs, p, r);
 }
 
-__global__ __launch_bounds__(JS_WG) void json_sum_kernel(AcgJsonPass p)
+__global__ __launch_bounds__(PK_WG) void json_sum_kernel(AcgSinkPass p)
 {
     __shared__ unsigned int sum_s;
     pk_sum(&sum_s, p.len, p.wg_sum, p.wg_cnt, p.nmax, p.total);
 }
 
-__global__ __launch_bounds__(JS_WG) void json_offsets_kernel(AcgJsonPass p)
+__global__ __launch_bounds__(PK_WG) void json_offsets_kernel(AcgSinkPass p)
 {
     __shared__ unsigned int base_s, cnt_s;
-    __shared__ unsigned int wave_n[JS_WG / 64];
+    __shared__ unsigned int wave_n[PK_WG / 64];
     pk_offsets(&base_s, &cnt_s, wave_n, p.len, p.off, p.wg_sum, p.wg_cnt, p.counters, p.nmax, p.total);
 }
 
-__global__ __launch_bounds__(64 * JS_WAVES) void json_render_kernel(AcgJsonPass p)
+__global__ __launch_bounds__(64 * PK_WAVES) void json_render_kernel(AcgSinkPass p)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char recs[JS_WAVES][JS_REC];
-    __shared__ __attribute__((aligned(16))) unsigned char rows[JS_WAVES][JS_ROW];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned int r = blockIdx.x * JS_WAVES + wv;                           // wave-uniform
-    if (r >= p.nmax || r >= *p.total) return;
-    const unsigned int len = p.len[r], off = p.off[r];
-    if (len == 0 || len > (unsigned int)ACG_JS_LINE_MAX || off > p.out_cap || len > p.out_cap - off) return;
-    pk_load(recs[wv], p.recs, p.oooi, p.idx_s[r], lane);
-    const unsigned int a = off & 15u;                                            // the row mirrors the output's alignment
-    bool near_mid;
-    const unsigned int n = json_line<true>(recs[wv], rows[wv] + a, p, lane, &near_mid);
-    if (n != len) return;                                                        // (cannot happen: one function measures and renders)
-    if (near_mid && lane == 0) atomicAdd(&p.counters[2], 1u);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    pk_flush_row(rows[wv], p.out, off, len, lane);
+    __shared__ __attribute__((aligned(16))) unsigned char recs[PK_WAVES][PK_REC];
+    __shared__ __attribute__((aligned(16))) unsigned char rows[PK_WAVES][JsonFmt::REC_MAX + 16];
+    pk_render<JsonFmt>(recs, rows, p);
 }
 
-extern "C" int acg_launch_json(const AcgJsonPass* p, void* stream)
+extern "C" int acg_launch_json(const AcgSinkPass* p, void* stream)
 {
-    if (p->nmax == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned int g = (p->nmax + JS_WG - 1) / JS_WG, gw = (p->nmax + JS_WAVES - 1) / JS_WAVES;
-    hipLaunchKernelGGL(json_keys_kernel, dim3(g), dim3(JS_WG), 0, s, *p);
-    int e = acg_launch_sort_pairs(p->key, p->idx, p->key_s, p->idx_s, p->total, 0u, stream);
-    if (e) return e;
-    hipLaunchKernelGGL(json_measure_kernel, dim3(gw), dim3(64 * JS_WAVES), 0, s, *p);
-    hipLaunchKernelGGL(json_sum_kernel, dim3(g), dim3(JS_WG), 0, s, *p);
-    hipLaunchKernelGGL(json_offsets_kernel, dim3(g), dim3(JS_WG), 0, s, *p);
-    hipLaunchKernelGGL(json_render_kernel, dim3(gw), dim3(64 * JS_WAVES), 0, s, *p);
-    return (int)hipGetLastError();
+    return pk_launch(p, stream, json_keys_kernel, json_measure_kernel, json_sum_kernel, json_offsets_kernel, json_render_kernel);
 }

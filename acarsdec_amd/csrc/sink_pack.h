@@ -1,12 +1,22 @@
 // sink_pack.h -- what the device renderers of the batch sink (json.hip, text.hip) have in common: a record and its acg_oooi into a
 // wave's LDS, the (chn, end_bit) sort key, the level's float and its guard, the two-launch exclusive scan of the record lengths
-// in sorted order, and the seam-safe flush of a wave's LDS row to its packed place in the output.  Device code only; every
-// function is inlined into the kernels of the unit that includes it, so each unit keeps kernels of its own.
+// in sorted order, the seam-safe flush of a wave's LDS row to its packed place in the output, and the skeleton of the passes.
+// Every device function is inlined into the kernels of the unit that includes it, so each unit keeps kernels of its own.
 //
 // THE SEAM.  Records are packed without padding, so two neighbours share a 16-byte chunk where they meet, and another wave writes
 // the neighbour.  No chunk is ever read back and merged: the row holds the record at the same offset mod 16 as its place in the
 // output, the first bytes up to the next 16-byte boundary and the last bytes behind the last one leave as BYTE stores, and only
 // chunks that lie wholly inside the record leave as 16-byte stores (LDS 16-byte reads, both sides aligned).
+//
+// THE SKELETON.  The bodies of the keys, measure and render kernels and the launch sequence are here too (pk_keys, pk_measure<F>,
+// pk_render<F>, pk_launch), written once over a format F that supplies
+//   F::REC_MAX                                   the longest record, a multiple of 64;
+//   F::record<W>(R, row, pass, lane, &near_mid)  the record's length; with W, its bytes at row (json_line, text_record);
+//   F::row_at(rows, wv, off)                     rows[wv] + off % 16: where wave wv's record starts in its row.  The same two
+//                                                operations in every unit; the order they are written in decides the order of two
+//                                                independent instructions of the render kernel, and each unit keeps its own.
+// A unit keeps its five __global__ kernels as thin wrappers (and with them its own names and __shared__ footprint; the measure
+// kernel also its two early-outs, see pk_measure) and its extern "C" launcher.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "acg_internal.h"
@@ -14,6 +24,7 @@
 
 #define PK_WG 256                           // threads of the keys / sum / offsets kernels
 #define PK_REC 384                          // the record (320 B) and its acg_oooi (40 B)
+#define PK_WAVES 2                          // independent waves (one record each) of a measure / render workgroup
 
 static_assert(sizeof(AcgMsgRec) == 320 && sizeof(acg_oooi) == 40 && sizeof(AcgMsgRec) + sizeof(acg_oooi) <= PK_REC, "record layout");
 
@@ -131,4 +142,61 @@ __device__ __forceinline__ void pk_flush_row(const unsigned char* row, unsigned 
     for (unsigned int x = a + lane; x < head_end; x += 64) dst[x] = row[x];      // (< 16 bytes, or < 31 when no chunk is whole)
     for (unsigned int x = tail_beg + lane; x < end; x += 64) dst[x] = row[x];
     for (unsigned int c = c0 + lane; c < c1; c += 64) ((uint4*)dst)[c] = ((const uint4*)row)[c];
+}
+
+// ---- the passes' bodies.  recs: PK_WAVES records of LDS; rows: PK_WAVES rows of F::REC_MAX + 16 bytes (the record at its output
+// offset mod 16), both 16-byte aligned and the calling kernel's own.
+__device__ __forceinline__ void pk_keys(const AcgSinkPass& p)
+{
+    const unsigned int i = blockIdx.x * PK_WG + threadIdx.x;
+    if (i >= p.nmax || i >= *p.total) return;
+    p.key[i] = pk_key(p.recs + i);
+    p.idx[i] = i;
+}
+
+// the wave's rank r has passed the kernel's own early-outs (out of range; a dropped record: length 0).  They stay in the kernel:
+// as returns inside an inlined function the compiler merges the two stores to len[r] and the kernel comes out longer.
+template <class F>
+__device__ __forceinline__ void pk_measure(unsigned char (*recs)[PK_REC], const AcgSinkPass& p, unsigned int r)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    pk_load(recs[wv], p.recs, p.oooi, p.idx_s[r], lane);
+    bool nm;
+    const unsigned int n = F::template record<false>(recs[wv], nullptr, p, lane, &nm);
+    if (lane == 0) p.len[r] = n > F::REC_MAX ? F::REC_MAX : n;
+}
+
+template <class F>
+__device__ __forceinline__ void pk_render(unsigned char (*recs)[PK_REC], unsigned char (*rows)[F::REC_MAX + 16], const AcgSinkPass& p)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned int r = blockIdx.x * PK_WAVES + wv;                           // wave-uniform
+    if (r >= p.nmax || r >= *p.total) return;
+    const unsigned int len = p.len[r], off = p.off[r];
+    if (len == 0 || len > F::REC_MAX || off > p.out_cap || len > p.out_cap - off) return;
+    pk_load(recs[wv], p.recs, p.oooi, p.idx_s[r], lane);
+    bool near_mid;
+    const unsigned int n = F::template record<true>(recs[wv], F::row_at(rows, wv, off), p, lane, &near_mid);
+    if (n != len) return;                                                        // (cannot happen: one function measures and renders)
+    if (near_mid && lane == 0) atomicAdd(&p.counters[2], 1u);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    pk_flush_row(rows[wv], p.out, off, len, lane);
+}
+
+// the launch sequence over a unit's five kernels, all on the stream of the label pass they hang on
+typedef void (*PkKernel)(AcgSinkPass);
+static inline int pk_launch(const AcgSinkPass* p, void* stream, PkKernel keys, PkKernel measure, PkKernel sum, PkKernel offsets, PkKernel render)
+{
+    if (p->nmax == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned int g = (p->nmax + PK_WG - 1) / PK_WG, gw = (p->nmax + PK_WAVES - 1) / PK_WAVES;
+    hipLaunchKernelGGL(keys, dim3(g), dim3(PK_WG), 0, s, *p);
+    int e = acg_launch_sort_pairs(p->key, p->idx, p->key_s, p->idx_s, p->total, 0u, stream);
+    if (e) return e;
+    hipLaunchKernelGGL(measure, dim3(gw), dim3(64 * PK_WAVES), 0, s, *p);
+    hipLaunchKernelGGL(sum, dim3(g), dim3(PK_WG), 0, s, *p);
+    hipLaunchKernelGGL(offsets, dim3(g), dim3(PK_WG), 0, s, *p);
+    hipLaunchKernelGGL(render, dim3(gw), dim3(64 * PK_WAVES), 0, s, *p);
+    return (int)hipGetLastError();
 }

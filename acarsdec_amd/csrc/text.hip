@@ -10,8 +10,8 @@
 // The passes are json.hip's, on the stream of the label pass they hang on: text_keys_kernel + flight.hip's sort, text_measure_kernel
 // (one WAVE per record: its length), text_sum_kernel / text_offsets_kernel (the exclusive scan in sorted order = the offset table),
 // text_render_kernel (one wave per record: the record assembled in a per-wave LDS row, flushed seam-safe).  Scan, flush, record
-// load, sort key and the level's float are shared with json.hip (sink_pack.h).  Measure and render run the SAME function
-// (text_record<false / true>).
+// load, sort key, the level's float, the kernels' bodies and the launch sequence are shared with json.hip (sink_pack.h); this unit
+// supplies text_record and keeps its kernels as wrappers.  Measure and render run the SAME function (text_record<false / true>).
 //
 // "%Ns" is a ballot and a find-first (the C string's end) and max(0, N - len) spaces in front; the text is four rounds of 64 lanes,
 // byte i at place i; lane j computes character j of a number or of the date (json_num.h, text_num.h).  No lane walks anything, no
@@ -19,9 +19,6 @@
 // loads, the channel's "F:" token as two quadwords, the station as dwords; a record leaves as 16-byte stores and < 30 byte stores).
 #include "sink_pack.h"
 #include "text_num.h"
-
-#define TX_WAVES 2
-#define TX_ROW (ACG_TX_REC_MAX + 16)        // the record at offset (its output offset mod 16)
 
 static_assert(ACG_TX_REC_MAX == ACG_TEXT_REC_MAX && ACG_TX_REC_MAX % 64 == 0, "record bound");
 
@@ -146,10 +143,10 @@ __device__ __forceinline__ unsigned int tx_words(unsigned char* row, unsigned in
 
 // One record.  R: the message and, at R + 320, its acg_oooi (LDS); row: where the record's first byte goes (W) or unused.
 template <bool W>
-__device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsigned char* row, const AcgTextPass& p, int lane, bool* near_mid)
+__device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsigned char* row, const AcgSinkPass& p, int lane, bool* near_mid)
 {
     const AcgMsgRec* r = (const AcgMsgRec*)R;
-    const AcgTextDev* cfg = p.cfg;
+    const AcgTextDev* cfg = (const AcgTextDev*)p.cfg;
     const int format = cfg->format;                               // (wave-uniform, as everything read from cfg and R)
     const unsigned int flags = cfg->flags;
     unsigned int pos = 0;
@@ -289,73 +286,56 @@ __device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsi
     return pos;
 }
 
-__global__ __launch_bounds__(PK_WG) void text_keys_kernel(AcgTextPass p)
-{
-    const unsigned int i = blockIdx.x * PK_WG + threadIdx.x;
-    if (i >= p.nmax || i >= *p.total) return;
-    p.key[i] = pk_key(p.recs + i);
-    p.idx[i] = i;
-}
+// what this unit gives the passes' skeleton (sink_pack.h)
+struct TextFmt {
+    static constexpr unsigned int REC_MAX = ACG_TX_REC_MAX;
+    template <bool W>
+    static __device__ __forceinline__ unsigned int record(const unsigned char* R, unsigned char* row, const AcgSinkPass& p, int lane, bool* near_mid)
+    {
+        return text_record<W>(R, row, p, lane, near_mid);
+    }
+    static __device__ __forceinline__ unsigned char* row_at(unsigned char (*rows)[REC_MAX + 16], int wv, unsigned int off)
+    {
+        return rows[wv] + (off & 15u);                            // the row mirrors the output's alignment (written in this order: sink_pack.h)
+    }
+};
 
-__global__ __launch_bounds__(64 * TX_WAVES) void text_measure_kernel(AcgTextPass p)
+// the passes (sink_pack.h): the kernels and their LDS are this unit's own
+__global__ __launch_bounds__(PK_WG) void text_keys_kernel(AcgSinkPass p) { pk_keys(p); }
+
+__global__ __launch_bounds__(64 * PK_WAVES) void text_measure_kernel(AcgSinkPass p)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char recs[TX_WAVES][PK_REC];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned int r = blockIdx.x * TX_WAVES + wv;                           // wave-uniform
-    if (r >= p.nmax || r >= *p.total) return;
+    __shared__ __attribute__((aligned(16))) unsigned char recs[PK_WAVES][PK_REC];
+    const unsigned int r = blockIdx.x * PK_WAVES + (threadIdx.x >> 6);        // wave-uniform
+    if (r >= p.nmax || r >= *p.total) return;                                    // (the early-outs are the kernel's: sink_pack.h, pk_measure)
     if (p.key_s[r] == ~0ull) {
-        if (lane == 0) p.len[r] = 0;
+        if ((threadIdx.x & 63) == 0) p.len[r] = 0;
         return;
     }
-    pk_load(recs[wv], p.recs, p.oooi, p.idx_s[r], lane);
-    bool nm;
-    const unsigned int n = text_record<false>(recs[wv], nullptr, p, lane, &nm);
-    if (lane == 0) p.len[r] = n > (unsigned int)ACG_TX_REC_MAX ? (unsigned int)ACG_TX_REC_MAX : n;
+    pk_measure<TextFmt>(recs, p, r);
 }
 
-__global__ __launch_bounds__(PK_WG) void text_sum_kernel(AcgTextPass p)
+__global__ __launch_bounds__(PK_WG) void text_sum_kernel(AcgSinkPass p)
 {
     __shared__ unsigned int sum_s;
     pk_sum(&sum_s, p.len, p.wg_sum, p.wg_cnt, p.nmax, p.total);
 }
 
-__global__ __launch_bounds__(PK_WG) void text_offsets_kernel(AcgTextPass p)
+__global__ __launch_bounds__(PK_WG) void text_offsets_kernel(AcgSinkPass p)
 {
     __shared__ unsigned int base_s, cnt_s;
     __shared__ unsigned int wave_n[PK_WG / 64];
     pk_offsets(&base_s, &cnt_s, wave_n, p.len, p.off, p.wg_sum, p.wg_cnt, p.counters, p.nmax, p.total);
 }
 
-__global__ __launch_bounds__(64 * TX_WAVES) void text_render_kernel(AcgTextPass p)
+__global__ __launch_bounds__(64 * PK_WAVES) void text_render_kernel(AcgSinkPass p)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char recs[TX_WAVES][PK_REC];
-    __shared__ __attribute__((aligned(16))) unsigned char rows[TX_WAVES][TX_ROW];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned int r = blockIdx.x * TX_WAVES + wv;                           // wave-uniform
-    if (r >= p.nmax || r >= *p.total) return;
-    const unsigned int len = p.len[r], off = p.off[r];
-    if (len == 0 || len > (unsigned int)ACG_TX_REC_MAX || off > p.out_cap || len > p.out_cap - off) return;
-    pk_load(recs[wv], p.recs, p.oooi, p.idx_s[r], lane);
-    bool near_mid;
-    const unsigned int n = text_record<true>(recs[wv], rows[wv] + (off & 15u), p, lane, &near_mid);   // the row mirrors the output's alignment
-    if (n != len) return;                                                        // (cannot happen: one function measures and renders)
-    if (near_mid && lane == 0) atomicAdd(&p.counters[2], 1u);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    pk_flush_row(rows[wv], p.out, off, len, lane);
+    __shared__ __attribute__((aligned(16))) unsigned char recs[PK_WAVES][PK_REC];
+    __shared__ __attribute__((aligned(16))) unsigned char rows[PK_WAVES][TextFmt::REC_MAX + 16];
+    pk_render<TextFmt>(recs, rows, p);
 }
 
-extern "C" int acg_launch_text(const AcgTextPass* p, void* stream)
+extern "C" int acg_launch_text(const AcgSinkPass* p, void* stream)
 {
-    if (p->nmax == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned int g = (p->nmax + PK_WG - 1) / PK_WG, gw = (p->nmax + TX_WAVES - 1) / TX_WAVES;
-    hipLaunchKernelGGL(text_keys_kernel, dim3(g), dim3(PK_WG), 0, s, *p);
-    int e = acg_launch_sort_pairs(p->key, p->idx, p->key_s, p->idx_s, p->total, 0u, stream);
-    if (e) return e;
-    hipLaunchKernelGGL(text_measure_kernel, dim3(gw), dim3(64 * TX_WAVES), 0, s, *p);
-    hipLaunchKernelGGL(text_sum_kernel, dim3(g), dim3(PK_WG), 0, s, *p);
-    hipLaunchKernelGGL(text_offsets_kernel, dim3(g), dim3(PK_WG), 0, s, *p);
-    hipLaunchKernelGGL(text_render_kernel, dim3(gw), dim3(64 * TX_WAVES), 0, s, *p);
-    return (int)hipGetLastError();
+    return pk_launch(p, stream, text_keys_kernel, text_measure_kernel, text_sum_kernel, text_offsets_kernel, text_render_kernel);
 }
