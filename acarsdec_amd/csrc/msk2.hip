@@ -111,11 +111,9 @@ __device__ __forceinline__ Decision decide(const float2 (*ring)[CPW], int slot, 
     div2_shared_rcp((double)vr, (double)vi, den, &qr, &qi);
     vr = (float)qr;
     vi = (float)qi;
-    // decision + phase detector, msk.c:115-121 (sign-bit arithmetic, see msk.hip)
-    d.vo = odd ? vi : vr;
-    const float ot = odd ? vr : vi;
-    const unsigned int flip = ((d.vo >= 0) == odd) ? 0x80000000u : 0u;
-    d.dphi = (double)__uint_as_float(__float_as_uint(ot) ^ flip);
+    const PhaseDet pd = phase_detect(odd ? 1u : 0u, vr, vi);               // msk.c:115-121
+    d.vo = pd.vo;
+    d.dphi = pd.dphi;
     return d;
 }
 
@@ -168,8 +166,7 @@ __global__ __launch_bounds__(128 * PAIRS) void msk_demod2_kernel(const MskArgs a
         int cont[2 * PAIRS];                     // per wave: some channel of mine still has a whole period ahead
     };
     __shared__ Lds lds;
-    for (int i = threadIdx.x; i < FLEN * MFLTOVER + 1; i += 128 * PAIRS) lds.hs[i] = a.h[i];
-    for (int i = threadIdx.x; i < 2 * ACG_SINCOS_N; i += 128 * PAIRS) lds.sc[i] = a.sctab[i];
+    lds_tables_load<128 * PAIRS>(lds.hs, lds.sc, a);
 
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int pair = wv >> 1;
@@ -208,14 +205,7 @@ __global__ __launch_bounds__(128 * PAIRS) void msk_demod2_kernel(const MskArgs a
         double p = st->phi, df = st->df;
         unsigned int idx = st->idx;
         bool odd = (st->S & 1u) != 0;
-        if (leader) {
-#pragma unroll
-            for (int j = 0; j < FLEN; ++j) {
-                const float2 x = make_float2(st->inb[2 * j], st->inb[2 * j + 1]);
-                P.ring[j][slot] = x;
-                P.ring[j + FLEN][slot] = x;
-            }
-        }
+        if (leader) ring_seed<CPW>(P.ring, slot, st);
         int n = 0;
         cont_post(n + 6 <= len);
         __syncthreads();                                                   // P0: tables, ring, window (H) are in place
@@ -291,7 +281,7 @@ __global__ __launch_bounds__(128 * PAIRS) void msk_demod2_kernel(const MskArgs a
                 const int c = vo > 0 ? 2 : (vo < 0 ? 1 : 0);
                 const bool reset = ((mg->verdict >> c) & 1) != 0;          // acars.c:242, inside putbit, before msk.c:130
                 const double dfb = reset ? 0.0 : df;
-                df = (double)0.52f * dfb + (1.0 - (double)0.52f) * (double)38e-4f * dphi;       // msk.c:130
+                df = loop_filter(dfb, dphi);
             }
             mg->df = df;
             cont_post(n + 6 <= len);
@@ -344,22 +334,13 @@ __global__ __launch_bounds__(128 * PAIRS) void msk_demod2_kernel(const MskArgs a
                     if (L.nbits <= 0) decode_acars(L, a, ch, txt, samp0 + n - 1, leader, &st->soh32);
                     L.nbit_total++;
                     L.S++;
-                    L.df = (double)0.52f * L.df + (1.0 - (double)0.52f) * (double)38e-4f * d.dphi;   // msk.c:130
+                    L.df = loop_filter(L.df, d.dphi);
                 }
             }
         }
         if (active && leader) {
-            st->phi = p; st->df = L.df; st->lvlsum = L.lvlsum;
-            st->clk = L.clk; st->bitcount = L.bitcount; st->S = L.S; st->idx = idx;
-            st->nbits = L.nbits; st->astate = L.astate; st->blen = L.blen; st->berr = L.berr;
-            st->outbits = L.outbits; st->crc0 = L.crc0; st->nbit_total = L.nbit_total;
-            st->nsamp_total = samp0 + len;
-#pragma unroll
-            for (int j = 0; j < FLEN; ++j) {
-                const float2 x = P.ring[j][slot];
-                st->inb[2 * j] = x.x;
-                st->inb[2 * j + 1] = x.y;
-            }
+            lane_store(st, L, p, idx, samp0, len);
+            ring_save<CPW>(st, P.ring, slot);
             a.nbits_out[ch] = nb;
         }
     } else {
@@ -467,23 +448,7 @@ __global__ __launch_bounds__(128 * PAIRS) void msk_demod2_kernel(const MskArgs a
                 const float sv = __uint_as_float(__float_as_uint(vo) ^ ((L.S & 2u) << 30));
                 bits[nb < bit_cap ? nb : bit_cap - 1] = make_float2(sv, lvl);
                 ++nb;
-                L.outbits = (L.outbits >> 1) & 0x7fu;
-                if (sv > 0) L.outbits |= 0x80u;
-                L.nbits--;
-                {
-                    const bool ev = L.nbits <= 0;
-                    const unsigned int r = L.outbits & 0xffu;
-                    const bool syn = (r == SYN) | (r == (0xffu & ~SYN));
-                    const bool hunt = ev & (L.astate == WSYN) & !syn;
-                    const bool term = (r == ETX) | (r == ETB) | (r == DLE);
-                    const bool plain = ev & (L.astate == TXT) & ((__popc(r) & 1) != 0) & !term & (L.blen < 240);
-                    txt[plain ? L.blen : 255] = (unsigned char)r;
-                    L.blen += plain ? 1 : 0;
-                    L.nbits = hunt ? 1 : (plain ? 8 : L.nbits);
-                    if (ev & !hunt & !plain) decode_acars(L, a, ch, txt, samp0 + prev_end - 1, leader, &st->soh32);
-                }
-                L.nbit_total++;
-                L.S++;
+                frame_bit(L, sv, a, ch, txt, samp0 + prev_end - 1, leader, &st->soh32);
             }
             // ---- verdict for THIS period's bit: would decodeAcars reset the loop (MskDf = 0) for either value of the bit?
             {
@@ -543,17 +508,9 @@ __global__ __launch_bounds__(128 * PAIRS) void msk_demod2_kernel(const MskArgs a
         }
         __syncthreads();                                                   // T1
     }
-    // the last workgroup out publishes the block-queue length of this launch (see msk.hip)
+    // the last workgroup out publishes the block-queue length of this launch
     __syncthreads();                                                       // T2: M's tail (it may queue blocks) is done
-    if (a.snap && threadIdx.x == 0) {
-        __threadfence();
-        const unsigned int d = atomicAdd(a.done_ctr, 1u);
-        if (d == gridDim.x - 1) {
-            const unsigned int c = __hip_atomic_load(a.frame_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.snap, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(a.done_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    publish_queue_length<1>(a);
 }
 
 extern "C" int acg_tune_has(const char* name);

@@ -1,6 +1,10 @@
-// msk_common.h -- device helpers shared by the demodulator kernels (msk.hip: one wave per channel group; msk2.hip: the
-// same stream split over two waves): constants of msk.c / acars.c, the framing state machine (acars.c:239-375), the mixer's
-// sin/cos, the loop's f64 quotients and square root.  Included by translation units built with -ffp-contract=off.
+// msk_common.h -- device helpers shared by the demodulator kernels (msk.hip: one wave per channel group; msk_lean.hip: the
+// same with the framing taken off the per-bit path; msk2.hip: the stream split over two waves): constants of msk.c / acars.c,
+// the channel state's way in and out of a launch, the LDS layout, the framing state machine (acars.c:239-375) and the one-bit
+// step in front of it, the phase detector and loop filter, the mixer's sin/cos, the loop's f64 quotients and square root.
+// Included by translation units built with -ffp-contract=off.
+// The kernels sit next to a register cliff and are bound by the instructions they issue: a helper here is used by a kernel
+// only where that kernel's instruction text is what it was with the piece spelled out (profiles/LEDGER.md).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "acg_internal.h"
@@ -31,6 +35,90 @@ struct Lane {
     unsigned int outbits, crc0;
     long long nbit_total;
 };
+
+// the channel's record -> the state a launch carries (the ring and nsamp_total go their own way)
+__device__ __forceinline__ void lane_load(Lane& L, const AcgChan* st)
+{
+    L.phi = st->phi; L.df = st->df; L.lvlsum = st->lvlsum;
+    L.clk = st->clk; L.bitcount = st->bitcount; L.S = st->S; L.idx = st->idx;
+    L.nbits = st->nbits; L.astate = st->astate; L.blen = st->blen; L.berr = st->berr;
+    L.outbits = st->outbits; L.crc0 = st->crc0; L.nbit_total = st->nbit_total;
+}
+
+// inb[] -> the ring in LDS, every sample twice (rows k and k + FLEN: the matched filter's 11 taps never wrap); one lane per channel
+template <int CPW>
+__device__ __forceinline__ void ring_seed(float2 (*ring)[CPW], int slot, const AcgChan* st)
+{
+#pragma unroll
+    for (int j = 0; j < FLEN; ++j) {
+        const float2 x = make_float2(st->inb[2 * j], st->inb[2 * j + 1]);
+        ring[j][slot] = x;
+        ring[j + FLEN][slot] = x;
+    }
+}
+
+// the state back into the channel's record after len samples more; p and idx are the loop's own copies of L.phi and L.idx; one
+// lane per channel.  (The sum is formed here, behind the stores in front of it, where the kernels had it: formed at the call it
+// is an instruction elsewhere in their write-back.)
+__device__ __forceinline__ void lane_store(AcgChan* st, const Lane& L, double p, unsigned int idx, long long samp0, int len)
+{
+    st->phi = p; st->df = L.df; st->lvlsum = L.lvlsum;
+    st->clk = L.clk; st->bitcount = L.bitcount; st->S = L.S; st->idx = idx;
+    st->nbits = L.nbits; st->astate = L.astate; st->blen = L.blen; st->berr = L.berr;
+    st->outbits = L.outbits; st->crc0 = L.crc0; st->nbit_total = L.nbit_total;
+    st->nsamp_total = samp0 + len;
+}
+
+// the ring -> inb[]; one lane per channel
+template <int CPW>
+__device__ __forceinline__ void ring_save(AcgChan* st, const float2 (*ring)[CPW], int slot)
+{
+#pragma unroll
+    for (int j = 0; j < FLEN; ++j) {
+        const float2 x = ring[j][slot];
+        st->inb[2 * j] = x.x;
+        st->inb[2 * j + 1] = x.y;
+    }
+}
+
+// the last workgroup out publishes the block-queue length of this launch to the host-mapped word of the call (no copy packet
+// on the launch chain; the host reads it after the call's event).  WPG: waves per workgroup that have not met yet
+template <int WPG>
+__device__ __forceinline__ void publish_queue_length(const MskArgs& a)
+{
+    if (a.snap) {
+        if (WPG > 1) __syncthreads();
+        if (threadIdx.x == 0) {
+            __threadfence();
+            const unsigned int d = atomicAdd(a.done_ctr, 1u);
+            if (d == gridDim.x - 1) {
+                const unsigned int c = __hip_atomic_load(a.frame_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(a.snap, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(a.done_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
+// LDS of the one-wave kernels.  inb[] of the wave's channels, every sample stored twice (k and k+FLEN) so that the 11 taps of
+// the matched filter are always 11 consecutive rows starting at idx: no wrap, constant offsets.
+// one struct = one layout: h[] first, so that its 11 reads h[o + 12 j] are immediate offsets (< 1 KiB) from the one
+// address o * 4 (placed after the ring, every pair of reads needed its own base register)
+template <int WPG, int CPW, int WSTR>
+struct alignas(16) MskLds {
+    float hs[(FLEN * MFLTOVER + 1 + 3) & ~3];
+    double sc[2 * ACG_SINCOS_N];               // (cos, sin)(j * 2 pi / 128): the mixer's table, 2 KiB
+    float2 ring_all[WPG][3 * FLEN + 1][CPW];   // rows 0..21: inb[] twice; rows 22 and 33: where lanes without a sample write
+    float win_all[WPG][CPW][WSTR];             // sliding window of dm: blocks j and j+1
+};
+
+// h[] and the mixer's table into LDS, by a workgroup of NT threads
+template <int NT>
+__device__ __forceinline__ void lds_tables_load(float* hs, double* sc, const MskArgs& a)
+{
+    for (int i = threadIdx.x; i < FLEN * MFLTOVER + 1; i += NT) hs[i] = a.h[i];
+    for (int i = threadIdx.x; i < 2 * ACG_SINCOS_N; i += NT) sc[i] = a.sctab[i];
+}
 
 __device__ __forceinline__ void reset_acars(Lane& L)          // acars.c:239-244
 {
@@ -137,6 +225,62 @@ __device__ __forceinline__ void decode_acars(Lane& L, const MskArgs& a, int ch, 
     }
 }
 
+// One decided bit through putbit (msk.c:53-63) and, when it closes a byte, decodeAcars (acars.c:246-375); sv is the soft bit
+// under MskS & 2.  Two cases cover nearly every call and are taken without a branch: hunting for sync with no SYN in sight
+// (acars.c:252-265, every bit of an idle channel) and a plain text byte -- good parity, no terminator, room left
+// (acars.c:303-341, every 8th bit of a channel inside a block).  Everything else (sync, SOH, parity errors, ETX/ETB/DLE, CRC
+// bytes, resets: a few per block) goes through the full state machine.
+__device__ __forceinline__ void frame_bit(Lane& L, float sv, const MskArgs& a, int ch, unsigned char* txt,
+                                          long long sample_index, bool leader, unsigned int* soh_slot)
+{
+    {
+        unsigned int ob = (L.outbits >> 1) & 0x7fu;
+        if (sv > 0) ob |= 0x80u;
+        L.outbits = ob;
+    }
+    L.nbits -= 1;
+    {
+        const bool ev = L.nbits <= 0;
+        const unsigned int r = L.outbits & 0xffu;
+        const bool syn = (r == SYN) | (r == (0xffu & ~SYN));
+        const bool hunt = ev & (L.astate == WSYN) & !syn;
+        const bool term = (r == ETX) | (r == ETB) | (r == DLE);
+        const bool plain = ev & (L.astate == TXT) & ((__popc(r) & 1) != 0) & !term & (L.blen < 240);
+        txt[plain ? L.blen : 255] = (unsigned char)r;          // byte 255 of the 256-byte text buffer is scratch (blen <= 241)
+        L.blen += plain ? 1 : 0;
+        L.nbits = hunt ? 1 : (plain ? 8 : L.nbits);
+        if (ev & !hunt & !plain) decode_acars(L, a, ch, txt, sample_index, leader, soh_slot);
+    }
+    L.nbit_total += 1;
+    L.S += 1u;
+}
+
+// decision + phase detector, msk.c:115-121, as sign-bit arithmetic (exact: only signs move):
+//   odd  S: vo = Im v, dphi = (vo >= 0) ? -Re v :  Re v
+//   even S: vo = Re v, dphi = (vo >= 0) ?  Im v : -Im v
+struct PhaseDet {
+    float vo;           // soft bit before the MskS & 2 sign
+    double dphi;
+};
+
+// (S, not its parity as a bool: handed over as a bool, the same operations come out of the compiler as other instructions)
+__device__ __forceinline__ PhaseDet phase_detect(unsigned int S, float vr, float vi)
+{
+    const bool odd = (S & 1) != 0;
+    PhaseDet d;
+    d.vo = odd ? vi : vr;
+    const float ot = odd ? vr : vi;
+    const unsigned int flip = ((d.vo >= 0) == odd) ? 0x80000000u : 0u;
+    d.dphi = (double)__uint_as_float(__float_as_uint(ot) ^ flip);
+    return d;
+}
+
+// PLL filter, msk.c:130 (float constants promoted to double)
+__device__ __forceinline__ double loop_filter(double df, double dphi)
+{
+    return (double)0.52f * df + (1.0 - (double)0.52f) * (double)38e-4f * dphi;
+}
+
 // sin/cos of x in [0, 2*pi) (any moderate |x| works): Cody-Waite reduction by pi/2 with a two-term
 // constant, then the classic minimax kernels on |r| <= pi/4 (coefficients: fdlibm k_sin.c/k_cos.c,
 // Sun Microsystems 1993, freely distributable; < 1 ulp).  The reference calls glibc's cexp (also
@@ -221,23 +365,10 @@ __device__ __forceinline__ void sincos_tab_entry(double x, const double* __restr
 __device__ __forceinline__ void sincos_tab_rotate(double r, double cj, double sj, double* sn, double* cs)
 {
     const double z = r * r;
-#ifdef ACG_MSK_AB_FMA3
-    // A/B build: the Horner steps as three-address v_fma_f64 with the constants as scalar / resident vector operands (left to the
-    // compiler each becomes v_mov_b64 + v_fmac_f64: the accumulator form overwrites the constant it starts from)
-    double ps, pc;
-    {
-        const double c2 = 8.33333333333333333333e-03, c5 = 4.16666666666666666667e-02;
-        asm("v_fma_f64 %0, %1, %2, %3" : "=v"(ps) : "v"(z), "s"(-1.98412698412698412698e-04), "v"(c2));
-        asm("v_fma_f64 %0, %1, %2, %3" : "=v"(ps) : "v"(z), "v"(ps), "s"(-1.66666666666666666667e-01));
-        asm("v_fma_f64 %0, %1, %2, %3" : "=v"(pc) : "v"(z), "s"(-1.38888888888888888889e-03), "v"(c5));
-    }
-    const double sm = (r * z) * ps;                                              // sin r - r
-#else
     double ps = __builtin_fma(z, -1.98412698412698412698e-04, 8.33333333333333333333e-03);
     ps = __builtin_fma(z, ps, -1.66666666666666666667e-01);
     const double sm = (r * z) * ps;                                              // sin r - r
     double pc = __builtin_fma(z, -1.38888888888888888889e-03, 4.16666666666666666667e-02);
-#endif
     pc = __builtin_fma(z, pc, -0.5);
     const double cm1 = z * pc;                                                   // cos r - 1
     const double sr = r + sm;
@@ -306,14 +437,7 @@ __device__ __forceinline__ float sqrtf_of_sum_of_squares(double x)
 // the loop is bound by the number of instructions it issues, not by the depth of this chain).
 __device__ __forceinline__ double wrap_2pi(double p)
 {
-#ifdef ACG_MSK_AB_WRAP3
-    // A/B build (round 6, on msk_lean.hip's shorter period): the difference beside the compare, then a two-word select -- one
-    // instruction more, one level less on the phase chain
-    const double w = p - K_TWOPI;
-    return p >= K_TWOPI ? w : p;
-#else
     const double k = __hiloint2double(p >= K_TWOPI ? (int)0xBFF00000 : (int)0x80000000, 0);
     return __builtin_fma(k, K_TWOPI, p);
-#endif
 }
 

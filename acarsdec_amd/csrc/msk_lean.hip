@@ -29,10 +29,10 @@
 // and "every lane fired, the segment goes on" is laid out as the fall-through.  One wave's LDS operations execute in order, so the
 // newest-tap reads see the ring write in front of them; every wait is a counted one that leaves the younger reads in flight
 // (which needs every scalar load retired before the loop: see where the epilogue's arguments are loaded).
-// Same operations on the same operands as before.  Each step has a switch that restores the order before it, so that
-// profiles/probe/build_ab.py can time both from one tree: ACG_LEAN_AB_TAPS0 (newest-tap reads in decide()), ACG_LEAN_AB_PIN0 (no
-// barrier in front of the mixer), ACG_LEAN_AB_TAB0 (table read inside the mixer), ACG_LEAN_AB_BRS0 (the compiler's block order).
-// Two more steps were measured and not taken (1 / s started where df is set; the branch hint on `quick` as well): DESIGN 4.
+// Same operations on the same operands as before.  Each step was timed against the order before it (newest-tap reads in decide(),
+// no barrier in front of the mixer, table read inside the mixer, the compiler's block order), and two more steps were measured and
+// not taken (1 / s started where df is set; the branch hint on `quick` as well): DESIGN 4, which also names the revision from
+// which profiles/probe/build_ab.py builds those arms again.
 // tests/test_lean_issue_order.py pins the order in the assembly.
 //
 // The front of a period (round 8).  A period takes up to six samples, each a VCO phase step (add, compare with 2 pi, select, fma) and
@@ -45,11 +45,15 @@
 // L.clk, fired: the same compares on the same values).  What keeps steps 1-4 in front of the branch is that steps 5 and 6 and the
 // picks use them there; steps 5 and 6 are held by an empty asm volatile each (LEAN_HOLD_STEP), without which the sixth sinks again.
 // Same operations on the same operands; a pick that a lane does not need (sample u >= cnt) goes to the ring's spare row as before.
-// Switches: ACG_LEAN_AB_SPEC0 (steps 5 and 6 under the branch), ACG_LEAN_AB_PICK0 (the picks in the guarded block), ACG_LEAN_AB_VCO0
-// (with both of those: no hold on steps 1-4 either, which is the order before round 8 and the parent commit's assembly),
-// ACG_LEAN_AB_HOLDS (which steps carry a hold).  Measured and not taken: a hold behind every step (1 % slower than holds on 5 and 6
-// only), the six newest taps as plain f32 (4 % slower), and the one-sample case by selects too; DESIGN 4.
+// Switches (kept: the layout test compiles the old order to show that its first condition can fail): ACG_LEAN_AB_SPEC0 (steps 5 and
+// 6 under the branch; steps 1-4 then carry a hold each, without which steps 2-4 sink behind it), ACG_LEAN_AB_PICK0 (the picks in the
+// guarded block), ACG_LEAN_AB_VCO0 (with both of those: no hold on steps 1-4 either, which is the order before round 8).  Measured
+// and not taken: a hold behind every step (1 % slower than holds on 5 and 6 only), the six newest taps as plain f32 (4 % slower), and
+// the one-sample case by selects too; DESIGN 4.
 // tests/test_lean_chain_layout.py pins the placement in the assembly.
+//
+// What this kernel shares with msk.hip -- the state's way in and out, the LDS layout, the phase detector, the loop filter, the inline
+// framing step of the closing period -- is in msk_common.h; the dm window's two lambdas are msk.hip's, spelled out here as there.
 #include <hip/hip_runtime.h>
 #include "acg_internal.h"
 
@@ -73,32 +77,13 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
     constexpr int WB = 64;                         // dm samples per refill block (msk.hip)
     constexpr int SPB = WB / LPC;
     constexpr int WSTR = 2 * WB + 4;
-#ifndef ACG_LEAN_SEG
-#define ACG_LEAN_SEG 8                             /* (A/B builds: 4, 6) */
-#endif
-    constexpr int SEG = ACG_LEAN_SEG;                         // bit periods per segment: 6 SEG <= WB - 1, and <= 8 so that a segment closes at most one byte
+    constexpr int SEG = 8;                         // bit periods per segment: 6 SEG <= WB - 1, and <= 8 so that a segment closes at most one byte
     static_assert(6 * (SEG + 1) <= WB - 1 && 12 * (SEG + 1) <= 2 * WB - 1, "a segment and its closing period stay inside the dm window");
     static_assert(LPC == 4 || LPC == 8, "lane groups of 4 or 8");
     static_assert(SEG >= 1 && SEG <= 8, "a segment closes at most one byte");
-    struct alignas(16) Lds {
-#ifdef ACG_LEAN_AB_HT
-        float hs[(MFLTOVER + 1) * 12];             // A/B build: h[] by tap phase, hs[o][j] = h[o + 12 j]: the 11 taps of a period are three b128 reads
-#else
-        float hs[(FLEN * MFLTOVER + 1 + 3) & ~3];
-#endif
-        double sc[2 * ACG_SINCOS_N];
-        float2 ring_all[WPG][3 * FLEN + 1][CPW];
-        float win_all[WPG][CPW][WSTR];
-    };
-    __shared__ Lds lds;
+    __shared__ MskLds<WPG, CPW, WSTR> lds;
     float* hs = lds.hs;
-
-#ifdef ACG_LEAN_AB_HT
-    for (int i = threadIdx.x; i < (MFLTOVER + 1) * 12; i += 64 * WPG) hs[i] = (i % 12) < FLEN ? a.h[i / 12 + MFLTOVER * (i % 12)] : 0.f;
-#else
-    for (int i = threadIdx.x; i < FLEN * MFLTOVER + 1; i += 64 * WPG) hs[i] = a.h[i];
-#endif
-    for (int i = threadIdx.x; i < 2 * ACG_SINCOS_N; i += 64 * WPG) lds.sc[i] = a.sctab[i];
+    lds_tables_load<64 * WPG>(hs, lds.sc, a);
 
     const int wv = threadIdx.x >> 6;
     const int tid = threadIdx.x & 63;
@@ -116,20 +101,11 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
     AcgChan* st = a.st + chc;
 
     Lane L;
-    L.phi = st->phi; L.df = st->df; L.lvlsum = st->lvlsum;
-    L.clk = st->clk; L.bitcount = st->bitcount; L.S = st->S; L.idx = st->idx;
-    L.nbits = st->nbits; L.astate = st->astate; L.blen = st->blen; L.berr = st->berr;
-    L.outbits = st->outbits & 0xffu; L.crc0 = st->crc0; L.nbit_total = st->nbit_total;
+    lane_load(L, st);
+    L.outbits &= 0xffu;
     const long long samp0 = st->nsamp_total;
     const long long nbt_in = L.nbit_total;
-    if (g == 0) {
-#pragma unroll
-        for (int j = 0; j < FLEN; ++j) {
-            const float2 x = make_float2(st->inb[2 * j], st->inb[2 * j + 1]);
-            ring[j][slot] = x;
-            ring[j + FLEN][slot] = x;
-        }
-    }
+    if (g == 0) ring_seed<CPW>(ring, slot, st);
 
     const float* __restrict__ dm = a.dm + (size_t)chc * a.dm_pitch;
     unsigned char* txt = a.txt + (size_t)chc * 256;
@@ -175,23 +151,10 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
     asm volatile("" :: "s"(a.snap), "s"(a.done_ctr));
 
     typedef float f2v __attribute__((ext_vector_type(2)));
-    // Block order: "the segment goes on" is laid out as the fall-through (ACG_LEAN_AB_BRS0: the compiler's own order, in which it jumps)
-#ifdef ACG_LEAN_AB_BRS0
-#define LEAN_UNLIKELY(c) (c)
-#else
-#define LEAN_UNLIKELY(c) __builtin_expect(!!(c), 0)
-#endif
 // holds a VCO / clock step where the source has it: an empty statement that the compiler must take to read and write the step's
 // phase and clock and the lane's pick (nothing is issued for it), so that neither sinking nor the scheduler carries the step past
-// it.  ACG_LEAN_AB_HOLDS (A/B builds): bit 0 = behind each of steps 1-4, bit 1 = behind steps 5 and 6, bit 2 = the pick is named too
-#ifndef ACG_LEAN_AB_HOLDS
-#ifdef ACG_LEAN_AB_SPEC0
-#define ACG_LEAN_AB_HOLDS 7                        /* (steps 5 and 6 under the branch: only a hold keeps steps 2-4 in front of it) */
-#else
-#define ACG_LEAN_AB_HOLDS 6
-#endif
-#endif
-#if defined(ACG_LEAN_AB_PICK0) || !(ACG_LEAN_AB_HOLDS & 4)
+// it.  Steps 5 and 6 always carry one; steps 1-4 only where steps 5 and 6 are under the branch (ACG_LEAN_AB_SPEC0)
+#ifdef ACG_LEAN_AB_PICK0
 #define LEAN_HOLD_STEP(pv, cv, mv) asm volatile("" : "+v"(pv), "+v"(cv))
 #else
 #define LEAN_HOLD_STEP(pv, cv, mv) asm volatile("" : "+v"(pv), "+v"(cv), "+v"(mv))
@@ -204,9 +167,7 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
     float clk_f;
     f2v hv2[(FLEN + 1) / 2];
     f2v acc;
-#ifndef ACG_LEAN_AB_TAPS0
     float2 xs[FLEN - 5];                           // the six newest taps' ring entries, read by front() right behind its ring write
-#endif
 
     // ---- front part of a bit period: msk.hip phases A, C0, B, operation for operation
     auto front = [&]() {
@@ -232,7 +193,7 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
             p4 = wrap_2pi(p4);
             c4 = (float)((double)c4 + s);
             pq[u] = p4;
-#if !defined(ACG_LEAN_AB_VCO0) && (ACG_LEAN_AB_HOLDS & 1)
+#if defined(ACG_LEAN_AB_SPEC0) && !defined(ACG_LEAN_AB_VCO0)
             // (only where steps 5 and 6 are under the branch: there machine sinking moves the phase step after them otherwise)
             LEAN_HOLD_STEP(p4, c4, myp[(u > 0 ? u - 1 : 0) / LPC]);
 #endif
@@ -248,9 +209,7 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
         double p5 = p4 + s;                                                // msk.c:82-83
         p5 = wrap_2pi(p5);
         float c5 = (float)((double)c4 + s);                          // msk.c:95
-#if ACG_LEAN_AB_HOLDS & 2
         LEAN_HOLD_STEP(p5, c5, myp[3 / LPC]);
-#endif
         const bool fired5 = (double)c5 >= thr;
 #ifndef ACG_LEAN_AB_PICK0
         if ((4 % LPC) == g) myp[4 / LPC] = p5;
@@ -258,9 +217,7 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
         double p6 = p5 + s;
         p6 = wrap_2pi(p6);
         float c6 = (float)((double)c5 + s);
-#if ACG_LEAN_AB_HOLDS & 2
         LEAN_HOLD_STEP(p6, c6, myp[4 / LPC]);
-#endif
         const bool fired6 = (double)c6 >= thr;
 #ifndef ACG_LEAN_AB_PICK0
         if ((5 % LPC) == g) myp[5 / LPC] = p6;
@@ -325,31 +282,21 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
         unsigned int idx_n = idx + (unsigned int)cnt;
         if (idx_n >= FLEN) idx_n -= FLEN;
         clk_f = fired ? (float)((double)L.clk - K_3PI2) : L.clk;           // msk.c:100
-#ifndef ACG_LEAN_AB_TAB0
         // the mixer's table entries first: kd, q, the LDS address and the read, so that the read's latency runs under the tap phase
         double mr[SPL], mcj[SPL], msj[SPL];
 #pragma unroll
         for (int j = 0; j < SPL; ++j) sincos_tab_entry(myp[j], lds.sc, &mr[j], &mcj[j], &msj[j]);
-#endif
         int o = (int)(MFLTOVER * (div1_rcp((double)clk_f, s) + 0.5));      // msk.c:103
         if (o > MFLTOVER) o = MFLTOVER;
         if (o < 0) o = 0;
         acc = f2v{0.f, 0.f};
         {
-#ifdef ACG_LEAN_AB_HT
-            typedef float f4h __attribute__((ext_vector_type(4)));
-            const f4h* hp = (const f4h*)&hs[o * 12];
-            const f4h q0 = hp[0], q1 = hp[1], q2 = hp[2];
-            hv2[0] = f2v{q0.x, q0.y}; hv2[1] = f2v{q0.z, q0.w}; hv2[2] = f2v{q1.x, q1.y};
-            hv2[3] = f2v{q1.z, q1.w}; hv2[4] = f2v{q2.x, q2.y}; hv2[5] = f2v{q2.z, q2.w};
-#else
             const float* hp = &hs[o];
 #pragma unroll
             for (int j = 0; j < FLEN; j += 2) {
                 hv2[j / 2].x = hp[j * MFLTOVER];
                 hv2[j / 2].y = hp[j + 1 < FLEN ? (j + 1) * MFLTOVER : j * MFLTOVER + 1];
             }
-#endif
         }
         float2 xo[5];
         {
@@ -357,19 +304,13 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
 #pragma unroll
             for (int j = 0; j < 5; ++j) xo[j] = rp0[j * CPW];
         }
-#ifndef ACG_LEAN_AB_PIN0
         // the tap phase and the h[] / old-ring reads stay in FRONT of the mixer: their LDS latency runs under its sin/cos series
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
             const int u = g + j * LPC;
             double sn, cs;
-#ifdef ACG_LEAN_AB_TAB0
-            sincos_tab(myp[j], lds.sc, &sn, &cs);
-#else
             sincos_tab_rotate(mr[j], mcj[j], msj[j], &sn, &cs);
-#endif
             const double in = (double)in_cur[j];
             unsigned int k = idx + (unsigned int)u;
             if (k >= FLEN) k -= FLEN;
@@ -380,7 +321,6 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
         }
         n += cnt;
         idx = idx_n;
-#ifndef ACG_LEAN_AB_TAPS0
         // the six newest taps, read right behind the ring write (one wave's LDS operations execute in order: the reads see the
         // writes of every lane); the five old taps' arithmetic and the wave-wide test run under their latency
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -391,7 +331,6 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
             for (int j = 5; j < FLEN; ++j) xs[j - 5] = rp[j * CPW];
         }
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
             const f2v x = {xo[j].x, xo[j].y};
@@ -406,12 +345,6 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
     auto decide = [&]() {
         L.clk = clk_f;                                                     // msk.c:100
         {
-#ifdef ACG_LEAN_AB_TAPS0
-            const float2* rp = &ring[idx][slot];
-            float2 xs[FLEN - 5];
-#pragma unroll
-            for (int j = 5; j < FLEN; ++j) xs[j - 5] = rp[j * CPW];
-#endif
 #pragma unroll
             for (int j = 5; j < FLEN; ++j) {
                 const f2v x = {xs[j - 5].x, xs[j - 5].y};
@@ -450,31 +383,20 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
         unsigned int P = 0, N = 0;                 // (vo > 0), (vo < 0) of the segment's bits, oldest in the highest place
         float lvk[SEG];
         int nk[SEG];
-#ifndef ACG_LEAN_AB_NOINIT
 #pragma unroll
         for (int k = 0; k < SEG; ++k) { lvk[k] = 0.f; nk[k] = 0; }
-#endif
         int c = 0;                                 // bits whose framing waits (wave-uniform)
         bool tail = false;                         // a period's front part is done and its bit decision is not
 #pragma unroll
         for (int k = 0; k < SEG; ++k) {
             front();
             // every lane fired a bit and may let its framing wait?  (One lane that cannot: the wave closes the segment and
-            // takes this period the way msk.hip does.)
-#ifdef ACG_LEAN_AB_UICMP
-            // A/B build: the wave-wide test as ONE compare whose lane mask is the answer (the ballot of an `and` of two conditions goes
-            // through v_cndmask + v_cmp_ne)
-            if (__builtin_amdgcn_uicmp((unsigned int)(fired ? lim : 0), (unsigned int)k, 34 /* ugt */) != ~0ull) { tail = true; break; }
-#else
-            if (LEAN_UNLIKELY(__builtin_amdgcn_ballot_w64(fired && lim > k) != ~0ull)) { tail = true; break; }
-#endif
+            // takes this period the way msk.hip does.)  The hint lays "the segment goes on" out as the fall-through.
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(fired && lim > k) != ~0ull, 0)) { tail = true; break; }
             decide();
             // decision + phase detector (msk.c:115-121); S + k is odd where S is odd and k even, ...
-            const bool odd = (k & 1) ? !odd0 : odd0;
-            const float vo = odd ? vi : vr;
-            const float ot = odd ? vr : vi;
-            const unsigned int flip = ((vo >= 0) == odd) ? 0x80000000u : 0u;
-            const double dphi = (double)__uint_as_float(__float_as_uint(ot) ^ flip);
+            const PhaseDet pd = phase_detect(((k & 1) ? !odd0 : odd0) ? 1u : 0u, vr, vi);          // (only the parity matters)
+            const float vo = pd.vo;
             P = shift_in(P, vo > 0);
             N = shift_in(N, vo < 0);
             if constexpr (LOG) {
@@ -483,7 +405,7 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
             }
             lvk[k] = lvl;
             nk[k] = n;
-            L.df = (double)0.52f * L.df + (1.0 - (double)0.52f) * (double)38e-4f * dphi;      // msk.c:130
+            L.df = loop_filter(L.df, pd.dphi);
             c = k + 1;
         }
         // ---- framing of the c bits that waited
@@ -577,67 +499,24 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
             if (fired) {
                 decide();
                 L.bitcount += 1;
-                const bool odd = (L.S & 1) != 0;
-                const float vo = odd ? vi : vr;
-                const float ot = odd ? vr : vi;
-                const unsigned int flip = ((vo >= 0) == odd) ? 0x80000000u : 0u;
-                const double dphi = (double)__uint_as_float(__float_as_uint(ot) ^ flip);
-                const float sv = __uint_as_float(__float_as_uint(vo) ^ ((L.S & 2u) << 30));   // msk.c:122-126
+                const PhaseDet pd = phase_detect(L.S, vr, vi);
+                const float sv = __uint_as_float(__float_as_uint(pd.vo) ^ ((L.S & 2u) << 30));   // msk.c:122-126
                 if constexpr (LOG) {
                     bits[nb < a.bit_cap ? nb : a.bit_cap - 1] = make_float2(sv, lvl);
                     nb += 1;
                 }
-                {
-                    unsigned int ob = (L.outbits >> 1) & 0x7fu;           // putbit, msk.c:53-63
-                    if (sv > 0) ob |= 0x80u;
-                    L.outbits = ob;
-                }
-                L.nbits -= 1;
-                {
-                    const bool ev = L.nbits <= 0;
-                    const unsigned int r = L.outbits & 0xffu;
-                    const bool syn = (r == SYN) | (r == (0xffu & ~SYN));
-                    const bool hunt = ev & (L.astate == WSYN) & !syn;
-                    const bool term = (r == ETX) | (r == ETB) | (r == DLE);
-                    const bool plain = ev & (L.astate == TXT) & ((__popc(r) & 1) != 0) & !term & (L.blen < 240);
-                    txt[plain ? L.blen : 255] = (unsigned char)r;
-                    L.blen += plain ? 1 : 0;
-                    L.nbits = hunt ? 1 : (plain ? 8 : L.nbits);
-                    if (ev & !hunt & !plain) decode_acars(L, a, ch, txt, samp0 + n - 1, leader, &st->soh32);
-                }
-                L.nbit_total += 1;
-                L.S += 1u;
-                L.df = (double)0.52f * L.df + (1.0 - (double)0.52f) * (double)38e-4f * dphi;  // msk.c:130
+                frame_bit(L, sv, a, ch, txt, samp0 + n - 1, leader, &st->soh32);
+                L.df = loop_filter(L.df, pd.dphi);
             }
         }
     }
 
     if (leader) {
-        st->phi = p; st->df = L.df; st->lvlsum = L.lvlsum;
-        st->clk = L.clk; st->bitcount = L.bitcount; st->S = L.S; st->idx = idx;
-        st->nbits = L.nbits; st->astate = L.astate; st->blen = L.blen; st->berr = L.berr;
-        st->outbits = L.outbits; st->crc0 = L.crc0; st->nbit_total = L.nbit_total;
-        st->nsamp_total = samp0 + len;
-#pragma unroll
-        for (int j = 0; j < FLEN; ++j) {
-            const float2 x = ring[j][slot];
-            st->inb[2 * j] = x.x;
-            st->inb[2 * j + 1] = x.y;
-        }
+        lane_store(st, L, p, idx, samp0, len);
+        ring_save<CPW>(st, ring, slot);
         a.nbits_out[ch] = LOG ? nb : (a.bit_append ? a.nbits_out[ch] : 0) + (int)(L.nbit_total - nbt_in);
     }
-    if (a.snap) {
-        if (WPG > 1) __syncthreads();
-        if (threadIdx.x == 0) {
-            __threadfence();
-            const unsigned int d = atomicAdd(a.done_ctr, 1u);
-            if (d == gridDim.x - 1) {
-                const unsigned int cq = __hip_atomic_load(a.frame_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(a.snap, cq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(a.done_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
+    publish_queue_length<WPG>(a);
 }
 
 // msk.hip's launcher hands over here when the launch qualifies (see the head of this file)

@@ -1,17 +1,19 @@
-"""A/B builds of the demodulator for same-box timing: python profiles/probe/build_ab.py NAME[:-DFLAG[,-DFLAG...]] ...
-Each NAME becomes acarsdec_amd/lib/ab/libNAME.so = the product objects with msk.hip recompiled under the given flags
-(a git revision may be given as NAME@REV:flags to take msk.hip from history).  profiles/probe/run_ab.sh times them all
-on one box through ACARSDEC_AMD_LIB.  Measurement aid only; nothing here is loaded by the product.
-Switches of msk_lean.hip may be given by their short names: a flag without a leading dash is taken as -DACG_LEAN_AB_<FLAG>
-(round 7: TAPS0, PIN0, TAB0, BRS0; round 8: VCO0, SPEC0, PICK0, TAPSF1), and R07PARENT / R08PARENT stand for every old-order
-switch of that round, the arm whose msk_lean assembly is the parent commit's."""
+"""A/B builds of the demodulator for same-box timing: python profiles/probe/build_ab.py NAME[@REV][:-DFLAG[,-DFLAG...]] ...
+Each NAME becomes acarsdec_amd/lib/ab/libNAME.so = the product objects with msk.hip and msk_lean.hip recompiled under the given
+flags.  With @REV the demodulator's sources (msk.hip, msk_lean.hip, msk_common.h) are taken from that git revision: the arms whose
+verdict is closed (profiles/LEDGER.md) are no longer in the tree, and the revision named there still has their switches
+(NAME@REV:-DSWITCH).  profiles/probe/run_ab.sh times them all on one box through ACARSDEC_AMD_LIB.  Measurement aid
+only; nothing here is loaded by the product.
+The switches msk_lean.hip keeps may be given by their short names: a flag without a leading dash is taken as -DACG_LEAN_AB_<FLAG>
+(VCO0, SPEC0, PICK0), and R08PARENT stands for all three, the order before round 8."""
 import os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 sys.path.insert(0, ROOT)
 from acarsdec_amd import _build as B
 
 MSK_FLAGS = B.MSK_FLAGS                 # the product's recipe (acarsdec_amd/_build.py)
-GROUPS = {"R07PARENT": ["TAPS0", "PIN0", "TAB0", "BRS0"], "R08PARENT": ["VCO0", "SPEC0", "PICK0"]}
+GROUPS = {"R08PARENT": ["VCO0", "SPEC0", "PICK0"]}
+SOURCES = ("msk.hip", "msk_lean.hip", "msk_common.h")
 B.build_lib()
 out = os.path.join(B.LIBDIR, "ab")
 os.makedirs(out, exist_ok=True)
@@ -31,16 +33,22 @@ for spec in sys.argv[1:]:
                 base += [f, v]
         elif not any(d in f for d in drop):
             base.append(f)
-    src = os.path.join(B.CSRC, "msk.hip")
+    srcdir, inc = B.CSRC, ["-I" + B.INC, "-I" + B.CSRC]
     if rev:
-        src = os.path.join(out, "msk_%s.hip" % name)
-        open(src, "w").write(subprocess.run(["git", "show", "%s:acarsdec_amd/csrc/msk.hip" % rev], cwd=ROOT, capture_output=True, text=True, check=True).stdout)
+        # the revision's demodulator sources in a directory of their own, in front of the tree's on the include path
+        srcdir = os.path.join(out, "src_%s" % name)
+        os.makedirs(srcdir, exist_ok=True)
+        for f in SOURCES:
+            text = subprocess.run(["git", "show", "%s:acarsdec_amd/csrc/%s" % (rev, f)], cwd=ROOT, capture_output=True, text=True, check=True).stdout
+            open(os.path.join(srcdir, f), "w").write(text)
+        inc = ["-I" + srcdir] + inc
+    cc = [B.hipcc(), "--offload-arch=gfx950", "-std=c++17", "-fPIC"] + inc
     obj = os.path.join(out, "msk_%s.o" % name)
-    B._run([B.hipcc(), "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + B.INC, "-I" + B.CSRC] + base + flags + ["-c", src, "-o", obj])
-    # msk_lean.hip (round 6) under the same flags: its A/B switches are ACG_LEAN_AB_*
+    B._run(cc + base + flags + ["-c", os.path.join(srcdir, "msk.hip"), "-o", obj])
+    # msk_lean.hip under the same flags, with machine sinking left on as in the product's recipe
     obj2 = os.path.join(out, "msk_lean_%s.o" % name)
     lean_base = [f for i, f in enumerate(base) if not (f == "-disable-machine-sink" or (f == "-mllvm" and i + 1 < len(base) and base[i + 1] == "-disable-machine-sink"))]
-    B._run([B.hipcc(), "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + B.INC, "-I" + B.CSRC] + lean_base + flags + ["-c", os.path.join(B.CSRC, "msk_lean.hip"), "-o", obj2])
+    B._run(cc + lean_base + flags + ["-c", os.path.join(srcdir, "msk_lean.hip"), "-o", obj2])
     # every other unit of the product library as build_lib() left it
     objs = [os.path.join(B.OBJDIR, n + ".o") for n, _, in_product in B.UNITS if in_product and n not in ("msk.hip", "msk_lean.hip")]
     objs += [os.path.join(B.OBJDIR, "host_setup.o"), obj, obj2]

@@ -65,8 +65,7 @@ def test_tuning_switches_go_through_one_table_not_the_environment():
     assert L.acg_is_lab_build() == 0 and K.load(lab=True).acg_is_lab_build() == 1
     assert L.acg_tune(b"ACG_FIR_VARIANT", b"3") == K.OK and L.acg_tune(b"ACG_FIR_VARIANT", None) == K.OK
     assert L.acg_tune(b"LD_PRELOAD", b"x") == K.EINVAL and L.acg_tune(None, b"1") == K.EINVAL
-    src = open(os.path.join(ROOT, "acarsdec_amd", "csrc", "fir.hip")).read() + open(os.path.join(ROOT, "acarsdec_amd", "csrc", "msk.hip")).read() + \
-        open(os.path.join(ROOT, "acarsdec_amd", "csrc", "msk_lean.hip")).read()
+    src = "".join(open(os.path.join(ROOT, "acarsdec_amd", "csrc", f)).read() for f in ("fir.hip", "msk.hip", "msk_lean.hip", "msk_common.h"))
     assert "getenv(" not in src                                   # no launch path reads the environment
     code = ("import os, sys; sys.path.insert(0, %r); os.environ['ACG_FIR_DEBUG_SHAPE'] = '1'\n"
             "from acarsdec_amd import _capi as K; K.tune('ACG_MSK_LPC', 4, lab=%%s)" % ROOT)
