@@ -282,6 +282,9 @@ int acg_launch_fir_mm1_prep(const FirArgs* a, void* stream);
 int acg_launch_fir_mm1(const FirArgs* a, void* stream);
 int acg_launch_fir_fmt(const FirArgs* a, int fmt, void* stream);     // fmt: 1 CS16, 2 split int16 planes, 3 real f32
 size_t acg_fir_lds_bytes(const FirArgs* a);
+// fir.hip: per-device launch state of every down-converter unit (not exported: the version script lists the public headers' names)
+int acg_fir_device_cus(int* num_cu);                                 // CUs of the current device; returns a HIP error or 0
+int acg_fir_lds_optin(const void* kernel, size_t bytes);             // opts `kernel` in for `bytes` of dynamic LDS on the current device
 int acg_launch_msk(const MskArgs* a, int lanes_per_channel, void* stream);
 int acg_launch_msk_lean(const MskArgs* a, int lanes_per_channel, int waves_per_group, unsigned int grid, void* stream);   // msk_lean.hip: the in_callback-shaped launches, with or without a bit log
 int acg_launch_msk2(const MskArgs* a, int pairs_per_group, void* stream);     // msk2.hip: the stream split over two waves (8 lanes per channel)

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "acg_internal.h"
+#include "fir_plan.h"
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -443,7 +444,6 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_u8_shared_kernel(const FirArgs
 //     requested a whole tile before it is needed; the next run's taps are fetched during the last tile.
 // Summation order: 8 sequential fused multiply-adds per chunk, then CPR sequential adds (the reference
 // adds M terms sequentially; its own -Ofast build reassociates, SURVEY 8c: dm within 1e-5 relative).
-#define FIRD_R 2
 
 template <int CPR, int U_ = 0, int B_ = 0>
 struct FirD {
@@ -474,6 +474,58 @@ __device__ __forceinline__ u4v_t fird_load(__amdgpu_buffer_rsrc_t r, unsigned in
 {
     return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 2 /* nt */);
 }
+
+// The sharded ticket dispenser as one wave sees it.  Shard s hands out runs s, s + SHARDS, s + 2 SHARDS, ...: the shards advance
+// together, so the whole grid reads ONE front that moves through the input in address order (HBM likes that better than eight
+// distant fronts), while the ticket atomics are spread over eight L2 channels.  The first run of wave wg is run wg (static);
+// tickets count on from there.  A wave whose shard has run dry moves on to the next one; the last wave to sign off re-arms
+// all words, so no memset launch precedes the kernel.
+// The members are REFERENCES to the kernel's own values (what the lambdas this replaced captured), and "is there a run?" is
+// asked by the caller (`if (run == NONE) run = disp.probe_after(s)`): with values held by copy, or with that test folded into a
+// member, the format kernels compile to other text (profiles/LEDGER.md, "Down-converter: one copy of the shared parts").
+struct RunDisp {
+    static constexpr unsigned int NONE = 0xffffffffu;
+    unsigned int* const& ctr;                                       // FirArgs::work_counter
+    const unsigned int &nrun, &nwaves;
+    const int& lane;
+    __device__ unsigned int shard_runs(unsigned int s) const { return (nrun + ACG_DISP_SHARDS - 1 - s) / ACG_DISP_SHARDS; }
+    __device__ unsigned int shard_static(unsigned int s) const { return (nwaves + ACG_DISP_SHARDS - 1 - s) / ACG_DISP_SHARDS; }
+    __device__ static unsigned int after(unsigned int s) { return (s + 1 == ACG_DISP_SHARDS) ? 0 : s + 1; }
+    __device__ unsigned int run_of_ticket(unsigned int s, unsigned int t) const
+    {
+        const unsigned long long k = (unsigned long long)shard_static(s) + t;
+        return k < shard_runs(s) ? (unsigned int)k * ACG_DISP_SHARDS + s : NONE;
+    }
+    __device__ unsigned int probe(unsigned int& s) const            // synchronous: next run of shard s, else of the following shards
+    {
+        for (int k = 0; k < ACG_DISP_SHARDS; ++k) {
+            unsigned int t = 0;
+            if (lane == 0) t = __hip_atomic_fetch_add(ctr + s * ACG_DISP_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            t = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
+            const unsigned int r = run_of_ticket(s, t);
+            if (r != NONE) return r;
+            s = after(s);
+        }
+        return NONE;
+    }
+    // shard s has run dry: on to the shards after it
+    __device__ unsigned int probe_after(unsigned int& s) const
+    {
+        s = after(s);
+        return probe(s);
+    }
+    __device__ void sign_off() const
+    {
+        if (lane == 0) {
+            const unsigned int d = atomicAdd(ctr + ACG_DISP_SHARDS * ACG_DISP_STRIDE, 1u);
+            if (d == nwaves - 1) {                                  // every wave's requests have been answered: re-arm
+#pragma unroll
+                for (int k = 0; k <= ACG_DISP_SHARDS; ++k)
+                    __hip_atomic_store(ctr + k * ACG_DISP_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+};
 
 // The ticket for the run after the current one is requested by lane 0 a whole tile before it is looked at.
 // As a compiler builtin the atomic is waited for on the spot (the uniform-address atomic optimiser wants
@@ -566,7 +618,7 @@ __device__ __forceinline__ void fird_tile(u4v_t* st /* [U] */, __amdgpu_buffer_r
 #pragma unroll
     for (int j = 0; j < CPR; ++j) D = D + Pr[j];
     if (FOLD) D = D - dc;
-    if (WT) {                                                      // write-through store (the default; 55 = write-back): see firc_flush
+    if (WT) {                                                      // write-through store (the default; 55 = write-back): DESIGN 4
         float* p = dm_out + lane;
         const float v = cabs_like_glibc(D.x, D.y);
         asm volatile("global_store_dword %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
@@ -580,7 +632,7 @@ __device__ __forceinline__ void fird_body(const FirArgs& a, const uint8_t* __res
                                           const int* __restrict__ stream_of, float* __restrict__ dm_base)
 {
     typedef FirD<CPR, UU, BB> F;
-    constexpr unsigned int NONE = 0xffffffffu;
+    constexpr unsigned int NONE = RunDisp::NONE;
     // beside demodulator waves (which have slack whenever this kernel is the longer stage) this stream wins the issue
     // arbitration: the demodulator then fills the gaps instead of stretching the bandwidth-bound stage
     if (a.high_prio) __builtin_amdgcn_s_setprio(2);
@@ -608,37 +660,7 @@ __device__ __forceinline__ void fird_body(const FirArgs& a, const uint8_t* __res
     const unsigned int voff = (unsigned int)lane << 4;
     const int nck = a.ntaps_pad >> 3;                                               // tap columns that carry taps
 
-    // Shard s hands out runs s, s + SHARDS, s + 2 SHARDS, ...: the shards advance together, so the whole grid reads
-    // ONE front that moves through the input in address order (HBM likes that better than eight distant fronts),
-    // while the ticket atomics are spread over eight L2 channels.  The first run of wave wg is run wg (static);
-    // tickets count on from there.
-    auto shard_runs = [&](unsigned int s) { return (nrun + ACG_DISP_SHARDS - 1 - s) / ACG_DISP_SHARDS; };
-    auto shard_static = [&](unsigned int s) { return (nwaves + ACG_DISP_SHARDS - 1 - s) / ACG_DISP_SHARDS; };
-    auto run_of_ticket = [&](unsigned int s, unsigned int t) -> unsigned int {
-        const unsigned long long k = (unsigned long long)shard_static(s) + t;
-        return k < shard_runs(s) ? (unsigned int)k * ACG_DISP_SHARDS + s : NONE;
-    };
-    auto probe = [&](unsigned int& s) -> unsigned int {             // synchronous: next run of shard s, else of the following shards
-        for (int k = 0; k < ACG_DISP_SHARDS; ++k) {
-            unsigned int t = 0;
-            if (lane == 0) t = __hip_atomic_fetch_add(ctr + s * ACG_DISP_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            t = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
-            const unsigned int r = run_of_ticket(s, t);
-            if (r != NONE) return r;
-            s = (s + 1 == ACG_DISP_SHARDS) ? 0 : s + 1;
-        }
-        return NONE;
-    };
-    auto sign_off = [&]() {
-        if (lane == 0) {
-            const unsigned int d = atomicAdd(ctr + ACG_DISP_SHARDS * ACG_DISP_STRIDE, 1u);
-            if (d == nwaves - 1) {                                  // every wave's requests have been answered: re-arm
-#pragma unroll
-                for (int k = 0; k <= ACG_DISP_SHARDS; ++k)
-                    __hip_atomic_store(ctr + k * ACG_DISP_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    };
+    const RunDisp disp = {ctr, nrun, nwaves, lane};
     auto run_base = [&](unsigned int run, unsigned int& ch, unsigned int& t0) -> const uint8_t* {
         ch = run / runs_per_ch;
         t0 = (run - ch * runs_per_ch) * FIRD_R * pairs;
@@ -677,12 +699,9 @@ __device__ __forceinline__ void fird_body(const FirArgs& a, const uint8_t* __res
     };
 
     unsigned int s = wg % ACG_DISP_SHARDS;
-    unsigned int run = wg < nrun ? wg : NONE;
-    if (run == NONE) {                                              // tiny launches: fewer runs than waves
-        s = (s + 1 == ACG_DISP_SHARDS) ? 0 : s + 1;
-        run = probe(s);
-    }
-    if (run == NONE) { sign_off(); return; }
+    unsigned int run = wg < nrun ? wg : NONE;                       // the first run of wave wg is run wg
+    if (run == NONE) run = disp.probe_after(s);                     // tiny launches: fewer runs than waves
+    if (run == NONE) { disp.sign_off(); return; }
 
     unsigned int ch, t0;
     const uint8_t* base = run_base(run, ch, t0);
@@ -714,11 +733,8 @@ __device__ __forceinline__ void fird_body(const FirArgs& a, const uint8_t* __res
             const uint8_t* nbase = base + run_bytes;                // the next body of this run ...
             if (j + 1 == pairs) {                                   // ... or the first body of the next run
                 // (U loads and a store are in flight, all younger than the ticket)
-                nrun_ = run_of_ticket(s, ticket_take<F::U + 1>(tk));
-                if (nrun_ == NONE) {
-                    s = (s + 1 == ACG_DISP_SHARDS) ? 0 : s + 1;
-                    nrun_ = probe(s);
-                }
+                nrun_ = disp.run_of_ticket(s, ticket_take<F::U + 1>(tk));
+                if (nrun_ == NONE) nrun_ = disp.probe_after(s);
                 has_next = nrun_ != NONE;
                 nbase = base;
                 if (has_next) nbase = run_base(nrun_, nch_, nt0);
@@ -736,7 +752,7 @@ __device__ __forceinline__ void fird_body(const FirArgs& a, const uint8_t* __res
         ch = nch_;
         t0 = nt0;
     }
-    sign_off();
+    disp.sign_off();
 }
 
 template <int CPR, int UU = 0, int BB = 0, bool FOLD = true, bool WT = false, bool NOMAC = false>
@@ -1074,7 +1090,7 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_fmt_direct_kernel(const FirArg
                                                                      const int* __restrict__ stream_of, float* __restrict__ dm_base)
 {
     typedef FirX<FMT, CPR, W> F;
-    constexpr unsigned int NONE = 0xffffffffu;
+    constexpr unsigned int NONE = RunDisp::NONE;
     if (a.high_prio) __builtin_amdgcn_s_setprio(2);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1099,33 +1115,7 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_fmt_direct_kernel(const FirArg
     const unsigned int voff = (unsigned int)lane << 4;
     const int nck = a.ntaps_pad / F::SPC;                                           // tap columns that carry taps
 
-    auto shard_runs = [&](unsigned int s) { return (nrun + ACG_DISP_SHARDS - 1 - s) / ACG_DISP_SHARDS; };
-    auto shard_static = [&](unsigned int s) { return (nwaves + ACG_DISP_SHARDS - 1 - s) / ACG_DISP_SHARDS; };
-    auto run_of_ticket = [&](unsigned int s, unsigned int t) -> unsigned int {
-        const unsigned long long k = (unsigned long long)shard_static(s) + t;
-        return k < shard_runs(s) ? (unsigned int)k * ACG_DISP_SHARDS + s : NONE;
-    };
-    auto probe = [&](unsigned int& s) -> unsigned int {
-        for (int k = 0; k < ACG_DISP_SHARDS; ++k) {
-            unsigned int t = 0;
-            if (lane == 0) t = __hip_atomic_fetch_add(ctr + s * ACG_DISP_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            t = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
-            const unsigned int r = run_of_ticket(s, t);
-            if (r != NONE) return r;
-            s = (s + 1 == ACG_DISP_SHARDS) ? 0 : s + 1;
-        }
-        return NONE;
-    };
-    auto sign_off = [&]() {
-        if (lane == 0) {
-            const unsigned int d = atomicAdd(ctr + ACG_DISP_SHARDS * ACG_DISP_STRIDE, 1u);
-            if (d == nwaves - 1) {
-#pragma unroll
-                for (int k = 0; k <= ACG_DISP_SHARDS; ++k)
-                    __hip_atomic_store(ctr + k * ACG_DISP_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    };
+    const RunDisp disp = {ctr, nrun, nwaves, lane};
     auto run_base = [&](unsigned int run, unsigned int& ch, unsigned int& t0) -> const uint8_t* {
         ch = run / runs_per_ch;
         t0 = (run - ch * runs_per_ch) * FIRD_R * pairs;
@@ -1158,12 +1148,9 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_fmt_direct_kernel(const FirArg
     };
 
     unsigned int s = wg % ACG_DISP_SHARDS;
-    unsigned int run = wg < nrun ? wg : NONE;
-    if (run == NONE) {
-        s = (s + 1 == ACG_DISP_SHARDS) ? 0 : s + 1;
-        run = probe(s);
-    }
-    if (run == NONE) { sign_off(); return; }
+    unsigned int run = wg < nrun ? wg : NONE;                       // the first run of wave wg is run wg
+    if (run == NONE) run = disp.probe_after(s);                     // tiny launches: fewer runs than waves
+    if (run == NONE) { disp.sign_off(); return; }
 
     unsigned int ch, t0;
     const uint8_t* base = run_base(run, ch, t0);
@@ -1195,11 +1182,8 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_fmt_direct_kernel(const FirArg
             // second tile of the body: where does the stream go next -- the next body of this run, or the next run's first
             const uint8_t* nbase = base + run_bytes;
             if (j + 1 == pairs) {
-                nrun_ = run_of_ticket(s, ticket_take<F::NLD * F::U + 1>(tk));
-                if (nrun_ == NONE) {
-                    s = (s + 1 == ACG_DISP_SHARDS) ? 0 : s + 1;
-                    nrun_ = probe(s);
-                }
+                nrun_ = disp.run_of_ticket(s, ticket_take<F::NLD * F::U + 1>(tk));
+                if (nrun_ == NONE) nrun_ = disp.probe_after(s);
                 has_next = nrun_ != NONE;
                 nbase = base;
                 if (has_next) nbase = run_base(nrun_, nch_, nt0);
@@ -1219,11 +1203,11 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_fmt_direct_kernel(const FirArg
         ch = nch_;
         t0 = nt0;
     }
-    sign_off();
+    disp.sign_off();
 }
 
 // Launch-side state is per DEVICE (function attributes belong to the device's code object; the CU count is
-// the device's): a process may hold contexts on several GPUs.
+// the device's): a process may hold contexts on several GPUs.  One table for every down-converter unit (fir_mm.hip too).
 #define FIR_MAXDEV 64
 struct FirDev {
     bool ready;
@@ -1233,6 +1217,7 @@ struct FirDev {
 static FirDev g_firdev[FIR_MAXDEV];
 static std::mutex g_firdev_mx;
 
+// the current device's record; g_firdev_mx is held
 static int fir_device(FirDev** out)
 {
     int dev = 0;
@@ -1240,7 +1225,6 @@ static int fir_device(FirDev** out)
     if (e != hipSuccess) return (int)e;
     if (dev < 0 || dev >= FIR_MAXDEV) return (int)hipErrorInvalidDevice;
     FirDev* d = &g_firdev[dev];
-    std::lock_guard<std::mutex> lk(g_firdev_mx);
     if (!d->ready) {
         d->num_cu = 256;
         (void)hipDeviceGetAttribute(&d->num_cu, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1251,15 +1235,24 @@ static int fir_device(FirDev** out)
     return 0;
 }
 
+extern "C" int acg_fir_device_cus(int* num_cu)
+{
+    std::lock_guard<std::mutex> lk(g_firdev_mx);
+    FirDev* d = nullptr;
+    if (int e = fir_device(&d)) return e;
+    *num_cu = d->num_cu;
+    return 0;
+}
+
 // Dynamic LDS above the default limit needs an opt-in per kernel (hipFuncAttributeMaxDynamicSharedMemorySize).  It is
 // made HERE, at the launch site, with the bytes the launch is about to ask for and for exactly the instantiation being
 // launched -- a table of instantiations kept elsewhere drifts from the launch switch (round 2's did: the write-through
 // kernels that are the default were not in it).
-static int fir_lds_optin(const void* kernel, size_t bytes)
+extern "C" int acg_fir_lds_optin(const void* kernel, size_t bytes)
 {
+    std::lock_guard<std::mutex> lk(g_firdev_mx);
     FirDev* d = nullptr;
     if (int e = fir_device(&d)) return e;
-    std::lock_guard<std::mutex> lk(g_firdev_mx);
     size_t& have = (*d->lds_optin)[kernel];
     if (bytes > have) {
         const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
@@ -1270,7 +1263,7 @@ static int fir_lds_optin(const void* kernel, size_t bytes)
 }
 #define FIR_LAUNCH(K_, grid_, blk_, lds_, stream_, ...)                                            \
     do {                                                                                           \
-        if (int oe_ = fir_lds_optin((const void*)(K_), (size_t)(lds_))) return oe_;                \
+        if (int oe_ = acg_fir_lds_optin((const void*)(K_), (size_t)(lds_))) return oe_;            \
         hipLaunchKernelGGL((K_), grid_, blk_, lds_, stream_, __VA_ARGS__);                         \
     } while (0)
 
@@ -1279,49 +1272,43 @@ extern "C" int acg_tune_get(const char* name, int dflt);
 extern "C" int acg_tune_has(const char* name);
 static int env_int(const char* name, int dflt) { return acg_tune_get(name, dflt); }
 
+// a wave-private kernel's launch: the plan's shape (fir_plan.h), its run length in the arguments
+typedef void (*FirWaveKernel)(const FirArgs, const uint8_t*, const float*, const int*, float*);
+static int launch_planned(FirWaveKernel kernel, const FirWavePlan& p, const FirArgs& a, hipStream_t stream)
+{
+    FirArgs b = a;
+    b.run_pairs = p.pairs;
+    FIR_LAUNCH(kernel, dim3((unsigned int)p.grid), dim3(64 * p.wpg), p.lds, stream, b, a.iq, a.taps, a.stream_of, a.dm);
+    return (int)hipGetLastError();
+}
+
 template <int FMT, int CPR, int W>
 static int launch_fmt_direct(const FirArgs* a, int num_cu, hipStream_t stream)
 {
-    typedef FirX<FMT, CPR, W> F;
-    // workgroup shape as for the u8 kernel (launch_direct): 4-wave workgroups alone, single-wave workgroups (seven per CU)
-    // beside demodulator workgroups on the same CUs, so that the demodulator's LDS fits next to them; 8 waves per CU at most
-    int wpg = env_int("ACG_FIR_WAVES_PER_WG", a->shares_cus ? 1 : 4);
-    if (wpg != 1 && wpg != 2 && wpg != 4) wpg = 4;
-    const size_t lds = (size_t)wpg * F::WAVE_LDS;
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 8 / wpg) per_cu = 8 / wpg;
-    if (a->shares_cus && wpg == 1 && per_cu > 7) per_cu = 7;
-    if (per_cu < 1) return (int)hipErrorInvalidValue;
-    per_cu = env_int("ACG_FIR_WG_PER_CU", per_cu);
-    long long grid = (long long)(a->ncu > 0 ? a->ncu : num_cu) * per_cu;
-    const long long bodies_per_ch = a->nwin / W / FIRD_R;
-    const long long bodies = (long long)a->nch * bodies_per_ch;
-    int pairs = 1;
-    while (pairs < 8 && bodies_per_ch % (2 * pairs) == 0 && bodies / (2 * pairs) >= 32 * grid * wpg) pairs *= 2;
-    pairs = env_int("ACG_FIR_RUN_PAIRS", pairs);
-    if (pairs < 1 || pairs > 8 || (pairs & (pairs - 1)) || bodies_per_ch % pairs) pairs = 1;      // 1, 2, 4 or 8
-    const long long nrun = bodies / pairs;
-    const long long need = (nrun + wpg - 1) / wpg;
-    if (grid > need) grid = need;
-    FirArgs b = *a;
-    b.run_pairs = pairs;
-    FIR_LAUNCH((fir_fmt_direct_kernel<FMT, CPR, W>), dim3((unsigned int)grid), dim3(64 * wpg), lds, stream, b, a->iq, a->taps,
-                       a->stream_of, a->dm);
+    const FirWavePlan p = acg_fir_wave_plan(a, num_cu, FirX<FMT, CPR, W>::WAVE_LDS, W, 8);
+    if (p.fit < 1) return (int)hipErrorInvalidValue;
+    return launch_planned(fir_fmt_direct_kernel<FMT, CPR, W>, p, *a, stream);
+}
+
+// the workgroup-granular format kernel
+template <int FMT>
+static int launch_fmt(const FirArgs* a, long long grid, size_t lds, hipStream_t stream)
+{
+    FIR_LAUNCH(fir_fmt_kernel<FMT>, dim3((unsigned int)grid), dim3(ACG_WG_FIR), lds, stream, *a, a->iq, a->taps, a->stream_of, a->dm);
     return (int)hipGetLastError();
 }
 
 extern "C" int acg_launch_fir_fmt(const FirArgs* a, int fmt, void* stream)
 {
     const size_t lds = (size_t)ACG_TILE_WIN * a->row_stride + 4 * 64 * sizeof(float4);
-    FirDev* fd = nullptr;
-    if (int e = fir_device(&fd)) return e;
-    const int num_cu = fd->num_cu;
+    int num_cu = 0;
+    if (int e = acg_fir_device_cus(&num_cu)) return e;
     // the wave-private streaming kernel where it is instantiated for the window length and the launch is whole runs
     // (ACG_FIR_VARIANT=3 forces the workgroup-granular kernel below)
-    if (env_int("ACG_FIR_VARIANT", 5) >= 5 && a->nwin > 0 && (long long)a->nch * a->nwin < (1ll << 31)) {
+    if (env_int("ACG_FIR_VARIANT", 5) >= 5) {
         const int cprw = a->cpr_total;                              // 16-byte chunks per window (per plane for split int16)
 #define FIRX_TRY(F_, C_, W_) \
-        if (fmt == F_ && (F_ == FMT_SPLIT ? cprw / 2 : cprw) == C_ && a->nwin % (W_ * FIRD_R) == 0) \
+        if (fmt == F_ && (F_ == FMT_SPLIT ? cprw / 2 : cprw) == C_ && acg_fir_fmt_wave_takes(a, W_)) \
             return launch_fmt_direct<F_, C_, W_>(a, num_cu, (hipStream_t)stream);
         FIRX_TRY(FMT_CS16, 40, 32) FIRX_TRY(FMT_CS16, 48, 32) FIRX_TRY(FMT_CS16, 50, 32)
         FIRX_TRY(FMT_F32R, 50, 32) FIRX_TRY(FMT_F32R, 60, 16) FIRX_TRY(FMT_F32R, 120, 8) FIRX_TRY(FMT_F32R, 200, 8)
@@ -1336,19 +1323,11 @@ extern "C" int acg_launch_fir_fmt(const FirArgs* a, int fmt, void* stream)
     long long grid = (long long)(a->ncu > 0 ? a->ncu : num_cu) * per_cu;
     if (grid > G) grid = G;
     switch (fmt) {
-    case FMT_CS16:
-        FIR_LAUNCH(fir_fmt_kernel<FMT_CS16>, dim3((unsigned int)grid), dim3(ACG_WG_FIR), lds, (hipStream_t)stream, *a, a->iq, a->taps, a->stream_of, a->dm);
-        break;
-    case FMT_SPLIT:
-        FIR_LAUNCH(fir_fmt_kernel<FMT_SPLIT>, dim3((unsigned int)grid), dim3(ACG_WG_FIR), lds, (hipStream_t)stream, *a, a->iq, a->taps, a->stream_of, a->dm);
-        break;
-    case FMT_F32R:
-        FIR_LAUNCH(fir_fmt_kernel<FMT_F32R>, dim3((unsigned int)grid), dim3(ACG_WG_FIR), lds, (hipStream_t)stream, *a, a->iq, a->taps, a->stream_of, a->dm);
-        break;
-    default:
-        return (int)hipErrorInvalidValue;
+    case FMT_CS16: return launch_fmt<FMT_CS16>(a, grid, lds, (hipStream_t)stream);
+    case FMT_SPLIT: return launch_fmt<FMT_SPLIT>(a, grid, lds, (hipStream_t)stream);
+    case FMT_F32R: return launch_fmt<FMT_F32R>(a, grid, lds, (hipStream_t)stream);
     }
-    return (int)hipGetLastError();
+    return (int)hipErrorInvalidValue;
 }
 
 // Exact-order kernel: one thread per output, the M terms accumulated sequentially with separately rounded products,
@@ -1393,42 +1372,16 @@ extern "C" size_t acg_fir_lds_bytes(const FirArgs* a)
 template <int CPR, int UU = 0, int BB = 0, bool FOLD = true, bool WT = false, bool NOMAC = false>
 static int launch_direct(const FirArgs* a, int num_cu, hipStream_t stream)
 {
-    // The waves of a workgroup are independent, so the workgroup size only decides in what pieces LDS is handed out
-    // (ACG_FIR_WAVES_PER_WG = 1, 2, 4).  Four measured best alone (+5 % over single-wave workgroups at 16 384
-    // channels) and within noise of the others beside the demodulator.  At most 8 waves per CU (2 per SIMD).
-    // Beside demodulator workgroups on the same CUs (no CU partition: > 2048 channels) single-wave workgroups, seven per
-    // CU: the demodulator's LDS (28 KiB per CU at 16 384 channels) then fits next to them instead of keeping a whole
-    // 4-wave workgroup out (+13 % whole job at 4096 channels, +2 % at 16 384).
-    int wpg = env_int("ACG_FIR_WAVES_PER_WG", a->shares_cus ? 1 : 4);
-    if (wpg != 1 && wpg != 2 && wpg != 4) wpg = 4;
-    const size_t lds = (size_t)wpg * FirD<CPR>::WAVE_LDS;
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 8 / wpg) per_cu = 8 / wpg;
-    if (a->shares_cus && wpg == 1 && per_cu > 7) per_cu = 7;
-    per_cu = env_int("ACG_FIR_WG_PER_CU", per_cu);
-    long long grid = (long long)(a->ncu > 0 ? a->ncu : num_cu) * per_cu;
-    // two-tile bodies per run: as many (1, 2, 4, 8) as leave every resident wave ~32 runs (the tail of the launch is
-    // one run long) and divide the bodies of a channel
-    const long long bodies_per_ch = a->nwin / ACG_TILE_WIN / FIRD_R;
-    const long long bodies = (long long)a->nch * bodies_per_ch;
-    int pairs = 1;
-    while (pairs < 8 && bodies_per_ch % (2 * pairs) == 0 && bodies / (2 * pairs) >= 32 * grid * wpg) pairs *= 2;
-    pairs = env_int("ACG_FIR_RUN_PAIRS", pairs);
-    if (pairs < 1 || pairs > 8 || (pairs & (pairs - 1)) || bodies_per_ch % pairs) pairs = 1;      // 1, 2, 4 or 8
-    const long long nrun = bodies / pairs;
-    const long long need = (nrun + wpg - 1) / wpg;
-    if (grid > need) grid = need;
+    static_assert(4 * FirD<CPR>::WAVE_LDS <= FIR_CU_LDS, "a four-wave workgroup fits a CU: the plan's fit is >= 1");
+    const FirWavePlan p = acg_fir_wave_plan(a, num_cu, FirD<CPR>::WAVE_LDS, ACG_TILE_WIN, 8);
     FirArgs b = *a;
-    b.run_pairs = pairs;
 #ifdef ACG_LAB
     if (acg_tune_get("ACG_FIR_DEBUG_DMPITCH0", 0)) b.dm_pitch = 0;          // measurement aid: every channel's dm lands in the first row (no write stream to HBM)
     if (acg_tune_has("ACG_FIR_DEBUG_SHAPE"))
         fprintf(stderr, "fir_u8_direct<%d>: nch %d nwin %d  wpg %d per_cu %d grid %lld  bodies/ch %lld pairs %d runs %lld  shares_cus %d prio %d\n",
-                CPR, a->nch, a->nwin, wpg, per_cu, grid, bodies_per_ch, pairs, nrun, a->shares_cus, a->high_prio);
+                CPR, a->nch, a->nwin, p.wpg, p.per_cu, p.grid, p.bodies_per_ch, p.pairs, p.nrun, a->shares_cus, a->high_prio);
 #endif
-    FIR_LAUNCH((fir_u8_direct_kernel<CPR, UU, BB, FOLD, WT, NOMAC>), dim3((unsigned int)grid), dim3(64 * wpg), lds, stream, b, a->iq, a->taps,
-                       a->stream_of, a->dm);
-    return (int)hipGetLastError();
+    return launch_planned(fir_u8_direct_kernel<CPR, UU, BB, FOLD, WT, NOMAC>, p, b, stream);
 }
 
 #ifdef ACG_LAB   // launchers of the lab variants
@@ -1438,9 +1391,8 @@ static int launch_direct(const FirArgs* a, int num_cu, hipStream_t stream)
 extern "C" int acg_launch_fir(const FirArgs* a, void* stream)
 {
     const size_t lds = acg_fir_lds_bytes(a);
-    FirDev* fd = nullptr;
-    if (int e = fir_device(&fd)) return e;
-    const int num_cu = fd->num_cu;
+    int num_cu = 0;
+    if (int e = acg_fir_device_cus(&num_cu)) return e;
     // ACG_FIR_VARIANT.  The PRODUCT library has two kernels behind this entry point: 5 (default) the wave-private streaming
     // kernel where it applies (whole two-tile bodies, rtlMult 160 / 192 / 200; dm stored write-through), and 3, the
     // workgroup-granular kernel with the dynamic run dispenser, for everything else (ragged launches, other window lengths).
@@ -1452,8 +1404,7 @@ extern "C" int acg_launch_fir(const FirArgs* a, void* stream)
 #ifndef ACG_LAB
     if (variant != 3) variant = 5;
 #else
-    if ((variant == 7 || variant == 8 || (variant >= 70 && variant <= 73)) && a->cpr == 25 && a->nwin > 0 && a->nwin % ACG_TILE_WIN == 0 && (a->nwin / ACG_TILE_WIN) % FIRD_R == 0 &&
-        (long long)a->nch * (a->nwin / ACG_TILE_WIN) < (1ll << 31) && a->ntaps_pad <= a->decim)
+    if ((variant == 7 || variant == 8 || (variant >= 70 && variant <= 73)) && a->cpr == 25 && acg_fir_u8_wave_takes(a))
     {            // 70..73: measurement knobs (staging slots, burst length)
         if (variant == 8) return launch_coltap<true, 13, 1, true>(a, num_cu, (hipStream_t)stream);      // results parked in LDS, chip-wide bursts
         if (variant == 70) return launch_coltap<true, 26, 1>(a, num_cu, (hipStream_t)stream);
@@ -1462,14 +1413,12 @@ extern "C" int acg_launch_fir(const FirArgs* a, void* stream)
         if (variant == 73) return launch_coltap<true, 4, 2>(a, num_cu, (hipStream_t)stream);
         return launch_coltap<>(a, num_cu, (hipStream_t)stream);
     }
-    if (variant == 6 && a->cpr == 25 && a->nwin > 0 && a->nwin % ACG_TILE_WIN == 0 && (a->nwin / ACG_TILE_WIN) % FIRD_R == 0 &&
-        (long long)a->nch * (a->nwin / ACG_TILE_WIN) < (1ll << 31) && a->ntaps_pad <= a->decim)
+    if (variant == 6 && a->cpr == 25 && acg_fir_u8_wave_takes(a))
         return launch_mfma<25>(a, num_cu, (hipStream_t)stream);
 #endif
-    if ((variant == 5 || (variant >= 50 && variant <= 56)) && a->nwin > 0 && a->nwin % ACG_TILE_WIN == 0 && (a->nwin / ACG_TILE_WIN) % FIRD_R == 0 &&
-        (long long)a->nch * (a->nwin / ACG_TILE_WIN) < (1ll << 31) && a->ntaps_pad <= a->decim) {
+    if ((variant == 5 || (variant >= 50 && variant <= 56)) && acg_fir_u8_wave_takes(a)) {
         switch (a->cpr) {
-        // (dm is stored write-through: beside the streaming reads a write-back line costs more, see firc_flush)
+        // (dm is stored write-through: beside the streaming reads a write-back line costs more)
         case 20: return launch_direct<20, 0, 0, true, true>(a, num_cu, (hipStream_t)stream);
         case 24: return launch_direct<24, 0, 0, true, true>(a, num_cu, (hipStream_t)stream);
         case 25:
@@ -1551,9 +1500,8 @@ extern "C" int acg_launch_fir(const FirArgs* a, void* stream)
 extern "C" int acg_launch_fir_shared(const FirArgs* a, void* stream)
 {
     const size_t lds = (size_t)ACG_TILE_WIN * a->row_stride + 16 * 64 * sizeof(float4) + 16;
-    FirDev* fd = nullptr;
-    if (int e = fir_device(&fd)) return e;
-    const int num_cu = fd->num_cu;
+    int num_cu = 0;
+    if (int e = acg_fir_device_cus(&num_cu)) return e;
     if (lds > 64 * 1024) return (int)hipErrorInvalidValue;
     int per_cu = (int)((160 * 1024) / lds);
     if (per_cu > 4) per_cu = 4;

@@ -33,8 +33,6 @@
 // wave involved.  8 waves per CU with 13.2 KiB of LDS and 10-12.5 KiB of loads in flight each, or (beside the demodulator) 4 waves
 // per CU with two tiles = 20-25 KiB in flight each.
 #include <hip/hip_runtime.h>
-#include <map>
-#include <mutex>
 #include "acg_internal.h"
 #include "fir_mm_plan.h"
 
@@ -448,52 +446,14 @@ void fir_u8_mm1_kernel(const FirArgs a, const uint8_t* __restrict__ iq_base, con
 
 // ---- launch side ------------------------------------------------------------------------------------------------------
 namespace {
-struct MmDev {
-    bool ready = false;
-    int num_cu = 256;
-    std::map<const void*, size_t> optin;
-};
-MmDev g_mmdev[64];
-std::mutex g_mm_mx;
-
-int mm_device(MmDev** out)
-{
-    int dev = 0;
-    const hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    if (dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
-    std::lock_guard<std::mutex> lk(g_mm_mx);
-    MmDev* d = &g_mmdev[dev];
-    if (!d->ready) {
-        (void)hipDeviceGetAttribute(&d->num_cu, hipDeviceAttributeMultiprocessorCount, dev);
-        d->ready = true;
-    }
-    *out = d;
-    return 0;
-}
-
-int mm_optin(MmDev* d, const void* kernel, size_t bytes)
-{
-    std::lock_guard<std::mutex> lk(g_mm_mx);
-    size_t& have = d->optin[kernel];
-    if (bytes > have) {
-        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return (int)e;
-        have = bytes;
-    }
-    return 0;
-}
-
 template <int CPR, int STAGES>
 int launch_mm(const FirArgs* a, const MmPlan& p, hipStream_t stream)
 {
     typedef FirMM<CPR> F;
-    MmDev* d = nullptr;
-    if (int e = mm_device(&d)) return e;
     FirArgs b = *a;
     b.run_pairs = (int)p.tiles_per_run;
     const size_t lds = (size_t)4 * F::WAVE_LDS;
-    if (int e = mm_optin(d, (const void*)fir_u8_mm_kernel<CPR, STAGES>, lds)) return e;
+    if (int e = acg_fir_lds_optin((const void*)fir_u8_mm_kernel<CPR, STAGES>, lds)) return e;
     hipLaunchKernelGGL((fir_u8_mm_kernel<CPR, STAGES>), dim3(p.workgroups), dim3(256), lds, stream, b, a->iq, (const u4m_t*)a->mm_img,
                        (const MmChan*)a->mm_chan, a->groups, a->group_ch, a->dm);
     return (int)hipGetLastError();
@@ -534,9 +494,9 @@ extern "C" int acg_launch_fir_mm_prep(const FirArgs* a, void* stream)
 extern "C" int acg_launch_fir_mm(const FirArgs* a, void* stream)
 {
     if (!acg_fir_mm_takes(a)) return (int)hipErrorInvalidValue;
-    MmDev* d = nullptr;
-    if (int e = mm_device(&d)) return e;
-    const MmPlan p = acg_fir_mm_plan(a, d->num_cu);
+    int num_cu = 0;
+    if (int e = acg_fir_device_cus(&num_cu)) return e;
+    const MmPlan p = acg_fir_mm_plan(a, num_cu);
     switch (p.cpr) {
     case 20: return p.stages == 2 ? launch_mm<20, 2>(a, p, (hipStream_t)stream) : launch_mm<20, 1>(a, p, (hipStream_t)stream);
     case 24: return p.stages == 2 ? launch_mm<24, 2>(a, p, (hipStream_t)stream) : launch_mm<24, 1>(a, p, (hipStream_t)stream);
@@ -551,12 +511,10 @@ template <int CPR>
 int launch_mm1(const FirArgs* a, const MmPlan& p, hipStream_t stream)
 {
     typedef FirMM<CPR> F;
-    MmDev* d = nullptr;
-    if (int e = mm_device(&d)) return e;
     FirArgs b = *a;
     b.run_pairs = (int)p.tiles_per_run;
     const size_t lds = (size_t)F::WAVE_LDS;
-    if (int e = mm_optin(d, (const void*)fir_u8_mm1_kernel<CPR>, lds)) return e;
+    if (int e = acg_fir_lds_optin((const void*)fir_u8_mm1_kernel<CPR>, lds)) return e;
     hipLaunchKernelGGL(fir_u8_mm1_kernel<CPR>, dim3(p.workgroups), dim3(64), lds, stream, b, a->iq, (const u4m_t*)a->mm_img,
                        (const MmChan*)a->mm_chan, a->stream_of, a->dm);
     return (int)hipGetLastError();
@@ -596,9 +554,9 @@ extern "C" int acg_launch_fir_mm1_prep(const FirArgs* a, void* stream)
 extern "C" int acg_launch_fir_mm1(const FirArgs* a, void* stream)
 {
     if (!acg_fir_mm1_takes(a)) return (int)hipErrorInvalidValue;
-    MmDev* d = nullptr;
-    if (int e = mm_device(&d)) return e;
-    const MmPlan p = acg_fir_mm1_plan(a, d->num_cu);
+    int num_cu = 0;
+    if (int e = acg_fir_device_cus(&num_cu)) return e;
+    const MmPlan p = acg_fir_mm1_plan(a, num_cu);
     switch (p.cpr) {
     case 20: return launch_mm1<20>(a, p, (hipStream_t)stream);
     case 24: return launch_mm1<24>(a, p, (hipStream_t)stream);

@@ -128,7 +128,7 @@ __device__ __forceinline__ void firc_body(const FirArgs& a, const uint8_t* __res
                                           const int* __restrict__ stream_of, float* __restrict__ dm_base)
 {
     typedef FirC<UU, BB> F;
-    constexpr unsigned int NONE = 0xffffffffu;
+    constexpr unsigned int NONE = RunDisp::NONE;
     if (a.high_prio) __builtin_amdgcn_s_setprio(2);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -169,33 +169,7 @@ __device__ __forceinline__ void firc_body(const FirArgs& a, const uint8_t* __res
     const unsigned int voff = (unsigned int)lane << 4;
     const int nck = a.ntaps_pad >> 3;                                               // tap columns that carry taps
 
-    auto shard_runs = [&](unsigned int s) { return (nrun + ACG_DISP_SHARDS - 1 - s) / ACG_DISP_SHARDS; };
-    auto shard_static = [&](unsigned int s) { return (nwaves + ACG_DISP_SHARDS - 1 - s) / ACG_DISP_SHARDS; };
-    auto run_of_ticket = [&](unsigned int s, unsigned int t) -> unsigned int {
-        const unsigned long long k = (unsigned long long)shard_static(s) + t;
-        return k < shard_runs(s) ? (unsigned int)k * ACG_DISP_SHARDS + s : NONE;
-    };
-    auto probe = [&](unsigned int& s) -> unsigned int {
-        for (int k = 0; k < ACG_DISP_SHARDS; ++k) {
-            unsigned int t = 0;
-            if (lane == 0) t = __hip_atomic_fetch_add(ctr + s * ACG_DISP_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            t = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
-            const unsigned int r = run_of_ticket(s, t);
-            if (r != NONE) return r;
-            s = (s + 1 == ACG_DISP_SHARDS) ? 0 : s + 1;
-        }
-        return NONE;
-    };
-    auto sign_off = [&]() {
-        if (lane == 0) {
-            const unsigned int d = atomicAdd(ctr + ACG_DISP_SHARDS * ACG_DISP_STRIDE, 1u);
-            if (d == nwaves - 1) {
-#pragma unroll
-                for (int k = 0; k <= ACG_DISP_SHARDS; ++k)
-                    __hip_atomic_store(ctr + k * ACG_DISP_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    };
+    const RunDisp disp = {ctr, nrun, nwaves, lane};
     auto run_base = [&](unsigned int run, unsigned int& ch, unsigned int& t0) -> const uint8_t* {
         ch = run / runs_per_ch;
         t0 = (run - ch * runs_per_ch) * FIRD_R * pairs;
@@ -238,11 +212,8 @@ __device__ __forceinline__ void firc_body(const FirArgs& a, const uint8_t* __res
 
     unsigned int s = wg % ACG_DISP_SHARDS;
     unsigned int run = wg < nrun ? wg : NONE;
-    if (run == NONE) {                                              // tiny launches: fewer runs than waves
-        s = (s + 1 == ACG_DISP_SHARDS) ? 0 : s + 1;
-        run = probe(s);
-    }
-    if (run == NONE) { sign_off(); return; }
+    if (run == NONE) run = disp.probe_after(s);                     // tiny launches: fewer runs than waves
+    if (run == NONE) { disp.sign_off(); return; }
 
     unsigned int ch, t0;
     const uint8_t* base = run_base(run, ch, t0);
@@ -273,11 +244,8 @@ __device__ __forceinline__ void firc_body(const FirArgs& a, const uint8_t* __res
             const uint8_t* nbase = base + run_bytes;                // the next body of this run ...
             if (j + 1 == pairs) {                                   // ... or the first body of the next run
                 // (U loads and a store are in flight, all younger than the ticket)
-                nrun_ = run_of_ticket(s, ticket_take<F::U + 1>(tk));
-                if (nrun_ == NONE) {
-                    s = (s + 1 == ACG_DISP_SHARDS) ? 0 : s + 1;
-                    nrun_ = probe(s);
-                }
+                nrun_ = disp.run_of_ticket(s, ticket_take<F::U + 1>(tk));
+                if (nrun_ == NONE) nrun_ = disp.probe_after(s);
                 has_next = nrun_ != NONE;
                 nbase = base;
                 if (has_next) nbase = run_base(nrun_, nch_, nt0);
@@ -297,7 +265,7 @@ __device__ __forceinline__ void firc_body(const FirArgs& a, const uint8_t* __res
         t0 = nt0;
     }
     if (STAGED && nst) firc_flush(stage, stage_dst, nst, lane);
-    sign_off();
+    disp.sign_off();
 }
 
 template <bool FOLD = true, int UU = 13, int BB = 1, bool STAGED = false>

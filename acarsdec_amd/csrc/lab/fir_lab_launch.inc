@@ -2,63 +2,27 @@
 // provides the helpers it uses; the product library never sees this file (tests/test_host_logic.py compares the product's
 // kernel list; the product object is byte-identical with and without it).
 // register-resident taps (ACG_FIR_VARIANT=7 / 8, 2.5 Msps): 13 / 17 KiB of LDS per wave
+// (twelve waves per CU fit and measure 1-6 % slower than eight, alone and beside the demodulator: profiles/r02_experiments)
 template <bool FOLD = true, int UU = 13, int BB = 1, bool STAGED = false>
 static int launch_coltap(const FirArgs* a, int num_cu, hipStream_t stream)
 {
-    int wpg = env_int("ACG_FIR_WAVES_PER_WG", a->shares_cus ? 1 : 4);
-    if (wpg != 1 && wpg != 2 && wpg != 4) wpg = 4;
-    const size_t lds = (size_t)wpg * (STAGED ? FirC<UU, BB>::WAVE_LDS_STAGED : FirC<UU, BB>::WAVE_LDS);
-    int per_cu = (int)((160 * 1024) / lds);
-    // (twelve waves per CU fit and measure 1-6 % slower than eight, alone and beside the demodulator: profiles/r02_experiments)
-    if (per_cu > 8 / wpg) per_cu = 8 / wpg;
-    if (a->shares_cus && wpg == 1 && per_cu > 7) per_cu = 7;        // leave the demodulator's workgroups their LDS (28 KiB per CU)
-    per_cu = env_int("ACG_FIR_WG_PER_CU", per_cu);
-    long long grid = (long long)(a->ncu > 0 ? a->ncu : num_cu) * per_cu;
-    const long long bodies_per_ch = a->nwin / ACG_TILE_WIN / FIRD_R;
-    const long long bodies = (long long)a->nch * bodies_per_ch;
-    int pairs = 1;
-    while (pairs < 8 && bodies_per_ch % (2 * pairs) == 0 && bodies / (2 * pairs) >= 32 * grid * wpg) pairs *= 2;
-    pairs = env_int("ACG_FIR_RUN_PAIRS", pairs);
-    if (pairs < 1 || pairs > 8 || (pairs & (pairs - 1)) || bodies_per_ch % pairs) pairs = 1;
-    const long long nrun = bodies / pairs;
-    const long long need = (nrun + wpg - 1) / wpg;
-    if (grid > need) grid = need;
-    FirArgs b = *a;
-    b.run_pairs = pairs;
+    constexpr int WAVE_LDS = STAGED ? FirC<UU, BB>::WAVE_LDS_STAGED : FirC<UU, BB>::WAVE_LDS;
+    static_assert(4 * WAVE_LDS <= FIR_CU_LDS, "a four-wave workgroup fits a CU: the plan's fit is >= 1");
+    const FirWavePlan p = acg_fir_wave_plan(a, num_cu, WAVE_LDS, ACG_TILE_WIN, 8);
     if (acg_tune_has("ACG_FIR_DEBUG_SHAPE"))
         fprintf(stderr, "fir_u8_coltap: nch %d nwin %d  wpg %d per_cu %d grid %lld  bodies/ch %lld pairs %d runs %lld  shares_cus %d prio %d lds %zu\n",
-                a->nch, a->nwin, wpg, per_cu, grid, bodies_per_ch, pairs, nrun, a->shares_cus, a->high_prio, lds);
-    FIR_LAUNCH((fir_u8_coltap_kernel<FOLD, UU, BB, STAGED>), dim3((unsigned int)grid), dim3(64 * wpg), lds, stream, b, a->iq, a->taps,
-                       a->stream_of, a->dm);
-    return (int)hipGetLastError();
+                a->nch, a->nwin, p.wpg, p.per_cu, p.grid, p.bodies_per_ch, p.pairs, p.nrun, a->shares_cus, a->high_prio, p.lds);
+    return launch_planned(fir_u8_coltap_kernel<FOLD, UU, BB, STAGED>, p, *a, stream);
 }
 
-// matrix-pipe variant (ACG_FIR_VARIANT=6): single-wave workgroups, as many as the LDS holds (5 per CU at 2.5 Msps)
+// matrix-pipe variant (ACG_FIR_VARIANT=6): as many waves as the LDS holds, twelve per CU at most (9 at 2.5 Msps)
 template <int CPR>
 static int launch_mfma(const FirArgs* a, int num_cu, hipStream_t stream)
 {
-    int wpg = env_int("ACG_FIR_WAVES_PER_WG", a->shares_cus ? 1 : 4);
-    if (wpg != 1 && wpg != 2 && wpg != 4) wpg = 4;
-    const size_t lds = (size_t)wpg * FirM<CPR>::WAVE_LDS;
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 12 / wpg) per_cu = 12 / wpg;
-    if (a->shares_cus && wpg == 1 && per_cu > 7) per_cu = 7;        // leave the demodulator's workgroups their LDS
-    per_cu = env_int("ACG_FIR_WG_PER_CU", per_cu);
-    long long grid = (long long)(a->ncu > 0 ? a->ncu : num_cu) * per_cu;
-    const long long bodies_per_ch = a->nwin / ACG_TILE_WIN / FIRD_R;
-    const long long bodies = (long long)a->nch * bodies_per_ch;
-    int pairs = 1;
-    while (pairs < 8 && bodies_per_ch % (2 * pairs) == 0 && bodies / (2 * pairs) >= 32 * grid * wpg) pairs *= 2;
-    pairs = env_int("ACG_FIR_RUN_PAIRS", pairs);
-    if (pairs < 1 || pairs > 8 || (pairs & (pairs - 1)) || bodies_per_ch % pairs) pairs = 1;
-    const long long nrun = bodies / pairs;
-    const long long need = (nrun + wpg - 1) / wpg;
-    if (grid > need) grid = need;
-    FirArgs b = *a;
-    b.run_pairs = pairs;
+    static_assert(4 * FirM<CPR>::WAVE_LDS <= FIR_CU_LDS, "a four-wave workgroup fits a CU: the plan's fit is >= 1");
+    const FirWavePlan p = acg_fir_wave_plan(a, num_cu, FirM<CPR>::WAVE_LDS, ACG_TILE_WIN, 12);
     if (acg_tune_has("ACG_FIR_DEBUG_SHAPE"))
-        fprintf(stderr, "fir_u8_mfma<%d>: nch %d nwin %d  wpg %d per_cu %d grid %lld pairs %d runs %lld lds %zu\n", CPR, a->nch, a->nwin, wpg, per_cu, grid, pairs, nrun, lds);
-    FIR_LAUNCH((fir_u8_mfma_kernel<CPR>), dim3((unsigned int)grid), dim3(64 * wpg), lds, stream, b, a->iq, a->taps, a->stream_of, a->dm);
-    return (int)hipGetLastError();
+        fprintf(stderr, "fir_u8_mfma<%d>: nch %d nwin %d  wpg %d per_cu %d grid %lld pairs %d runs %lld lds %zu\n", CPR, a->nch, a->nwin, p.wpg, p.per_cu, p.grid, p.pairs,
+                p.nrun, p.lds);
+    return launch_planned(fir_u8_mfma_kernel<CPR>, p, *a, stream);
 }
-

@@ -65,7 +65,7 @@ def test_tuning_switches_go_through_one_table_not_the_environment():
     assert L.acg_is_lab_build() == 0 and K.load(lab=True).acg_is_lab_build() == 1
     assert L.acg_tune(b"ACG_FIR_VARIANT", b"3") == K.OK and L.acg_tune(b"ACG_FIR_VARIANT", None) == K.OK
     assert L.acg_tune(b"LD_PRELOAD", b"x") == K.EINVAL and L.acg_tune(None, b"1") == K.EINVAL
-    src = "".join(open(os.path.join(ROOT, "acarsdec_amd", "csrc", f)).read() for f in ("fir.hip", "msk.hip", "msk_lean.hip", "msk_common.h"))
+    src = "".join(open(os.path.join(ROOT, "acarsdec_amd", "csrc", f)).read() for f in ("fir.hip", "fir_plan.h", "msk.hip", "msk_lean.hip", "msk_common.h"))
     assert "getenv(" not in src                                   # no launch path reads the environment
     code = ("import os, sys; sys.path.insert(0, %r); os.environ['ACG_FIR_DEBUG_SHAPE'] = '1'\n"
             "from acarsdec_amd import _capi as K; K.tune('ACG_MSK_LPC', 4, lab=%%s)" % ROOT)
@@ -335,6 +335,26 @@ def test_async_ticket_register_is_left_alone_until_its_wait():
     assert not [l for l in body if re.search(r"\bv_(pk_)?(fma|fmac|mac|mad)_(f32|legacy_f32)", l)], "fused multiply-add in the exact-order kernel"
     # (re, im) ride in packed pairs: two packed products, their packed difference / sum, one packed accumulate per tap
     assert sum("v_pk_mul_f32" in l for l in body) >= 2 and sum("v_pk_add_f32" in l for l in body) >= 3, "\n".join(body)
+
+
+def test_wave_private_launch_plan_keeps_what_the_kernels_assume(tmp_path):
+    """csrc/fir_plan.h decides the launch of the wave-private down-converters (fir_u8_direct_kernel, fir_fmt_direct_kernel, the
+    lab's coltap and mfma kernels); the kernels rely on it ("(launcher)" in their comments).  tests/fir_plan_check.cpp compiles
+    the header for the host, under the address and undefined-behaviour sanitizers, and sweeps channels, callbacks, CU counts,
+    shared CUs, every instantiation's (LDS per wave, windows per tile, wave cap) and the ACG_FIR_WAVES_PER_WG / ACG_FIR_RUN_PAIRS
+    overrides: pairs is 1, 2, 4 or 8 and divides a channel's bodies, nrun < 2^31, 1 <= grid <= ceil(nrun / wpg), the waves per
+    CU stay under the cap and their LDS under 160 KiB."""
+    import shutil
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "a host C++ compiler"
+    exe = str(tmp_path / "fir_plan_check")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] +
+                       ([] if "clang" in os.path.basename(cxx) else ["-static-libasan", "-static-libubsan"]) +      # (clang links them statically anyway)
+                       ["-I" + os.path.join(ROOT, "acarsdec_amd", "csrc"), os.path.join(ROOT, "tests", "fir_plan_check.cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.stdout[-2000:], r.stderr[-2000:])
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-2000:]
 
 
 def test_demodulator_loop_keeps_its_state_in_registers():
