@@ -77,6 +77,12 @@ class Route(C.Structure):
                 ("sa", C.c_char * 5), ("da", C.c_char * 5), ("addr", C.c_char * 8), ("reserved", C.c_char * 7)]
 
 
+class FlightTextConfig(C.Structure):
+    """acg_flight_text_config: the monitor's mask columns (the reference's nbch) and the route line's station id"""
+    _fields_ = [("nbch", C.c_int), ("station_id", C.c_char * 33)]
+
+
+MONITOR_CLS_LEN, MONITOR_HDR_LEN, MONITOR_ROW_MAX, ROUTE_LINE_MAX = 7, 110, 78, 363
 JSON_LINE_MAX = 2496
 
 
@@ -148,6 +154,10 @@ SYMBOLS = {
     "acg_flights_enable": (C.c_int, [C.c_void_p, C.POINTER(FlightConfig)]),
     "acg_flight_snapshot": (C.c_int, [C.c_void_p, C.POINTER(Flight), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "acg_drain_routes": (C.c_int, [C.c_void_p, C.POINTER(Route), C.c_int, C.POINTER(C.c_int)]),
+    "acg_flight_text_enable": (C.c_int, [C.c_void_p, C.POINTER(FlightTextConfig)]),
+    "acg_flight_monitor_text": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int)]),
+    "acg_drain_routes_json": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "acg_json_enable": (C.c_int, [C.c_void_p, C.POINTER(JsonConfig), C.c_void_p]),
     "acg_drain_json": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "acg_collect_json": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
@@ -190,6 +200,9 @@ LAB_SYMBOLS = {
     "acg_selftest_flights": (C.c_int, [C.POINTER(Msg), C.POINTER(C.c_int), C.c_int, C.POINTER(FlightConfig), C.POINTER(MsgFilter),
                                        C.POINTER(Flight), C.c_int, C.POINTER(C.c_int), C.POINTER(Route), C.c_int, C.POINTER(C.c_int),
                                        C.POINTER(C.c_int)]),
+    "acg_selftest_flight_text": (C.c_int, [C.POINTER(Flight), C.c_int, C.POINTER(Route), C.c_int, C.POINTER(FlightConfig),
+                                           C.POINTER(FlightTextConfig), C.c_longlong, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "acg_selftest_msg_json": (C.c_int, [C.POINTER(Msg), C.c_int, C.POINTER(MsgFilter), C.POINTER(JsonConfig), C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "acg_lab_json_level_guard": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint)]),

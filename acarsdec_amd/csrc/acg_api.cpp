@@ -2050,6 +2050,95 @@ extern "C" int acg_selftest_msg_json(const acg_msg* in, int n, const acg_msg_fil
     return sink_selftest(&SINK_JSON, json_blob(cfg, Fr_hz, nch), in, n, f, nch, out, cap, nbytes, nullptr, nlines);
 }
 
+// ---- the flight table's text (flight_text.hip; host side: flights.cpp): the monitor screen and the route lines ------------------
+static_assert(ACG_FT_ROW_MAX == ACG_MONITOR_ROW_MAX && ACG_FT_LINE_MAX == ACG_ROUTE_LINE_MAX && ACG_FT_HDR_LEN == ACG_MONITOR_HDR_LEN, "record bounds");
+
+static bool flight_text_config_ok(const acg_flight_text_config* c)
+{
+    return c && c->nbch >= 0 && c->nbch <= 16 && std::memchr(c->station_id, 0, sizeof(c->station_id));
+}
+
+// nbch and the station stretch of a route line, escaped as the JSON sink's; cfg has passed flight_text_config_ok
+static AcgFlightTextDev flight_text_dev(const acg_flight_text_config* cfg)
+{
+    AcgFlightTextDev h;
+    std::memset(&h, 0, sizeof(h));
+    h.nbch = cfg->nbch;
+    if (cfg->station_id[0]) {                                     // output.c:444
+        h.pre_len = json_append(h.pre, 0, ",\"station_id\":\"");
+        h.pre_len = json_escape(h.pre, h.pre_len, cfg->station_id);
+        h.pre_len = json_append(h.pre, h.pre_len, "\"");          // (at most 208 of ACG_JS_PRE_MAX bytes)
+    }
+    return h;
+}
+
+extern "C" int acg_flight_text_enable(acg_ctx* ctx, const acg_flight_text_config* cfg)
+{
+    if (!ctx) return ACG_EINVAL;
+    if (cfg && !flight_text_config_ok(cfg)) return fail(ctx, ACG_EINVAL, "flight text: nbch outside 0..16, or an unterminated station_id");
+    if (!ctx->flights || !acg_fl_text_enable) return fail(ctx, ACG_ESTATE, "flight text: the flight table is off (acg_flights_enable first)");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    if (!cfg) return acg_fl_text_enable(ctx->flights, nullptr);
+    const AcgFlightTextDev h = flight_text_dev(cfg);
+    const int rc = acg_fl_text_enable(ctx->flights, &h);
+    return rc == ACG_OK ? rc : fail(ctx, rc, "flight text: allocation failed");
+}
+
+extern "C" int acg_flight_monitor_text(acg_ctx* ctx, long long hdr_soh_sample, char* out, size_t cap, size_t* nbytes, int* nrows, int* dropped)
+{
+    if (!ctx || !nbytes || !nrows || (cap > 0 && !out)) return ACG_EINVAL;
+    *nbytes = 0;
+    *nrows = 0;
+    if (!ctx->flights) return fail(ctx, ACG_ESTATE, "flight table is off");
+    if (!acg_fl_text_on(ctx->flights)) return fail(ctx, ACG_ESTATE, "flight text is off: acg_flight_text_enable first");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int rc = acg_fl_monitor_text(ctx->flights, ctx->copy_stream, hdr_soh_sample, out, cap, nbytes, nrows, dropped);
+    return rc == ACG_OK ? rc : fail(ctx, rc, rc == ACG_EAGAIN ? "the frame does not fit: *nbytes says how many bytes it needs" : "monitor frame failed");
+}
+
+extern "C" int acg_drain_routes_json(acg_ctx* ctx, char* out, size_t cap, size_t* nbytes, int* nlines)
+{
+    if (!ctx || !nbytes || !nlines || (cap > 0 && !out)) return ACG_EINVAL;
+    *nbytes = 0;
+    *nlines = 0;
+    if (!ctx->flights) return fail(ctx, ACG_ESTATE, "flight table is off");
+    if (!acg_fl_text_on(ctx->flights)) return fail(ctx, ACG_ESTATE, "flight text is off: acg_flight_text_enable first");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int rc = acg_fl_routes_json(ctx->flights, ctx->copy_stream, out, cap, nbytes, nlines);
+    return rc == ACG_OK ? rc : fail(ctx, rc, rc == ACG_EAGAIN ? "the route lines do not fit: *nbytes says how many bytes they need" :
+                                             rc == ACG_ESTATE ? "routes are pending from an acg_drain_routes that returned ACG_EAGAIN: drain them there first" :
+                                                                "route lines failed");
+}
+
+extern "C" int acg_selftest_flight_text(const acg_flight* in, int n, const acg_route* rt, int nr, const acg_flight_config* cfg,
+                                        const acg_flight_text_config* tcfg, long long hdr_soh_sample, char* mon, size_t mon_cap, size_t* mon_nbytes,
+                                        int* nrows, char* rts, size_t rts_cap, size_t* rts_nbytes, int* nlines)
+{
+    if (n < 0 || nr < 0 || n > (1 << 24) || (n > 0 && !in) || (nr > 0 && !rt) || !acg_fl_config_ok(cfg) || !flight_text_config_ok(tcfg) || !mon_nbytes ||
+        !nrows || !rts_nbytes || !nlines || (mon_cap > 0 && !mon) || (rts_cap > 0 && !rts))
+        return ACG_EINVAL;
+    *mon_nbytes = *rts_nbytes = 0;
+    *nrows = *nlines = 0;
+    int ndev = 0;
+    if (!acg_fl_create || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
+    acg_flight_config c = *cfg;
+    c.max_flights = std::max(c.max_flights, std::max(n, 1));
+    AcgFlights* t = nullptr;
+    int rc = acg_fl_create(&t, &c);
+    if (rc != ACG_OK) return rc;
+    const AcgFlightTextDev h = flight_text_dev(tcfg);
+    rc = acg_fl_text_enable(t, &h);
+    if (rc == ACG_OK) rc = acg_fl_load_designed(t, in, n, rt, nr);
+    if (rc == ACG_OK) {
+        const int rm = acg_fl_monitor_text(t, nullptr, hdr_soh_sample, mon, mon_cap, mon_nbytes, nrows, nullptr);
+        const int rr = (rm == ACG_OK || rm == ACG_EAGAIN) ? acg_fl_routes_json(t, nullptr, rts, rts_cap, rts_nbytes, nlines) : rm;
+        rc = (rr == ACG_OK || rr == ACG_EAGAIN) ? (rm != ACG_OK ? rm : rr) : rr;
+    }
+    acg_fl_destroy(t);
+    return rc;
+}
+
 // ---- the text sink: its configuration and entry points ------------------------------------------------------------------------
 static bool text_config_ok(const acg_text_config* c)
 {

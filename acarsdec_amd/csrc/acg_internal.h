@@ -188,6 +188,39 @@ struct AcgSinkPass {
     unsigned int out_cap;
 };
 
+// ---- the flight table's text (flight_text.hip): printmonitor()'s screen (output.c:458-484) and routejson()'s line (output.c:428-456)
+#define ACG_FT_ROW_MAX 78       // == ACG_MONITOR_ROW_MAX of the public header (derived there)
+#define ACG_FT_LINE_MAX 363     // == ACG_ROUTE_LINE_MAX of the public header (derived there)
+#define ACG_FT_HDR_LEN 110      // cls() 7 + "             Acarsdec monitor " 30 + printtime() 12 + the column header line 61
+// What acg_flight_text_enable renders once on the host
+struct AcgFlightTextDev {
+    int nbch;                   // mask columns shown, 0 .. 16
+    unsigned int pre_len;
+    unsigned char pre[ACG_JS_PRE_MAX];      // ,"station_id":"<escaped>" or nothing, as AcgJsonDev's
+};
+
+// One pass of flight_text.hip: the monitor frame over the live slots in snapshot order, or the route lines over the queue
+struct AcgFlightTextPass {
+    const AcgFlightTextDev* cfg;
+    long long t0_sec;
+    int t0_usec;
+    int pad_;
+    long long hdr_soh;          // monitor: the header's message, tv = t0 + hdr_soh / 12500 s; < 0: the newest live entry's tl (none: t0)
+    const AcgFlightSlot* slots; // monitor: the table ...
+    const AcgFlightState* st;   // ... and its state (nlive = the rows, dropped)
+    const AcgRouteRec* routes;  // routes: the queue
+    const unsigned int* total;  // a device word: the rows / lines of this pass
+    unsigned int nmax;          // >= *total: what the work space is sized for
+    unsigned int base;          // bytes in front of the first record (the monitor's header)
+    unsigned long long *key, *key_s;    // routes: the (pass, rank) tag and the sorted tags
+    unsigned int *idx, *idx_s;          // routes: queue index, and in sorted order; monitor: idx_s = the slots in snapshot order
+    unsigned int *len, *off;            // per sorted rank: length, byte offset behind base
+    unsigned int *wg_sum, *wg_cnt;      // per 256 ranks: bytes, records
+    unsigned int* counters;     // [0] bytes behind base, [1] records; [2] monitor: the table's `dropped`; [3] routes: the lines of this pass
+    unsigned char* out;         // 16-byte aligned
+    unsigned int out_cap;
+};
+
 struct FirArgs {
     const uint8_t* iq;          // [nstreams] rows
     size_t pitch;               // bytes between stream rows (multiple of 16)
@@ -312,6 +345,13 @@ int acg_launch_flight_pass(const AcgMsgRec* recs, unsigned int n, const AcgLabel
 // flight.hip: the live entries, latest update first, as acg_flight records in out[cap]; st->nlive = how many
 int acg_launch_flight_snapshot(const AcgFlightPass* p, unsigned long long* skey, unsigned long long* skey_s, unsigned int* sval,
                                unsigned int* sval_s, void* out, void* stream);
+// flight.hip: the snapshot's first half -- the live slots compacted and put in snapshot order: sval_s[0 .. st->nlive)
+int acg_launch_flight_snapkeys(const AcgFlightPass* p, unsigned long long* skey, unsigned long long* skey_s, unsigned int* sval,
+                               unsigned int* sval_s, void* stream);
+// flight_text.hip: measure, scan and render the monitor frame over the slots idx_s[0 .. *total) (behind acg_launch_flight_snapkeys);
+// keys, sort, measure, scan and render the lines of the first n queued routes.  p->counters says how much.
+int acg_launch_flight_monitor_text(const AcgFlightTextPass* p, void* stream);
+int acg_launch_flight_route_text(const AcgFlightTextPass* p, unsigned int n, void* stream);
 // flight.hip: the pass's stable radix sort of (64-bit key, 32-bit value) pairs by one workgroup, for other passes: n = *n_ptr
 // (a device word) or n_fixed; the result lies in (kb, vb)
 int acg_launch_sort_pairs(unsigned long long* ka, unsigned int* va, unsigned long long* kb, unsigned int* vb, const unsigned int* n_ptr,

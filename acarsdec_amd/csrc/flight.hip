@@ -488,14 +488,24 @@ __global__ __launch_bounds__(FL_WG) void flight_snapshot_kernel(AcgFlightPass p,
     for (int k = 35; k < 40; ++k) b[k] = 0;
 }
 
-extern "C" int acg_launch_flight_snapshot(const AcgFlightPass* p, unsigned long long* skey, unsigned long long* skey_s, unsigned int* sval,
-                                          unsigned int* sval_s, void* out, void* stream)
+extern "C" int acg_launch_flight_snapkeys(const AcgFlightPass* p, unsigned long long* skey, unsigned long long* skey_s, unsigned int* sval,
+                                          unsigned int* sval_s, void* stream)
 {
     hipStream_t s = (hipStream_t)stream;
     const unsigned int g = (p->cap + FL_WG - 1) / FL_WG;
     if (hipMemsetAsync(&p->st->nlive, 0, sizeof(unsigned int), s) != hipSuccess) return (int)hipErrorUnknown;
     hipLaunchKernelGGL(flight_snapkeys_kernel, dim3(g), dim3(FL_WG), 0, s, *p, skey, sval);
     hipLaunchKernelGGL(flight_sort_kernel, dim3(1), dim3(RS_WG), 0, s, skey, sval, skey_s, sval_s, (const unsigned int*)&p->st->nlive, 0u);
+    return (int)hipGetLastError();
+}
+
+extern "C" int acg_launch_flight_snapshot(const AcgFlightPass* p, unsigned long long* skey, unsigned long long* skey_s, unsigned int* sval,
+                                          unsigned int* sval_s, void* out, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned int g = (p->cap + FL_WG - 1) / FL_WG;
+    const int e = acg_launch_flight_snapkeys(p, skey, skey_s, sval, sval_s, stream);
+    if (e) return e;
     hipLaunchKernelGGL(flight_snapshot_kernel, dim3(g), dim3(FL_WG), 0, s, *p, (const unsigned long long*)skey_s, (const unsigned int*)sval_s, (unsigned char*)out);
     return (int)hipGetLastError();
 }

@@ -23,6 +23,15 @@ struct AcgFlights {
     unsigned char* snap_out = nullptr;
     size_t route_bound = 0;             // no more routes than this can be queued on the device
     std::deque<acg_route> pending;      // routes already fetched and ordered, not yet handed out
+    // ---- the table's text (flight_text.hip), acg_fl_text_enable
+    AcgFlightTextDev* d_tcfg = nullptr; // null: the renderer is off
+    unsigned int* t_cnt = nullptr;      // [4]: bytes, records of the last pass; dropped; the route pass's lines
+    void* m_work = nullptr;             // monitor: len, off [cap], wg_sum, wg_cnt, the frame
+    unsigned int *m_len = nullptr, *m_wg = nullptr;
+    unsigned char* m_out = nullptr;
+    size_t m_out_cap = 0;
+    void* r_work = nullptr;             // routes, grown on demand: keys, indices, len, off [r_cap], wg_sum, wg_cnt, the lines
+    size_t r_cap = 0;
 };
 
 #define FLCHK(call)                          \
@@ -39,10 +48,20 @@ static void free_work(AcgFlights* t)
     t->work_cap = 0;
 }
 
+static void free_text(AcgFlights* t)
+{
+    hipFree(t->d_tcfg); hipFree(t->t_cnt); hipFree(t->m_work); hipFree(t->r_work);
+    t->d_tcfg = nullptr;
+    t->t_cnt = nullptr;
+    t->m_work = t->r_work = nullptr;
+    t->r_cap = 0;
+}
+
 void acg_fl_destroy(AcgFlights* t)
 {
     if (!t) return;
     free_work(t);
+    free_text(t);
     hipFree(t->p.slots); hipFree(t->p.st); hipFree(t->p.routes);
     hipFree(t->snap_key); hipFree(t->snap_val); hipFree(t->snap_out);
     delete t;
@@ -193,4 +212,201 @@ int acg_fl_drain_routes(AcgFlights* t, void* stream, acg_route* out, int max, in
     }
     *n = k;
     return t->pending.empty() ? ACG_OK : ACG_EAGAIN;
+}
+
+// ---- the table's text (flight_text.hip) ---------------------------------------------------------------------------------------
+static size_t wg_words(size_t n) { return n / 256 + 1; }
+
+int acg_fl_text_on(const AcgFlights* t) { return t->d_tcfg != nullptr; }
+
+int acg_fl_text_enable(AcgFlights* t, const AcgFlightTextDev* cfg)
+{
+    FLCHK(hipDeviceSynchronize());
+    free_text(t);
+    if (!cfg) return ACG_OK;
+    // the monitor's work space is sized like the snapshot's: for every slot of the table
+    const size_t cap = t->p.cap, b_32 = up256(cap * 4), b_wg = up256(wg_words(cap) * 4);
+    t->m_out_cap = ACG_FT_HDR_LEN + cap * ACG_FT_ROW_MAX;
+    if (t->m_out_cap > 0xffffffffull) return ACG_EINVAL;             // (cannot happen: 2^24 slots of 78 bytes)
+    if (hipMalloc(&t->d_tcfg, sizeof(*cfg)) != hipSuccess || hipMalloc(&t->t_cnt, 4 * sizeof(unsigned int)) != hipSuccess ||
+        hipMalloc(&t->m_work, 2 * b_32 + 2 * b_wg + up256(t->m_out_cap + 16)) != hipSuccess) {
+        free_text(t);
+        return ACG_ENOMEM;
+    }
+    unsigned char* w = (unsigned char*)t->m_work;
+    t->m_len = (unsigned int*)w; w += 2 * b_32;
+    t->m_wg = (unsigned int*)w; w += 2 * b_wg;
+    t->m_out = w;
+    if (hipMemcpy(t->d_tcfg, cfg, sizeof(*cfg), hipMemcpyHostToDevice) != hipSuccess || hipMemset(t->t_cnt, 0, 4 * sizeof(unsigned int)) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        free_text(t);
+        return ACG_EHIP;
+    }
+    return ACG_OK;
+}
+
+static AcgFlightTextPass text_pass(const AcgFlights* t)
+{
+    AcgFlightTextPass q;
+    std::memset(&q, 0, sizeof(q));
+    q.cfg = t->d_tcfg;
+    q.t0_sec = t->p.t0_sec;
+    q.t0_usec = t->p.t0_usec;
+    q.slots = t->p.slots;
+    q.st = t->p.st;
+    q.routes = t->p.routes;
+    q.counters = t->t_cnt;
+    return q;
+}
+
+int acg_fl_monitor_text(AcgFlights* t, void* stream, long long hdr_soh, char* out, size_t cap, size_t* nbytes, int* nrows, int* dropped)
+{
+    if (!t->d_tcfg) return ACG_ESTATE;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned int slots = t->p.cap;
+    if (acg_launch_flight_snapkeys(&t->p, t->snap_key, t->snap_key + slots, t->snap_val, t->snap_val + slots, stream) != 0) return ACG_EHIP;
+    AcgFlightTextPass q = text_pass(t);
+    q.hdr_soh = hdr_soh;
+    q.total = &t->p.st->nlive;
+    q.nmax = slots;
+    q.base = ACG_FT_HDR_LEN;
+    q.idx_s = t->snap_val + slots;
+    q.len = t->m_len; q.off = t->m_len + up256((size_t)slots * 4) / 4;
+    q.wg_sum = t->m_wg; q.wg_cnt = t->m_wg + up256(wg_words(slots) * 4) / 4;
+    q.out = t->m_out;
+    q.out_cap = (unsigned int)t->m_out_cap;
+    if (acg_launch_flight_monitor_text(&q, stream) != 0) return ACG_EHIP;
+    unsigned int cnt[4] = {0, 0, 0, 0};
+    FLCHK(hipMemcpyAsync(cnt, t->t_cnt, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    FLCHK(hipStreamSynchronize(s));
+    if (cnt[1] > slots || (size_t)cnt[0] > (size_t)cnt[1] * ACG_FT_ROW_MAX) return ACG_EHIP;
+    *nbytes = (size_t)ACG_FT_HDR_LEN + cnt[0];
+    *nrows = (int)cnt[1];
+    if (dropped) *dropped = (int)cnt[2];
+    if (*nbytes > cap) return ACG_EAGAIN;
+    FLCHK(hipMemcpyAsync(out, t->m_out, *nbytes, hipMemcpyDeviceToHost, s));
+    FLCHK(hipStreamSynchronize(s));
+    return ACG_OK;
+}
+
+// work space for the lines of n routes
+static int ensure_route_text(AcgFlights* t, size_t n, hipStream_t s)
+{
+    if (n <= t->r_cap) return ACG_OK;
+    FLCHK(hipStreamSynchronize(s));
+    hipFree(t->r_work);
+    t->r_work = nullptr;
+    t->r_cap = 0;
+    const size_t want = std::max<size_t>(n, 1024);
+    FLCHK(hipMalloc(&t->r_work, 2 * up256(want * 8) + 4 * up256(want * 4) + 2 * up256(wg_words(want) * 4) + up256(want * ACG_FT_LINE_MAX + 16)));
+    t->r_cap = want;
+    return ACG_OK;
+}
+
+int acg_fl_routes_json(AcgFlights* t, void* stream, char* out, size_t cap, size_t* nbytes, int* nlines)
+{
+    if (!t->d_tcfg || !t->pending.empty()) return ACG_ESTATE;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned int queued = 0;
+    FLCHK(hipMemcpyAsync(&queued, &t->p.st->nroutes, sizeof(queued), hipMemcpyDeviceToHost, s));
+    FLCHK(hipStreamSynchronize(s));
+    const unsigned int got = std::min(queued, t->p.route_cap);
+    *nbytes = 0;
+    *nlines = 0;
+    if (!got) {
+        t->route_bound = 0;
+        return ACG_OK;
+    }
+    if ((size_t)got * ACG_FT_LINE_MAX > 0xffffffffull) return ACG_ENOMEM;
+    const int rc = ensure_route_text(t, got, s);
+    if (rc != ACG_OK) return rc;
+    const size_t b_64 = up256(t->r_cap * 8), b_32 = up256(t->r_cap * 4), b_wg = up256(wg_words(t->r_cap) * 4);
+    unsigned char* w = (unsigned char*)t->r_work;
+    AcgFlightTextPass q = text_pass(t);
+    q.total = t->t_cnt + 3;
+    q.nmax = got;
+    q.key = (unsigned long long*)w; w += b_64;
+    q.key_s = (unsigned long long*)w; w += b_64;
+    q.idx = (unsigned int*)w; w += b_32;
+    q.idx_s = (unsigned int*)w; w += b_32;
+    q.len = (unsigned int*)w; w += b_32;
+    q.off = (unsigned int*)w; w += b_32;
+    q.wg_sum = (unsigned int*)w; w += b_wg;
+    q.wg_cnt = (unsigned int*)w; w += b_wg;
+    q.out = w;
+    q.out_cap = (unsigned int)((size_t)got * ACG_FT_LINE_MAX);
+    if (acg_launch_flight_route_text(&q, got, stream) != 0) return ACG_EHIP;
+    unsigned int cnt[4] = {0, 0, 0, 0};
+    FLCHK(hipMemcpyAsync(cnt, t->t_cnt, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    FLCHK(hipStreamSynchronize(s));
+    if (cnt[1] != got || cnt[0] > q.out_cap) return ACG_EHIP;       // (every route has a line)
+    *nbytes = cnt[0];
+    *nlines = (int)cnt[1];
+    if (cnt[0] > cap) return ACG_EAGAIN;                             // nothing consumed
+    FLCHK(hipMemcpyAsync(out, q.out, cnt[0], hipMemcpyDeviceToHost, s));
+    FLCHK(hipMemsetAsync(&t->p.st->nroutes, 0, sizeof(unsigned int), s));
+    FLCHK(hipStreamSynchronize(s));
+    t->route_bound = 0;
+    return ACG_OK;
+}
+
+// a C string of at most n bytes as a word, NUL padded
+static unsigned long long str_word(const char* src, size_t n)
+{
+    unsigned long long v = 0;
+    for (size_t i = 0; i < n && src[i]; ++i) v |= (unsigned long long)(unsigned char)src[i] << (8 * i);
+    return v;
+}
+
+int acg_fl_load_designed(AcgFlights* t, const acg_flight* in, int n, const acg_route* rt, int nr)
+{
+    if (n < 0 || nr < 0 || (unsigned int)n > t->p.cap) return ACG_EINVAL;
+    int rc = acg_fl_reset(t);
+    if (rc != ACG_OK) return rc;
+    std::vector<AcgFlightSlot> slots((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        AcgFlightSlot& S = slots[(size_t)i];
+        const acg_flight& f = in[i];
+        std::memset(&S, 0, sizeof(S));
+        S.key = str_word(f.addr, 7) | (1ull << 63);
+        S.seq = (unsigned long long)(n - i);                          // in[0]: the latest update
+        S.fid = str_word(f.fid, 7);
+        S.chm = f.chm;
+        S.ts_sample = f.ts_sample; S.tl_sample = f.tl_sample; S.ts_sec = f.ts_sec; S.tl_sec = f.tl_sec;
+        S.ts_usec = f.ts_usec; S.tl_usec = f.tl_usec; S.first_chn = f.first_chn; S.last_chn = f.last_chn;
+        S.nbm = f.nbm;
+        S.rt = f.rt ? 1u : 0u;
+        const char* fl[7] = {f.da, f.sa, f.eta, f.gout, f.gin, f.woff, f.won};
+        for (int k = 0; k < 7; ++k) S.fld[k] = (unsigned int)str_word(fl[k], 4);
+    }
+    if (n) FLCHK(hipMemcpy(t->p.slots, slots.data(), (size_t)n * sizeof(AcgFlightSlot), hipMemcpyHostToDevice));   // (G = LLONG_MIN: all live)
+    if ((unsigned int)nr > t->p.route_cap) {
+        AcgRouteRec* bigger = nullptr;
+        FLCHK(hipMalloc(&bigger, (size_t)nr * sizeof(AcgRouteRec)));
+        hipFree(t->p.routes);
+        t->p.routes = bigger;
+        t->p.route_cap = (unsigned int)nr;
+    }
+    if (nr) {
+        // stored in a shuffled order (a fixed linear congruential walk), tagged (pass, rank) ascending with the index
+        std::vector<unsigned int> at((size_t)nr);
+        for (int i = 0; i < nr; ++i) at[(size_t)i] = (unsigned int)i;
+        unsigned long long x = 0x9e3779b97f4a7c15ull;
+        for (int i = nr - 1; i > 0; --i) {
+            x = x * 6364136223846793005ull + 1442695040888963407ull;
+            std::swap(at[(size_t)i], at[(size_t)((x >> 33) % (unsigned long long)(i + 1))]);
+        }
+        std::vector<AcgRouteRec> h((size_t)nr);
+        for (int i = 0; i < nr; ++i) {
+            AcgRouteRec& R = h[at[(size_t)i]];
+            R.order = ((unsigned long long)(i / 7 + 1) << 32) | (unsigned long long)(i % 7);
+            std::memcpy(R.r, rt + i, sizeof(R.r));
+        }
+        const unsigned int cnt = (unsigned int)nr;
+        FLCHK(hipMemcpy(t->p.routes, h.data(), (size_t)nr * sizeof(AcgRouteRec), hipMemcpyHostToDevice));
+        FLCHK(hipMemcpy(&t->p.st->nroutes, &cnt, sizeof(cnt), hipMemcpyHostToDevice));
+    }
+    FLCHK(hipDeviceSynchronize());
+    t->route_bound = (size_t)nr;
+    return ACG_OK;
 }

@@ -21,3 +21,11 @@ ACG_FL_WEAK int acg_fl_reset(AcgFlights* t);                                    
 ACG_FL_WEAK int acg_fl_prepare(AcgFlights* t, unsigned int n, void* stream, const AcgFlightPass** pass);
 ACG_FL_WEAK int acg_fl_snapshot(AcgFlights* t, void* stream, acg_flight* out, int max, int* n, int* dropped);
 ACG_FL_WEAK int acg_fl_drain_routes(AcgFlights* t, void* stream, acg_route* out, int max, int* n);
+// ---- the table's text (flight_text.hip).  cfg: nbch and the escaped station stretch (null: the renderer off and its buffers freed)
+ACG_FL_WEAK int acg_fl_text_enable(AcgFlights* t, const AcgFlightTextDev* cfg);
+ACG_FL_WEAK int acg_fl_text_on(const AcgFlights* t);
+// all or nothing, ACG_EAGAIN with *nbytes needed; the renderer must be on
+ACG_FL_WEAK int acg_fl_monitor_text(AcgFlights* t, void* stream, long long hdr_soh, char* out, size_t cap, size_t* nbytes, int* nrows, int* dropped);
+ACG_FL_WEAK int acg_fl_routes_json(AcgFlights* t, void* stream, char* out, size_t cap, size_t* nbytes, int* nlines);   // ACG_ESTATE: routes pending on the host
+// lab: the table's content replaced by n designed entries (in[0] the latest update; cap >= n) and nr designed routes
+ACG_FL_WEAK int acg_fl_load_designed(AcgFlights* t, const acg_flight* in, int n, const acg_route* rt, int nr);

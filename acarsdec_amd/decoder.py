@@ -348,6 +348,44 @@ class Decoder:
             if rc == K.OK:
                 return out
 
+    # ---- the flight table's text (acg_flight_text_enable, acg_flight_monitor_text, acg_drain_routes_json) -------------------
+    def enable_flight_text(self, nbch, station_id=""):
+        """printmonitor()'s screen and routejson()'s lines (output.c:428-484) rendered on the device from the flight table, which
+        must be on.  nbch: the mask columns (0..16, the reference's nbch); station_id: the CLI's -i ("" = no key in a route line)."""
+        sid = station_id if isinstance(station_id, bytes) else str(station_id).encode("latin1")
+        self._chk(self.L.acg_flight_text_enable(self.ctx, C.byref(K.FlightTextConfig(int(nbch), sid))))
+
+    def disable_flight_text(self):
+        self._chk(self.L.acg_flight_text_enable(self.ctx, None))
+
+    def _all_or_nothing(self, call, cap):
+        """bytes of an entry point that says ACG_EAGAIN and the bytes needed when its buffer is too small; (bytes, records)"""
+        while True:
+            if getattr(self, "_ftbuf_cap", 0) < cap:
+                self._ftbuf = C.create_string_buffer(cap)
+                self._ftbuf_cap = cap
+            nb, n = C.c_size_t(0), C.c_int(0)
+            rc = self._chk(call(self._ftbuf, self._ftbuf_cap, C.byref(nb), C.byref(n)), allow=(K.EAGAIN,))
+            if rc == K.OK:
+                return self._ftbuf.raw[:nb.value], n.value
+            cap = max(nb.value, cap + 1)
+
+    def monitor_text(self, soh_sample=-1):
+        """One monitor frame (bytes), as the reference prints it for a message whose soh_sample is given (-1: the newest live
+        entry's last time); self.monitor_rows_n = its rows, self.flights_dropped as flights()."""
+        dropped = C.c_int(0)
+        call = lambda buf, cap, nb, n: self.L.acg_flight_monitor_text(self.ctx, int(soh_sample), buf, cap, nb, n, C.byref(dropped))
+        out, self.monitor_rows_n = self._all_or_nothing(call, K.MONITOR_HDR_LEN + 64 * K.MONITOR_ROW_MAX)
+        self.flights_dropped = dropped.value
+        return out
+
+    def drain_routes_json(self):
+        """The route lines queued so far (bytes, each ended by a newline), in the order of their triggering messages; the queue is
+        emptied.  self.route_lines_n = how many."""
+        call = lambda buf, cap, nb, n: self.L.acg_drain_routes_json(self.ctx, buf, cap, nb, n)
+        out, self.route_lines_n = self._all_or_nothing(call, 64 * K.ROUTE_LINE_MAX)
+        return out
+
     # ---- the JSON sink (acg_json_enable, acg_drain_json, acg_collect_json) -------------------------------------------------
     def enable_json(self, t0, station_id="", app_name="acarsdec", app_ver="", freqs_hz=None):
         """buildjson()'s lines (output.c:227-324, what -o 4 prints) rendered on the device from now on.  t0: wall clock of the

@@ -369,6 +369,60 @@ int  acg_flight_snapshot(acg_ctx *ctx, acg_flight *out, int max, int *n, int *dr
  * alone still drains them now and then, or the queue grows by one record per route emitted. */
 int  acg_drain_routes(acg_ctx *ctx, acg_route *out, int max, int *n);
 
+/* ---- the flight table's text: the monitor screen (-o 3) and the route line (-o 5), rendered on the device -------------------
+ * Off by default; with it off every entry point launches, copies and returns exactly what it does without this section, and
+ * with it on the message entry points, acg_flight_snapshot and acg_drain_routes still hand out the same bytes.  The two entry
+ * points below hand out TEXT, byte for byte what the reference built without libacars writes:
+ *   acg_flight_monitor_text   one frame of printmonitor() (output.c:458-484): the 7 bytes of cls() ("\x1b[H\x1b[2J",
+ *                             ACG_MONITOR_CLS_LEN: a host that writes to a file skips them), "             Acarsdec monitor ",
+ *                             printtime(tv), the column header line (ACG_MONITOR_HDR_LEN bytes so far), then one row per live
+ *                             entry in acg_flight_snapshot's order:
+ *                               " %-8s %-7s %3d " addr fid nbm, nbch mask columns ('x' / '.': bit i of chm) padded with spaces
+ *                               to 16, " ", printtime(ts), " %4s " or six spaces for each of sa, da, eta, "\n".
+ *   acg_drain_routes_json     the queued route records as routejson()'s lines (output.c:428-456,677-683, cJSON fmt = 0):
+ *                               {"timestamp":T[,"station_id":".."],"flight":"..","depa":"..","dsta":".."} and '\n',
+ *                             in the order of their triggering messages (the tag is sorted on the device), packed back to back.
+ * printtime() is "%02d:%02d:%02d.%03ld" of gmtime_r(tv_sec) and tv_usec / 1000 in integer arithmetic (the text sink's date rule:
+ * exact from 1970 to the year 9999).  "%-8s", "%-7s", "%4s" and "%3d" pad and never cut.  T is the JSON sink's "timestamp"
+ * (print_number's text, exact for 10^9 <= tv_sec < 9999999998), strings are escaped as the JSON sink escapes them.
+ *
+ * ACG_MONITOR_ROW_MAX, the longest row, token by token:
+ *   " " 1 + "%-8s" 8 (an addr has at most 7 characters) + " " 1 + "%-7s" 7 + " " 1 + "%3d" 11 ("-2147483648"; 3 while
+ *   0 <= nbm <= 999, 10 for 2^31 - 1) + " " 1 + the mask 16 + " " 1 + printtime 12 + 3 x 6 + "\n" 1
+ * = 78; a row is 70 bytes while nbm <= 999.  A frame is at most ACG_MONITOR_HDR_LEN + rows * ACG_MONITOR_ROW_MAX bytes.
+ * ACG_ROUTE_LINE_MAX, the longest line, every string byte a control character that costs 6 ("\u00xx"), key by key:
+ *   {"timestamp":        13 + 18   ten integer digits, the point, seven fraction digits ("%1.17g")
+ *   ,"station_id":".."   15 + 32 * 6 + 1 = 208
+ *   ,"flight":".."       11 + 7 * 6 + 1 = 54   (acg_route's fid[7] read as at most 7 bytes; a message's flight id has 6: 48)
+ *   ,"depa":".."          9 + 4 * 6 + 1 = 34     ,"dsta":".."   34
+ *   }  1,   '\n'  1
+ * = 363 (357 for anything traffic can produce). */
+#define ACG_MONITOR_CLS_LEN  7
+#define ACG_MONITOR_HDR_LEN  110  /* 7 + 30 + 12 + 61 ("\n Aircraft Flight   Nb Channels     First    DEP   ARR   ETA\n") */
+#define ACG_MONITOR_ROW_MAX  78
+#define ACG_ROUTE_LINE_MAX   363
+typedef struct {
+	int nbch;                     /* 0 .. 16: the mask columns printmonitor() shows (the reference's nbch, padded to MAXNBCHANNELS = 16) */
+	char station_id[33];          /* idstation (-i) for the route line; "" = the key is absent (output.c:444) */
+} acg_flight_text_config;
+/* Switches the renderer on (cfg) or off (NULL).  The station is escaped once, like the JSON sink's.  ACG_EINVAL: nbch outside
+ * 0..16, an unterminated station_id; ACG_ESTATE: the flight table is not enabled.  acg_reset keeps the configuration; switching
+ * the table off -- or on again: acg_flights_enable replaces it -- switches the renderer off too. */
+int  acg_flight_text_enable(acg_ctx *ctx, const acg_flight_text_config *cfg);
+/* One frame.  The header's time is the time of the message the frame is printed for -- the reference prints a frame per kept
+ * message with that message's tv, also for messages that never reach addFlight() (an uplink without -A) -- so the caller names
+ * it: tv = t0 + hdr_soh_sample / 12500 s in integers (acg_msg's soh_sample; t0 from acg_flight_config).  hdr_soh_sample < 0: the
+ * newest live entry's tl, or t0 when the table is empty.  *nbytes bytes, *nrows rows, *dropped (may be NULL) as
+ * acg_flight_snapshot; out is not NUL terminated.  ALL OR NOTHING: cap too small returns ACG_EAGAIN with *nbytes = the bytes
+ * needed and leaves out untouched.  Waits for the passes issued so far and consumes nothing, like the snapshot.
+ * ACG_ESTATE: the table or the renderer is off. */
+int  acg_flight_monitor_text(acg_ctx *ctx, long long hdr_soh_sample, char *out, size_t cap, size_t *nbytes, int *nrows, int *dropped);
+/* The queued routes as lines.  ALL OR NOTHING: cap too small returns ACG_EAGAIN with *nbytes = the bytes needed and nothing is
+ * consumed; otherwise the queue is emptied.  It is the queue of acg_drain_routes: each entry point consumes what it hands out.
+ * ACG_ESTATE: the table or the renderer is off, or an earlier acg_drain_routes returned ACG_EAGAIN and left records pending on
+ * the host -- a host uses one of the two, or switches only behind an ACG_OK. */
+int  acg_drain_routes_json(acg_ctx *ctx, char *out, size_t cap, size_t *nbytes, int *nlines);
+
 /* ---- the JSON sink: buildjson() (output.c:227-324), what -o 4 prints, -j sends and the MQTT sink publishes ------------------
  * Off by default; with it off every entry point launches, copies and returns exactly what it does without this section.
  * acg_drain_json / acg_collect_json are message entry points like acg_drain_msgs / acg_collect_msgs (ACG_F_REPAIR, the filters

@@ -80,6 +80,17 @@ int  acg_selftest_msg_labels(const acg_msg *in, int n, const acg_msg_filter *f, 
 int  acg_selftest_flights(const acg_msg *in, const int *batch, int nbatch, const acg_flight_config *cfg, const acg_msg_filter *f,
 			  acg_flight *snaps, int snap_cap, int *snap_n, acg_route *routes, int route_cap, int *nroutes, int *dropped);
 
+/* diagnostics: the flight table's text (flight_text.hip) on caller-supplied entries and routes, without traffic: a table made
+ * from cfg (at least n slots) holds in[0 .. n) as its live entries, in[0] the latest update, and its queue holds rt[0 .. nr),
+ * stored in a shuffled order under tags that ascend with their index; then exactly what acg_flight_monitor_text (tcfg,
+ * hdr_soh_sample) and acg_drain_routes_json launch.  An entry's strings are read up to their NUL: addr 7, fid 7, sa / da / eta 4
+ * bytes; chm's low 16 bits, nbm, ts_sec, ts_usec, tl_sec, tl_usec as they stand.  mon / rts: the two output buffers, each all or
+ * nothing as its entry point (ACG_EAGAIN when either is too small, both byte counts say what is needed).
+ * ACG_EINVAL: n or nr < 0, a bad cfg or tcfg; ACG_ENODEV: no GPU. */
+int  acg_selftest_flight_text(const acg_flight *in, int n, const acg_route *rt, int nr, const acg_flight_config *cfg,
+			      const acg_flight_text_config *tcfg, long long hdr_soh_sample, char *mon, size_t mon_cap, size_t *mon_nbytes,
+			      int *nrows, char *rts, size_t rts_cap, size_t *rts_nbytes, int *nlines);
+
 /* diagnostics: the JSON sink's passes (label.hip's filter and compaction, then json.hip's order / measure / scan / render) on n
  * caller-supplied records, taken as acg_drain_msgs hands them out, without a demodulator: the lines of the records the filter f
  * (NULL = none) keeps, in (chn, end_bit) order (equal keys: input order), packed into out; *nbytes, *nlines as acg_drain_json.
