@@ -16,8 +16,8 @@
 // msk.hip does it (framing inline, between the bit decision and the loop filter, msk.c:122-130).  Same operations in the
 // same order per channel as msk.hip and the reference; tests compare state, blocks and text of both kernels bit for bit.
 //
-// Used for every in_callback-shaped launch, with or without a bit log (with ACG_F_BITLOG the segment's per-bit records are stored
-// under the polarity of MskS + k and turned on the rare branch that finds a ~SYN behind them): 16-byte aligned dm rows,
+// Used for every in_callback-shaped launch, with or without a bit log (with ACG_F_BITLOG the segment's per-bit records are made
+// under the polarity of MskS + k and turned on the rare branch that finds a ~SYN in front of them): 16-byte aligned dm rows,
 // len % 32 == 0, not the precise-mixer mode, 4 or 8 lanes per channel (ACG_MSK_LEAN4=0 keeps msk.hip's kernel for 4);
 // ACG_MSK_NOLEAN=1 (tuning table) keeps msk.hip's kernel for same-process A/B.
 //
@@ -51,6 +51,17 @@
 // and not taken: a hold behind every step (1 % slower than holds on 5 and 6 only), the six newest taps as plain f32 (4 % slower), and
 // the one-sample case by selects too; DESIGN 4.
 // tests/test_lean_chain_layout.py pins the placement in the assembly.
+//
+// Where the bit records leave (round 9).  Every lane of a channel's group computes the identical record {soft symbol, level} of a
+// period, and every period used to store it: a global_store_dwordx2 of all 64 lanes -- 64 addresses and 64 records out of the
+// register file for 8 (or 16) distinct records -- issued by the one wave of its SIMD, so paid in full on the chain that sets the bit
+// rate (the log cost 3.2 % of the kernel, alone on the chip exactly as beside the down-converter).  Now lane g of the group KEEPS
+// records g, g + LPC, ... of the segment (two selects a period, on the lane masks the phase pick already has), the ~SYN branch
+// turns the kept records in registers instead of reading them back from memory, and ONE store per lane (two with 4 lanes per
+// channel) behind the segment's framing writes them: the same values at the same places.  The period that closes a segment
+// msk.hip's way stores its own record as before.  Measured and not taken: the segment's text byte parked until behind the next
+// refill's loads (the refill's `s_waitcnt vmcnt(0)` also waits for younger stores) -- nil.  ACG_LEAN_AB_REC0 is the order before;
+// tests/test_lean_record_store.py pins the periods free of stores and compiles that switch to show the condition can fail.
 //
 // What this kernel shares with msk.hip -- the state's way in and out, the LDS layout, the phase detector, the loop filter, the inline
 // framing step of the closing period -- is in msk_common.h; the dm window's two lambdas are msk.hip's, spelled out here as there.
@@ -383,6 +394,12 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
         unsigned int P = 0, N = 0;                 // (vo > 0), (vo < 0) of the segment's bits, oldest in the highest place
         float lvk[SEG];
         int nk[SEG];
+#ifndef ACG_LEAN_AB_REC0
+        // the segment's bit records: every lane of a group computes the identical record of period k, and lane g KEEPS records g,
+        // g + LPC, ... (two selects a period); they leave behind the segment's framing, one store per lane, instead of one store
+        // of all 64 lanes per period
+        float2 rec[SEG / LPC] = {};
+#endif
 #pragma unroll
         for (int k = 0; k < SEG; ++k) { lvk[k] = 0.f; nk[k] = 0; }
         int c = 0;                                 // bits whose framing waits (wave-uniform)
@@ -401,7 +418,14 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
             N = shift_in(N, vo < 0);
             if constexpr (LOG) {
                 // the record under the polarity S + k carries; a ~SYN found when the segment is framed turns the records behind it
-                brec[k] = make_float2(__uint_as_float(__float_as_uint(vo) ^ (((S0 + (unsigned int)k) & 2u) << 30)), lvl);
+                const float sv = __uint_as_float(__float_as_uint(vo) ^ (((S0 + (unsigned int)k) & 2u) << 30));
+#ifdef ACG_LEAN_AB_REC0
+                brec[k] = make_float2(sv, lvl);
+#else
+                const bool mine = g == k % LPC;
+                rec[k / LPC].x = mine ? sv : rec[k / LPC].x;
+                rec[k / LPC].y = mine ? lvl : rec[k / LPC].y;
+#endif
             }
             lvk[k] = lvl;
             nk[k] = n;
@@ -461,10 +485,16 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
                         const unsigned int Bx = (B0 & lowm) | (B1 & ~lowm);
                         out_end = (((Bx << 8) | old) >> uc) & 0xffu;
                         if constexpr (LOG) {
+#ifdef ACG_LEAN_AB_REC0
                             for (unsigned int j = k + 1u; j < uc; ++j) {
                                 const float v = brec[j].x;
                                 brec[j].x = -v;
                             }
+#else
+#pragma unroll
+                            for (int q = 0; q < SEG / LPC; ++q)
+                                if ((unsigned int)(g + q * LPC) > k) rec[q].x = -rec[q].x;
+#endif
                         }
                     }
                 } else {
@@ -490,6 +520,13 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
                     L.nbit_total = nbt0 + c;
                 }
             }
+#ifndef ACG_LEAN_AB_REC0
+            if constexpr (LOG) {
+#pragma unroll
+                for (int q = 0; q < SEG / LPC; ++q)
+                    if (g + q * LPC < c) brec[g + q * LPC] = rec[q];
+            }
+#endif
             L.nbits = nbits_n;
             L.outbits = out_end;
             L.S = S_n;

@@ -5,7 +5,8 @@ verdict is closed (profiles/LEDGER.md) are no longer in the tree, and 
 (NAME@REV:-DSWITCH).  profiles/probe/run_ab.sh times them all on one box through ACARSDEC_AMD_LIB.  Measurement aid
 only; nothing here is loaded by the product.
 The switches msk_lean.hip keeps may be given by their short names: a flag without a leading dash is taken as -DACG_LEAN_AB_<FLAG>
-(VCO0, SPEC0, PICK0), and R08PARENT stands for all three, the order before round 8."""
+(VCO0, SPEC0, PICK0, REC0), R08PARENT stands for the first three, the order before round 8, and REC0 is the order before round 9
+(a bit record stored by all 64 lanes in every period)."""
 import os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 sys.path.insert(0, ROOT)
