@@ -60,6 +60,7 @@ UNITS = [("fir.hip", ["-O3"], True), ("fir_mm.hip", ["-O3"], True), ("msk.hip", 
          ("json.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE, nothing fused: the level's float and the time stamp's double are computed here
          ("text.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE like json.hip: the same level float
          ("flight_text.hip", ["-O3", "-ffp-contract=off"], True),   # text.hip's flags: the route line's time stamp is json.hip's double
+         ("pcm.hip", ["-O3"], True),        # a transpose: the int16 scale is exact, the f32 path moves words (nothing to contract)
          ("flights.cpp", ["-O2"], True), ("acg_api.cpp", ["-O2"], True)]
 # which units see which define (the others are compiled once and shared between the libraries)
 SEES = {"-DACG_LAB": ("fir.hip", "msk2.hip", "acg_api.cpp"), "-DACG_MSK_STAMP": ("msk.hip", "msk2.hip", "acg_api.cpp"),
@@ -174,7 +175,8 @@ def patched_source(front_end):
                  acarsdec_amd_in_callback() instead of the static in_callback()
       soapy.c    soapy.c:228-254: the per-channel loop of the reader thread becomes acarsdec_amd_soapy_samples(soapyInBuf, res)
       air.c      air.c:293-338: the body of rx_callback() becomes acarsdec_amd_air_samples(samples, sample_count, AIRMULT)
-      sdrplay.c  sdrplay.c:213-236: the body of myStreamCallback() becomes acarsdec_amd_sdrplay_samples(xi, xq, numSamples)"""
+      sdrplay.c  sdrplay.c:213-236: the body of myStreamCallback() becomes acarsdec_amd_sdrplay_samples(xi, xq, numSamples)
+      soundfile.c  soundfile.c:71-77: the per-channel de-interleave + demodMSK() loop becomes acarsdec_amd_pcm_frames(sndbuff, nbi / nbch)"""
     src = open(os.path.join(REF, front_end)).read()
     if front_end == "rtl.c":
         old = "\trtlsdr_read_async(dev, in_callback, NULL, 4, rtlInBufSize);\n"
@@ -203,6 +205,12 @@ def patched_source(front_end):
         src = (src[:a] + "\tacarsdec_amd_sdrplay_samples(xi, xq, (int)numSamples);          /* acarsdec_amd: replaces sdrplay.c:213-236 */\n" + src[b:])
         a = src.index("static\nint current_index = 0;")
         return src[:a] + COMPAT_INCLUDE + src[a:]
+    if front_end == "soundfile.c":
+        a, b = _cut(src, "\t\tfor (n = 0; n < nbch; n++) {\n", "\t\t\tdemodMSK(&(channel[n]),len);\n\t\t}\n", front_end)
+        assert src.count("demodMSK(") == 1 and "demodMSK(" in src[a:b]
+        src = src[:a] + "\t\tacarsdec_amd_pcm_frames(sndbuff, nbi / nbch);          /* acarsdec_amd: replaces soundfile.c:71-77 */\n" + src[b:]
+        a = src.index("#define MAXNBFRAMES")
+        return src[:a] + COMPAT_INCLUDE + src[a:]
     raise ValueError(front_end)
 
 
@@ -224,7 +232,7 @@ def _build_bound_demo(out, macro, front_end, standin, force, extra_inc=()):
     mine = [os.path.join(CSRC, "compat_msk.c"), os.path.join(demo_dir, standin)]
     srcs = [os.path.join(REF, u) for u in ref_units] + mine
     incs = ["-I" + REF, "-I" + INC] + ["-I" + i for i in extra_inc] + ["-I" + stub]
-    if force or _newer(srcs + [LIB, os.path.join(REF, front_end), os.path.join(INC, "acarsdec_amd_compat.h"), os.path.abspath(__file__)], out):
+    if force or _newer(srcs + [LIB, os.path.join(REF, front_end), os.path.join(INC, "acarsdec_amd_compat.h"), os.path.join(INC, "acarsdec_amd_compat_pcm.h"), os.path.abspath(__file__)], out):
         obj = os.path.join(OBJDIR, front_end + "_bound.o")
         r = subprocess.run(["gcc", "-O2", "-w", "-D" + macro] + incs + ["-x", "c", "-c", "-", "-o", obj],
                            input=patched_source(front_end), capture_output=True, text=True)
@@ -252,6 +260,15 @@ def build_demo_sdrplay(force=False):
     return _build_bound_demo(DEMO_SDRPLAY, "WITH_SDRPLAY", "sdrplay.c", "demo_sdrplay_file.c", force)
 
 
+DEMO_FILE = os.path.join(LIBDIR, "acarsdec_gpu_file")
+
+
+def build_demo_file(force=False):
+    """soundfile.c itself (not wav_frontend.c) with its one hunk, on csrc/demo's libsndfile stand-in: every read of the file is
+    ONE GPU call for all its channels where lib/acarsdec_gpu makes one per channel"""
+    return _build_bound_demo(DEMO_FILE, "WITH_SNDFILE", "soundfile.c", "demo_sndfile_wav.c", force, extra_inc=(os.path.join(CSRC, "demo"),))
+
+
 MULTIDEV = os.path.join(LIBDIR, "host_multidev")
 
 
@@ -277,6 +294,7 @@ def build_all(force=False):
     build_demo_soapy(force)
     build_demo_air(force)
     build_demo_sdrplay(force)
+    build_demo_file(force)
     build_multidev(force)
     return lib, demo
 

@@ -14,6 +14,7 @@ F_BITLOG, F_TIMING, F_REPAIR, F_EXACT_FIR, F_PRECISE_MIXER = 1, 2, 4, 8, 16
 INTRATE, BLOCK, MAXDECIM, FLEN, TXTMAX = 12500, 1024, 320, 11, 250
 MAXDECIM_SAMPLES = 1024
 FMT_CS16, FMT_S16_SPLIT, FMT_F32_REAL = 1, 2, 3
+PCM_S16, PCM_F32 = 1, 2
 
 
 class Config(C.Structure):
@@ -139,6 +140,8 @@ SYMBOLS = {
     "acg_airspy_taps": (C.c_int, [C.c_int, C.c_int, C.c_uint, C.c_void_p]),
     "acg_process_samples_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]),
     "acg_feed_samples_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]),
+    "acg_process_pcm_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "acg_feed_pcm_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "acg_host_alloc": (C.c_void_p, [C.c_size_t]),
     "acg_host_free": (None, [C.c_void_p]),
     "acg_host_register": (C.c_int, [C.c_void_p, C.c_size_t]),
@@ -215,6 +218,7 @@ LAB_SYMBOLS = {
     "acg_lab_block_ring_size": (C.c_uint, [C.c_void_p]),
     "acg_lab_set_stream_counters": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong]),
     "acg_lab_fir_launch_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(LaunchShape)]),
+    "acg_lab_pcm_deinterleave": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_float]),
 }
 # declared in acarsdec_amd_lab.h, present in the stamp build only (-DACG_MSK_STAMP)
 STAMP_SYMBOLS = ("acg_msk_stamp_read", "acg_msk_lanes_per_channel")

@@ -1173,6 +1173,121 @@ extern "C" int acg_process_dm_host(acg_ctx* ctx, const float* dm_host, size_t pi
     return end_of_call(ctx);
 }
 
+// ---- the 12.5 kHz front ends (soundfile.c, alsa.c): interleaved PCM frames, all channels in one call ----
+static size_t pcm_elem(int fmt) { return fmt == ACG_PCM_S16 ? 2 : 4; }
+
+static int check_pcm_args(acg_ctx* ctx, int fmt, const void* frames)
+{
+    if (!ctx || !frames) return ACG_EINVAL;
+    if (fmt != ACG_PCM_S16 && fmt != ACG_PCM_F32) return fail(ctx, ACG_EINVAL, "unknown PCM format");
+    if (((uintptr_t)frames) & 3) return fail(ctx, ACG_EINVAL, "PCM frames must be 4-byte aligned");
+    if (!acg_launch_pcm_deint) return fail(ctx, ACG_ESTATE, "this build has no PCM unit");
+    return ACG_OK;
+}
+
+static int launch_pcm(acg_ctx* ctx, int fmt, const void* frames_dev, int nframes, float* dm, size_t pitch, hipStream_t s)
+{
+    PcmArgs p{frames_dev, dm, pitch, ctx->cfg.nch, nframes, fmt};
+    RoctxRange range("acg:pcm-deinterleave");
+    const int e = acg_launch_pcm_deint(&p, s);
+    if (e != 0) {
+        ctx->err = std::string("PCM de-interleave launch: ") + hipGetErrorString((hipError_t)e);
+        return ACG_EHIP;
+    }
+    return ACG_OK;
+}
+
+// acg_process_dm_host with the copy replaced by the de-interleave kernel: it fills the context's dm image, the demodulator
+// follows on its own stream, and the guard record is the same.  The kernel is the only reader of frames_dev and runs on the
+// CALLER's stream, behind the guards of the image: what the caller enqueues next is ordered behind it and does not wait for the
+// demodulator.  (Launched on the demodulator's stream instead -- in order there, no guard needed -- the kernel cost the same,
+// but the demodulator launch behind it took 1.81 ms instead of 1.20 ms at 16 384 channels x 8192 frames, with or without a
+// host synchronise between the two; at 4096 channels nothing: profiles/LEDGER.md, "12.5 kHz PCM front end".)
+extern "C" int acg_process_pcm_dev(acg_ctx* ctx, int fmt, const void* frames_dev, int nframes, void* hip_stream)
+{
+    int r = check_pcm_args(ctx, fmt, frames_dev);
+    if (r != ACG_OK) return r;
+    if (nframes < 0 || nframes > ctx->max_len) return fail(ctx, ACG_EINVAL, "nframes out of range");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    if ((r = begin_call(ctx)) != ACG_OK) return r;
+    if (nframes > 0) {
+        // the dm image may still be read by the demodulator launch of the call before (the guard acg_process_dm_host and the
+        // pipeline record); then the kernel, on the CALLER's stream like the down-converter's chunks
+        const int nb = std::min(ctx->cfg.max_blocks, (nframes + ACG_BLOCK - 1) / ACG_BLOCK);
+        if ((r = guard_wait(ctx, s, 0, nb)) != ACG_OK) return r;
+        if ((r = launch_pcm(ctx, fmt, frames_dev, nframes, ctx->d_dm, ctx->dm_pitch, s)) != ACG_OK) return r;
+        HIPCHK(ctx, hipEventRecord(ctx->in_ev, s));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->msk_stream, ctx->in_ev, 0));
+    }
+    if ((r = launch_msk(ctx, ctx->d_dm, ctx->dm_pitch, nframes, ctx->msk_stream)) != ACG_OK) return r;
+    if (nframes > 0 && (r = guard_record(ctx, 0, std::min(ctx->cfg.max_blocks, (nframes + ACG_BLOCK - 1) / ACG_BLOCK))) != ACG_OK) return r;
+    return end_of_call(ctx);
+}
+
+// Host frames of any count: chunks of at most max_len frames, each ONE contiguous copy into the staging buffer the chunk before
+// the previous one used (acg_process_iq_u8_host's scheme: the copy of chunk k + 1 runs beside the kernels of chunk k), then the
+// device path.  Returns when the last copy has left the caller's buffer.
+extern "C" int acg_feed_pcm_host(acg_ctx* ctx, int fmt, const void* frames, size_t nframes)
+{
+    int r = check_pcm_args(ctx, fmt, frames);
+    if (r != ACG_OK) return r;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    if (ctx->feed_fill) return fail(ctx, ACG_ESTATE, "acg_feed_samples_host is carrying a partial window in the staging buffers (acg_reset drops it)");
+    if (nframes == 0) return acg_process_pcm_dev(ctx, fmt, frames, 0, nullptr);
+    const size_t fb = (size_t)ctx->cfg.nch * pcm_elem(fmt);          // bytes per frame
+    if ((r = ensure_stage(ctx, ((size_t)ctx->max_len * fb + 3) & ~(size_t)3)) != ACG_OK) return r;
+    for (size_t done = 0; done < nframes;) {
+        const size_t take = std::min(nframes - done, (size_t)ctx->max_len);
+        const int slot = (int)(ctx->stage_seq++ & 1u);
+        if (ctx->stage_free_valid[slot]) HIPCHK(ctx, hipStreamWaitEvent(ctx->h2d_stream, ctx->stage_free[slot], 0));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[slot], (const unsigned char*)frames + done * fb, take * fb, hipMemcpyHostToDevice, ctx->h2d_stream));
+        HIPCHK(ctx, hipEventRecord(ctx->h2d_done, ctx->h2d_stream));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->h2d_done, 0));
+        r = acg_process_pcm_dev(ctx, fmt, ctx->d_stage[slot], (int)take, nullptr);
+        if (r != ACG_OK) {
+            (void)hipEventSynchronize(ctx->h2d_done);           // the copy may still be reading the caller's buffer: not after we return
+            return r;
+        }
+        // (the context's stream is ordered behind the de-interleave kernel, the buffer's only reader)
+        HIPCHK(ctx, hipEventRecord(ctx->stage_free[slot], ctx->stream));
+        ctx->stage_free_valid[slot] = true;
+        done += take;
+    }
+    HIPCHK(ctx, hipEventSynchronize(ctx->h2d_done));           // the caller's buffer is free again (the copy stream runs in order)
+    return ACG_OK;
+}
+
+// Only the kernel, into a scratch image of nch x pitch_floats words pre-filled with `fill`; the input lies in a device buffer
+// of exactly its own size (rounded up to a word), so that a read or a write outside the ranges pcm.hip promises shows.
+extern "C" int acg_lab_pcm_deinterleave(acg_ctx* ctx, int fmt, const void* frames_host, int nframes, float* dm_host, size_t pitch_floats,
+                                        float fill)
+{
+    int r = check_pcm_args(ctx, fmt, frames_host);
+    if (r != ACG_OK) return r;
+    if (!dm_host || nframes < 0 || pitch_floats < (size_t)nframes || pitch_floats == 0) return fail(ctx, ACG_EINVAL, "image smaller than the frames");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const size_t img = (size_t)ctx->cfg.nch * pitch_floats, in_bytes = ((size_t)nframes * ctx->cfg.nch * pcm_elem(fmt) + 3) & ~(size_t)3;
+    for (size_t i = 0; i < img; ++i) dm_host[i] = fill;
+    float* d_img = nullptr;
+    void* d_in = nullptr;
+    hipError_t e = hipMalloc(&d_img, img * sizeof(float));
+    if (e == hipSuccess && in_bytes) e = hipMalloc(&d_in, in_bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_img, dm_host, img * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && in_bytes) e = hipMemcpy(d_in, frames_host, (size_t)nframes * ctx->cfg.nch * pcm_elem(fmt), hipMemcpyHostToDevice);
+    r = ACG_OK;
+    if (e == hipSuccess && nframes > 0) r = launch_pcm(ctx, fmt, d_in, nframes, d_img, pitch_floats, ctx->stream);
+    if (e == hipSuccess && r == ACG_OK) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess && r == ACG_OK) e = hipMemcpy(dm_host, d_img, img * sizeof(float), hipMemcpyDeviceToHost);
+    if (d_img) (void)hipFree(d_img);
+    if (d_in) (void)hipFree(d_in);
+    if (e != hipSuccess) {
+        ctx->err = std::string("acg_lab_pcm_deinterleave: ") + hipGetErrorString(e);
+        return ACG_EHIP;
+    }
+    return r;
+}
+
 extern "C" int acg_sync(acg_ctx* ctx)
 {
     if (!ctx) return ACG_EINVAL;

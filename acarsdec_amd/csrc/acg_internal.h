@@ -297,6 +297,16 @@ struct MskArgs {
     int precise_mixer;          // ACG_F_PRECISE_MIXER: the < 1 ulp polynomial sin/cos instead of table + rotation
 };
 
+// pcm.hip: interleaved PCM frames [nframes][nch] -> columns [0, nframes) of the planar dm rows
+struct PcmArgs {
+    const void* frames;         // 4-byte aligned
+    float* dm;                  // [nch][dm_pitch]
+    size_t dm_pitch;            // floats, >= nframes
+    int nch;
+    int nframes;
+    int fmt;                    // ACG_PCM_S16 / ACG_PCM_F32
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -362,6 +372,8 @@ int acg_launch_sort_pairs(unsigned long long* ka, unsigned int* va, unsigned lon
 __attribute__((weak)) int acg_launch_json(const AcgSinkPass* p, void* stream);
 // text.hip: the same for the text formats (weak for the same reason)
 __attribute__((weak)) int acg_launch_text(const AcgSinkPass* p, void* stream);
+// pcm.hip: the de-interleave of one call (weak for the same reason: there the PCM entry points say ACG_ESTATE)
+__attribute__((weak)) int acg_launch_pcm_deint(const PcmArgs* a, void* stream);
 int acg_launch_sincos_selftest(const double* x, double* s, double* c, int n, const double* sctab, void* stream);
 int acg_launch_div2_selftest(const double* n0, const double* n1, const double* d, double* out, int n, void* stream);
 int acg_launch_synth_iq(uint8_t* iq, size_t pitch, int nrows, int nout, int decim, const float* env,

@@ -13,6 +13,8 @@
  *                                             (pass it to rtlsdr_read_async at rtl.c:364)
  *     void acarsdec_amd_soapy_samples(const int16_t *iq, int nsamples);       (-DWITH_SOAPY)
  *                                             replaces the per-channel loop of soapy.c:228-254
+ *     void acarsdec_amd_pcm_frames(const float *interleaved, int nframes);
+ *                                             replaces the per-channel loop of soundfile.c:71-77
  *
  * Division of labour: the GPU runs the down-converter and the MSK loop (with a device mirror of
  * the framing FSM, needed because decodeAcars() writes MskDf/MskS back into the loop,
@@ -88,6 +90,8 @@ static void account(double t0)
 
 static acg_ctx *g_msk;          /* 1-channel context behind demodMSK() */
 static int g_msk_blocks;
+static acg_ctx *g_pcm;          /* nbch-channel context behind acarsdec_amd_pcm_frames() */
+static int g_pcm_blocks;
 static acg_ctx *g_rtl;          /* nbch-channel context behind acarsdec_amd_in_callback() */
 static channel_t *g_msk_last;   /* the channel whose state the demodMSK() context holds */
 
@@ -141,7 +145,7 @@ static void pack(acg_chan_state *st, const channel_t *ch)
 	st->blk_err = ch->blk ? ch->blk->err : 0;
 }
 
-static shadow_t g_msk_sh, g_rtl_sh, g_front_sh;
+static shadow_t g_msk_sh, g_rtl_sh, g_front_sh, g_pcm_sh;
 
 /* channels chs[0..n) -> device slots 0..n-1, one transfer, and only if anything differs from what the device has */
 static void upload_all(acg_ctx *c, shadow_t *sh, channel_t *const *chs, int n)
@@ -237,13 +241,14 @@ static acg_ctx *make_front_ctx(int mult, int max_blocks, float complex *const *t
 	return c;
 }
 
-static acg_ctx *make_msk_ctx(int blocks)
+/* a context fed with 12.5 kHz samples: no down-converter runs, its geometry is a formality */
+static acg_ctx *make_msk_ctx(int nchan, int blocks)
 {
 	acg_config cfg;
 	acg_ctx *c = NULL;
 	int rc;
 	memset(&cfg, 0, sizeof(cfg));
-	cfg.nch = 1; cfg.nstreams = 1; cfg.decim = 8; cfg.ntaps = 8;
+	cfg.nch = nchan; cfg.nstreams = 1; cfg.decim = 8; cfg.ntaps = 8;
 	cfg.max_blocks = blocks;
 	cfg.flags = ACG_F_BITLOG;
 	cfg.max_lag = 1;                              /* drained after every call */
@@ -257,7 +262,8 @@ static acg_ctx *make_msk_ctx(int blocks)
 static void null_sink(void *user, int slot, float vo, float lvl) { (void)user; (void)slot; (void)vo; (void)lvl; }
 
 /* One throw-away call through every entry point the real calls use (kernels get loaded, staging buffers pinned), then the
- * context goes back to the state acg_create left it in.  fmt < 0: the 12.5 kHz path of demodMSK(). */
+ * context goes back to the state acg_create left it in.  fmt -1: the 12.5 kHz path of demodMSK(); fmt -2: the interleaved
+ * frames of acarsdec_amd_pcm_frames() (mult = the channels of a frame). */
 static int warm_up(acg_ctx *c, int fmt, int mult, int nchan)
 {
 	const size_t ns = (size_t)ACG_BLOCK * (size_t)(mult > 0 ? mult : 1);
@@ -268,6 +274,8 @@ static int warm_up(acg_ctx *c, int fmt, int mult, int nchan)
 	int rc = ACG_OK, n = 0;
 	if (st == NULL || buf == NULL || (fmt == ACG_FMT_S16_SPLIT && buf2 == NULL))
 		rc = ACG_ENOMEM;
+	else if (fmt == -2)
+		rc = acg_feed_pcm_host(c, ACG_PCM_F32, buf, ACG_BLOCK);
 	else if (fmt < 0)
 		rc = acg_process_dm_host(c, (const float *)buf, ns, ACG_BLOCK);
 	else if (fmt == 0) {
@@ -301,7 +309,7 @@ void demodMSK(channel_t *ch, int len)
 		g_msk_blocks = (len + ACG_BLOCK - 1) / ACG_BLOCK;
 		if (g_msk_blocks < 4)
 			g_msk_blocks = 4;                     /* soundfile.c:27 MAXNBFRAMES 4096 */
-		if ((g_msk = make_msk_ctx(g_msk_blocks)) == NULL)
+		if ((g_msk = make_msk_ctx(1, g_msk_blocks)) == NULL)
 			exit(1);
 		g_msk_sh.valid = 0;
 	}
@@ -316,6 +324,45 @@ void demodMSK(channel_t *ch, int len)
 		die("replay", g_msk, rc);
 	download_all(g_msk, &g_msk_sh, one, 1);
 	discard_device_blocks(g_msk);
+	account(t0);
+}
+
+/*
+ * The per-channel loop of soundfile.c:71-77 for all channels: `nframes` interleaved float frames as sf_read_float() delivered
+ * them, ONE GPU call and one state download per read where demodMSK() makes nbch of each.  The device de-interleaves; the bits
+ * are replayed through decodeAcars() channel by channel in channel order -- the order in which the reference's loop queues its
+ * blocks, so the printed output is the same.  The binding a maintainer adds is one hunk in soundfile.c:
+ *     -		for (n = 0; n < nbch; n++) { ... demodMSK(&(channel[n]),len); }       soundfile.c:71-77
+ *     +		acarsdec_amd_pcm_frames(sndbuff, nbi / nbch);
+ */
+void acarsdec_amd_pcm_frames(const float *interleaved, int nframes)
+{
+	unsigned int n;
+	int rc;
+	channel_t *chs[MAXNBCHANNELS];
+	const double t0 = now_s();
+
+	if (nframes <= 0 || nbch == 0)
+		return;
+	if (g_pcm == NULL || (nframes + ACG_BLOCK - 1) / ACG_BLOCK > g_pcm_blocks) {       /* (made by initMsk(); here: a longer read than foreseen) */
+		if (g_pcm)
+			acg_destroy(g_pcm);
+		g_pcm_blocks = (nframes + ACG_BLOCK - 1) / ACG_BLOCK;
+		if (g_pcm_blocks < 4)
+			g_pcm_blocks = 4;                     /* soundfile.c:27 MAXNBFRAMES 4096 */
+		if ((g_pcm = make_msk_ctx((int)nbch, g_pcm_blocks)) == NULL)
+			exit(1);
+		g_pcm_sh.valid = 0;
+	}
+	for (n = 0; n < nbch; n++)
+		chs[n] = &channel[n];
+	upload_all(g_pcm, &g_pcm_sh, chs, (int)nbch);
+	if ((rc = acg_feed_pcm_host(g_pcm, ACG_PCM_F32, interleaved, (size_t)nframes)) != ACG_OK)
+		die("feed_pcm", g_pcm, rc);
+	if ((rc = acg_replay_bits(g_pcm, bit_sink, chs)) != ACG_OK)             /* channel order, as soundfile.c:71 iterates */
+		die("replay", g_pcm, rc);
+	download_all(g_pcm, &g_pcm_sh, chs, (int)nbch);
+	discard_device_blocks(g_pcm);
 	account(t0);
 }
 
@@ -535,9 +582,15 @@ static int compat_prepare(void)
 #endif
 	if (!made && g_msk == NULL) {                                    /* soundfile.c / alsa.c feed demodMSK() directly */
 		g_msk_blocks = 4;                                            /* soundfile.c:27 MAXNBFRAMES 4096 */
-		if ((g_msk = make_msk_ctx(g_msk_blocks)) == NULL)
+		if ((g_msk = make_msk_ctx(1, g_msk_blocks)) == NULL)
 			return -1;
 		rc = warm_up(g_msk, -1, 0, 1);
+	}
+	if (!made && g_pcm == NULL && rc == ACG_OK) {                    /* ... or, bound, all channels of a read at once */
+		g_pcm_blocks = 4;
+		if ((g_pcm = make_msk_ctx((int)nbch, g_pcm_blocks)) == NULL)
+			return -1;
+		rc = warm_up(g_pcm, -2, (int)nbch, (int)nbch);
 	}
 	g_prepare = now_s() - t0;
 	return rc == ACG_OK ? 0 : -1;

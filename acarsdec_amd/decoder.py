@@ -199,6 +199,21 @@ class Decoder:
         dm = dm.reshape(self.nch, dm.size // self.nch)
         self._chk(self.L.acg_process_dm_host(self.ctx, dm.ctypes.data, dm.shape[1], dm.shape[1]))
 
+    def feed_pcm(self, frames):
+        """demodMSK() for all channels from interleaved frames as a sound file or a sound card delivers them: numpy [nframes, nch],
+        int16 (PCM16, scaled by 1/32768 on the device) or float32, C-contiguous, any nframes (acg_feed_pcm_host)."""
+        if not isinstance(frames, np.ndarray) or frames.dtype not in (np.int16, np.float32):
+            raise TypeError("frames: a numpy array of int16 or float32")
+        if frames.ndim != 2 or frames.shape[1] != self.nch or not frames.flags["C_CONTIGUOUS"]:
+            raise ValueError("frames: C-contiguous [nframes, %d]" % self.nch)
+        fmt = K.PCM_S16 if frames.dtype == np.int16 else K.PCM_F32
+        self._chk(self.L.acg_feed_pcm_host(self.ctx, fmt, frames.ctypes.data, frames.shape[0]))
+
+    def process_pcm(self, dev_tensor, fmt, nframes, stream=None):
+        """The same from a device tensor of nframes * nch interleaved elements (K.PCM_S16 / K.PCM_F32), nframes <= max_blocks * 1024,
+        asynchronous on `stream` (acg_process_pcm_dev)."""
+        self._chk(self.L.acg_process_pcm_dev(self.ctx, int(fmt), dev_tensor.data_ptr(), int(nframes), stream))
+
     def sync(self):
         self._chk(self.L.acg_sync(self.ctx))
 

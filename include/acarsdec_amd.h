@@ -221,6 +221,22 @@ int  acg_process_samples_dev(acg_ctx *ctx, int fmt, const void *dev, size_t pitc
 int  acg_feed_samples_host(acg_ctx *ctx, int fmt, const void *p0, const void *p1, size_t pitch_samples,
 			   size_t nsamples);
 
+/* ---- the 12.5 kHz front ends' own shape: interleaved PCM frames (soundfile.c, alsa.c) ------- */
+#define ACG_PCM_S16 1   /* interleaved int16 frames, x/32768: what sf_read_float makes of a PCM16 file (soundfile.c:65) */
+#define ACG_PCM_F32 2   /* interleaved float32 frames: sf_read_float's own output, alsa.c:66,114 */
+/* demodMSK() for every channel from frames as a sound file, a sound card or a recorder delivers them: [nframes][nch], frame i
+ * at frames + i*nch elements, 4-byte aligned base.  A device kernel de-interleaves (and scales: exact) into the context's dm
+ * image; the results are those of acg_process_dm_host on the de-interleaved floats.
+ * frames_dev: on the device, nframes <= max_blocks*1024; asynchronous, the contract of acg_process_dm_dev -- except that later
+ * work on hip_stream is ordered behind the de-interleave kernel (the only reader of frames_dev), not behind the demodulator. */
+int  acg_process_pcm_dev(acg_ctx *ctx, int fmt, const void *frames_dev, int nframes, void *hip_stream);
+/* frames in host memory, ANY nframes (chunks of max_blocks*1024 frames, one contiguous copy each into the two staging buffers
+ * of the *_host entry points, the copy of a chunk beside the kernels of the chunk before); returns when the input has left the
+ * caller's buffer (the contract of acg_process_iq_u8_host / acg_feed_samples_host).  ACG_ESTATE while acg_feed_samples_host
+ * carries a partial window in those buffers.  The bit log (ACG_F_BITLOG: acg_read_bits*, acg_replay_bits) holds the bits of the
+ * call's LAST chunk only (every chunk is a call of its own): a host that replays bits feeds at most max_blocks*1024 frames per call. */
+int  acg_feed_pcm_host(acg_ctx *ctx, int fmt, const void *frames, size_t nframes);
+
 /* pinned host memory for the *_host entry points (hipHostMalloc / hipHostRegister behind a C face, so that a C host needs
  * no HIP headers): acg_host_alloc returns NULL on failure */
 void *acg_host_alloc(size_t bytes);

@@ -15,6 +15,7 @@
 #define ACARSDEC_AMD_COMPAT_H
 
 #include <stdint.h>
+#include "acarsdec_amd_compat_pcm.h"   /* the 12.5 kHz front ends' binding (soundfile.c) */
 
 #ifdef __cplusplus
 extern "C" {

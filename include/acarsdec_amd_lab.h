@@ -157,6 +157,13 @@ typedef struct acg_lab_launch_shape {
 } acg_lab_launch_shape;
 int  acg_lab_fir_launch_shape(acg_ctx *ctx, int nblocks, acg_lab_launch_shape *out);
 
+/* diagnostics: ONLY the de-interleave kernel of acg_process_pcm_dev (pcm.hip) on nframes host frames of the context's nch channels:
+ * dm_host, an image of nch rows of pitch_floats words, is filled with `fill`, goes to the device, the kernel writes columns
+ * [0, nframes) of its rows, and the WHOLE image comes back -- every word outside those columns must still be `fill`.  The input
+ * is copied to a device buffer of exactly nframes*nch elements (rounded up to 4 bytes).  ACG_EINVAL: unknown fmt, a base that is
+ * not 4-byte aligned, nframes < 0, pitch_floats < nframes. */
+int  acg_lab_pcm_deinterleave(acg_ctx *ctx, int fmt, const void *frames_host, int nframes, float *dm_host, size_t pitch_floats, float fill);
+
 /* only in the stamp build (libacarsdec_amd_stamp.so, -DACG_MSK_STAMP): phase cycle sums of the LAST demodulator launch,
  * [waves][10], and the lanes per channel of the context's demodulator */
 int  acg_msk_stamp_read(acg_ctx *ctx, unsigned long long *out, int nwaves);
