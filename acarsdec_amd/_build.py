@@ -84,7 +84,7 @@ def build_lib(force=False, stamp=False, poly=False, lab=False):
     os.makedirs(OBJDIR, exist_ok=True)
     defs = (["-DACG_LAB"] if (lab or stamp or poly) else []) + (["-DACG_MSK_STAMP"] if stamp else []) + (["-DACG_MSK_SINCOS_POLY"] if poly else [])
     out_lib = LIB_STAMP if stamp else LIB_POLY if poly else LIB_LAB if lab else LIB
-    hdrs = [os.path.join(CSRC, "acg_internal.h"), os.path.join(CSRC, "flights.h"), os.path.join(CSRC, "msk_common.h"), os.path.join(CSRC, "json_num.h"), os.path.join(CSRC, "text_num.h"), os.path.join(CSRC, "flight_text_num.h"), os.path.join(CSRC, "sink_pack.h"), os.path.join(CSRC, "fir_mm_plan.h"), os.path.join(CSRC, "fir_plan.h"), os.path.join(INC, "acarsdec_amd.h"),
+    hdrs = [os.path.join(CSRC, "acg_internal.h"), os.path.join(CSRC, "flights.h"), os.path.join(CSRC, "msk_common.h"), os.path.join(CSRC, "json_num.h"), os.path.join(CSRC, "text_num.h"), os.path.join(CSRC, "flight_text_num.h"), os.path.join(CSRC, "sink_pack.h"), os.path.join(CSRC, "sink_put.h"), os.path.join(CSRC, "fir_mm_plan.h"), os.path.join(CSRC, "fir_plan.h"), os.path.join(INC, "acarsdec_amd.h"),
             os.path.join(INC, "acarsdec_amd_lab.h"), os.path.abspath(__file__)]   # flags live here
     hdrs += sorted(os.path.join(CSRC, "lab", f) for f in os.listdir(os.path.join(CSRC, "lab")))       # the lab-only kernel families fir.hip includes
     objs = []

@@ -20,10 +20,10 @@
 // is a ballot and a find-first; "%-8s", "%-7s", "%4s" and "%3d" pad and never cut; measure and render run the SAME function
 // (ft_row / ft_line <false / true>); no scratch, no per-byte global traffic of whole records.  sink_pack.h's pieces are used as
 // they are (PkLit, pk_sum, pk_offsets, pk_flush_row).  Its pk_measure / pk_render / pk_launch are written over AcgSinkPass and a
-// message record, so this unit has bodies of its own; and the put helpers and the escape of a string (put_lit, put_words,
-// put_escaped, put_round, put_str) live inside json.hip, not in a header: moving them out would change that unit's text, so a
-// COPY is kept here (ft_*), byte for byte the same rules (cJSON.c:858-877).
-#include "sink_pack.h"
+// message record, so this unit has loop bodies of its own.  The row writers and the escape's rules (cJSON.c:858-877) are the
+// sinks' own, sink_put.h; what only the monitor row uses ("%-Ns", the OOOI field, printtime()) is here and stores through pk_st,
+// and so is the one round a route's short strings need (ft_str_json, over the shared classes and escaped byte).
+#include "sink_put.h"
 #include "flight_text_num.h"
 
 #define FT_ROW_BUF 128                      // a wave's LDS row: the monitor's header (110) and its rows (<= 78)
@@ -34,60 +34,18 @@ static_assert(ACG_FT_ROW_MAX == ACG_MONITOR_ROW_MAX && ACG_FT_LINE_MAX == ACG_RO
 static_assert(ACG_FT_ROW_MAX <= FT_ROW_BUF && ACG_FT_HDR_LEN <= FT_ROW_BUF && ACG_FT_LINE_MAX <= FT_LINE_BUF, "row buffers");
 static_assert(sizeof(AcgFlightSlot) == 120 && sizeof(AcgRouteRec) == 64 && offsetof(AcgFlightSlot, fld) == 92 && offsetof(AcgFlightSlot, fid) == 16, "layouts");
 
-// characters [from, from + 16) of a literal
-constexpr PkLit ft_lit_part(const char* s, unsigned int from)
-{
-    unsigned int n = 0;
-    while (s[n]) ++n;
-    char part[17] = {};
-    for (unsigned int i = 0; i < 16 && from + i < n; ++i) part[i] = s[from + i];
-    return pk_lit(part);
-}
-
-template <bool W, unsigned int B>
-__device__ __forceinline__ void ft_st(unsigned char* row, unsigned int p, unsigned char v)
-{
-    if (W && p < B) row[p] = v;                                    // (the bound holds by construction; this keeps a bug inside the row)
-}
-
-template <bool W, unsigned int B>
-__device__ __forceinline__ unsigned int ft_lit(unsigned char* row, unsigned int pos, const PkLit l, int lane)
-{
-    if (W && (unsigned int)lane < l.n) ft_st<W, B>(row, pos + lane, (unsigned char)((lane < 8 ? l.lo : l.hi) >> (8 * (lane & 7))));
-    return pos + l.n;
-}
-// a literal of at most 64 characters
-#define FT_LIT(s) do { static_assert(sizeof(s) - 1 <= 64, "literal"); \
-                       constexpr PkLit a_ = ft_lit_part(s, 0); pos = ft_lit<W, B>(row, pos, a_, lane); \
-                       if (sizeof(s) - 1 > 16) { constexpr PkLit b_ = ft_lit_part(s, 16); pos = ft_lit<W, B>(row, pos, b_, lane); } \
-                       if (sizeof(s) - 1 > 32) { constexpr PkLit c_ = ft_lit_part(s, 32); pos = ft_lit<W, B>(row, pos, c_, lane); } \
-                       if (sizeof(s) - 1 > 48) { constexpr PkLit d_ = ft_lit_part(s, 48); pos = ft_lit<W, B>(row, pos, d_, lane); } } while (0)
-
-template <bool W, unsigned int B>
-__device__ __forceinline__ unsigned int ft_fill(unsigned char* row, unsigned int pos, unsigned char c, unsigned int n, int lane)
-{
-    if (W && (unsigned int)lane < n) ft_st<W, B>(row, pos + lane, c);
-    return pos + n;
-}
-
-// the C string at s (at most maxlen < 64 bytes): its bytes in b, its length returned
-__device__ __forceinline__ int ft_strlen(const unsigned char* s, int maxlen, int lane, unsigned int* b)
-{
-    *b = lane < maxlen ? s[lane] : 0u;
-    const unsigned long long nul = __ballot(*b == 0);             // (never 0: maxlen < 64)
-    return __ffsll((unsigned long long)nul) - 1;
-}
+#define FT_LIT(s) PK_PUT_LIT(B, s)
 
 // "%-<width>s": left-justified to at least width, never cut
 template <bool W, unsigned int B>
 __device__ __forceinline__ unsigned int ft_str_left(unsigned char* row, unsigned int pos, const unsigned char* s, int maxlen, int width, int lane)
 {
     unsigned int b;
-    const int n = ft_strlen(s, maxlen, lane, &b);
+    const int n = pk_strlen(s, maxlen, lane, &b);
     const int pad = width > n ? width - n : 0;
     if (W) {
-        if (lane < n) ft_st<W, B>(row, pos + lane, (unsigned char)b);
-        if (lane < pad) ft_st<W, B>(row, pos + n + lane, ' ');
+        if (lane < n) pk_st<W, B>(row, pos + lane, (unsigned char)b);
+        if (lane < pad) pk_st<W, B>(row, pos + n + lane, ' ');
     }
     return pos + (unsigned int)(n + pad);
 }
@@ -97,9 +55,9 @@ template <bool W, unsigned int B>
 __device__ __forceinline__ unsigned int ft_field(unsigned char* row, unsigned int pos, const unsigned char* s, int lane)
 {
     unsigned int b;
-    const int n = ft_strlen(s, 4, lane, &b);
+    const int n = pk_strlen(s, 4, lane, &b);
     const int j = lane - (5 - n);                                  // place `lane` of the six shows the string's byte j: 5 - n spaces in front
-    if (W && lane < 6) ft_st<W, B>(row, pos + lane, (unsigned char)(j >= 0 && j < n ? s[j] : ' '));
+    if (W && lane < 6) pk_st<W, B>(row, pos + lane, (unsigned char)(j >= 0 && j < n ? s[j] : ' '));
     return pos + 6;
 }
 
@@ -108,7 +66,7 @@ template <bool W, unsigned int B>
 __device__ __forceinline__ unsigned int ft_time(unsigned char* row, unsigned int pos, long long sec, int usec, int lane)
 {
     const TnDate d = tn_date(sec, usec);
-    if (W && lane < FTN_TIME_LEN) ft_st<W, B>(row, pos + lane, ftn_time_char(d, lane));
+    if (W && lane < FTN_TIME_LEN) pk_st<W, B>(row, pos + lane, ftn_time_char(d, lane));
     return pos + FTN_TIME_LEN;
 }
 
@@ -119,25 +77,25 @@ __device__ __forceinline__ unsigned int ft_row(const unsigned char* S, unsigned 
     constexpr unsigned int B = ACG_FT_ROW_MAX;
     const AcgFlightSlot* s = (const AcgFlightSlot*)S;
     unsigned int pos = 0;
-    pos = ft_fill<W, B>(row, pos, ' ', 1, lane);
+    pos = pk_fill<W, B>(row, pos, ' ', 1, lane);
     pos = ft_str_left<W, B>(row, pos, S + offsetof(AcgFlightSlot, key), 7, 8, lane);      // " %-8s": the key's low 7 bytes are the addr
-    pos = ft_fill<W, B>(row, pos, ' ', 1, lane);
+    pos = pk_fill<W, B>(row, pos, ' ', 1, lane);
     pos = ft_str_left<W, B>(row, pos, S + offsetof(AcgFlightSlot, fid), 7, 7, lane);      // " %-7s"
-    pos = ft_fill<W, B>(row, pos, ' ', 1, lane);
+    pos = pk_fill<W, B>(row, pos, ' ', 1, lane);
     const FtnInt3 nb = ftn_int3(s->nbm);                                                  // " %3d "
-    if (W && lane < nb.len) ft_st<W, B>(row, pos + lane, ftn_int3_char(nb, lane));
+    if (W && lane < nb.len) pk_st<W, B>(row, pos + lane, ftn_int3_char(nb, lane));
     pos += (unsigned int)nb.len;
-    pos = ft_fill<W, B>(row, pos, ' ', 1, lane);
+    pos = pk_fill<W, B>(row, pos, ' ', 1, lane);
     const unsigned int chm = (unsigned int)s->chm;                                       // output.c:472-473: nbch columns, padded to 16
-    if (W && lane < 16) ft_st<W, B>(row, pos + lane, (unsigned char)(lane >= nbch ? ' ' : ((chm >> lane) & 1u) ? 'x' : '.'));
+    if (W && lane < 16) pk_st<W, B>(row, pos + lane, (unsigned char)(lane >= nbch ? ' ' : ((chm >> lane) & 1u) ? 'x' : '.'));
     pos += 16;
-    pos = ft_fill<W, B>(row, pos, ' ', 1, lane);
+    pos = pk_fill<W, B>(row, pos, ' ', 1, lane);
     pos = ft_time<W, B>(row, pos, s->ts_sec, s->ts_usec, lane);
     const unsigned char* f = S + offsetof(AcgFlightSlot, fld);                            // da sa eta ...: the screen shows sa, da, eta
     pos = ft_field<W, B>(row, pos, f + 4, lane);
     pos = ft_field<W, B>(row, pos, f + 0, lane);
     pos = ft_field<W, B>(row, pos, f + 8, lane);
-    pos = ft_fill<W, B>(row, pos, '\n', 1, lane);
+    pos = pk_fill<W, B>(row, pos, '\n', 1, lane);
     return pos;
 }
 
@@ -154,57 +112,21 @@ __device__ __forceinline__ unsigned int ft_header(unsigned char* row, long long 
     return pos;
 }
 
-// ---- the route line's strings: json.hip's rules (a copy, see above) ----------------------------------------------------------
-// n bytes that are already escaped (the station stretch), 4-byte aligned: a dword load per lane
-template <bool W, unsigned int B>
-__device__ __forceinline__ unsigned int ft_words(unsigned char* row, unsigned int pos, const unsigned char* src, unsigned int n, int lane)
-{
-    if (W)
-        for (unsigned int i = 4u * lane; i < n; i += 256) {
-            const unsigned int w = *(const unsigned int*)(src + i);
-#pragma unroll
-            for (unsigned int k = 0; k < 4; ++k)
-                if (i + k < n) ft_st<W, B>(row, pos + i + k, (unsigned char)(w >> (8 * k)));
-        }
-    return pos + n;
-}
-
-// print_string_ptr's classes (cJSON.c:858-877)
-__device__ __forceinline__ bool ft_two(unsigned int b)
-{
-    return b == '"' || b == '\\' || b == '\b' || b == '\f' || b == '\n' || b == '\r' || b == '\t';
-}
-
-// "<C string at s, at most maxlen < 64 bytes>" escaped as print_string_ptr does: a byte's place is its index + the two-character
-// escapes before it + 5 x the \u00xx escapes before it
+// "<C string at s, at most maxlen < 64 bytes>" escaped: pk_put_str's one round over the shared length, classes and escaped byte,
+// without pk_put_round's "no NUL among the 64 lanes" case (with pk_put_str the route pass over 16 384 routes measured 0.295-0.296 ms
+// against the parent's 0.293-0.295 in two sessions, outside its run-to-run range; this spelling 0.294: LEDGER)
 template <bool W, unsigned int B>
 __device__ __forceinline__ unsigned int ft_str_json(unsigned char* row, unsigned int pos, const unsigned char* s, int maxlen, int lane)
 {
     unsigned int b;
-    const int n = ft_strlen(s, maxlen, lane, &b);
+    const int n = pk_strlen(s, maxlen, lane, &b);
     const bool live = lane < n;
-    const bool two = live && ft_two(b), six = live && b < 32u && !two;
+    const bool two = live && pk_two(b), six = live && b < 32u && !two;
     const unsigned long long m2 = __ballot(two), m6 = __ballot(six), below = (1ull << lane) - 1ull;
     const unsigned int esc = (unsigned int)n + (unsigned int)__popcll(m2) + 5u * (unsigned int)__popcll(m6);
-    if (W) {
-        if (lane == 0) ft_st<W, B>(row, pos, '"');
-        const unsigned int p = pos + 1 + (unsigned int)lane + (unsigned int)__popcll(m2 & below) + 5u * (unsigned int)__popcll(m6 & below);
-        if (two) {
-            ft_st<W, B>(row, p, '\\');
-            ft_st<W, B>(row, p + 1, (unsigned char)(b == '\b' ? 'b' : b == '\f' ? 'f' : b == '\n' ? 'n' : b == '\r' ? 'r' : b == '\t' ? 't' : b));
-        } else if (six) {                                          // sprintf("u%04x"): lower-case hex, b < 32
-            ft_st<W, B>(row, p, '\\');
-            ft_st<W, B>(row, p + 1, 'u');
-            ft_st<W, B>(row, p + 2, '0');
-            ft_st<W, B>(row, p + 3, '0');
-            ft_st<W, B>(row, p + 4, (unsigned char)('0' + (b >> 4)));
-            const unsigned int lo = b & 15u;
-            ft_st<W, B>(row, p + 5, (unsigned char)(lo < 10 ? '0' + lo : 'a' + lo - 10));
-        } else if (live) {
-            ft_st<W, B>(row, p, (unsigned char)b);
-        }
-        if (lane == 0) ft_st<W, B>(row, pos + 1 + esc, '"');
-    }
+    if (lane == 0) pk_st<W, B>(row, pos, '"');
+    if (live) pk_put_escaped<W, B>(row, pos + 1 + (unsigned int)lane + (unsigned int)__popcll(m2 & below) + 5u * (unsigned int)__popcll(m6 & below), b, two, six);
+    if (lane == 0) pk_st<W, B>(row, pos + 1 + esc, '"');
     return pos + esc + 2;
 }
 
@@ -216,11 +138,9 @@ __device__ __forceinline__ unsigned int ft_line(const unsigned char* R, unsigned
     const unsigned char* r = R + offsetof(AcgRouteRec, r);
     unsigned int pos = 0;
     FT_LIT("{\"timestamp\":");
-    const JnTok t = jn_timestamp(*(const long long*)(r + offsetof(acg_route, sec)), *(const int*)(r + offsetof(acg_route, usec)));
-    if (W && lane < t.len) ft_st<W, B>(row, pos + lane, jn_char(t, lane));
-    pos += (unsigned int)t.len;
+    pos = pk_put_tok<W, B>(row, pos, jn_timestamp(*(const long long*)(r + offsetof(acg_route, sec)), *(const int*)(r + offsetof(acg_route, usec))), lane);
     const unsigned int pre_len = cfg->pre_len > ACG_JS_PRE_MAX ? ACG_JS_PRE_MAX : cfg->pre_len;
-    pos = ft_words<W, B>(row, pos, cfg->pre, pre_len, lane);                              // ,"station_id":".." or nothing
+    pos = pk_put_words<W, B>(row, pos, cfg->pre, pre_len, lane);                         // ,"station_id":".." or nothing
     FT_LIT(",\"flight\":");
     pos = ft_str_json<W, B>(row, pos, r + offsetof(acg_route, fid), 7, lane);
     FT_LIT(",\"depa\":");

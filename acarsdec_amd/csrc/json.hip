@@ -19,109 +19,24 @@
 // room for is the length it is rendered with.
 //
 // THE SEAM, the scan, the record load, the level's float, the bodies of the keys / measure / render kernels and the launch sequence
-// are shared with the text renderer (text.hip): sink_pack.h.  This unit supplies json_line and keeps its kernels as wrappers.
+// are shared with the text renderer (text.hip): sink_pack.h.  The row writers (bounded store, literal, number token, dword copy,
+// the string escape) are shared with text.hip and flight_text.hip: sink_put.h.  This unit supplies json_line and keeps its kernels
+// as wrappers.
 //
 // No scratch (no indexed private array: a record's fields are read out of LDS, digits are computed, not stored), no per-byte
 // global traffic (a record comes in as 80 + 10 dword loads, the constant stretches as dwords, a line leaves as 16-byte stores and < 30 byte stores), two
 // independent waves per workgroup (2 x 2 944 B of LDS): these passes run beside a down-converter that saturates HBM.
-#include "sink_pack.h"
-#include "json_num.h"
+#include "sink_put.h"
 
 static_assert(ACG_JS_LINE_MAX == ACG_JSON_LINE_MAX && ACG_JS_LINE_MAX % 64 == 0, "line bound");
 
-template <bool W>
-__device__ __forceinline__ void js_st(unsigned char* row, unsigned int p, unsigned char v)
-{
-    if (W && p < (unsigned int)ACG_JS_LINE_MAX) row[p] = v;       // (the bound holds by construction; this keeps a bug inside the row)
-}
-
-template <bool W>
-__device__ __forceinline__ unsigned int put_lit(unsigned char* row, unsigned int pos, const PkLit l, int lane)
-{
-    if (W && (unsigned int)lane < l.n) js_st<W>(row, pos + lane, (unsigned char)((lane < 8 ? l.lo : l.hi) >> (8 * (lane & 7))));
-    return pos + l.n;
-}
-#define PUT_LIT(s) do { constexpr PkLit l_ = pk_lit(s); static_assert(sizeof(s) - 1 <= 16, "literal"); pos = put_lit<W>(row, pos, l_, lane); } while (0)
-
-// n bytes that are already escaped (the station and app stretches), 4-byte aligned: a dword load per lane, not a load per byte
-template <bool W>
-__device__ __forceinline__ unsigned int put_words(unsigned char* row, unsigned int pos, const unsigned char* src, unsigned int n, int lane)
-{
-    if (W)
-        for (unsigned int i = 4u * lane; i < n; i += 256) {
-            const unsigned int w = *(const unsigned int*)(src + i);
-#pragma unroll
-            for (unsigned int k = 0; k < 4; ++k)
-                if (i + k < n) js_st<W>(row, pos + i + k, (unsigned char)(w >> (8 * k)));
-        }
-    return pos + n;
-}
-
-template <bool W>
-__device__ __forceinline__ unsigned int put_tok(unsigned char* row, unsigned int pos, const JnTok& t, int lane)
-{
-    if (W && lane < t.len) js_st<W>(row, pos + lane, jn_char(t, lane));
-    return pos + (unsigned int)t.len;
-}
-
-// print_string_ptr's classes (cJSON.c:858-877)
-__device__ __forceinline__ bool js_two(unsigned int b)
-{
-    return b == '"' || b == '\\' || b == '\b' || b == '\f' || b == '\n' || b == '\r' || b == '\t';
-}
-
-// one lane's byte, escaped, at p
-template <bool W>
-__device__ __forceinline__ void put_escaped(unsigned char* row, unsigned int p, unsigned int b, bool two, bool six)
-{
-    if (!W) return;
-    if (two) {
-        js_st<W>(row, p, '\\');
-        js_st<W>(row, p + 1, (unsigned char)(b == '\b' ? 'b' : b == '\f' ? 'f' : b == '\n' ? 'n' : b == '\r' ? 'r' : b == '\t' ? 't' : b));
-    } else if (six) {                                              // sprintf("u%04x"): lower-case hex, b < 32
-        js_st<W>(row, p, '\\');
-        js_st<W>(row, p + 1, 'u');
-        js_st<W>(row, p + 2, '0');
-        js_st<W>(row, p + 3, '0');
-        js_st<W>(row, p + 4, (unsigned char)('0' + (b >> 4)));
-        const unsigned int lo = b & 15u;
-        js_st<W>(row, p + 5, (unsigned char)(lo < 10 ? '0' + lo : 'a' + lo - 10));
-    } else {
-        js_st<W>(row, p, (unsigned char)b);
-    }
-}
-
-// up to 64 bytes of a string whose lane's byte is b (0 = at or behind its end): `live` lanes are those before the first NUL.
-// Returns the escaped length; *more = no NUL among the 64 (the string goes on in the next round).
-template <bool W>
-__device__ __forceinline__ unsigned int put_round(unsigned char* row, unsigned int pos, unsigned int b, int lane, bool* more)
-{
-    const unsigned long long nul = __ballot(b == 0);
-    const int n = nul ? __ffsll((unsigned long long)nul) - 1 : 64;
-    const bool live = lane < n;
-    const bool two = live && js_two(b), six = live && b < 32u && !two;
-    const unsigned long long m2 = __ballot(two), m6 = __ballot(six), below = (1ull << lane) - 1ull;
-    if (live) put_escaped<W>(row, pos + (unsigned int)lane + (unsigned int)__popcll(m2 & below) + 5u * (unsigned int)__popcll(m6 & below), b, two, six);
-    *more = n == 64;
-    return (unsigned int)n + (unsigned int)__popcll(m2) + 5u * (unsigned int)__popcll(m6);
-}
-
-// "<C string at s, at most maxlen < 64 bytes>" escaped as print_string_ptr does
-template <bool W>
-__device__ __forceinline__ unsigned int put_str(unsigned char* row, unsigned int pos, const unsigned char* s, int maxlen, int lane)
-{
-    const unsigned int b = lane < maxlen ? s[lane] : 0u;
-    bool more;
-    if (lane == 0) js_st<W>(row, pos, '"');
-    const unsigned int n = put_round<W>(row, pos + 1, b, lane, &more);
-    if (lane == 0) js_st<W>(row, pos + 1 + n, '"');
-    return pos + n + 2;
-}
+#define PUT_LIT(s) PK_PUT_LIT(B, s)
 
 // One line.  R: the record and, at R + 320, its acg_oooi (LDS); row: where the line's first byte goes (W) or unused.
 template <bool W>
 __device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsigned char* row, const AcgSinkPass& p, int lane, bool* near_mid)
 {
+    constexpr unsigned int B = ACG_JS_LINE_MAX;
     const AcgMsgRec* r = (const AcgMsgRec*)R;
     const AcgJsonDev* cfg = (const AcgJsonDev*)p.cfg;
     unsigned int pos = 0;
@@ -131,16 +46,16 @@ __device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsign
     long long q = us / 1000000ll, rem = us % 1000000ll;
     if (rem < 0) { rem += 1000000ll; --q; }
     PUT_LIT("{\"timestamp\":");
-    pos = put_tok<W>(row, pos, jn_timestamp(cfg->t0_sec + q, (int)rem), lane);
-    pos = put_words<W>(row, pos, cfg->pre, cfg->pre_len, lane);                   // ,"station_id":".." or nothing
+    pos = pk_put_tok<W, B>(row, pos, jn_timestamp(cfg->t0_sec + q, (int)rem), lane);
+    pos = pk_put_words<W, B>(row, pos, cfg->pre, cfg->pre_len, lane);                   // ,"station_id":".." or nothing
     const int chn = r->chn;
     PUT_LIT(",\"channel\":");
-    pos = put_tok<W>(row, pos, jn_int(chn), lane);
+    pos = pk_put_tok<W, B>(row, pos, jn_int(chn), lane);
     PUT_LIT(",\"freq\":");
     if ((unsigned int)chn < (unsigned int)cfg->nch) {
         const unsigned long long ft = ((const unsigned long long*)p.freq)[chn];    // 7 characters and their count: one load
         const unsigned int fn = (unsigned int)(ft >> 56) & 7u;
-        if (W && (unsigned int)lane < fn) js_st<W>(row, pos + lane, (unsigned char)(ft >> (8 * lane)));
+        if (W && (unsigned int)lane < fn) pk_st<W, B>(row, pos + lane, (unsigned char)(ft >> (8 * lane)));
         pos += fn;
     } else {
         PUT_LIT("0.000");
@@ -148,30 +63,30 @@ __device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsign
     // ---- "level": the float of acars.c:351, then "%2.1f" cut to 7 characters (json_num.h)
     const float lvl = pk_level(r, p.lvl_from_rec, near_mid);
     PUT_LIT(",\"level\":");
-    pos = put_tok<W>(row, pos, jn_level(lvl), lane);
+    pos = pk_put_tok<W, B>(row, pos, jn_level(lvl), lane);
     PUT_LIT(",\"error\":");
-    pos = put_tok<W>(row, pos, jn_int(r->err), lane);
+    pos = pk_put_tok<W, B>(row, pos, jn_int(r->err), lane);
     PUT_LIT(",\"mode\":");
-    pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, mode), 1, lane);           // "%c": a NUL gives ""
+    pos = pk_put_str<W, B>(row, pos, R + offsetof(AcgMsgRec, mode), 1, lane);           // "%c": a NUL gives ""
     PUT_LIT(",\"label\":");
-    pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, label), 2, lane);
+    pos = pk_put_str<W, B>(row, pos, R + offsetof(AcgMsgRec, label), 2, lane);
     const char bid = r->bid;
     if (bid) {
         PUT_LIT(",\"block_id\":");
-        pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, bid), 1, lane);
+        pos = pk_put_str<W, B>(row, pos, R + offsetof(AcgMsgRec, bid), 1, lane);
         if (r->ack == '!') {
             PUT_LIT(",\"ack\":false");
         } else {
             PUT_LIT(",\"ack\":");
-            pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, ack), 1, lane);
+            pos = pk_put_str<W, B>(row, pos, R + offsetof(AcgMsgRec, ack), 1, lane);
         }
         PUT_LIT(",\"tail\":");
-        pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, addr), 7, lane);
+        pos = pk_put_str<W, B>(row, pos, R + offsetof(AcgMsgRec, addr), 7, lane);
         if (bid >= '0' && bid <= '9') {                                          // IS_DOWNLINK_BLK, output.c:31,269
             PUT_LIT(",\"flight\":");
-            pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, fid), 6, lane);
+            pos = pk_put_str<W, B>(row, pos, R + offsetof(AcgMsgRec, fid), 6, lane);
             PUT_LIT(",\"msgno\":");
-            pos = put_str<W>(row, pos, R + offsetof(AcgMsgRec, no), 4, lane);
+            pos = pk_put_str<W, B>(row, pos, R + offsetof(AcgMsgRec, no), 4, lane);
         }
     }
     // ---- "text": a C string within txt_len bytes, four rounds of 64 lanes
@@ -184,7 +99,7 @@ __device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsign
             const int i = 64 * rd + lane;
             const unsigned int b = i < tl ? txt[i] : 0u;
             bool more;
-            pos += put_round<W>(row, pos, b, lane, &more);
+            pos += pk_put_round<W, B>(row, pos, b, lane, &more);
             if (!more) break;                                                    // (wave-uniform)
         }
         PUT_LIT("\"");
@@ -193,15 +108,15 @@ __device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsign
     // ---- the OOOI keys in buildjson's order (output.c:280-295): sa da eta gout gin woff won of {da sa eta gout gin woff won}
     const unsigned char* O = R + sizeof(AcgMsgRec);
     if (O[35]) {
-        if (O[5]) { PUT_LIT(",\"depa\":"); pos = put_str<W>(row, pos, O + 5, 4, lane); }
-        if (O[0]) { PUT_LIT(",\"dsta\":"); pos = put_str<W>(row, pos, O + 0, 4, lane); }
-        if (O[10]) { PUT_LIT(",\"eta\":"); pos = put_str<W>(row, pos, O + 10, 4, lane); }
-        if (O[15]) { PUT_LIT(",\"gtout\":"); pos = put_str<W>(row, pos, O + 15, 4, lane); }
-        if (O[20]) { PUT_LIT(",\"gtin\":"); pos = put_str<W>(row, pos, O + 20, 4, lane); }
-        if (O[25]) { PUT_LIT(",\"wloff\":"); pos = put_str<W>(row, pos, O + 25, 4, lane); }
-        if (O[30]) { PUT_LIT(",\"wlin\":"); pos = put_str<W>(row, pos, O + 30, 4, lane); }
+        if (O[5]) { PUT_LIT(",\"depa\":"); pos = pk_put_str<W, B>(row, pos, O + 5, 4, lane); }
+        if (O[0]) { PUT_LIT(",\"dsta\":"); pos = pk_put_str<W, B>(row, pos, O + 0, 4, lane); }
+        if (O[10]) { PUT_LIT(",\"eta\":"); pos = pk_put_str<W, B>(row, pos, O + 10, 4, lane); }
+        if (O[15]) { PUT_LIT(",\"gtout\":"); pos = pk_put_str<W, B>(row, pos, O + 15, 4, lane); }
+        if (O[20]) { PUT_LIT(",\"gtin\":"); pos = pk_put_str<W, B>(row, pos, O + 20, 4, lane); }
+        if (O[25]) { PUT_LIT(",\"wloff\":"); pos = pk_put_str<W, B>(row, pos, O + 25, 4, lane); }
+        if (O[30]) { PUT_LIT(",\"wlin\":"); pos = pk_put_str<W, B>(row, pos, O + 30, 4, lane); }
     }
-    pos = put_words<W>(row, pos, cfg->post, cfg->post_len, lane);                 // ,"app":{"name":"..","ver":".."}}\n
+    pos = pk_put_words<W, B>(row, pos, cfg->post, cfg->post_len, lane);                 // ,"app":{"name":"..","ver":".."}}\n
     return pos;
 }
 

@@ -10,78 +10,43 @@
 // The passes are json.hip's, on the stream of the label pass they hang on: text_keys_kernel + flight.hip's sort, text_measure_kernel
 // (one WAVE per record: its length), text_sum_kernel / text_offsets_kernel (the exclusive scan in sorted order = the offset table),
 // text_render_kernel (one wave per record: the record assembled in a per-wave LDS row, flushed seam-safe).  Scan, flush, record
-// load, sort key, the level's float, the kernels' bodies and the launch sequence are shared with json.hip (sink_pack.h); this unit
-// supplies text_record and keeps its kernels as wrappers.  Measure and render run the SAME function (text_record<false / true>).
+// load, sort key, the level's float, the kernels' bodies and the launch sequence are shared with json.hip (sink_pack.h), the row
+// writers (bounded store, literal, fill, number token) with json.hip and flight_text.hip (sink_put.h); this unit supplies
+// text_record, keeps its kernels as wrappers and what only these formats use (tx_*).  Measure and render run the SAME function
+// (text_record<false / true>).
 //
 // "%Ns" is a ballot and a find-first (the C string's end) and max(0, N - len) spaces in front; the text is four rounds of 64 lanes,
 // byte i at place i; lane j computes character j of a number or of the date (json_num.h, text_num.h).  No lane walks anything, no
 // scratch (fields are read out of LDS, digits are computed), no per-byte global traffic (a record comes in as 80 + 10 dword
 // loads, the channel's "F:" token as two quadwords, the station as dwords; a record leaves as 16-byte stores and < 30 byte stores).
-#include "sink_pack.h"
+#include "sink_put.h"
 #include "text_num.h"
 
 static_assert(ACG_TX_REC_MAX == ACG_TEXT_REC_MAX && ACG_TX_REC_MAX % 64 == 0, "record bound");
 
-// characters [from, from + 16) of a literal
-constexpr PkLit tx_lit_part(const char* s, unsigned int from)
-{
-    unsigned int n = 0;
-    while (s[n]) ++n;
-    char part[17] = {};
-    for (unsigned int i = 0; i < 16 && from + i < n; ++i) part[i] = s[from + i];
-    return pk_lit(part);
-}
-
-template <bool W>
-__device__ __forceinline__ void tx_st(unsigned char* row, unsigned int p, unsigned char v)
-{
-    if (W && p < (unsigned int)ACG_TX_REC_MAX) row[p] = v;        // (the bound holds by construction; this keeps a bug inside the row)
-}
-
-template <bool W>
-__device__ __forceinline__ unsigned int tx_lit(unsigned char* row, unsigned int pos, const PkLit l, int lane)
-{
-    if (W && (unsigned int)lane < l.n) tx_st<W>(row, pos + lane, (unsigned char)((lane < 8 ? l.lo : l.hi) >> (8 * (lane & 7))));
-    return pos + l.n;
-}
-// a literal of at most 32 characters
-#define TX_LIT(s) do { static_assert(sizeof(s) - 1 <= 32, "literal"); constexpr PkLit a_ = tx_lit_part(s, 0); pos = tx_lit<W>(row, pos, a_, lane); \
-                       if (sizeof(s) - 1 > 16) { constexpr PkLit b_ = tx_lit_part(s, 16); pos = tx_lit<W>(row, pos, b_, lane); } } while (0)
+constexpr unsigned int TX_B = ACG_TX_REC_MAX;                     // the row's bound (sink_put.h)
+#define TX_LIT(s) PK_PUT_LIT(TX_B, s)
 
 // one and two characters
 template <bool W>
 __device__ __forceinline__ unsigned int tx_ch(unsigned char* row, unsigned int pos, unsigned int c, int lane)
 {
-    if (W && lane == 0) tx_st<W>(row, pos, (unsigned char)c);
+    if (W && lane == 0) pk_st<W, TX_B>(row, pos, (unsigned char)c);
     return pos + 1;
 }
 
 template <bool W>
 __device__ __forceinline__ unsigned int tx_ch2(unsigned char* row, unsigned int pos, unsigned int c0, unsigned int c1, int lane)
 {
-    if (W && lane < 2) tx_st<W>(row, pos + lane, (unsigned char)(lane ? c1 : c0));
+    if (W && lane < 2) pk_st<W, TX_B>(row, pos + lane, (unsigned char)(lane ? c1 : c0));
     return pos + 2;
-}
-
-template <bool W>
-__device__ __forceinline__ unsigned int tx_fill(unsigned char* row, unsigned int pos, unsigned char c, unsigned int n, int lane)
-{
-    if (W && (unsigned int)lane < n) tx_st<W>(row, pos + lane, c);
-    return pos + n;
-}
-
-template <bool W>
-__device__ __forceinline__ unsigned int tx_tok(unsigned char* row, unsigned int pos, const JnTok& t, int lane)
-{
-    if (W && lane < t.len) tx_st<W>(row, pos + lane, jn_char(t, lane));
-    return pos + (unsigned int)t.len;
 }
 
 // the first n characters of printdate()'s text
 template <bool W>
 __device__ __forceinline__ unsigned int tx_date(unsigned char* row, unsigned int pos, const TnDate& d, int n, int lane)
 {
-    if (W && lane < n) tx_st<W>(row, pos + lane, tn_date_char(d, lane));
+    if (W && lane < n) pk_st<W, TX_B>(row, pos + lane, tn_date_char(d, lane));
     return pos + (unsigned int)n;
 }
 
@@ -89,7 +54,7 @@ template <bool W>
 __device__ __forceinline__ unsigned int tx_level(unsigned char* row, unsigned int pos, float lvl, int lane)
 {
     const TnLevel l = tn_level(lvl);
-    if (W && lane < l.len) tx_st<W>(row, pos + lane, tn_level_char(l, lane));
+    if (W && lane < l.len) pk_st<W, TX_B>(row, pos + lane, tn_level_char(l, lane));
     return pos + (unsigned int)l.len;
 }
 
@@ -97,13 +62,13 @@ __device__ __forceinline__ unsigned int tx_level(unsigned char* row, unsigned in
 template <bool W>
 __device__ __forceinline__ unsigned int tx_str(unsigned char* row, unsigned int pos, const unsigned char* s, int maxlen, int width, int lane)
 {
-    const unsigned int b = lane < maxlen ? s[lane] : 0u;
+    const unsigned int b = lane < maxlen ? s[lane] : 0u;          // (written out: through pk_strlen text_render_kernel moves, 6796 -> 6717)
     const unsigned long long nul = __ballot(b == 0);              // (never 0: maxlen < 64)
     const int n = __ffsll((unsigned long long)nul) - 1;
     const int pad = width > n ? width - n : 0;
     if (W) {
-        if (lane < pad) tx_st<W>(row, pos + lane, ' ');
-        if (lane < n) tx_st<W>(row, pos + pad + lane, (unsigned char)b);
+        if (lane < pad) pk_st<W, TX_B>(row, pos + lane, ' ');
+        if (lane < n) pk_st<W, TX_B>(row, pos + pad + lane, (unsigned char)b);
     }
     return pos + (unsigned int)(pad + n);
 }
@@ -118,7 +83,7 @@ __device__ __forceinline__ unsigned int tx_text(unsigned char* row, unsigned int
         const unsigned long long nul = __ballot(b == 0);
         const int n = nul ? __ffsll((unsigned long long)nul) - 1 : 64;
         if (subst && (b == '\n' || b == '\r')) b = ' ';
-        if (W && lane < n) tx_st<W>(row, pos + lane, (unsigned char)b);
+        if (W && lane < n) pk_st<W, TX_B>(row, pos + lane, (unsigned char)b);
         pos += (unsigned int)n;
         if (n < 64) break;                                         // (wave-uniform)
     }
@@ -126,6 +91,7 @@ __device__ __forceinline__ unsigned int tx_text(unsigned char* row, unsigned int
 }
 
 // n <= 32 bytes the host prepared (SV's station), 4-byte aligned: a dword load per lane
+// (one guarded load, not pk_put_words' 256-byte loop: with the loop text_render_kernel moves, 6796 -> 6825 instructions)
 template <bool W>
 __device__ __forceinline__ unsigned int tx_words(unsigned char* row, unsigned int pos, const unsigned char* src, unsigned int n, int lane)
 {
@@ -133,7 +99,7 @@ __device__ __forceinline__ unsigned int tx_words(unsigned char* row, unsigned in
         const unsigned int w = *(const unsigned int*)(src + 4u * lane);
 #pragma unroll
         for (unsigned int k = 0; k < 4; ++k)
-            if (4u * lane + k < n) tx_st<W>(row, pos + 4u * lane + k, (unsigned char)(w >> (8 * k)));
+            if (4u * lane + k < n) pk_st<W, TX_B>(row, pos + 4u * lane + k, (unsigned char)(w >> (8 * k)));
     }
     return pos + n;
 }
@@ -168,11 +134,11 @@ __device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsi
 
     if (format == ACG_TEXT_ONELINE) {                             // output.c:338-344
         pos = tx_ch<W>(row, pos, '#', lane);
-        pos = tx_tok<W>(row, pos, jn_int((long long)chn + 1), lane);
+        pos = pk_put_tok<W, TX_B>(row, pos, jn_int((long long)chn + 1), lane);
         TX_LIT(" (L:");
         pos = tx_level<W>(row, pos, lvl, lane);
         TX_LIT(" E:");
-        pos = tx_tok<W>(row, pos, jn_int(r->err), lane);
+        pos = pk_put_tok<W, TX_B>(row, pos, jn_int(r->err), lane);
         TX_LIT(") ");
         if (flags & ACG_TEXT_F_DATE) pos = tx_date<W>(row, pos, date, TN_DATE_LEN, lane);
         pos = tx_ch<W>(row, pos, ' ', lane);
@@ -191,14 +157,14 @@ __device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsi
     }
     if (format == ACG_TEXT_STD) {                                 // output.c:166-215
         TX_LIT("\n[#");
-        pos = tx_tok<W>(row, pos, jn_int((long long)chn + 1), lane);
+        pos = pk_put_tok<W, TX_B>(row, pos, jn_int((long long)chn + 1), lane);
         TX_LIT(" (");
         if (flags & ACG_TEXT_F_FREQ) {
             if ((unsigned int)chn < (unsigned int)cfg->nch) {
                 const unsigned long long* ft = (const unsigned long long*)(p.freq + (size_t)chn * ACG_TX_FREQ_SLOT);
                 const unsigned long long lo = ft[0], hi = ft[1];
                 const unsigned int fn = (unsigned int)(hi >> 56) & 15u;
-                if (W && (unsigned int)lane < fn) tx_st<W>(row, pos + lane, (unsigned char)((lane < 8 ? lo : hi) >> (8 * (lane & 7))));
+                if (W && (unsigned int)lane < fn) pk_st<W, TX_B>(row, pos + lane, (unsigned char)((lane < 8 ? lo : hi) >> (8 * (lane & 7))));
                 pos += fn;
             } else {                                              // (no caller gets here: the entry points keep chn < nch.  It only
                 TX_LIT("F:0.000 ");                               //  keeps the token table's load in bounds and the record well formed)
@@ -207,11 +173,11 @@ __device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsi
         TX_LIT("L:");
         pos = tx_level<W>(row, pos, lvl, lane);
         TX_LIT(" E:");
-        pos = tx_tok<W>(row, pos, jn_int(r->err), lane);
+        pos = pk_put_tok<W, TX_B>(row, pos, jn_int(r->err), lane);
         TX_LIT(") ");
         if (flags & ACG_TEXT_F_DATE) pos = tx_date<W>(row, pos, date, TN_DATE_LEN, lane);
         pos = tx_ch<W>(row, pos, ' ', lane);
-        pos = tx_fill<W>(row, pos, '-', 32, lane);
+        pos = pk_fill<W, TX_B>(row, pos, '-', 32, lane);
         TX_LIT("\nMode : ");
         pos = tx_ch<W>(row, pos, mode, lane);
         TX_LIT(" Label : ");
@@ -244,7 +210,7 @@ __device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsi
         if (r->be == 0x17) TX_LIT("ETB\n");
         const unsigned char* O = R + sizeof(AcgMsgRec);          // oooi_t: da sa eta gout gin woff won, then `decoded`
         if (O[35]) {
-            pos = tx_fill<W>(row, pos, '#', 26, lane);
+            pos = pk_fill<W, TX_B>(row, pos, '#', 26, lane);
             pos = tx_ch<W>(row, pos, '\n', lane);
             TX_OOOI(0, "Destination Airport : ");
             TX_OOOI(5, "Departure Airport : ");
@@ -260,13 +226,13 @@ __device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsi
     if (format == ACG_TEXT_SV) {
         pos = tx_words<W>(row, pos, cfg->station, cfg->station_len, lane);
         pos = tx_ch<W>(row, pos, ' ', lane);
-        pos = tx_tok<W>(row, pos, jn_int((long long)chn + 1), lane);
+        pos = pk_put_tok<W, TX_B>(row, pos, jn_int((long long)chn + 1), lane);
         pos = tx_ch<W>(row, pos, ' ', lane);
         pos = tx_date<W>(row, pos, date, TN_DATE_SV_LEN, lane);
         pos = tx_ch<W>(row, pos, ' ', lane);
-        pos = tx_tok<W>(row, pos, jn_int(r->err), lane);
+        pos = pk_put_tok<W, TX_B>(row, pos, jn_int(r->err), lane);
         pos = tx_ch<W>(row, pos, ' ', lane);
-        pos = tx_tok<W>(row, pos, tn_int0(tn_trunc_int(lvl), 3), lane);
+        pos = pk_put_tok<W, TX_B>(row, pos, tn_int0(tn_trunc_int(lvl), 3), lane);
         pos = tx_ch<W>(row, pos, ' ', lane);
     } else {
         TX_LIT("AC");

@@ -5,7 +5,8 @@ full (the live count is printed; a table stops taking new aircraft a little befo
 
     python profiles/probe/flight_text.py [rounds]
 
-Prints one line per table size (1024 and 16384 slots): live entries, frame bytes, median / min / max in ms of both calls."""
+Prints per table size (1024 and 16384 slots): live entries, frame bytes, median / min / max in ms of both calls; then the same
+for the route pass (acg_drain_routes_json) over the routes that traffic queued."""
 import ctypes as C
 import os
 import sys
@@ -61,10 +62,21 @@ def measure(x, chunk, slots, rounds):
         if r >= 5:
             t_snap.append((t1 - t0) * 1e3)
             t_text.append((t2 - t1) * 1e3)
-    dec.close()
     f = lambda t: "%.3f / %.3f / %.3f" % (float(np.median(t)), min(t), max(t))
     print("slots %d: messages %d, live entries %d, frame %d bytes (snapshot %d bytes); ms median / min / max over %d rounds: "
           "acg_flight_snapshot %s, acg_flight_monitor_text %s" % (slots, got, n.value, nb.value, 120 * n.value, rounds, f(t_snap), f(t_text)), flush=True)
+    # the route pass on the routes this traffic queued: with no room for the lines the call runs all of it (keys, sort, measure,
+    # scan, render, the counters' copy), answers ACG_EAGAIN and consumes nothing, so it can be repeated; what it leaves out is
+    # the copy of the lines
+    t_route = []
+    for r in range(5 + rounds):
+        t0 = time.perf_counter()
+        rc = dec.L.acg_drain_routes_json(dec.ctx, None, 0, C.byref(nb), C.byref(nrows))
+        t_route.append((time.perf_counter() - t0) * 1e3)
+        assert rc == (K.EAGAIN if nrows.value else K.OK), rc
+    dec.close()
+    print("slots %d: route pass over %d queued routes, %d bytes of lines; ms median / min / max over %d rounds: %s"
+          % (slots, nrows.value, nb.value, rounds, f(t_route[5:])), flush=True)
 
 
 if __name__ == "__main__":
