@@ -2,38 +2,22 @@
 // acg_host_sincos_table): the same operations in the same order (fma = one rounding).  Test infrastructure: built and run by
 // tests/test_host_logic.py; prints the worst error in ulp against long-double libm and how many of the float-rounded mixer
 // products (msk.c:90: what the demodulator keeps) differ from glibc's cexp.  usage: sincos_model [samples]
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <stdint.h>
 #include <complex.h>
-static double tab[128][2];
-void acg_host_sincos_table(double* t);       // the product's own table builder (acarsdec_amd/csrc/host_setup.c, linked in)
-static void build(void) { acg_host_sincos_table(&tab[0][0]); }
-static inline void sc_tab(double x, double* sn, double* cs) {
-    const double kd = rint(x * (6.36619772367581382433e-01 * 32.0));
-    const int q = (int)kd;
-    double r = fma(-kd, 1.57079632673412561417e+00 / 32.0, x);
-    r = fma(-kd, 6.07710050650619224932e-11 / 32.0, r);
-    const double cj = tab[q & 127][0], sj = tab[q & 127][1];
-    const double z = r * r;
-    // sin r - r = r z (S1 + z (S2 + z S3)),  cos r - 1 = z (C0 + z (C1 + z C2))
-    double ps = fma(z, -1.98412698412698412698e-04, 8.33333333333333333333e-03);
-    ps = fma(z, ps, -1.66666666666666666667e-01);
-    const double sm = (r * z) * ps;            // sin r - r
-    double pc = fma(z, -1.38888888888888888889e-03, 4.16666666666666666667e-02);
-    pc = fma(z, pc, -0.5);
-    const double cm1 = z * pc;                 // cos r - 1
-    const double sr = r + sm;
-    // cos p = cj + (cj (cos r - 1) - sj sin r);  sin p = sj + (sj (cos r - 1) + cj sin r)
-    const double u = fma(cj, cm1, -(sj * sr));
-    const double w = fma(sj, cm1, cj * sr);
-    *cs = cj + u;
-    *sn = sj + w;
-}
+#include "sincos_model.h"                    // tab[128][2], build() = acg_host_sincos_table(&tab[0][0]), sc_tab()
+// the constants of the device function as acarsdec_amd/csrc/msk_common.h spells them: test_host_logic.py compares this text with
+// the device's, main() compares the values with the header's
+static const double dev_consts[8][2] = {
+    {6.36619772367581382433e-01 * 32.0, SC_128_OVER_2PI}, {1.57079632673412561417e+00 / 32.0, SC_2PI_OVER_128_HI},
+    {6.07710050650619224932e-11 / 32.0, SC_2PI_OVER_128_LO}, {-1.98412698412698412698e-04, SC_S3},
+    {8.33333333333333333333e-03, SC_S2}, {-1.66666666666666666667e-01, SC_S1},
+    {-1.38888888888888888889e-03, SC_C2}, {4.16666666666666666667e-02, SC_C1}};
 static double ulp_of(double v) { double a = fabs(v); if (a < 1e-300) return 4.9e-324; int e; frexp(a, &e); return ldexp(1.0, e - 53); }
 int main(int argc, char** argv) {
     build();
+    for (int k = 0; k < 8; k++) if (dev_consts[k][0] != dev_consts[k][1]) { fprintf(stderr, "sincos_model.h: constant %d is not the device's\n", k); return 1; }
     uint64_t st = 88172645463325252ull;
     double maxs = 0, maxc = 0; long nid_s = 0, nid_c = 0, n = argc > 1 ? atol(argv[1]) : 20000000, prodmis = 0, prodn = 0;
     for (long i = 0; i < n; i++) {

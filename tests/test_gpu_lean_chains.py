@@ -23,59 +23,17 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 NCH = 17
-TWO_PI = 2.0 * 3.14159265358979323846
-K_VCO = 1800.0 / 12500 * 2.0 * 3.14159265358979323846
-K_3PI2 = 3 * 3.14159265358979323846 / 2.0
 # "ends": planted once, in front of the first call; "plants": planted in front of every call, every plant on every planted channel
 SEQS = {"ends": [32, 64, 96, 128, 1024, 8192], "plants": [32, 64, 96, 128] * 4}
 NSAMP = max(sum(v) for v in SEQS.values())
 
 
-def period(phi, clk, df):
-    """one six-sample pass from (phi, clk, df) as the kernels compute it: [(running sum before its wrap, clock)] per sample taken"""
-    s = np.float64(K_VCO) + np.float64(df)
-    thr = np.float64(K_3PI2) - s / 2
-    p, c, out = np.float64(phi), np.float32(clk), []
-    for _ in range(6):
-        p = p + s
-        c = np.float32(np.float64(c) + s)
-        out.append((p, c))
-        if p >= TWO_PI:
-            p = p - np.float64(TWO_PI)                                  # fma(-1, 2 pi, p): one rounding, as the subtraction
-        if np.float64(c) >= thr:
-            break
-    return out
-
-
 @pytest.fixture(scope="module")
 def plants():
-    """[(phi, df, clk)]: for j = 1..6 the wrap exactly at step j, then the same one ulp lower, then df = -1 and df = +3"""
-    exact, below = [], []
-    for j in range(1, 7):
-        clk = -0.5 if j == 6 else 0.0
-        centre = np.float64(TWO_PI) - j * np.float64(K_VCO)
-        found = None
-        cands = [centre]
-        up = down = centre
-        for _ in range(64):
-            up, down = np.nextafter(up, np.inf), np.nextafter(down, -np.inf)
-            cands += [up, down]
-        for phi in cands:
-            steps = period(phi, clk, 0.0)
-            if len(steps) >= j and steps[j - 1][0] == TWO_PI and all(q[0] < TWO_PI for q in steps[:j - 1]):
-                found = phi
-                break
-        assert found is not None, "no phase within 64 ulps whose sum number %d is 2 pi" % j
-        lower = np.nextafter(found, -np.inf)
-        steps = period(lower, clk, 0.0)
-        assert len(steps) >= j and all(q[0] < TWO_PI for q in steps[:j]), j
-        exact.append((float(found), 0.0, clk))
-        below.append((float(lower), 0.0, clk))
-    # five samples from clk = 0, six from clk = -0.5 (the sixth step is taken at all)
-    assert len(period(exact[0][0], 0.0, 0.0)) == 5 and len(period(exact[5][0], -0.5, 0.0)) == 6
-    # df = -1: the step is negative, never the six-sample pass; df = +3: the clock fires on the first sample
-    assert K_VCO - 1.0 < 0 and len(period(1.0, 0.0, 3.0)) == 1
-    return exact + below + [(1.0, -1.0, 0.0), (1.0, 3.0, 0.0)]
+    """[(phi, df, clk)]: for j = 1..6 the wrap exactly at step j, then the same one ulp lower, then df = -1 and df = +3 (derived and
+    checked in tests/msk_exact_inputs.py, which holds them to the oracle as well)"""
+    import msk_exact_inputs as X
+    return X.plants()
 
 
 @pytest.fixture(scope="module")
