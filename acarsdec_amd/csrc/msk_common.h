@@ -378,6 +378,34 @@ __device__ __forceinline__ void sincos_tab_rotate(double r, double cj, double sj
     *sn = sj + w;
 }
 
+// z * c + d as ONE three-address v_fma_f64, c a scalar operand and d a register that is left alone (left to the compiler the step
+// is v_mov_b64 + v_fmac_f64: d copied into the accumulator)
+__device__ __forceinline__ double fma_zsv(double z, double c, double d)
+{
+    double r;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(z), "s"(c), "v"(d));
+    return r;
+}
+
+// sincos_tab_rotate with the three Horner steps whose constant addend the compiler copies into the accumulator as three-address
+// fmas (fma_zsv twice, fma_zc once): the same operations on the same operands, three register copies fewer (msk_lean.hip; msk.hip
+// and msk2.hip keep the text they have)
+__device__ __forceinline__ void sincos_tab_rotate3(double r, double cj, double sj, double* sn, double* cs)
+{
+    const double z = r * r;
+    double ps = fma_zsv(z, -1.98412698412698412698e-04, 8.33333333333333333333e-03);
+    ps = fma_zc(ps, z, -1.66666666666666666667e-01);
+    const double sm = (r * z) * ps;                                              // sin r - r
+    double pc = fma_zsv(z, -1.38888888888888888889e-03, 4.16666666666666666667e-02);
+    pc = __builtin_fma(z, pc, -0.5);
+    const double cm1 = z * pc;                                                   // cos r - 1
+    const double sr = r + sm;
+    const double u = __builtin_fma(cj, cm1, -(sj * sr));
+    const double w = __builtin_fma(sj, cm1, cj * sr);
+    *cs = cj + u;
+    *sn = sj + w;
+}
+
 // n0 / d and n1 / d, both correctly rounded, for d in [1e-8, ~1e2] and |n| < ~1e2 or n == +0 (the matched filter's
 // sum starts from +0 and so is never -0, the one numerator whose quotient would come out as +0 here): see the call site.
 // acg_selftest_div2 compares it with the compiler's IEEE division on the device.

@@ -63,6 +63,19 @@
 // refill's loads (the refill's `s_waitcnt vmcnt(0)` also waits for younger stores) -- nil.  ACG_LEAN_AB_REC0 is the order before;
 // tests/test_lean_record_store.py pins the periods free of stores and compiles that switch to show the condition can fail.
 //
+// Slots that carry no arithmetic (round 10).  The period is paced by the number of slots it issues, and a wait, a no-operation or a
+// register copy takes one: two `s_nop 0` MORE in front() cost 0.24 % of the kernel.  Eight came out of a period's 262: the
+// compiler's three counted waits in front of the five old taps (lgkmcnt 9, 8, 7: for reads a whole sin/cos series old) are ONE,
+// pinned behind the newest-tap reads (left free, the scheduler moves it behind the taps and the three come back); the hold of step 5
+// leaves the clock out, so the fifth clock step fills the two slots that were `s_nop 0` in front of the phase picks; and the
+// mixer's Horner steps that add a constant held in registers are three-address fmas (sincos_tab_rotate3, msk_common.h: left to the
+// compiler, v_mov_b64 + v_fmac_f64 each).  Same operations on the same operands.  Measured and not taken: one wait in front of the
+// six newest taps (they are not back yet: 0.7 % slower), the odd old taps' h[] half picked by op_sel in an asm (two copies fewer,
+// 0.25 % slower), x - 3 pi / 2 with the constant negated in the operand and the segment's bit count set where a period leaves it
+// (both longer, the second by 50 registers: not run), and a prologue that issues all its loads in one block, no branch around
+// any of them (one round trip to memory instead of four in front of the loop: nil on the trace).  ACG_LEAN_AB_WAIT0 / _NOP0 / _HORN0 are the orders before;
+// tests/test_lean_slots.py pins the counts and compiles those switches to show that its bounds can fail.  DESIGN 4.
+//
 // What this kernel shares with msk.hip -- the state's way in and out, the LDS layout, the phase detector, the loop filter, the inline
 // framing step of the closing period -- is in msk_common.h; the dm window's two lambdas are msk.hip's, spelled out here as there.
 #include <hip/hip_runtime.h>
@@ -170,7 +183,17 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
 #else
 #define LEAN_HOLD_STEP(pv, cv, mv) asm volatile("" : "+v"(pv), "+v"(cv), "+v"(mv))
 #endif
+// the hold of step 5 leaves the clock out (round 10): the sixth step's hold keeps both clock steps in the block anyway, and with the
+// fifth clock step free to move, its operations fill the two slots that the phase chain's tail in front of the hold cost as
+// `s_nop 0` (a compare's lane mask is read two instructions later at the earliest, a wrap fma's sum one later)
+#if defined(ACG_LEAN_AB_NOP0) || defined(ACG_LEAN_AB_PICK0)
+#define LEAN_HOLD_STEP5(pv, cv, mv) LEAN_HOLD_STEP(pv, cv, mv)
+#else
+#define LEAN_HOLD_STEP5(pv, cv, mv) asm volatile("" : "+v"(pv), "+v"(mv))
+#endif
 #define MSK_TAP(j, x) (f2v{(j & 1) ? hv2[j / 2].y : hv2[j / 2].x, (j & 1) ? hv2[j / 2].y : hv2[j / 2].x} * x)
+// `s_waitcnt lgkmcnt(n)` alone (gfx9 encoding: the other counters at their maximum)
+#define LEAN_WAIT_LGKM(n) __builtin_amdgcn_s_waitcnt(0xC07F | ((n) << 8))
 
     // what a period's front part (VCO / clock steps, mixer, the five oldest filter taps) hands to its bit decision
     int cnt;
@@ -220,7 +243,7 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
         double p5 = p4 + s;                                                // msk.c:82-83
         p5 = wrap_2pi(p5);
         float c5 = (float)((double)c4 + s);                          // msk.c:95
-        LEAN_HOLD_STEP(p5, c5, myp[3 / LPC]);
+        LEAN_HOLD_STEP5(p5, c5, myp[3 / LPC]);
         const bool fired5 = (double)c5 >= thr;
 #ifndef ACG_LEAN_AB_PICK0
         if ((4 % LPC) == g) myp[4 / LPC] = p5;
@@ -321,7 +344,11 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
         for (int j = 0; j < SPL; ++j) {
             const int u = g + j * LPC;
             double sn, cs;
+#ifdef ACG_LEAN_AB_HORN0
             sincos_tab_rotate(mr[j], mcj[j], msj[j], &sn, &cs);
+#else
+            sincos_tab_rotate3(mr[j], mcj[j], msj[j], &sn, &cs);
+#endif
             const double in = (double)in_cur[j];
             unsigned int k = idx + (unsigned int)u;
             if (k >= FLEN) k -= FLEN;
@@ -342,6 +369,13 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
             for (int j = 5; j < FLEN; ++j) xs[j - 5] = rp[j * CPW];
         }
         __builtin_amdgcn_sched_barrier(0);
+#ifndef ACG_LEAN_AB_WAIT0
+        // ONE counted wait for all the old taps use (h[0..5]; the ring entries are older).  Still in flight behind it, in the order
+        // of issue: the h[] reads of the newest taps (two pairs and the last), the ring write(s), the three newest-tap reads
+        // (pinned: left free, the scheduler moves the wait behind the taps it is for and the compiler's own three come back)
+        LEAN_WAIT_LGKM(6 + SPL);
+        __builtin_amdgcn_sched_barrier(0);
+#endif
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
             const f2v x = {xo[j].x, xo[j].y};

@@ -6,14 +6,16 @@ verdict is closed (profiles/LEDGER.md) are no longer in the tree, and 
 only; nothing here is loaded by the product.
 The switches msk_lean.hip keeps may be given by their short names: a flag without a leading dash is taken as -DACG_LEAN_AB_<FLAG>
 (VCO0, SPEC0, PICK0, REC0), R08PARENT stands for the first three, the order before round 8, and REC0 is the order before round 9
-(a bit record stored by all 64 lanes in every period)."""
+(a bit record stored by all 64 lanes in every period).  Round 10's steps, each the order before it: WAIT0 (the compiler's three waits
+in front of the old taps), NOP0 (the clock in the hold of step 5), HORN0 (the Horner steps of the mixer's series left to the compiler);
+R10PARENT stands for all three."""
 import os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 sys.path.insert(0, ROOT)
 from acarsdec_amd import _build as B
 
 MSK_FLAGS = B.MSK_FLAGS                 # the product's recipe (acarsdec_amd/_build.py)
-GROUPS = {"R08PARENT": ["VCO0", "SPEC0", "PICK0"]}
+GROUPS = {"R08PARENT": ["VCO0", "SPEC0", "PICK0"], "R10PARENT": ["WAIT0", "NOP0", "HORN0"]}
 SOURCES = ("msk.hip", "msk_lean.hip", "msk_common.h")
 B.build_lib()
 out = os.path.join(B.LIBDIR, "ab")
