@@ -230,6 +230,12 @@ __device__ __forceinline__ void decode_acars(Lane& L, const MskArgs& a, int ch, 
 // (acars.c:252-265, every bit of an idle channel) and a plain text byte -- good parity, no terminator, room left
 // (acars.c:303-341, every 8th bit of a channel inside a block).  Everything else (sync, SOH, parity errors, ETX/ETB/DLE, CRC
 // bytes, resets: a few per block) goes through the full state machine.
+// CLOSES (msk_lean.hip, whose closing period is the one place it calls this): the closes behind a sync by selects as well -- on an
+// idle channel a false sync comes about every 128 bits, and the byte behind it is the close that ends a segment there four times
+// out of five, one lane taking its whole wave through the state machine's walk.  msk.hip and msk2.hip, which frame after EVERY bit,
+// leave it off: the dozen selects per bit made msk.hip's kernel 5.4 % slower (profiles/LEDGER.md round 11).  ACG_LEAN_AB_CLOSE0
+// is the text before, everywhere.
+template <bool CLOSES = false>
 __device__ __forceinline__ void frame_bit(Lane& L, float sv, const MskArgs& a, int ch, unsigned char* txt,
                                           long long sample_index, bool leader, unsigned int* soh_slot)
 {
@@ -248,8 +254,35 @@ __device__ __forceinline__ void frame_bit(Lane& L, float sv, const MskArgs& a, i
         const bool plain = ev & (L.astate == TXT) & ((__popc(r) & 1) != 0) & !term & (L.blen < 240);
         txt[plain ? L.blen : 255] = (unsigned char)r;          // byte 255 of the 256-byte text buffer is scratch (blen <= 241)
         L.blen += plain ? 1 : 0;
-        L.nbits = hunt ? 1 : (plain ? 8 : L.nbits);
-        if (ev & !hunt & !plain) decode_acars(L, a, ch, txt, sample_index, leader, soh_slot);
+#ifdef ACG_LEAN_AB_CLOSE0
+        constexpr bool closes = false;
+#else
+        constexpr bool closes = CLOSES;
+#endif
+        if constexpr (!closes) {
+            L.nbits = hunt ? 1 : (plain ? 8 : L.nbits);
+            if (ev & !hunt & !plain) decode_acars(L, a, ch, txt, sample_index, leader, soh_slot);
+        } else {
+            // The closes that end a segment of msk_lean.hip on idle channels, by selects as well: the byte behind a (mostly false) sync
+            // -- SYN2 with SYN, ~SYN or neither (acars.c:267-279) --, a SOH1 that is no SOH (acars.c:299-300) and the byte behind a
+            // block (acars.c:370-373).  Each sets the fields decode_acars() / reset_acars() set in that case.  What is left for the
+            // state machine: a sync from WSYN, a SOH (time stamp), text bytes that are not plain, the CRC bytes.
+            const unsigned int as = (unsigned int)L.astate;
+            const bool s2 = ev & (as == SYN2);
+            const bool s2miss = s2 & !syn;
+            const bool s1miss = ev & (as == SOH1) & (r != SOH);
+            const bool endc = ev & (as >= END);
+            const bool rst = s2miss | s1miss | endc;               // reset_acars()
+            const bool closed = s2 | s1miss | endc;
+            if (ev & !hunt & !plain & !closed) {
+                __builtin_assume(L.astate != SYN2 && (unsigned int)L.astate < END && (L.astate != SOH1 || r == SOH));
+                decode_acars(L, a, ch, txt, sample_index, leader, soh_slot);
+            }
+            L.S ^= (s2 & (r == (0xffu & ~SYN))) ? 2u : 0u;
+            L.astate = rst ? WSYN : ((s2 & (r == SYN)) ? SOH1 : L.astate);
+            L.df = rst ? 0 : L.df;
+            L.nbits = (hunt | s2miss | s1miss) ? 1 : ((plain | closed) ? 8 : L.nbits);
+        }
     }
     L.nbit_total += 1;
     L.S += 1u;

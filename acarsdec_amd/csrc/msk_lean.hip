@@ -76,6 +76,16 @@
 // any of them (one round trip to memory instead of four in front of the loop: nil on the trace).  ACG_LEAN_AB_WAIT0 / _NOP0 / _HORN0 are the orders before;
 // tests/test_lean_slots.py pins the counts and compiles those switches to show that its bounds can fail.  DESIGN 4.
 //
+// The closes that end a segment (round 11).  On the bench's traffic a wave gets 6.9 periods per segment, not 8: one period in 22
+// closes a segment msk.hip's way, and in four cases out of five the channel that forces it stands in SYN2 behind a false sync
+// (profiles/probe/lean_segment_stats.py).  frame_bit<true>() (msk_common.h) applies the closes in SYN2, SOH1-without-SOH and END by
+// selects (here only: msk.hip frames after every bit, where the selects cost more than the walk saves), so that the closing period enters decode_acars() only for a sync, a SOH, a text byte that is not plain and the CRC bytes:
+// 68 instructions and 4 of 26 branches fewer laid out in that period.  ACG_LEAN_AB_CLOSE0 is the text before;
+// tests/test_lean_exits.py pins the figures and compiles the switch to show they can fail.  The periods of the segment are untouched.
+// Built and not taken: lvk[] / nk[] without their zero fill, which is what the per-exit copy blocks behind the unrolled loop mostly
+// write (both: one or two taken branches per exit, but a register copy MORE in each of periods 3-8, over test_lean_slots.py's
+// bound; lvk[] alone: the periods hold, the copy blocks halve, worth ~0.1 % by the price of a slot: not run).  profiles/LEDGER.md, round 11.
+//
 // What this kernel shares with msk.hip -- the state's way in and out, the LDS layout, the phase detector, the loop filter, the inline
 // framing step of the closing period -- is in msk_common.h; the dm window's two lambdas are msk.hip's, spelled out here as there.
 #include <hip/hip_runtime.h>
@@ -576,7 +586,7 @@ __global__ __launch_bounds__(64 * WPG) void msk_lean_kernel(const MskArgs a)
                     bits[nb < a.bit_cap ? nb : a.bit_cap - 1] = make_float2(sv, lvl);
                     nb += 1;
                 }
-                frame_bit(L, sv, a, ch, txt, samp0 + n - 1, leader, &st->soh32);
+                frame_bit<true>(L, sv, a, ch, txt, samp0 + n - 1, leader, &st->soh32);
                 L.df = loop_filter(L.df, pd.dphi);
             }
         }

@@ -8,7 +8,8 @@ The switches msk_lean.hip keeps may be given by their short names: a flag withou
 (VCO0, SPEC0, PICK0, REC0), R08PARENT stands for the first three, the order before round 8, and REC0 is the order before round 9
 (a bit record stored by all 64 lanes in every period).  Round 10's steps, each the order before it: WAIT0 (the compiler's three waits
 in front of the old taps), NOP0 (the clock in the hold of step 5), HORN0 (the Horner steps of the mixer's series left to the compiler);
-R10PARENT stands for all three."""
+R10PARENT stands for all three.  CLOSE0 (round 11): the lean kernel's closing period without frame_bit()'s select paths for the
+byte closes in SYN2, SOH1 and END -- every close that is neither `hunt` nor `plain` through decode_acars(), as in msk.hip."""
 import os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 sys.path.insert(0, ROOT)
