@@ -78,6 +78,17 @@ class Route(C.Structure):
                 ("sa", C.c_char * 5), ("da", C.c_char * 5), ("addr", C.c_char * 8), ("reserved", C.c_char * 7)]
 
 
+class FlightEvent(C.Structure):
+    """acg_flight_event: one message that reaches addFlight(), as it travels from a peer context to the owner of the table"""
+    _fields_ = [("end_sample", C.c_longlong), ("soh_sample", C.c_longlong), ("sec", C.c_longlong), ("usec", C.c_int), ("chn", C.c_int),
+                ("addr", C.c_char * 8), ("fid", C.c_char * 7), ("e_ok", C.c_ubyte), ("oooi", Oooi)]
+
+
+# the same record as a numpy structured dtype (Decoder.drain_flight_events hands out arrays of it); oooi: its 40 bytes
+FLIGHT_EVENT_DTYPE = [("end_sample", "<i8"), ("soh_sample", "<i8"), ("sec", "<i8"), ("usec", "<i4"), ("chn", "<i4"), ("addr", "S8"),
+                      ("fid", "S7"), ("e_ok", "u1"), ("oooi", "V40")]
+
+
 class FlightTextConfig(C.Structure):
     """acg_flight_text_config: the monitor's mask columns (the reference's nbch) and the route line's station id"""
     _fields_ = [("nbch", C.c_int), ("station_id", C.c_char * 33)]
@@ -110,7 +121,7 @@ class LaunchShape(C.Structure):
                 ("runs", C.c_uint), ("wave_slots", C.c_uint), ("workgroups", C.c_uint), ("waves", C.c_uint)]
 
 
-assert C.sizeof(Flight) == 120 and C.sizeof(Route) == 56
+assert C.sizeof(Flight) == 120 and C.sizeof(Route) == 56 and C.sizeof(FlightEvent) == 88
 
 BIT_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_float, C.c_float)
 
@@ -157,6 +168,12 @@ SYMBOLS = {
     "acg_flights_enable": (C.c_int, [C.c_void_p, C.POINTER(FlightConfig)]),
     "acg_flight_snapshot": (C.c_int, [C.c_void_p, C.POINTER(Flight), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "acg_drain_routes": (C.c_int, [C.c_void_p, C.POINTER(Route), C.c_int, C.POINTER(C.c_int)]),
+    "acg_flights_set_channels": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "acg_flights_export": (C.c_int, [C.c_void_p, C.c_int]),
+    "acg_drain_flight_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "acg_flight_events_check": (C.c_int, [C.c_void_p, C.c_int]),
+    "acg_flights_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "acg_flights_commit": (C.c_int, [C.c_void_p]),
     "acg_flight_text_enable": (C.c_int, [C.c_void_p, C.POINTER(FlightTextConfig)]),
     "acg_flight_monitor_text": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                           C.POINTER(C.c_int)]),
@@ -203,6 +220,9 @@ LAB_SYMBOLS = {
     "acg_selftest_flights": (C.c_int, [C.POINTER(Msg), C.POINTER(C.c_int), C.c_int, C.POINTER(FlightConfig), C.POINTER(MsgFilter),
                                        C.POINTER(Flight), C.c_int, C.POINTER(C.c_int), C.POINTER(Route), C.c_int, C.POINTER(C.c_int),
                                        C.POINTER(C.c_int)]),
+    "acg_selftest_flights_sharded": (C.c_int, [C.POINTER(Msg), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(FlightConfig), C.POINTER(MsgFilter),
+                                               C.POINTER(Flight), C.c_int, C.POINTER(C.c_int), C.POINTER(Route), C.c_int, C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "acg_selftest_flight_text": (C.c_int, [C.POINTER(Flight), C.c_int, C.POINTER(Route), C.c_int, C.POINTER(FlightConfig),
                                            C.POINTER(FlightTextConfig), C.c_longlong, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                            C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),

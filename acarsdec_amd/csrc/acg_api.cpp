@@ -1504,6 +1504,16 @@ static int grow_label_stage(acg_ctx* ctx, unsigned int take)
     return ACG_OK;
 }
 
+// The owner of a flight table shared by several contexts, in a message entry point that consumes no blocks: the pass still runs,
+// over the imported events alone.  Looks at the import queue only when the table is on; nothing queued: nothing launched.
+static int commit_imports(acg_ctx* ctx)
+{
+    if (!ctx->flights || !acg_fl_imports_queued(ctx->flights)) return ACG_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int rc = acg_fl_commit(ctx->flights, ctx->copy_stream);
+    return rc == ACG_OK ? rc : fail(ctx, rc, "flight table: the pass over the imported events failed");
+}
+
 // The split of the `take` oldest blocks into d_msgs on the copy stream (it writes every byte of a record, text tail zeroed, so
 // nothing stale crosses the ABI); with `labels`, label.hip's pass behind it into d_kmsgs / d_oooi (the caller has grown the label
 // stage) and, the flight table on, its pass.  *d_total: the label pass's count of kept records, a device word.
@@ -1525,7 +1535,8 @@ static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int m
     unsigned int upto = 0, pending = 0, take = 0;
     bool any = false;
     int rc = ring_upto(ctx, lag, &upto, &any);
-    if (rc != ACG_OK || !any) return rc;
+    if (rc != ACG_OK) return rc;
+    if (!any) return commit_imports(ctx);
     if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
     // A call splits and copies the oldest min(pending, max_msgs) blocks only (a block yields at most one message, so they
     // all fit) and consumes exactly those: draining a long queue through a small buffer costs what it hands out, not the
@@ -1554,6 +1565,8 @@ static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int m
             HIPCHK(ctx, hipMemcpyAsync(ctx->h_msgs, ctx->d_msgs, (size_t)take * sizeof(AcgMsgRec), hipMemcpyDeviceToHost, ctx->copy_stream));
         }
         HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+    } else if (const int cr = commit_imports(ctx)) {
+        return cr;
     }
     const AcgMsgRec* rec = ctx->h_msgs;
     ctx->consumed += take;
@@ -1643,9 +1656,14 @@ struct LabStage {
     // h[0, n) to the device and the label pass over them; 0, or anything else for a HIP error
     int label(unsigned int n, const AcgLabelFilter* f, unsigned char* d_keep = nullptr, const AcgFlightPass* flights = nullptr)
     {
+        return upload(n) || launch(n, f, d_keep, flights);
+    }
+    // ... in two steps, for a caller that times the passes without the records' way to the device
+    int upload(unsigned int n) { return hipMemcpy(d_in, h.data(), (size_t)n * sizeof(AcgMsgRec), hipMemcpyHostToDevice) != hipSuccess; }
+    int launch(unsigned int n, const AcgLabelFilter* f, unsigned char* d_keep = nullptr, const AcgFlightPass* flights = nullptr)
+    {
         const AcgLabelPass pass{f, d_work, d_out, d_oooi, d_total(), d_keep, flights};
-        return hipMemcpy(d_in, h.data(), (size_t)n * sizeof(AcgMsgRec), hipMemcpyHostToDevice) != hipSuccess ||
-               acg_launch_msg_split(nullptr, 0, 0, n, d_in, nullptr, &pass) != 0;
+        return acg_launch_msg_split(nullptr, 0, 0, n, d_in, nullptr, &pass) != 0;
     }
 };
 
@@ -1775,6 +1793,68 @@ extern "C" int acg_drain_routes(acg_ctx* ctx, acg_route* out, int max, int* n)
     return rc == ACG_OK ? rc : fail(ctx, rc, rc == ACG_EAGAIN ? "more routes queued than fit: call again" : "route hand-over failed");
 }
 
+// ---- one flight table for the channels of several contexts: events leave the peers and enter the owner ---------------------
+extern "C" int acg_flight_events_check(const acg_flight_event* ev, int n)
+{
+    if (n < 0 || (n > 0 && !ev)) return ACG_EINVAL;
+    for (int i = 0; i < n; ++i) {
+        const acg_flight_event& e = ev[i];
+        if (e.usec < 0 || e.usec > 999999 || e.addr[0] == 0 || e.chn < 0 || e.chn >= (1 << 20) || e.end_sample < 0 || e.end_sample >= (1ll << 43) ||
+            (e.e_ok != 0 && e.e_ok != 1))
+            return ACG_EINVAL;
+    }
+    return ACG_OK;
+}
+
+extern "C" int acg_flights_set_channels(acg_ctx* ctx, const int* chn)
+{
+    if (!ctx) return ACG_EINVAL;
+    if (!ctx->flights) return fail(ctx, ACG_ESTATE, "flight table is off");
+    for (int c = 0; chn && c < ctx->cfg.nch; ++c)
+        if (chn[c] < 0 || chn[c] >= (1 << 20)) return fail(ctx, ACG_EINVAL, "flight table: a channel number outside 0 .. 2^20 - 1");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int rc = acg_fl_set_channels(ctx->flights, chn, ctx->cfg.nch);
+    return rc == ACG_OK ? rc : fail(ctx, rc, "flight table: channel map");
+}
+
+extern "C" int acg_flights_export(acg_ctx* ctx, int on)
+{
+    if (!ctx) return ACG_EINVAL;
+    if (!ctx->flights) return fail(ctx, ACG_ESTATE, "flight table is off");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int rc = acg_fl_export(ctx->flights, on);
+    return rc == ACG_OK ? rc : fail(ctx, rc, "flight table: export queue");
+}
+
+extern "C" int acg_drain_flight_events(acg_ctx* ctx, acg_flight_event* out, int max, int* n)
+{
+    if (!ctx || !n || max < 0 || (max > 0 && !out)) return ACG_EINVAL;
+    *n = 0;
+    if (!ctx->flights) return fail(ctx, ACG_ESTATE, "flight table is off");
+    if (!acg_fl_exporting(ctx->flights)) return fail(ctx, ACG_ESTATE, "flight table: export is off (acg_flights_export first)");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    const int rc = acg_fl_drain_events(ctx->flights, ctx->copy_stream, out, max, n);
+    return rc == ACG_OK ? rc : fail(ctx, rc, rc == ACG_EAGAIN ? "more flight events queued than fit: call again" : "flight event hand-over failed");
+}
+
+extern "C" int acg_flights_import(acg_ctx* ctx, const acg_flight_event* ev, int n)
+{
+    if (!ctx || n < 0 || (n > 0 && !ev)) return ACG_EINVAL;
+    if (acg_flight_events_check(ev, n) != ACG_OK) return fail(ctx, ACG_EINVAL, "flight event import: a field out of range (acg_flight_events_check)");
+    if (!ctx->flights) return fail(ctx, ACG_ESTATE, "flight table is off");
+    if (acg_fl_exporting(ctx->flights)) return fail(ctx, ACG_ESTATE, "flight table: this context exports its events, it cannot import");
+    const int rc = n ? acg_fl_import(ctx->flights, ev, n) : ACG_OK;
+    return rc == ACG_OK ? rc : fail(ctx, rc, "flight event import");
+}
+
+extern "C" int acg_flights_commit(acg_ctx* ctx)
+{
+    if (!ctx) return ACG_EINVAL;
+    if (!ctx->flights) return fail(ctx, ACG_ESTATE, "flight table is off");
+    if (acg_fl_exporting(ctx->flights)) return fail(ctx, ACG_ESTATE, "flight table: this context exports its events");
+    return commit_imports(ctx);
+}
+
 extern "C" int acg_selftest_flights(const acg_msg* in, const int* batch, int nbatch, const acg_flight_config* cfg, const acg_msg_filter* f,
                                     acg_flight* snaps, int snap_cap, int* snap_n, acg_route* routes, int route_cap, int* nroutes, int* dropped)
 {
@@ -1818,6 +1898,106 @@ extern "C" int acg_selftest_flights(const acg_msg* in, const int* batch, int nba
         if (rc == ACG_OK) rc = acg_fl_drain_routes(t, nullptr, routes, route_cap, nroutes);
     }
     acg_fl_destroy(t);
+    return rc;
+}
+
+// acg_selftest_flights over SEVERAL tables, as a host that shards its channels `c mod nshards` drives them: in[i].chn is the global
+// channel; shard r = chn % nshards holds it as local channel chn / nshards under the map l -> l * nshards + r; shards 1 .. export,
+// shard 0 owns the table.  A batch is a round: every peer's pass and the drain of its events, their import at the owner, the
+// owner's pass (no records of its own in the round: acg_fl_commit, as a message entry point that consumes no blocks).
+extern "C" int acg_selftest_flights_sharded(const acg_msg* in, const int* batch, int nbatch, int nshards, const acg_flight_config* cfg,
+                                            const acg_msg_filter* f, acg_flight* snaps, int snap_cap, int* snap_n, acg_route* routes, int route_cap,
+                                            int* nroutes, int* dropped, float* pass_ms)
+{
+    if (nbatch < 0 || nshards < 1 || nshards > 64 || !acg_fl_config_ok(cfg) || snap_cap < 0 || route_cap < 0 || !nroutes ||
+        (nbatch > 0 && (!batch || !snap_n || !dropped)) || (snap_cap > 0 && !snaps) || (route_cap > 0 && !routes))
+        return ACG_EINVAL;
+    AcgLabelFilter d;
+    if (label_filter_dev(f, &d) != ACG_OK) return ACG_EINVAL;
+    size_t total = 0, biggest = 0;
+    for (int b = 0; b < nbatch; ++b) {
+        if (batch[b] < 0) return ACG_EINVAL;
+        total += (size_t)batch[b];
+        biggest = std::max(biggest, (size_t)batch[b]);
+    }
+    if (total > 0 && !in) return ACG_EINVAL;
+    int nloc = 1;                                                  // local channels per shard
+    for (size_t i = 0; i < total; ++i) {
+        if (in[i].chn < 0 || in[i].chn >= (1 << 20)) return ACG_EINVAL;
+        nloc = std::max(nloc, in[i].chn / nshards + 1);
+    }
+    *nroutes = 0;
+    int ndev = 0;
+    if (!acg_fl_create || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
+    std::vector<AcgFlights*> T((size_t)nshards, nullptr);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int rc = ACG_OK;
+    if (pass_ms && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) rc = ACG_EHIP;
+    for (int r = 0; r < nshards && rc == ACG_OK; ++r) {
+        std::vector<int> map((size_t)nloc);
+        for (int l = 0; l < nloc; ++l) map[(size_t)l] = l * nshards + r;
+        rc = acg_fl_create(&T[(size_t)r], cfg);
+        if (rc == ACG_OK && nshards > 1) rc = acg_fl_set_channels(T[(size_t)r], map.data(), nloc);       // (one shard: the identity, left unset)
+        if (rc == ACG_OK && r > 0) rc = acg_fl_export(T[(size_t)r], 1);
+    }
+    if (rc == ACG_OK) {
+        LabStage lab(biggest);
+        if (!lab.ok()) rc = ACG_ENOMEM;
+        std::vector<acg_msg> part(std::max<size_t>(biggest, 1));
+        std::vector<acg_flight_event> evs(std::max<size_t>(biggest, 1));
+        size_t at = 0;
+        int snap_at = 0;
+        for (int b = 0; b < nbatch && rc == ACG_OK; ++b) {
+            for (int r = nshards > 1 ? 1 : 0; rc == ACG_OK; r = (r + 1) % nshards) {      // the peers, then the owner
+                unsigned int n = 0;
+                for (size_t i = at; i < at + (size_t)batch[b]; ++i)
+                    if (in[i].chn % nshards == r) {
+                        part[n] = in[i];
+                        part[n++].chn = in[i].chn / nshards;
+                    }
+                AcgFlights* t = T[(size_t)r];
+                const AcgFlightPass* fp = nullptr;
+                lab.stage(part.data(), n, false, true);
+                if (n && lab.upload(n) != 0) rc = ACG_EHIP;
+                if (rc == ACG_OK && r == 0 && pass_ms && hipEventRecord(ev0, nullptr) != hipSuccess) rc = ACG_EHIP;
+                if (rc == ACG_OK && n) {
+                    rc = acg_fl_prepare(t, n, nullptr, &fp);
+                    if (rc == ACG_OK && lab.launch(n, &d, nullptr, fp) != 0) rc = ACG_EHIP;
+                } else if (rc == ACG_OK && r == 0) {
+                    rc = acg_fl_commit(t, nullptr);
+                }
+                if (rc == ACG_OK && r > 0) {
+                    int k = 0;
+                    rc = acg_fl_drain_events(t, nullptr, evs.data(), (int)evs.size(), &k);
+                    if (rc == ACG_OK && acg_flight_events_check(evs.data(), k) != ACG_OK) rc = ACG_ESTATE;
+                    if (rc == ACG_OK && k) rc = acg_fl_import(T[0], evs.data(), k);
+                }
+                if (r == 0) break;
+            }
+            if (rc == ACG_OK && pass_ms) {
+                if (hipEventRecord(ev1, nullptr) != hipSuccess || hipEventSynchronize(ev1) != hipSuccess ||
+                    hipEventElapsedTime(&pass_ms[b], ev0, ev1) != hipSuccess)
+                    rc = ACG_EHIP;
+            }
+            at += (size_t)batch[b];
+            if (rc == ACG_OK) {
+                rc = acg_fl_snapshot(T[0], nullptr, snaps + snap_at, snap_cap - snap_at, &snap_n[b], &dropped[b]);
+                if (rc == ACG_OK) snap_at += snap_n[b];
+            }
+        }
+        if (rc == ACG_OK) rc = acg_fl_drain_routes(T[0], nullptr, routes, route_cap, nroutes);
+        for (int r = 1; r < nshards && rc == ACG_OK; ++r) {        // a peer's table stays empty and emits nothing
+            acg_flight one;
+            acg_route rt;
+            int k = 0, kr = 0, dr = 0;
+            const int rs = acg_fl_snapshot(T[(size_t)r], nullptr, &one, 1, &k, &dr), rr = acg_fl_drain_routes(T[(size_t)r], nullptr, &rt, 1, &kr);
+            if (rs != ACG_OK || rr != ACG_OK || k || kr || dr) rc = ACG_ESTATE;
+        }
+    }
+    for (AcgFlights* t : T)
+        if (t) acg_fl_destroy(t);
+    if (ev0) hipEventDestroy(ev0);
+    if (ev1) hipEventDestroy(ev1);
     return rc;
 }
 
@@ -1971,9 +2151,13 @@ static int sink_fetch(acg_ctx* ctx, const AcgSinkFormat* fmt, AcgSinkState* st, 
     unsigned int upto = 0, pending = 0, take = 0;
     bool any = false;
     int rc = ring_upto(ctx, lag, &upto, &any);
-    if (rc != ACG_OK || !any) return rc;
+    if (rc != ACG_OK) return rc;
+    if (!any) return commit_imports(ctx);
     rc = ring_claim(ctx, upto, (int)fit, &pending, &take);
-    if (!take) return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
+    if (!take) {
+        if (const int cr = commit_imports(ctx)) return cr;
+        return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
+    }
     if (const int gr = grow_msg_stage(ctx, take)) return gr;
     if (const int gr = grow_label_stage(ctx, take)) return gr;
     if (sink_reserve(st, take) != ACG_OK) return fail(ctx, ACG_ENOMEM, "sink: work space");

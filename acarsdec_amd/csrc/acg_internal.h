@@ -116,7 +116,7 @@ struct AcgFlightState {
     unsigned int nroutes;       // routes queued
     unsigned int dropped;       // new aircraft that found no slot
     unsigned int nlive;         // snapshot: live entries
-    unsigned int pad_;
+    unsigned int nexport;       // export queue: events queued (acg_flights_export)
 };
 
 struct AcgRouteRec {
@@ -139,6 +139,13 @@ struct AcgFlightPass {
     unsigned int *idx1, *idx1s, *rank2, *rank2s;
     long long* pmax;
     uint2* segs;
+    // ---- the table across contexts (acg_flights_set_channels / _export / _import); all null / 0 unless those are used
+    const int* chmap;           // or null: the channel number an event records for local channel l, [nmap]
+    unsigned int nmap;
+    unsigned int n_import;      // events of other contexts uploaded for this pass, applied with its own
+    const void* imp;            // acg_flight_event[n_import]
+    void* xq;                   // or null: export is on -- the pass ends behind the extraction, its events go to this queue
+    unsigned int xq_cap;        // acg_flight_event records xq holds
 };
 
 // ---- the JSON line renderer (json.hip): buildjson() + cJSON_PrintPreallocated (output.c:227-324) over a call's kept records ----
@@ -350,7 +357,8 @@ int acg_launch_msg_split(const AcgFrameRec* frames, unsigned int cap, unsigned i
 int acg_launch_msg_labels(const AcgMsgRec* recs, unsigned int n, const AcgLabelPass* p, void* stream);
 // label.hip: the events of n records (filter f: -A / -b decide, -e is only noted), compacted, with the keys of the time sort
 int acg_launch_flight_extract(const AcgMsgRec* recs, unsigned int n, const AcgLabelFilter* f, const AcgFlightPass* p, void* stream);
-// flight.hip: extraction, ordering, segment walk and table update for n records
+// flight.hip: extraction, ordering, segment walk and table update for n records and p->n_import uploaded events (p->xq set:
+// extraction and the hand-over of the events to the export queue, nothing else)
 int acg_launch_flight_pass(const AcgMsgRec* recs, unsigned int n, const AcgLabelFilter* f, const AcgFlightPass* p, void* stream);
 // flight.hip: the live entries, latest update first, as acg_flight records in out[cap]; st->nlive = how many
 int acg_launch_flight_snapshot(const AcgFlightPass* p, unsigned long long* skey, unsigned long long* skey_s, unsigned int* sval,

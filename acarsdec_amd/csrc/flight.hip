@@ -4,6 +4,9 @@
 // The reference walks a move-to-front list once per message.  Here one pass handles all messages a drain / collect consumes:
 //   flight_extract_kernel (label.hip)  a thread per record: the messages that reach addFlight() become events (aircraft key,
 //                                      tv, fid, decoded OOOI fields, "passes -e") with the sort key (end_sample, chn);
+//   fl_events_import_kernel            only at the owner of a table shared by several contexts, when events of the others
+//                                      are queued: they join the pass's events (a peer's pass ends here instead:
+//                                      fl_events_export_kernel hands its events out and nothing below runs);
 //   flight_sort_kernel                 the events in time order;
 //   flight_order_kernel                tv_sec in that order and its inclusive running maximum seeded with the table's G:
 //                                      pmax[r - 1] is the newest second any message BEFORE event r carried;
@@ -415,21 +418,111 @@ __global__ void flight_finish_kernel(AcgFlightPass p)
     p.st->nseg = 0;
 }
 
+// ---- the table across contexts: a peer's events leave (export), the owner takes them in (import) ------------------------------
+static_assert(sizeof(acg_flight_event) == 88 && offsetof(acg_flight_event, chn) == 28 && offsetof(acg_flight_event, addr) == 32 &&
+                  offsetof(acg_flight_event, e_ok) == 47 && offsetof(acg_flight_event, oooi) == 48 && offsetof(AcgFlightEv, oooi) == 40,
+              "acg_flight_event layout");
+
+// a 7-byte C string as a word: nothing behind its NUL counts (as the extraction reads addr and fid)
+__device__ __forceinline__ unsigned long long fl_cstr7(unsigned long long v)
+{
+    v &= 0x00ffffffffffffffull;
+    for (int b = 1; b < 7; ++b)
+        if (((v >> (8 * (b - 1))) & 0xff) == 0) v &= (1ull << (8 * b)) - 1ull;
+    return v;
+}
+
+// Export: a thread per extracted event (event i has the key key1[i]: the extraction writes idx1[i] = i).  The events are appended
+// to the queue through its counter, one atomic per wave as in the extraction; an event without an address has no record.  The
+// last workgroup out re-arms the pass's counters (nseg counts the workgroups here: the pass has no segments).
+__global__ __launch_bounds__(FL_WG) void fl_events_export_kernel(AcgFlightPass p)
+{
+    const unsigned int m = p.st->m;
+    const unsigned int i = blockIdx.x * FL_WG + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const AcgFlightEv* e = p.ev + i;
+    const bool go = i < m && (e->key & 0xffull) != 0;
+    const unsigned long long bm = __ballot(go);
+    if (bm) {
+        unsigned int base = 0;
+        if (lane == 0) base = atomicAdd(&p.st->nexport, (unsigned int)__popcll(bm));
+        base = (unsigned int)__shfl((int)base, 0);
+        const unsigned int at = base + (unsigned int)__popcll(bm & ((1ull << lane) - 1ull));
+        if (go && at < p.xq_cap) {
+            unsigned long long* w = (unsigned long long*)((acg_flight_event*)p.xq + at);
+            const unsigned long long* o = (const unsigned long long*)e->oooi;
+            w[0] = p.key1[i] >> 20;                                          // end_sample
+            w[1] = (unsigned long long)e->soh_sample;
+            w[2] = (unsigned long long)e->sec;
+            w[3] = (unsigned long long)(unsigned int)e->usec | ((unsigned long long)(unsigned int)e->chn << 32);
+            w[4] = e->key & 0x00ffffffffffffffull;                           // addr[8]
+            w[5] = e->fid | ((unsigned long long)(e->e_ok ? 1u : 0u) << 56); // fid[7], e_ok
+#pragma unroll
+            for (int k = 0; k < 5; ++k) w[6 + k] = o[k];
+        }
+    }
+    __syncthreads();                                                         // (every wave of this workgroup has read m)
+    if (threadIdx.x == 0 && atomicAdd(&p.st->nseg, 1u) == gridDim.x - 1) {
+        p.st->m = 0;
+        p.st->nseg = 0;
+    }
+}
+
+// Import: a thread per uploaded event, appended to the pass's events behind (or among: the counter decides) the extracted ones,
+// with the key of the time sort.  Runs between the extraction and the first sort.
+__global__ __launch_bounds__(FL_WG) void fl_events_import_kernel(AcgFlightPass p)
+{
+    const unsigned int i = blockIdx.x * FL_WG + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool go = i < p.n_import;
+    const unsigned long long bm = __ballot(go);
+    if (!bm) return;
+    unsigned int base = 0;
+    if (lane == 0) base = atomicAdd(&p.st->m, (unsigned int)__popcll(bm));
+    base = (unsigned int)__shfl((int)base, 0);
+    if (!go) return;
+    const unsigned int at = base + (unsigned int)__popcll(bm & ((1ull << lane) - 1ull));
+    const unsigned long long* w = (const unsigned long long*)((const acg_flight_event*)p.imp + i);
+    AcgFlightEv* e = p.ev + at;
+    const unsigned int chn = (unsigned int)(w[3] >> 32);
+    e->key = fl_cstr7(w[4]) | (1ull << 63);
+    e->soh_sample = (long long)w[1];
+    e->sec = (long long)w[2];
+    e->usec = (int)(unsigned int)w[3];
+    e->chn = (int)chn;
+    e->fid = fl_cstr7(w[5]);
+    unsigned long long* o = (unsigned long long*)e->oooi;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) o[k] = w[6 + k];
+    e->e_ok = (w[5] >> 56) & 0xffull ? 1u : 0u;
+    e->pad_ = 0u;
+    p.key1[at] = ((w[0] & ((1ull << 43) - 1ull)) << 20) | ((unsigned long long)chn & 0xfffffull);
+    p.idx1[at] = at;
+}
+
 extern "C" int acg_launch_flight_pass(const AcgMsgRec* recs, unsigned int n, const AcgLabelFilter* f, const AcgFlightPass* p, void* stream)
 {
-    if (n == 0) return 0;
+    const unsigned int tot = n + p->n_import;                                // (the host keeps imports away from an exporting context)
+    if (tot == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    int e = acg_launch_flight_extract(recs, n, f, p, stream);
-    if (e) return e;
-    const unsigned int g = (n + FL_WG - 1) / FL_WG;
+    if (n) {
+        const int e = acg_launch_flight_extract(recs, n, f, p, stream);
+        if (e) return e;
+    }
+    const unsigned int g = (tot + FL_WG - 1) / FL_WG;
+    if (p->xq) {
+        hipLaunchKernelGGL(fl_events_export_kernel, dim3(g), dim3(FL_WG), 0, s, *p);
+        return (int)hipGetLastError();
+    }
+    if (p->n_import) hipLaunchKernelGGL(fl_events_import_kernel, dim3((p->n_import + FL_WG - 1) / FL_WG), dim3(FL_WG), 0, s, *p);
     hipLaunchKernelGGL(flight_sort_kernel, dim3(1), dim3(RS_WG), 0, s, p->key1, p->idx1, p->key1s, p->idx1s, (const unsigned int*)&p->st->m, 0u);
     hipLaunchKernelGGL(flight_order_kernel, dim3(1), dim3(RS_WG), 0, s, *p);
     hipLaunchKernelGGL(flight_sort_kernel, dim3(1), dim3(RS_WG), 0, s, p->key2, p->rank2, p->key2s, p->rank2s, (const unsigned int*)&p->st->m, 0u);
-    hipLaunchKernelGGL(flight_heads_kernel, dim3(g), dim3(FL_WG), 0, s, *p, n);
+    hipLaunchKernelGGL(flight_heads_kernel, dim3(g), dim3(FL_WG), 0, s, *p, tot);
     // a wave per segment, the waves looping.  The host does not know the pass's events or segments (no round trip), only its n
-    // records >= both: at most one wave per record, at most 1024 waves (as the block repair: what such a pass costs beside the
-    // down-converter is workgroups finding a place, not the segments a wave takes in turn)
-    unsigned int wgs = (n + FL_WAVES - 1) / FL_WAVES;
+    // records and imported events >= both: at most one wave per record, at most 1024 waves (as the block repair: what such a pass
+    // costs beside the down-converter is workgroups finding a place, not the segments a wave takes in turn)
+    unsigned int wgs = (tot + FL_WAVES - 1) / FL_WAVES;
     wgs = wgs > 256 ? 256 : wgs;
     hipLaunchKernelGGL(flight_walk_kernel, dim3(wgs), dim3(FL_WG), 0, s, *p);
     hipLaunchKernelGGL(flight_finish_kernel, dim3(1), dim3(1), 0, s, *p);

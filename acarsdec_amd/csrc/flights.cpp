@@ -1,6 +1,7 @@
 // flights.cpp -- host side of the flight table (flight.hip): the table and its work space in device memory, grown on demand
-// like the message staging of acg_api.cpp, the snapshot and the route hand-over.  Used by a context (acg_flights_enable) and,
-// without one, by acg_selftest_flights.
+// like the message staging of acg_api.cpp, the snapshot and the route hand-over; the channel map, the export queue and the import
+// queue of a table kept for the channels of several contexts.  Used by a context (acg_flights_enable) and, without one, by
+// acg_selftest_flights and acg_selftest_flights_sharded.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -32,6 +33,14 @@ struct AcgFlights {
     size_t m_out_cap = 0;
     void* r_work = nullptr;             // routes, grown on demand: keys, indices, len, off [r_cap], wg_sum, wg_cnt, the lines
     size_t r_cap = 0;
+    // ---- one table for several contexts: this one exports its events (p.xq set) or takes in those of others
+    int* d_chmap = nullptr;             // p.chmap, or null
+    size_t xq_bound = 0;                // no more events than this can be queued for export
+    std::deque<acg_flight_event> xpending;      // events already fetched, not yet handed out
+    std::vector<acg_flight_event> imp_pending;  // imported, waiting for the next pass
+    std::vector<acg_flight_event> imp_up;       // the upload of the last pass (alive until the stream has taken it)
+    void* d_imp = nullptr;              // p.imp
+    size_t imp_cap = 0;
 };
 
 #define FLCHK(call)                          \
@@ -64,6 +73,7 @@ void acg_fl_destroy(AcgFlights* t)
     free_text(t);
     hipFree(t->p.slots); hipFree(t->p.st); hipFree(t->p.routes);
     hipFree(t->snap_key); hipFree(t->snap_val); hipFree(t->snap_out);
+    hipFree(t->d_chmap); hipFree(t->p.xq); hipFree(t->d_imp);
     delete t;
 }
 
@@ -78,6 +88,10 @@ int acg_fl_reset(AcgFlights* t)
     t->p.pass = 0;
     t->route_bound = 0;
     t->pending.clear();
+    t->xq_bound = 0;                                                  // (the channel map and the export switch stay)
+    t->xpending.clear();
+    t->imp_pending.clear();
+    t->p.n_import = 0;
     return ACG_OK;
 }
 
@@ -134,33 +148,148 @@ static int ensure_work(AcgFlights* t, unsigned int n, hipStream_t s)
     return ACG_OK;
 }
 
+// Room for `n` more records in a device queue (the routes, the exported events) that is appended to through the counter *d_count.
+// *bound counts records that MAY have been queued since the last drain, not records queued: before the queue grows on its account,
+// ask the device how many it really holds (the stream is idle here: every entry point ends with a synchronise), so a host that
+// never drains pays for what it leaves queued, not for the records it has seen
+static int queue_room(void** q, unsigned int* cap, size_t rec, size_t* bound, const unsigned int* d_count, size_t n, hipStream_t s)
+{
+    if (*bound + n > *cap) {
+        unsigned int queued = 0;
+        FLCHK(hipMemcpyAsync(&queued, d_count, sizeof(queued), hipMemcpyDeviceToHost, s));
+        FLCHK(hipStreamSynchronize(s));
+        *bound = std::min(queued, *cap);
+    }
+    if (*bound + n > *cap) {
+        const size_t want = std::max<size_t>(2 * (size_t)*cap, *bound + n);
+        if (want > 0xffffffffull) return ACG_ENOMEM;
+        void* bigger = nullptr;
+        FLCHK(hipMalloc(&bigger, want * rec));
+        FLCHK(hipMemcpyAsync(bigger, *q, (size_t)*cap * rec, hipMemcpyDeviceToDevice, s));
+        FLCHK(hipStreamSynchronize(s));
+        hipFree(*q);
+        *q = bigger;
+        *cap = (unsigned int)want;
+    }
+    *bound += n;
+    return ACG_OK;
+}
+
 int acg_fl_prepare(AcgFlights* t, unsigned int n, void* stream, const AcgFlightPass** pass)
 {
     hipStream_t s = (hipStream_t)stream;
-    int rc = ensure_work(t, n, s);
+    t->p.n_import = 0;
+    if (t->p.xq) {                                                    // a peer: the pass ends behind the extraction, its events are queued
+        int rc = ensure_work(t, n, s);
+        if (rc == ACG_OK) rc = queue_room(&t->p.xq, &t->p.xq_cap, sizeof(acg_flight_event), &t->xq_bound, &t->p.st->nexport, n, s);
+        if (rc != ACG_OK) return rc;
+        t->p.pass += 1;
+        *pass = &t->p;
+        return ACG_OK;
+    }
+    // the owner of a shared table: the events imported since the last pass join this one
+    const size_t n_imp = t->imp_pending.size(), tot = (size_t)n + n_imp;
+    if (tot > (1u << 30)) return ACG_ENOMEM;
+    int rc = ensure_work(t, (unsigned int)tot, s);
     if (rc != ACG_OK) return rc;
-    // a pass of n records queues at most n routes.  route_bound counts records, not routes: before the queue grows on its
-    // account, ask the device how many routes it really holds (the stream is idle here: every entry point ends with a
-    // synchronise), so a host that never drains pays for the routes it leaves queued, not for the records it has seen
-    if (t->route_bound + n > t->p.route_cap) {
-        unsigned int queued = 0;
-        FLCHK(hipMemcpyAsync(&queued, &t->p.st->nroutes, sizeof(queued), hipMemcpyDeviceToHost, s));
-        FLCHK(hipStreamSynchronize(s));
-        t->route_bound = std::min(queued, t->p.route_cap);
+    if (n_imp) {
+        if (n_imp > t->imp_cap) {
+            FLCHK(hipStreamSynchronize(s));
+            hipFree(t->d_imp);
+            t->d_imp = nullptr;
+            t->imp_cap = 0;
+            const size_t want = std::max<size_t>(n_imp, 4096);
+            FLCHK(hipMalloc(&t->d_imp, want * sizeof(acg_flight_event)));
+            t->imp_cap = want;
+        }
+        t->imp_up.swap(t->imp_pending);                               // (the previous upload is long done: every entry point ends with a synchronise)
+        t->imp_pending.clear();
+        FLCHK(hipMemcpyAsync(t->d_imp, t->imp_up.data(), n_imp * sizeof(acg_flight_event), hipMemcpyHostToDevice, s));
+        t->p.imp = t->d_imp;
+        t->p.n_import = (unsigned int)n_imp;
     }
-    if (t->route_bound + n > t->p.route_cap) {
-        const size_t want = std::max<size_t>(2 * (size_t)t->p.route_cap, t->route_bound + n);
-        AcgRouteRec* bigger = nullptr;
-        FLCHK(hipMalloc(&bigger, want * sizeof(AcgRouteRec)));
-        FLCHK(hipMemcpyAsync(bigger, t->p.routes, (size_t)t->p.route_cap * sizeof(AcgRouteRec), hipMemcpyDeviceToDevice, s));
-        FLCHK(hipStreamSynchronize(s));
-        hipFree(t->p.routes);
-        t->p.routes = bigger;
-        t->p.route_cap = (unsigned int)want;
-    }
-    t->route_bound += n;
+    // a pass of tot events queues at most tot routes
+    void* rq = t->p.routes;
+    rc = queue_room(&rq, &t->p.route_cap, sizeof(AcgRouteRec), &t->route_bound, &t->p.st->nroutes, tot, s);
+    t->p.routes = (AcgRouteRec*)rq;
+    if (rc != ACG_OK) return rc;
     t->p.pass += 1;
     *pass = &t->p;
+    return ACG_OK;
+}
+
+// ---- one table for several contexts ----------------------------------------------------------------------------------------------
+int acg_fl_set_channels(AcgFlights* t, const int* chn, int nch)
+{
+    FLCHK(hipDeviceSynchronize());
+    hipFree(t->d_chmap);
+    t->d_chmap = nullptr;
+    t->p.chmap = nullptr;
+    t->p.nmap = 0;
+    if (!chn || nch <= 0) return ACG_OK;
+    FLCHK(hipMalloc(&t->d_chmap, (size_t)nch * sizeof(int)));
+    FLCHK(hipMemcpy(t->d_chmap, chn, (size_t)nch * sizeof(int), hipMemcpyHostToDevice));
+    t->p.chmap = t->d_chmap;
+    t->p.nmap = (unsigned int)nch;
+    return ACG_OK;
+}
+
+int acg_fl_exporting(const AcgFlights* t) { return t->p.xq != nullptr; }
+
+int acg_fl_export(AcgFlights* t, int on)
+{
+    const int rc = acg_fl_reset(t);                                   // the table and both queues are emptied either way
+    if (rc != ACG_OK) return rc;
+    hipFree(t->p.xq);
+    t->p.xq = nullptr;
+    t->p.xq_cap = 0;
+    if (!on) return ACG_OK;
+    FLCHK(hipMalloc(&t->p.xq, 4096 * sizeof(acg_flight_event)));
+    t->p.xq_cap = 4096;
+    return ACG_OK;
+}
+
+int acg_fl_drain_events(AcgFlights* t, void* stream, acg_flight_event* out, int max, int* n)
+{
+    hipStream_t s = (hipStream_t)stream;
+    unsigned int queued = 0;
+    FLCHK(hipMemcpyAsync(&queued, &t->p.st->nexport, sizeof(queued), hipMemcpyDeviceToHost, s));
+    FLCHK(hipStreamSynchronize(s));
+    const unsigned int got = std::min(queued, t->p.xq_cap);
+    if (got) {
+        std::vector<acg_flight_event> h(got);
+        FLCHK(hipMemcpyAsync(h.data(), t->p.xq, (size_t)got * sizeof(acg_flight_event), hipMemcpyDeviceToHost, s));
+        FLCHK(hipMemsetAsync(&t->p.st->nexport, 0, sizeof(unsigned int), s));
+        FLCHK(hipStreamSynchronize(s));
+        t->xpending.insert(t->xpending.end(), h.begin(), h.end());
+    }
+    t->xq_bound = 0;
+    int k = 0;
+    while (k < max && !t->xpending.empty()) {
+        out[k++] = t->xpending.front();
+        t->xpending.pop_front();
+    }
+    *n = k;
+    return t->xpending.empty() ? ACG_OK : ACG_EAGAIN;
+}
+
+int acg_fl_import(AcgFlights* t, const acg_flight_event* ev, int n)
+{
+    if (t->imp_pending.size() + (size_t)n > (1u << 30)) return ACG_ENOMEM;
+    t->imp_pending.insert(t->imp_pending.end(), ev, ev + n);
+    return ACG_OK;
+}
+
+int acg_fl_imports_queued(const AcgFlights* t) { return !t->imp_pending.empty(); }
+
+int acg_fl_commit(AcgFlights* t, void* stream)
+{
+    if (t->imp_pending.empty()) return ACG_OK;
+    const AcgFlightPass* fp = nullptr;
+    const int rc = acg_fl_prepare(t, 0, stream, &fp);
+    if (rc != ACG_OK) return rc;
+    if (acg_launch_flight_pass(nullptr, 0, nullptr, fp, stream) != 0) return ACG_EHIP;
+    FLCHK(hipStreamSynchronize((hipStream_t)stream));
     return ACG_OK;
 }
 

@@ -21,6 +21,19 @@ ACG_FL_WEAK int acg_fl_reset(AcgFlights* t);                                    
 ACG_FL_WEAK int acg_fl_prepare(AcgFlights* t, unsigned int n, void* stream, const AcgFlightPass** pass);
 ACG_FL_WEAK int acg_fl_snapshot(AcgFlights* t, void* stream, acg_flight* out, int max, int* n, int* dropped);
 ACG_FL_WEAK int acg_fl_drain_routes(AcgFlights* t, void* stream, acg_route* out, int max, int* n);
+// ---- one table for several contexts (acg_flights_set_channels / _export / _import of the public header)
+// the number recorded for local channel l: chn[nch], null = identity (the values are checked by the caller); synchronises
+ACG_FL_WEAK int acg_fl_set_channels(AcgFlights* t, const int* chn, int nch);
+// on: acg_fl_prepare's passes end behind the extraction and queue their events for acg_fl_drain_events.  Either way the table
+// and both event queues are emptied (acg_fl_reset, which keeps the switch and the channel map)
+ACG_FL_WEAK int acg_fl_export(AcgFlights* t, int on);
+ACG_FL_WEAK int acg_fl_exporting(const AcgFlights* t);
+ACG_FL_WEAK int acg_fl_drain_events(AcgFlights* t, void* stream, acg_flight_event* out, int max, int* n);
+// n checked events for the next acg_fl_prepare, whose pass then covers its n records and these (AcgFlightPass::n_import)
+ACG_FL_WEAK int acg_fl_import(AcgFlights* t, const acg_flight_event* ev, int n);
+ACG_FL_WEAK int acg_fl_imports_queued(const AcgFlights* t);
+// the pass over the queued imports alone, on `stream`, waited for; nothing queued: nothing happens
+ACG_FL_WEAK int acg_fl_commit(AcgFlights* t, void* stream);
 // ---- the table's text (flight_text.hip).  cfg: nbch and the escaped station stretch (null: the renderer off and its buffers freed)
 ACG_FL_WEAK int acg_fl_text_enable(AcgFlights* t, const AcgFlightTextDev* cfg);
 ACG_FL_WEAK int acg_fl_text_on(const AcgFlights* t);

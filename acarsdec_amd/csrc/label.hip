@@ -289,12 +289,14 @@ __global__ __launch_bounds__(LBL_WG) void flight_extract_kernel(const AcgMsgRec*
     e->soh_sample = soh;
     e->sec = p.t0_sec + q;
     e->usec = (int)rem;
-    e->chn = r->chn;
+    // the number the table records for this channel (acg_flights_set_channels: a shard's channels under their global numbers)
+    const int chn = p.chmap && (unsigned int)r->chn < p.nmap ? p.chmap[r->chn] : r->chn;
+    e->chn = chn;
     e->fid = fid;
     decode_label(r, e->oooi);
     e->e_ok = msg_keep_e(r, f) ? 1u : 0u;
     e->pad_ = 0u;
-    p.key1[at] = (((unsigned long long)r->end_sample & ((1ull << 43) - 1ull)) << 20) | ((unsigned long long)(unsigned int)r->chn & 0xfffffull);
+    p.key1[at] = (((unsigned long long)r->end_sample & ((1ull << 43) - 1ull)) << 20) | ((unsigned long long)(unsigned int)chn & 0xfffffull);
     p.idx1[at] = at;
 }
 

@@ -363,6 +363,42 @@ class Decoder:
             if rc == K.OK:
                 return out
 
+    # ---- one flight table for the channels of several decoders (acg_flights_set_channels / _export / _import / _commit) -----
+    def set_flight_channels(self, chn=None):
+        """The channel number the table records for each local channel (None: the local index).  For `c mod N` sharding:
+        shard.flight_channel_map(nch, rank, world)."""
+        if chn is None:
+            return self._chk(self.L.acg_flights_set_channels(self.ctx, None))
+        arr = np.ascontiguousarray(np.asarray(chn, dtype=np.int32))
+        if arr.shape != (self.nch,):
+            raise ValueError("one channel number per local channel")
+        self._chk(self.L.acg_flights_set_channels(self.ctx, arr.ctypes.data))
+
+    def export_flights(self, on=True):
+        """A peer of a shared table: the message entry points queue this decoder's flight events instead of applying them."""
+        self._chk(self.L.acg_flights_export(self.ctx, 1 if on else 0))
+
+    def drain_flight_events(self, max_events=4096):
+        """The events exported so far, a numpy structured array of K.FLIGHT_EVENT_DTYPE (88 bytes a record), in any order."""
+        buf = np.zeros(max(1, int(max_events)), dtype=K.FLIGHT_EVENT_DTYPE)
+        parts = []
+        while True:
+            n = C.c_int(0)
+            rc = self._chk(self.L.acg_drain_flight_events(self.ctx, buf.ctypes.data, len(buf), C.byref(n)), allow=(K.EAGAIN,))
+            parts.append(buf[:n.value].copy())
+            if rc == K.OK:
+                return np.concatenate(parts)
+
+    def import_flight_events(self, events):
+        """The owner of a shared table: events of other decoders (arrays as drain_flight_events / shard.gather_flight_events hand
+        them out), applied by the next message entry point together with this decoder's own."""
+        ev = np.ascontiguousarray(np.asarray(events, dtype=K.FLIGHT_EVENT_DTYPE))
+        self._chk(self.L.acg_flights_import(self.ctx, ev.ctypes.data if len(ev) else None, len(ev)))
+
+    def commit_flights(self):
+        """A pass over the imported events alone (an owner without channels of its own, the end of a run)."""
+        self._chk(self.L.acg_flights_commit(self.ctx))
+
     # ---- the flight table's text (acg_flight_text_enable, acg_flight_monitor_text, acg_drain_routes_json) -------------------
     def enable_flight_text(self, nbch, station_id=""):
         """printmonitor()'s screen and routejson()'s lines (output.c:428-484) rendered on the device from the flight table, which

@@ -7,7 +7,9 @@ own input and keeps its own state.  There is NO data-path collective.  torch.dis
 GPUs, gloo in the CPU tests) carries only the trivial exchanges: the per-channel configuration from
 rank 0 (ONE BROADCAST of the whole table, 32 B per channel, from which every rank keeps its own rows --
 not an ncclSend/Recv scatter: 0.5 MB at 16 384 channels is not worth one), the barrier around the
-timed region and the reduction/gather of counts, timings and decoded blocks.
+timed region and the reduction/gather of counts, timings and decoded blocks -- and, where ONE flight
+table is kept for all channels, each round's flight events (88 B per message that reaches addFlight())
+on their way to the rank that owns the table.
 """
 import numpy as np
 
@@ -83,3 +85,38 @@ def gather_scalars(x, world, dist=None, device=None):
     box = [torch.zeros(1, dtype=torch.float64, device=device) for _ in range(world)]
     dist.all_gather(box, mine)
     return [float(b.item()) for b in box]
+
+
+def flight_channel_map(nch_local, rank, world):
+    """The channel numbers a rank's flight table records (Decoder.set_flight_channels): local channel l of rank r is the global
+    channel l * world + r, the inverse of owned_channels."""
+    return np.arange(int(nch_local), dtype=np.int32) * np.int32(world) + np.int32(rank)
+
+
+def gather_flight_events(events, dst=0, dist=None, device=None):
+    """Every rank's flight events (Decoder.drain_flight_events: a structured array of 88-byte records) moved to `dst` as bytes.
+    The counts differ from rank to rank: they are exchanged first (one int64 per rank), then ONE gather carries the records, each
+    rank's padded to the largest count.  CPU tensors over gloo, device tensors (device = the rank's GPU) over RCCL, as the other
+    helpers here.  Returns on `dst` the concatenation in rank order (what Decoder.import_flight_events takes; the owner's own
+    part is empty when it exports nothing), None elsewhere."""
+    from . import _capi as K
+    ev = np.ascontiguousarray(np.asarray(events, dtype=K.FLIGHT_EVENT_DTYPE))
+    if dist is None:
+        return ev
+    import torch
+    rank, world = dist.get_rank(), dist.get_world_size()
+    rec = ev.dtype.itemsize
+    mine = torch.tensor([len(ev)], dtype=torch.int64, device=device)
+    counts = [torch.zeros(1, dtype=torch.int64, device=device) for _ in range(world)]
+    dist.all_gather(counts, mine)
+    counts = [int(c.item()) for c in counts]
+    width = max(max(counts), 1) * rec
+    row = torch.zeros(width, dtype=torch.uint8, device=device)
+    if len(ev):
+        row[: len(ev) * rec] = torch.from_numpy(ev.view(np.uint8).reshape(-1).copy()).to(row.device)
+    box = [torch.zeros(width, dtype=torch.uint8, device=device) for _ in range(world)] if rank == dst else None
+    dist.gather(row, box, dst=dst)
+    if rank != dst:
+        return None
+    parts = [np.frombuffer(b.cpu().numpy()[: n * rec].tobytes(), dtype=ev.dtype) for b, n in zip(box, counts)]
+    return np.concatenate(parts)

@@ -330,7 +330,8 @@ int  acg_collect_msgs_oooi(acg_ctx *ctx, int lag, acg_msg *out, acg_oooi *oooi, 
  *                    consumed an arbitrary oldest part of the block queue: the rule then still holds per call, not globally.
  *   expiry           an entry whose last message is more than mdly seconds older than the newest message second seen so far
  *                    is gone (output.c:407-423; the CLI's -t, default 600); its aircraft starts anew with its next message.
- * One table per context: a host that spreads its channels over several devices merges the tables itself. */
+ * One table per context.  A host that spreads its channels over several devices keeps one table at one of them and moves the
+ * other contexts' EVENTS there (acg_flights_export / acg_flights_import below): that is exact, merging snapshots is not. */
 typedef struct {
 	long long t0_sec;             /* wall clock of the channels' first sample since acg_reset */
 	int t0_usec;                  /* 0 .. 999999 */
@@ -370,7 +371,8 @@ typedef struct {
 
 /* Switches the table on (cfg) or off and frees it (NULL).  Enabling an enabled table replaces it by an empty one.
  * ACG_EINVAL: mdly < 1, max_flights < 1, t0_usec outside 0..999999; ACG_ESTATE: context without ACG_F_REPAIR.
- * acg_reset() empties the table and the pending routes (the sample clock restarts there). */
+ * acg_reset() empties the table, the pending routes and the event queues of export and import (the sample clock restarts
+ * there); switching the table off does too. */
 int  acg_flights_enable(acg_ctx *ctx, const acg_flight_config *cfg);
 /* The live entries in printmonitor()'s order (output.c:467-481): latest update first (the order is total).  ACG_EAGAIN: max is
  * too small, *n is the number needed.  *dropped (may be NULL) counts, since enable / reset, every (call, aircraft) pair in which an
@@ -384,6 +386,62 @@ int  acg_flight_snapshot(acg_ctx *ctx, acg_flight *out, int max, int *n, int *dr
  * Routes stay queued until they are drained or the table is reset or switched off: a host that enables the table for the monitor
  * alone still drains them now and then, or the queue grows by one record per route emitted. */
 int  acg_drain_routes(acg_ctx *ctx, acg_route *out, int max, int *n);
+
+/* ---- one flight table for the channels of several contexts: export and import of flight EVENTS --------------------------
+ * A host that shards its channels over several contexts (devices) keeps ONE table, at an OWNER context.  Tables cannot be merged
+ * exactly from snapshots (the per-field "last non-empty value" and the "first message that ..." route rule are gone there); the
+ * stream of events can: every message that reaches addFlight() is one event with the order key (end_sample, chn), and the rest
+ * of the pass is defined by that order alone.  So the other contexts (the PEERS) hand their events out instead of applying them,
+ * the owner takes them in and runs its ordinary pass over its own and the imported events together.
+ * Nothing here is used by default: with these entry points unused every other one launches, copies and returns what it did.
+ *
+ * THE ROUND that makes it exact.  One process call on every context over the same sample span; then one message entry point on
+ * every peer, followed by acg_drain_flight_events; then the owner imports all of them and makes its own message entry point
+ * call.  As long as no call of a round returns ACG_EAGAIN, the owner's table, routes and `dropped` are those of one context
+ * that holds all channels and makes the same calls.  (Merging once per shard instead of once per round is NOT the same: the
+ * running "newest second seen" and the restart of expired entries depend on the order of all messages.)
+ *
+ * One event.  88 bytes, every byte defined. */
+typedef struct {
+	long long end_sample;         /* with chn: the order key of the pass */
+	long long soh_sample;
+	long long sec;                /* tv of the message, already t0 + soh_sample / 12500 s of the exporting context */
+	int usec;                     /* 0 .. 999999 */
+	int chn;                      /* the channel number the table records (see acg_flights_set_channels) */
+	char addr[8];                 /* NUL padded, never empty */
+	char fid[7];                  /* NUL padded, may be empty */
+	char e_ok;                    /* 1: the message also passed -e */
+	acg_oooi oooi;                /* all zero when the label did not decode */
+} acg_flight_event;
+
+/* The number recorded for each local channel in events and therefore in first_chn, last_chn, chm, acg_route.chn and the order
+ * key: chn[nch], or NULL for the identity.  It applies to the context's own table and to what it exports; for `c mod N` sharding
+ * on rank r local channel l gets l * N + r.  ACG_EINVAL: a value outside 0 .. 2^20 - 1 (the key holds 20 bits); ACG_ESTATE: the
+ * table is off.  acg_reset keeps the map; acg_flights_enable drops it with the table.
+ * KNOWN FOLLOW-UP: acg_frame / acg_msg and the JSON and text sinks are untouched, their channel numbers stay local. */
+int  acg_flights_set_channels(acg_ctx *ctx, const int *chn);
+/* on != 0: this context is a peer.  Its flight pass stops behind the extraction (after -A / -b, before -e, as ever): the events
+ * of the blocks a message entry point consumes go to an export queue on the device, channel numbers applied, and the table stays
+ * empty.  The queue grows until it is drained, like the route queue.  The message, JSON and text records handed out are the same
+ * bytes with export on and off.  A message whose address is empty (seven dots on the air) is no event of an export: acg_flight_event
+ * has no room for "no address", a single context gives it a row.  Turning export on or off empties the table and both queues;
+ * acg_reset empties them too and keeps the switch.  ACG_ESTATE: the table is off. */
+int  acg_flights_export(acg_ctx *ctx, int on);
+/* The events exported so far, in any order; their (end_sample, chn) pairs are distinct.  ACG_EAGAIN: more are queued than fit,
+ * nothing is lost, call again.  Waits only for the passes issued so far.  ACG_ESTATE: the table or export is off. */
+int  acg_drain_flight_events(acg_ctx *ctx, acg_flight_event *out, int max, int *n);
+/* ACG_OK when every one of the n events is one acg_flights_import takes, else ACG_EINVAL: usec outside 0 .. 999999, addr[0] == 0,
+ * chn outside 0 .. 2^20 - 1, end_sample negative or >= 2^43, e_ok not 0 or 1.  Host arithmetic only, no context. */
+int  acg_flight_events_check(const acg_flight_event *ev, int n);
+/* Queues events of other contexts at the owner (table on, export off).  They are applied by the owner's NEXT message entry
+ * point, in the same pass as the events of the blocks that call consumes, in ascending (end_sample, chn) over both; a call that
+ * consumes no blocks still runs the pass over the imports alone.  Checked on the host first (acg_flight_events_check):
+ * ACG_EINVAL queues nothing.  sec / usec are used as they come, so a peer may have its own t0.  end_sample is the caller's
+ * business: contexts that were reset together and fed in lock step share it as it is, otherwise the host rebases the field
+ * before the import.  ACG_ESTATE: the table is off, or this context exports. */
+int  acg_flights_import(acg_ctx *ctx, const acg_flight_event *ev, int n);
+/* A pass over the queued imports alone: for an owner with no channels of its own, or the end of a run.  Nothing queued: no-op. */
+int  acg_flights_commit(acg_ctx *ctx);
 
 /* ---- the flight table's text: the monitor screen (-o 3) and the route line (-o 5), rendered on the device -------------------
  * Off by default; with it off every entry point launches, copies and returns exactly what it does without this section, and

@@ -79,6 +79,19 @@ int  acg_selftest_msg_labels(const acg_msg *in, int n, const acg_msg_filter *f, 
  * ACG_EAGAIN: snaps or routes too small; ACG_ENODEV: no GPU. */
 int  acg_selftest_flights(const acg_msg *in, const int *batch, int nbatch, const acg_flight_config *cfg, const acg_msg_filter *f,
 			  acg_flight *snaps, int snap_cap, int *snap_n, acg_route *routes, int route_cap, int *nroutes, int *dropped);
+/* diagnostics: the same records through nshards (1 .. 64) tables, driven as a host that shards its channels `c mod nshards` over
+ * as many contexts drives them (acg_flights_set_channels / _export / _import of the product header).  in[i].chn is the GLOBAL
+ * channel (0 .. 2^20 - 1): shard r = chn % nshards holds it as local channel chn / nshards under the map l -> l * nshards + r.
+ * Shards 1 .. export, shard 0 owns the table.  Batch b is one ROUND: each peer's pass over its records and the drain of its events,
+ * their import at the owner, then the owner's pass over its records and the imports -- the pass over the imports alone
+ * (acg_flights_commit's) when the round has no record of the owner's.  snaps, snap_n, routes, *nroutes are the OWNER's, as
+ * acg_selftest_flights fills them; dropped[b] (nbatch entries) is its `dropped` after round b.  pass_ms (nbatch entries, or NULL):
+ * the device time of the owner's part of round b in milliseconds, HIP events around the upload of the imported events, the label
+ * pass and the flight pass (the way of the owner's records to the device is outside).
+ * ACG_ESTATE: a peer's table or route queue is not empty at the end, or it exported an event acg_flight_events_check refuses. */
+int  acg_selftest_flights_sharded(const acg_msg *in, const int *batch, int nbatch, int nshards, const acg_flight_config *cfg,
+				  const acg_msg_filter *f, acg_flight *snaps, int snap_cap, int *snap_n, acg_route *routes, int route_cap,
+				  int *nroutes, int *dropped, float *pass_ms);
 
 /* diagnostics: the flight table's text (flight_text.hip) on caller-supplied entries and routes, without traffic: a table made
  * from cfg (at least n slots) holds in[0 .. n) as its live entries, in[0] the latest update, and its queue holds rt[0 .. nr),
