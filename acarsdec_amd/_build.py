@@ -60,6 +60,7 @@ UNITS = [("fir.hip", ["-O3"], True), ("fir_mm.hip", ["-O3"], True), ("msk.hip", 
          ("json.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE, nothing fused: the level's float and the time stamp's double are computed here
          ("text.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE like json.hip: the same level float
          ("flight_text.hip", ["-O3", "-ffp-contract=off"], True),   # text.hip's flags: the route line's time stamp is json.hip's double
+         ("stats.hip", ["-O3", "-ffp-contract=off"], True),     # IEEE: the level ratio's double division is the host's
          ("pcm.hip", ["-O3"], True),        # a transpose: the int16 scale is exact, the f32 path moves words (nothing to contract)
          ("flights.cpp", ["-O2"], True), ("acg_api.cpp", ["-O2"], True)]
 # which units see which define (the others are compiled once and shared between the libraries)
@@ -84,7 +85,7 @@ def build_lib(force=False, stamp=False, poly=False, lab=False):
     os.makedirs(OBJDIR, exist_ok=True)
     defs = (["-DACG_LAB"] if (lab or stamp or poly) else []) + (["-DACG_MSK_STAMP"] if stamp else []) + (["-DACG_MSK_SINCOS_POLY"] if poly else [])
     out_lib = LIB_STAMP if stamp else LIB_POLY if poly else LIB_LAB if lab else LIB
-    hdrs = [os.path.join(CSRC, "acg_internal.h"), os.path.join(CSRC, "flights.h"), os.path.join(CSRC, "msk_common.h"), os.path.join(CSRC, "json_num.h"), os.path.join(CSRC, "text_num.h"), os.path.join(CSRC, "flight_text_num.h"), os.path.join(CSRC, "sink_pack.h"), os.path.join(CSRC, "sink_put.h"), os.path.join(CSRC, "fir_mm_plan.h"), os.path.join(CSRC, "fir_plan.h"), os.path.join(INC, "acarsdec_amd.h"),
+    hdrs = [os.path.join(CSRC, "acg_internal.h"), os.path.join(CSRC, "flights.h"), os.path.join(CSRC, "msk_common.h"), os.path.join(CSRC, "json_num.h"), os.path.join(CSRC, "text_num.h"), os.path.join(CSRC, "flight_text_num.h"), os.path.join(CSRC, "sink_pack.h"), os.path.join(CSRC, "sink_put.h"), os.path.join(CSRC, "msg_keep.h"), os.path.join(CSRC, "fir_mm_plan.h"), os.path.join(CSRC, "fir_plan.h"), os.path.join(INC, "acarsdec_amd.h"),
             os.path.join(INC, "acarsdec_amd_lab.h"), os.path.abspath(__file__)]   # flags live here
     hdrs += sorted(os.path.join(CSRC, "lab", f) for f in os.listdir(os.path.join(CSRC, "lab")))       # the lab-only kernel families fir.hip includes
     objs = []

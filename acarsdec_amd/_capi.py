@@ -94,6 +94,18 @@ class FlightTextConfig(C.Structure):
     _fields_ = [("nbch", C.c_int), ("station_id", C.c_char * 33)]
 
 
+class ChanStats(C.Structure):
+    """acg_chan_stats: one channel's reception statistics (the events the reference reports under -v)"""
+    _fields_ = [(n, C.c_uint) for n in ("blocks", "too_short", "parity_many", "parity_blocks", "parity_errs", "crc_errors", "unfixable",
+                                        "fixed", "parity_problem", "kept", "miss_txt_end", "uplink_dropped", "label_dropped",
+                                        "empty_dropped", "delivered", "reserved")] + \
+               [("lvl_min", C.c_double), ("lvl_max", C.c_double), ("last_end_sample", C.c_longlong)]
+
+
+# the same record as a numpy structured dtype (Decoder.stats hands out arrays of it)
+CHAN_STATS_DTYPE = [(n, "<u4") for n, _ in ChanStats._fields_[:16]] + [("lvl_min", "<f8"), ("lvl_max", "<f8"), ("last_end_sample", "<i8")]
+
+
 MONITOR_CLS_LEN, MONITOR_HDR_LEN, MONITOR_ROW_MAX, ROUTE_LINE_MAX = 7, 110, 78, 363
 JSON_LINE_MAX = 2496
 
@@ -121,6 +133,7 @@ class LaunchShape(C.Structure):
                 ("runs", C.c_uint), ("wave_slots", C.c_uint), ("workgroups", C.c_uint), ("waves", C.c_uint)]
 
 
+assert C.sizeof(ChanStats) == 88
 assert C.sizeof(Flight) == 120 and C.sizeof(Route) == 56 and C.sizeof(FlightEvent) == 88
 
 BIT_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_float, C.c_float)
@@ -184,6 +197,8 @@ SYMBOLS = {
     "acg_text_enable": (C.c_int, [C.c_void_p, C.POINTER(TextConfig), C.c_void_p]),
     "acg_drain_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "acg_collect_text": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "acg_stats_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "acg_stats_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "acg_read_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "acg_read_bits_all": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acg_bit_capacity": (C.c_int, [C.c_void_p]),

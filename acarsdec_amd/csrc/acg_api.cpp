@@ -220,6 +220,8 @@ struct acg_ctx {
     AcgFlights* flights = nullptr;          // acg_flights_enable: the flight table (flights.cpp), updated by every message entry point
     struct AcgSinkState* text = nullptr;    // acg_text_enable: the text sink (text.hip), as json
     struct AcgSinkState* json = nullptr;    // acg_json_enable: the JSON sink (json.hip): configuration, work space, rendered lines
+    AcgChanStats* d_stats = nullptr;        // acg_stats_enable: the per-channel statistics (stats.hip), [nch]; null = off
+    unsigned long long lost_blocks = 0;     // ... and the blocks lost to a lapped ring since the table was zeroed
     unsigned int* d_work = nullptr;     // FIR run dispensers, ACG_DISP_WORDS words per chunk slot
     bool stream_identity = true;        // channel c reads stream c
     unsigned short* d_crctab = nullptr; // [256] + syndromes [1936] (ACG_F_REPAIR)
@@ -301,6 +303,7 @@ static void free_all(acg_ctx* c)
     hipFree(c->d_taps); hipFree(c->d_stream_of); hipFree(c->d_groups); hipFree(c->d_group_ch); hipFree(c->d_gtaps); hipFree(c->d_mm_img); hipFree(c->d_mm1_img); hipFree(c->d_mm_chan); hipFree(c->d_dm_all); hipFree(c->d_st);
     hipFree(c->d_h); hipFree(c->d_sctab); hipFree(c->d_txt); hipFree(c->d_frames); hipFree(c->d_frame_count);
     hipFree(c->d_stamp);
+    hipFree(c->d_stats);
     hipFree(c->d_msgs); std::free(c->h_msgs);
     hipFree(c->d_kmsgs); hipFree(c->d_oooi); hipFree(c->d_kwork); std::free(c->h_oooi);
     if (c->flights) acg_fl_destroy(c->flights);
@@ -608,6 +611,13 @@ extern "C" int acg_create(acg_ctx** out, const acg_config* cfg)
     return ACG_OK;
 }
 
+// the statistics table as acg_stats_enable and acg_reset leave it: all zero (AcgChanStats: its "none yet" values are zeros)
+static int stats_zero(acg_ctx* ctx)
+{
+    ctx->lost_blocks = 0;
+    return zero_sync(ctx, ctx->d_stats, (size_t)ctx->cfg.nch * sizeof(AcgChanStats));
+}
+
 extern "C" int acg_reset(acg_ctx* ctx)
 {
     if (!ctx) return ACG_EINVAL;
@@ -635,6 +645,7 @@ extern "C" int acg_reset(acg_ctx* ctx)
     ctx->last_len = 0;
     ctx->last_had_demod = false;
     if (ctx->flights && acg_fl_reset(ctx->flights) != ACG_OK) return fail(ctx, ACG_EHIP, "flight table reset");
+    if (ctx->d_stats) return stats_zero(ctx);
     return ACG_OK;
 }
 
@@ -1370,6 +1381,7 @@ static int ring_claim(acg_ctx* ctx, unsigned int upto, int max, unsigned int* pe
         char msg[96];
         std::snprintf(msg, sizeof(msg), "block queue lapped: the %u oldest blocks are lost", *pending - ctx->frame_cap);
         ctx->err = msg;
+        if (ctx->d_stats) ctx->lost_blocks += *pending - ctx->frame_cap;   // (they belong to no channel: their records are gone)
         ctx->consumed = upto - ctx->frame_cap;
         *pending = ctx->frame_cap;
         rc = ACG_EOVERFLOW;
@@ -1384,6 +1396,17 @@ static int ring_result(acg_ctx* ctx, int rc, unsigned int pending, unsigned int 
 {
     if (rc != ACG_OK) return rc;
     if (take < pending) return fail(ctx, ACG_EAGAIN, again);
+    return ACG_OK;
+}
+
+// Statistics on: stats.hip's pass over the blocks [consumed, consumed + take) this call consumes, on the copy stream behind
+// whatever the entry point has put there (msg_entry: the split's records lie in d_msgs).  Off: nothing is launched.
+static int launch_stats(acg_ctx* ctx, unsigned int take, bool msg_entry)
+{
+    if (!ctx->d_stats || !take) return ACG_OK;
+    const AcgStatsPass sp{ctx->d_frames, ctx->frame_cap, ctx->consumed, take, msg_entry ? ctx->d_msgs : nullptr, &ctx->msg_filter,
+                          msg_entry && ctx->msg_filter_on ? 1 : 0, ctx->d_stats, ctx->cfg.nch};
+    if (acg_launch_chan_stats(&sp, ctx->copy_stream) != 0) return fail(ctx, ACG_EHIP, "statistics pass failed");
     return ACG_OK;
 }
 
@@ -1420,6 +1443,7 @@ static int fetch_frames(acg_ctx* ctx, int lag, acg_frame* out, int max_frames, i
         const unsigned int cap = ctx->frame_cap;
         const unsigned int first = ctx->consumed & (cap - 1);      // (cap is a power of two)
         const unsigned int n1 = std::min(take, cap - first);
+        if (const int sr = launch_stats(ctx, take, false)) return sr;
         HIPCHK(ctx, hipMemcpyAsync(rec, ctx->d_frames + first, (size_t)n1 * sizeof(AcgFrameRec),
                                    hipMemcpyDeviceToHost, ctx->copy_stream));
         if (take > n1)
@@ -1527,7 +1551,7 @@ static int launch_split(acg_ctx* ctx, unsigned int take, bool labels, unsigned i
     }
     if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, take, ctx->d_msgs, ctx->copy_stream, labels ? &pass : nullptr) != 0)
         return fail(ctx, ACG_EHIP, "message split launch failed");
-    return ACG_OK;
+    return launch_stats(ctx, take, true);
 }
 
 static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
@@ -2564,6 +2588,45 @@ extern "C" int acg_lab_time_sink_passes(const acg_msg* in, int n, const acg_json
 
 extern "C" int acg_bit_capacity(const acg_ctx* ctx) { return ctx ? ctx->bit_cap : 0; }
 extern "C" int acg_max_lag(const acg_ctx* ctx) { return ctx ? ctx->lag_max : 0; }
+
+// ------------------------------------------------------------------------------------------
+// Per-channel reception statistics (stats.hip)
+extern "C" int acg_stats_enable(acg_ctx* ctx, int on)
+{
+    if (!ctx) return ACG_EINVAL;
+    if (!acg_launch_chan_stats) return fail(ctx, ACG_ESTATE, "no statistics unit");
+    if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    if (!on) {
+        hipFree(ctx->d_stats);
+        ctx->d_stats = nullptr;
+        ctx->lost_blocks = 0;
+        return ACG_OK;
+    }
+    if (!ctx->d_stats) HIPCHK(ctx, hipMalloc(&ctx->d_stats, (size_t)ctx->cfg.nch * sizeof(AcgChanStats)));
+    return stats_zero(ctx);
+}
+
+extern "C" int acg_stats_read(acg_ctx* ctx, int ch0, int n, acg_chan_stats* out, unsigned long long* lost_blocks)
+{
+    if (!ctx) return ACG_EINVAL;
+    if (!ctx->d_stats) return fail(ctx, ACG_ESTATE, "statistics are off");
+    if (ch0 < 0 || n < 0 || ch0 > ctx->cfg.nch || n > ctx->cfg.nch - ch0 || (n > 0 && !out)) return fail(ctx, ACG_EINVAL, "statistics: bad channel range");
+    static_assert(sizeof(AcgChanStats) == sizeof(acg_chan_stats), "device and public statistics record must have one layout");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    if (n) HIPCHK(ctx, hipMemcpy(out, ctx->d_stats + ch0, (size_t)n * sizeof(AcgChanStats), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {                                 // the device's encodings, chosen so that zero means "none yet"
+        unsigned long long inv;
+        std::memcpy(&inv, &out[i].lvl_min, sizeof(inv));
+        inv = inv ? ~inv : 0ull;                                  // (lvl_max_bits is the ratio's own bit pattern)
+        std::memcpy(&out[i].lvl_min, &inv, sizeof(inv));
+        out[i].last_end_sample -= 1;
+    }
+    if (lost_blocks) *lost_blocks = ctx->lost_blocks;
+    return ACG_OK;
+}
 
 extern "C" int acg_read_bits(acg_ctx* ctx, int ch, float* vo, float* lvl, int max_bits, int* nbits)
 {

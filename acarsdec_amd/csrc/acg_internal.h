@@ -43,9 +43,47 @@ struct AcgFrameRec {
     long long end_sample;
     unsigned char crc[2];
     unsigned char status;       // 0 raw (as queued by decodeAcars), 1 processed + kept, 2 processed + dropped
-    unsigned char pad[1];
+    unsigned char pad[1];       // what the repair pass made of the block: ACG_BLK_* below (0 while status is 0); no public record has it
     int soh_back;               // end_sample - (sample at which the SOH byte completed): where the reference stamps blk->tv (acars.c:290)
     unsigned char txt[256];     // 16-byte aligned, 16-byte multiples for vector copies
+};
+
+// AcgFrameRec::pad[0], written by blk_repair_kernel beside `status` and read by stats.hip: the exit the block took through
+// acars.c:123-207 and what the reference printed on the way
+#define ACG_BLK_SHORT 1u            // acars.c:124
+#define ACG_BLK_PARITY_MANY 2u      // :145
+#define ACG_BLK_UNFIXABLE 3u        // :171, :183
+#define ACG_BLK_PARITY_PROBLEM 4u   // :202
+#define ACG_BLK_KEPT 5u             // :209
+#define ACG_BLK_REASON 7u
+#define ACG_BLK_F_PARITY 8u         // "parity error(s): k" (:154), k = 1 .. 3 in bits 6-7
+#define ACG_BLK_F_CRC 16u           // "crc error" (:167)
+#define ACG_BLK_F_DEL 32u           // queued by the DEL rule (:324-332)
+#define ACG_BLK_PN_SHIFT 6
+
+// One channel's statistics on the device: the public acg_chan_stats field for field, except that the last three are encoded so
+// that an all-zero record means "nothing yet" and every update is an integer atomic MAX: the bit pattern of a non-negative double
+// orders like the double, so lvl_max_bits is the greatest ratio's pattern, lvl_min_inv the COMPLEMENT of the least ratio's, and
+// end_sample_p1 the newest kept block's end_sample + 1.  acg_stats_read decodes them.
+struct AcgChanStats {
+    unsigned int blocks, too_short, parity_many, parity_blocks, parity_errs, crc_errors, unfixable, fixed, parity_problem, kept,
+        miss_txt_end, uplink_dropped, label_dropped, empty_dropped, delivered, reserved;
+    unsigned long long lvl_min_inv, lvl_max_bits;
+    long long end_sample_p1;
+};
+
+// One pass of stats.hip over blocks [first, first + n) of the ring
+struct AcgMsgRec;
+struct AcgLabelFilter;
+struct AcgStatsPass {
+    const AcgFrameRec* frames;
+    unsigned int cap, first, n;
+    const AcgMsgRec* msgs;      // message entry points: the split's records of the same blocks (read only when filter_on); else null
+    const AcgLabelFilter* f;    // HOST pointer to the context's filter (the launcher passes it by value)
+    int filter_on;              // 1: a message entry point with a filter set (kept = the filters' drops + delivered); 0: every
+                                // kept block is delivered (a frame entry point, or no filter)
+    AcgChanStats* stats;        // [nch]
+    int nch;
 };
 
 // One split message on the device: the public acg_msg (include/acarsdec_amd.h) field for field, with the two
@@ -380,6 +418,9 @@ int acg_launch_sort_pairs(unsigned long long* ka, unsigned int* va, unsigned lon
 __attribute__((weak)) int acg_launch_json(const AcgSinkPass* p, void* stream);
 // text.hip: the same for the text formats (weak for the same reason)
 __attribute__((weak)) int acg_launch_text(const AcgSinkPass* p, void* stream);
+// stats.hip: the per-channel statistics of the blocks an entry point consumes (weak for the same reason: there acg_stats_enable
+// says ACG_ESTATE)
+__attribute__((weak)) int acg_launch_chan_stats(const AcgStatsPass* p, void* stream);
 // pcm.hip: the de-interleave of one call (weak for the same reason: there the PCM entry points say ACG_ESTATE)
 __attribute__((weak)) int acg_launch_pcm_deint(const PcmArgs* a, void* stream);
 int acg_launch_sincos_selftest(const double* x, double* s, double* c, int n, const double* sctab, void* stream);

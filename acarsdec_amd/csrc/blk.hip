@@ -11,6 +11,7 @@
 
 #define MAXPERR 3
 #define ETX 0x83
+#define ETB 0x97
 #define STX 0x02
 
 __device__ __forceinline__ bool crc_acceptable(const unsigned short* synd, unsigned short crc)
@@ -116,8 +117,21 @@ __global__ __launch_bounds__(64 * BLK_WAVES) void blk_repair_kernel(AcgFrameRec*
         const unsigned int crcb = ncrcb;
         const int len = nlen;
         if (q + nwaves - lo < hi - lo) request(q + nwaves);
+        // Which rule queued the block, for the statistics (stats.hip): through acars.c:319-322 it ends in ETX or ETB AS RECEIVED,
+        // through the DEL rule (acars.c:324-332) it never does -- the raw last byte, before byte 12 is forced and before any repair
+        // (len is wave-uniform: one select and one cross-lane read; lane 0 writes the outcome byte beside `status` on every exit)
+        unsigned int why = 0;
+        {
+            const int li = len > 0 ? (len - 1) & 255 : 0;
+            const unsigned int sel = (li >> 6) == 0 ? raw[0] : (li >> 6) == 1 ? raw[1] : (li >> 6) == 2 ? raw[2] : raw[3];
+            const unsigned int last = (unsigned int)__shfl((int)sel, li & 63);
+            if (len > 0 && last != ETX && last != ETB) why = ACG_BLK_F_DEL;
+        }
         if (len < 13) {                                                    // acars.c:124
-            if (lane == 0) f->status = 2;
+            if (lane == 0) {
+                f->status = 2;
+                f->pad[0] = (unsigned char)(why | ACG_BLK_SHORT);
+            }
             continue;
         }
         unsigned int c[4];
@@ -143,9 +157,13 @@ __global__ __launch_bounds__(64 * BLK_WAVES) void blk_repair_kernel(AcgFrameRec*
         const unsigned short crc = (unsigned short)x;
         const int pn = __popcll(bad[0]) + __popcll(bad[1]) + __popcll(bad[2]) + __popcll(bad[3]);
         if (pn > MAXPERR) {                                                // acars.c:145
-            if (lane == 0) f->status = 2;
+            if (lane == 0) {
+                f->status = 2;
+                f->pad[0] = (unsigned char)(why | ACG_BLK_PARITY_MANY);
+            }
             continue;
         }
+        why |= (pn ? ACG_BLK_F_PARITY | ((unsigned int)pn << ACG_BLK_PN_SHIFT) : 0u) | (crc ? ACG_BLK_F_CRC : 0u);   // acars.c:153-167
         int pr[MAXPERR] = {0, 0, 0};                                       // positions of the flagged bytes, ascending
         {
             int k = 0;
@@ -221,7 +239,10 @@ __global__ __launch_bounds__(64 * BLK_WAVES) void blk_repair_kernel(AcgFrameRec*
             }
         }
         if (!ok) {
-            if (lane == 0) f->status = 2;
+            if (lane == 0) {
+                f->status = 2;
+                f->pad[0] = (unsigned char)(why | ACG_BLK_UNFIXABLE);
+            }
             continue;
         }
         int pn2 = 0;                                                        // acars.c:195-207: parity once more, then strip it
@@ -233,6 +254,7 @@ __global__ __launch_bounds__(64 * BLK_WAVES) void blk_repair_kernel(AcgFrameRec*
         if (lane == 0) {
             f->err = pn;                                                    // acars.c:156
             f->status = pn2 ? 2 : 1;
+            f->pad[0] = (unsigned char)(why | (pn2 ? ACG_BLK_PARITY_PROBLEM : ACG_BLK_KEPT));
         }
     }
     // the last workgroup out moves the mark (every workgroup has read it by then) and re-arms the counter

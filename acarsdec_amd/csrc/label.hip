@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "acg_internal.h"
 #include "acarsdec_amd.h"
+#include "msg_keep.h"
 
 #define LBL_WG 256
 #define LBL_NG 7                // guards per label (44 has 7)
@@ -95,48 +96,7 @@ __constant__ LblEntry k_labels[] = {
 static_assert(sizeof(acg_oooi) == 40 && offsetof(acg_oooi, decoded) == 35, "acg_oooi layout (oooi_t + decoded + padding)");
 static_assert(ACG_MSG_TXT == ACG_MSGTXTMAX, "text row");
 
-// a record's text as the decoder sees it: bytes at or past txt_len (clamped to the row) are 0
-struct Txt {
-    const unsigned char* p;
-    int n;
-    __device__ unsigned char operator()(int i) const { return (unsigned)i < (unsigned)n ? p[i] : (unsigned char)0; }
-};
-
-__device__ __forceinline__ Txt rec_txt(const AcgMsgRec* r)
-{
-    int n = r->txt_len;
-    n = n < 0 ? 0 : n > ACG_MSG_TXT ? ACG_MSG_TXT : n;
-    return Txt{(const unsigned char*)r->txt, n};
-}
-
-// output.c:537-540, 650 (and outputmsg()'s callers: blocks the repair dropped never get there)
-// -A and -b: what decides whether a block reaches addFlight() (output.c:537-540)
-__device__ __forceinline__ bool msg_keep_ab(const AcgMsgRec* r, const AcgLabelFilter& f)
-{
-    if (!r->valid) return false;
-    if ((f.flags & ACG_MSGF_DOWNLINK_ONLY) && !r->down) return false;
-    if (f.nlabels > 0) {
-        // the label as a C string (label[2] is the split's terminator), packed like the normalised tokens
-        const unsigned int l0 = (unsigned char)r->label[0], l1 = l0 ? (unsigned char)r->label[1] : 0u;
-        const unsigned int key = l0 | (l1 << 8);
-        bool hit = false;
-        for (int i = 0; i < f.nlabels; ++i) hit |= (l0 != 0) & (f.tok[i] == key);
-        if (!hit) return false;
-    }
-    return true;
-}
-
-// -e (output.c:650)
-__device__ __forceinline__ bool msg_keep_e(const AcgMsgRec* r, const AcgLabelFilter& f)
-{
-    return !((f.flags & ACG_MSGF_SKIP_EMPTY) && rec_txt(r)(0) == 0);
-}
-
-// output.c:537-540, 650 (and outputmsg()'s callers: blocks the repair dropped never get there)
-__device__ __forceinline__ bool msg_keep(const AcgMsgRec* r, const AcgLabelFilter& f)
-{
-    return msg_keep_ab(r, f) && msg_keep_e(r, f);
-}
+// (the record's text view and the three keep predicates: msg_keep.h, shared with stats.hip)
 
 __device__ __forceinline__ int find_byte(const Txt& t, int from, unsigned char c)   // strchr: stops at the first NUL
 {

@@ -322,6 +322,24 @@ class Decoder:
             if rc == K.OK:
                 return out
 
+    # ---- per-channel reception statistics (acg_stats_enable, acg_stats_read) ----------------------------------------------
+    def enable_stats(self):
+        """Starts (or zeroes) the per-channel statistics: the events the reference reports under -v, counted on the device over
+        the blocks every entry point consumes from now on (needs repair=True)."""
+        self._chk(self.L.acg_stats_enable(self.ctx, 1))
+
+    def disable_stats(self):
+        self._chk(self.L.acg_stats_enable(self.ctx, 0))
+
+    def stats(self, ch0=0, n=None):
+        """(table, lost_blocks): the records of channels ch0 .. ch0 + n - 1 (default: all from ch0) as a numpy structured array
+        of K.CHAN_STATS_DTYPE, and the blocks lost to a lapped queue.  Waits for everything issued, like a drain."""
+        n = self.nch - int(ch0) if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=K.CHAN_STATS_DTYPE)
+        lost = C.c_ulonglong(0)
+        self._chk(self.L.acg_stats_read(self.ctx, int(ch0), n, out.ctypes.data, C.byref(lost)))
+        return out, int(lost.value)
+
     # ---- the flight table (acg_flights_enable, acg_flight_snapshot, acg_drain_routes) --------------------------------------
     def enable_flights(self, t0=0.0, mdly=600, max_flights=4096):
         """addFlight() / routejson() (output.c:361-456) on the device for every message entry point from now on.  t0: wall clock
@@ -650,6 +668,25 @@ def route_json(route, station=None):
     out["depa"] = route.sa.decode("latin1")
     out["dsta"] = route.da.decode("latin1")
     return out
+
+
+def stats_level_db(stats):
+    """(lvl_min_db, lvl_max_db) as float32 arrays: the table's two level ratios through acars.c:351's arithmetic, 10 * log10 in
+    double narrowed to float (what acg_frame.lvl and acg_msg.lvl hold); -inf for a ratio of 0 (no kept block yet)"""
+    import math
+
+    def db(v):
+        return np.array([10 * math.log10(x) if x > 0 else -math.inf for x in v.tolist()], dtype=np.float64).astype(np.float32)
+    return db(stats["lvl_min"]), db(stats["lvl_max"])
+
+
+def scan_report(stats, freqs_hz):
+    """scan.sh's last line for a whole table: rows (freq, delivered, kept, blocks), one per channel, busiest first (by
+    delivered, then kept, then blocks; ties in channel order)"""
+    assert len(freqs_hz) == len(stats)
+    rows = [(freqs_hz[i], int(stats["delivered"][i]), int(stats["kept"][i]), int(stats["blocks"][i])) for i in range(len(stats))]
+    order = sorted(range(len(rows)), key=lambda i: (-rows[i][1], -rows[i][2], -rows[i][3], i))
+    return [rows[i] for i in order]
 
 
 def frame_tuple(f):

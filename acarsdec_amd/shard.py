@@ -120,3 +120,38 @@ def gather_flight_events(events, dst=0, dist=None, device=None):
         return None
     parts = [np.frombuffer(b.cpu().numpy()[: n * rec].tobytes(), dtype=ev.dtype) for b, n in zip(box, counts)]
     return np.concatenate(parts)
+
+
+def gather_chan_stats(stats, rank, world, dst=0, dist=None, device=None):
+    """Every rank's per-channel statistics (Decoder.stats: a structured array of 88-byte records in LOCAL channel order) as ONE
+    table in GLOBAL channel order on `dst`: local channel l of rank r is global channel l * world + r (owned_channels), and the
+    channels are disjoint, so there is nothing to merge -- rows only move.  The ranks may own different numbers of channels (a
+    total that is no multiple of the world): the counts are exchanged first, then ONE gather carries the rows, padded to the
+    largest count.  CPU tensors over gloo, device tensors over RCCL, like gather_flight_events.  None on the other ranks."""
+    from . import _capi as K
+    st = np.ascontiguousarray(np.asarray(stats, dtype=K.CHAN_STATS_DTYPE))
+    if dist is None:
+        assert world == 1 and rank == 0
+        return st
+    import torch
+    rec = st.dtype.itemsize
+    mine = torch.tensor([len(st)], dtype=torch.int64, device=device)
+    counts = [torch.zeros(1, dtype=torch.int64, device=device) for _ in range(world)]
+    dist.all_gather(counts, mine)
+    counts = [int(c.item()) for c in counts]
+    width = max(max(counts), 1) * rec
+    row = torch.zeros(width, dtype=torch.uint8, device=device)
+    if len(st):
+        row[: len(st) * rec] = torch.from_numpy(st.view(np.uint8).reshape(-1).copy()).to(row.device)
+    box = [torch.zeros(width, dtype=torch.uint8, device=device) for _ in range(world)] if rank == dst else None
+    dist.gather(row, box, dst=dst)
+    if rank != dst:
+        return None
+    total = sum(counts)
+    out = np.zeros(total, dtype=st.dtype)
+    for r, (b, n) in enumerate(zip(box, counts)):
+        own = owned_channels(total, r, world)
+        if len(own) != n:
+            raise ValueError("rank %d holds %d channels, the round-robin map gives it %d of %d" % (r, n, len(own), total))
+        out[own] = np.frombuffer(b.cpu().numpy()[: n * rec].tobytes(), dtype=st.dtype)
+    return out

@@ -599,6 +599,51 @@ int  acg_text_enable(acg_ctx *ctx, const acg_text_config *cfg, const int *Fr_hz)
 int  acg_drain_text(acg_ctx *ctx, char *out, size_t cap, size_t *nbytes, unsigned int *offs, int max_recs, int *nrecs);
 int  acg_collect_text(acg_ctx *ctx, int lag, char *out, size_t cap, size_t *nbytes, unsigned int *offs, int max_recs, int *nrecs);
 
+/* ---- per-channel reception statistics: what the reference says under -v, counted on the device --------------------------------
+ * One record per channel, resident on the device across calls and updated in the round trips the entry points above already make
+ * (csrc/stats.hip: one launch behind the split / label pass of a message entry point, one of its own in the frame entry points).
+ * Every counter is the number of times the reference prints the line named beside it (acars.c, output.c); blocks the repair drops
+ * and blocks a filter drops never cross to the host, so this table is the only place they can be told apart.
+ *
+ * Counting rules.  A block is counted when, and only when, an entry point consumes it: a call that returns ACG_EAGAIN has counted
+ * what it handed out or dropped and nothing else, a call that consumes nothing counts nothing, no block is counted twice.  The frame
+ * entry points move the block-level fields and `delivered`; the three filter fields move in the message entry points (acg_*_msgs*,
+ * acg_*_json, acg_*_text) only.  Blocks lost to a lapped queue (ACG_EOVERFLOW) belong to no channel: they go to `lost_blocks`.
+ * After every call  blocks == too_short + parity_many + unfixable + parity_problem + kept, and on a channel consumed through message
+ * entry points only  kept == uplink_dropped + label_dropped + empty_dropped + delivered.
+ * The counters are 32-bit and WRAP: at ten blocks per second a channel fills one in 13 years.  Every accumulator is an integer add
+ * or an integer minimum / maximum, so a snapshot does not depend on the order the device took the blocks in.
+ * Not counted: the two resets only the framing sees ("too many parity errors" without a count, acars.c:313, and "too long", :336);
+ * they queue no block, and counting them inside the demodulator was not free (profiles/LEDGER.md, "Per-channel reception statistics"). */
+typedef struct {
+    unsigned int blocks;            /* blocks taken off the queue                          "get message #n"            acars.c:121 */
+    unsigned int too_short;         /* dropped: fewer than 13 bytes                        "too short"                 :126 */
+    unsigned int parity_many;       /* dropped                                             "too many parity errors: k" :148 */
+    unsigned int parity_blocks;     /* "parity error(s): k" lines ...                                                   :154 */
+    unsigned int parity_errs;       /* ... and the sum of their k */
+    unsigned int crc_errors;        /*                                                     "crc error"                 :167 */
+    unsigned int unfixable;         /* dropped                                             "not able to fix errors"    :173, :185 */
+    unsigned int fixed;             /* (with parity errors also when the CRC was clean)    "errors fixed"              :178, :190 */
+    unsigned int parity_problem;    /* dropped                                             "parity check problem"      :203 */
+    unsigned int kept;              /* blocks that reach outputmsg()                                                    :209 */
+    unsigned int miss_txt_end;      /* blocks queued by the DEL rule, whatever became of them  "miss txt end"           :326 */
+    unsigned int uplink_dropped;    /* dropped by -A, -b, -e: a block is charged to the FIRST filter that drops it, in the */
+    unsigned int label_dropped;     /* reference's order (output.c:537, 539, 650)  */
+    unsigned int empty_dropped;
+    unsigned int delivered;         /* handed to the caller */
+    unsigned int reserved;
+    double lvl_min, lvl_max;        /* least and greatest MskLvlSum / MskBitCount over kept blocks (acg_host_level_db turns a ratio
+                                     * into the dB of acars.c:351); blocks with MskBitCount <= 0 are skipped; 0 and 0 while none */
+    long long last_end_sample;      /* end_sample of the newest kept block, -1 while none */
+} acg_chan_stats;
+/* on = 1: allocates and zeroes the table and starts counting (already on: zeroes); on = 0: stops and frees -- every entry point
+ * then issues exactly what it issues without this section.  acg_reset zeroes the table and keeps the switch.  A slot's statistics
+ * stay with the slot: acg_set_state does not move them.  ACG_ESTATE: context without ACG_F_REPAIR. */
+int  acg_stats_enable(acg_ctx *ctx, int on);
+/* Waits for everything issued (like a drain) and copies the records of channels ch0 .. ch0 + n - 1; *lost_blocks (may be null):
+ * blocks lost to a lapped queue since the table was zeroed.  ACG_ESTATE while off, ACG_EINVAL: a range outside the context. */
+int  acg_stats_read(acg_ctx *ctx, int ch0, int n, acg_chan_stats *out, unsigned long long *lost_blocks);
+
 /* Per-bit records of the LAST process call for one channel (needs ACG_F_BITLOG):
  * vo = the value putbit() receives (msk.c:122-126), lvl = cabsf(v) (msk.c:110). */
 int  acg_read_bits(acg_ctx *ctx, int ch, float *vo, float *lvl, int max_bits, int *nbits);
