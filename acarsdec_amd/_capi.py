@@ -113,6 +113,8 @@ JSON_LINE_MAX = 2496
 TEXT_REC_MAX = 704
 TEXT_ONELINE, TEXT_STD, TEXT_PP, TEXT_SV = 1, 2, 3, 4
 TEXT_F_DATE, TEXT_F_FREQ = 1, 2
+SINK_JSON, SINK_TEXT = 1, 2             # acg_sink_keys
+SINK_KEY_END_BITS = 44                   # a key is (channel number handed out) << 44 | end_bit
 
 
 class TextConfig(C.Structure):
@@ -197,6 +199,9 @@ SYMBOLS = {
     "acg_text_enable": (C.c_int, [C.c_void_p, C.POINTER(TextConfig), C.c_void_p]),
     "acg_drain_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "acg_collect_text": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "acg_channel_numbers_check": (C.c_int, [C.c_void_p, C.c_int]),
+    "acg_set_channel_numbers": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "acg_sink_keys": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "acg_stats_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "acg_stats_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "acg_read_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),

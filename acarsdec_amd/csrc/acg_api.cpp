@@ -220,6 +220,8 @@ struct acg_ctx {
     AcgFlights* flights = nullptr;          // acg_flights_enable: the flight table (flights.cpp), updated by every message entry point
     struct AcgSinkState* text = nullptr;    // acg_text_enable: the text sink (text.hip), as json
     struct AcgSinkState* json = nullptr;    // acg_json_enable: the JSON sink (json.hip): configuration, work space, rendered lines
+    std::vector<int> chnum;                 // acg_set_channel_numbers: the number handed out for each slot; empty = the slot's own
+    int* d_chnum = nullptr;                 // ... on the device, for the sinks' passes and the flight table; null = identity
     AcgChanStats* d_stats = nullptr;        // acg_stats_enable: the per-channel statistics (stats.hip), [nch]; null = off
     unsigned long long lost_blocks = 0;     // ... and the blocks lost to a lapped ring since the table was zeroed
     unsigned int* d_work = nullptr;     // FIR run dispensers, ACG_DISP_WORDS words per chunk slot
@@ -304,6 +306,7 @@ static void free_all(acg_ctx* c)
     hipFree(c->d_h); hipFree(c->d_sctab); hipFree(c->d_txt); hipFree(c->d_frames); hipFree(c->d_frame_count);
     hipFree(c->d_stamp);
     hipFree(c->d_stats);
+    hipFree(c->d_chnum);
     hipFree(c->d_msgs); std::free(c->h_msgs);
     hipFree(c->d_kmsgs); hipFree(c->d_oooi); hipFree(c->d_kwork); std::free(c->h_oooi);
     if (c->flights) acg_fl_destroy(c->flights);
@@ -1410,6 +1413,15 @@ static int launch_stats(acg_ctx* ctx, unsigned int take, bool msg_entry)
     return ACG_OK;
 }
 
+// acg_set_channel_numbers: the staged records' slots become the numbers handed out, before anything is ordered or copied out
+template <class Rec>
+static void number_channels(const acg_ctx* ctx, Rec* rec, unsigned int n)
+{
+    const size_t nmap = ctx->chnum.size();
+    for (unsigned int i = 0; nmap && i < n; ++i)
+        if ((size_t)(unsigned int)rec[i].chn < nmap) rec[i].chn = ctx->chnum[(size_t)rec[i].chn];
+}
+
 // per channel in order (the contract): sorts an index into the records, not the records
 template <class Rec>
 static void order_by_channel(std::vector<unsigned int>& order, const Rec* rec)
@@ -1452,6 +1464,7 @@ static int fetch_frames(acg_ctx* ctx, int lag, acg_frame* out, int max_frames, i
         HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
     }
     ctx->consumed += take;
+    number_channels(ctx, rec, take);
     std::vector<unsigned int> order(take);
     for (unsigned int i = 0; i < take; ++i) order[i] = i;
     order_by_channel(order, rec);
@@ -1592,6 +1605,7 @@ static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int m
     } else if (const int cr = commit_imports(ctx)) {
         return cr;
     }
+    number_channels(ctx, ctx->h_msgs, nrec);
     const AcgMsgRec* rec = ctx->h_msgs;
     ctx->consumed += take;
     std::vector<unsigned int> order;
@@ -1779,6 +1793,43 @@ extern "C" int acg_selftest_msg_labels(const acg_msg* in, int n, const acg_msg_f
     return rc;
 }
 
+// ---- the channel numbers a sharded host hands out (acg_set_channel_numbers; the sinks' order keys: acg_sink_keys below) ---
+extern "C" int acg_channel_numbers_check(const int* chn, int n)
+{
+    if (n < 0 || (n > 0 && !chn)) return ACG_EINVAL;
+    if (n > (1 << 20)) return ACG_EINVAL;                         // (more values than numbers: two are equal)
+    unsigned char* seen = (unsigned char*)std::calloc(1u << 17, 1);      // a bit per number
+    if (!seen) return ACG_ENOMEM;
+    int rc = ACG_OK;
+    for (int i = 0; i < n && rc == ACG_OK; ++i) {
+        const unsigned int v = (unsigned int)chn[i];              // (a negative value is a large one)
+        if (v >= (1u << 20) || (seen[v >> 3] >> (v & 7u) & 1u)) rc = ACG_EINVAL;
+        else seen[v >> 3] |= (unsigned char)(1u << (v & 7u));
+    }
+    std::free(seen);
+    return rc;
+}
+
+extern "C" int acg_set_channel_numbers(acg_ctx* ctx, const int* chn)
+{
+    if (!ctx) return ACG_EINVAL;
+    const int nch = ctx->cfg.nch;
+    if (chn && acg_channel_numbers_check(chn, nch) != ACG_OK) return fail(ctx, ACG_EINVAL, "channel numbers: outside 0 .. 2^20 - 1, or not distinct");
+    int* d_new = nullptr;
+    // (every entry point that reads the map ends with a synchronise of its stream: nothing in flight holds the old array)
+    if (hipSetDevice(ctx->cfg.device) != hipSuccess || hipStreamSynchronize(ctx->copy_stream) != hipSuccess ||
+        (chn && (hipMalloc(&d_new, (size_t)nch * sizeof(int)) != hipSuccess ||
+                 hipMemcpy(d_new, chn, (size_t)nch * sizeof(int), hipMemcpyHostToDevice) != hipSuccess))) {
+        hipFree(d_new);
+        return fail(ctx, ACG_EHIP, "channel numbers: upload failed");
+    }
+    hipFree(ctx->d_chnum);
+    ctx->d_chnum = d_new;
+    ctx->chnum.assign(chn, chn ? chn + nch : chn);
+    if (ctx->flights) acg_fl_context_channels(ctx->flights, ctx->d_chnum, (unsigned int)nch);
+    return ACG_OK;
+}
+
 // ---- the flight table (flight.hip, flights.cpp) -------------------------------------------------------------------------
 extern "C" int acg_flights_enable(acg_ctx* ctx, const acg_flight_config* cfg)
 {
@@ -1794,7 +1845,9 @@ extern "C" int acg_flights_enable(acg_ctx* ctx, const acg_flight_config* cfg)
     if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "flight table: context created without ACG_F_REPAIR");
     if (ctx->cfg.nch > (1 << 20)) return fail(ctx, ACG_EINVAL, "flight table: more than 2^20 channels");
     const int rc = acg_fl_create(&ctx->flights, cfg);
-    return rc == ACG_OK ? rc : fail(ctx, rc, "flight table: allocation failed");
+    if (rc != ACG_OK) return fail(ctx, rc, "flight table: allocation failed");
+    acg_fl_context_channels(ctx->flights, ctx->d_chnum, (unsigned int)ctx->cfg.nch);     // (acg_set_channel_numbers, until the table gets a map of its own)
+    return ACG_OK;
 }
 
 extern "C" int acg_flight_snapshot(acg_ctx* ctx, acg_flight* out, int max, int* n, int* dropped)
@@ -2059,6 +2112,7 @@ struct AcgSinkState {
     unsigned long long *d_key = nullptr, *d_key_s = nullptr;
     unsigned int *d_idx = nullptr, *d_idx_s = nullptr, *d_len = nullptr, *d_off = nullptr, *d_wg = nullptr;
     unsigned char* d_out = nullptr;         // cap * fmt->rec_max bytes
+    unsigned int last_nrecs = 0;            // records the most recent fetch handed out: the first keys of d_key_s (acg_sink_keys)
 };
 
 static void sink_free_work(AcgSinkState* st)
@@ -2171,6 +2225,7 @@ static int sink_fetch(acg_ctx* ctx, const AcgSinkFormat* fmt, AcgSinkState* st, 
 {
     if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
     if (!st) return fail(ctx, ACG_ESTATE, fmt->is_off);
+    st->last_nrecs = 0;
     const size_t fit = std::min<size_t>(std::min<size_t>(cap / fmt->rec_max, (size_t)max_recs), fmt->max_take);
     unsigned int upto = 0, pending = 0, take = 0;
     bool any = false;
@@ -2187,7 +2242,9 @@ static int sink_fetch(acg_ctx* ctx, const AcgSinkFormat* fmt, AcgSinkState* st, 
     if (sink_reserve(st, take) != ACG_OK) return fail(ctx, ACG_ENOMEM, "sink: work space");
     unsigned int* d_total = nullptr;
     if (const int lr = launch_split(ctx, take, true, &d_total)) return lr;
-    const AcgSinkPass sp = sink_pass(st, ctx->d_kmsgs, ctx->d_oooi, d_total, take, false);
+    AcgSinkPass sp = sink_pass(st, ctx->d_kmsgs, ctx->d_oooi, d_total, take, false);
+    sp.chmap = ctx->d_chnum;                                      // the map in force at hand-out (acg_set_channel_numbers)
+    sp.nmap = ctx->d_chnum ? (unsigned int)ctx->cfg.nch : 0u;
     if (fmt->launch(&sp, ctx->copy_stream) != 0) return sink_fail(ctx, ACG_EHIP, fmt, " pass launch failed");
     unsigned int cnt[2] = {0, 0};
     HIPCHK(ctx, hipMemcpyAsync(cnt, st->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->copy_stream));
@@ -2200,6 +2257,7 @@ static int sink_fetch(acg_ctx* ctx, const AcgSinkFormat* fmt, AcgSinkState* st, 
     }
     if (offs) offs[cnt[1]] = cnt[0];
     ctx->consumed += take;
+    st->last_nrecs = cnt[1];
     *nbytes = cnt[0];
     *nrecs = (int)cnt[1];
     return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
@@ -2212,6 +2270,22 @@ static int sink_level_guard(acg_ctx* ctx, const AcgSinkFormat* fmt, const AcgSin
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
     HIPCHK(ctx, hipMemcpy(near_midpoint, st->d_cnt + 2, sizeof(unsigned int), hipMemcpyDeviceToHost));
+    return ACG_OK;
+}
+
+// the order keys of the records the most recent fetch of a sink handed out: one small copy, no kernel
+extern "C" int acg_sink_keys(acg_ctx* ctx, int sink, unsigned long long* keys, int max, int* n)
+{
+    if (!ctx || !n || max < 0 || (max > 0 && !keys) || (sink != ACG_SINK_JSON && sink != ACG_SINK_TEXT)) return ACG_EINVAL;
+    *n = 0;
+    const AcgSinkState* st = sink == ACG_SINK_JSON ? ctx->json : ctx->text;
+    if (!st) return fail(ctx, ACG_ESTATE, (sink == ACG_SINK_JSON ? SINK_JSON : SINK_TEXT).is_off);
+    *n = (int)st->last_nrecs;
+    if (st->last_nrecs > (unsigned int)max) return fail(ctx, ACG_EAGAIN, "sink keys: *n keys do not fit");
+    // (kept records sort in front of dropped ones: the first keys; the pass that wrote them has been waited for)
+    if (st->last_nrecs && (hipSetDevice(ctx->cfg.device) != hipSuccess ||
+                           hipMemcpy(keys, st->d_key_s, (size_t)st->last_nrecs * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(ctx, ACG_EHIP, "sink keys: copy failed");
     return ACG_OK;
 }
 
@@ -2558,6 +2632,7 @@ extern "C" int acg_lab_time_sink_passes(const acg_msg* in, int n, const acg_json
     AcgLabelFilter none;
     std::memset(&none, 0, sizeof(none));
     hipEvent_t ev[2] = {nullptr, nullptr};
+    int* d_map = nullptr;
     int rc = sink_create(&st[0], &SINK_JSON, json_blob(jcfg, nullptr, nch));
     if (rc == ACG_OK) rc = sink_create(&st[1], &SINK_TEXT, text_blob(tcfg, nullptr, nch));
     if (rc == ACG_OK) rc = sink_reserve(st[0], (size_t)n);
@@ -2566,11 +2641,19 @@ extern "C" int acg_lab_time_sink_passes(const acg_msg* in, int n, const acg_json
         LabStage lab((size_t)n);
         lab.stage(in, (unsigned int)n, true, true);
         if (!lab.ok()) rc = ACG_ENOMEM;
+        if (rc == ACG_OK && acg_tune_get("ACG_SINK_MAP", 0)) {    // the passes under a channel map (slot l -> nch - 1 - l): what the look-up costs
+            std::vector<int> m((size_t)nch);
+            for (int l = 0; l < nch; ++l) m[(size_t)l] = nch - 1 - l;
+            if (hipMalloc(&d_map, m.size() * sizeof(int)) != hipSuccess || hipMemcpy(d_map, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+                rc = ACG_EHIP;
+        }
         if (rc == ACG_OK && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)) rc = ACG_EHIP;
         if (rc == ACG_OK && (lab.label((unsigned int)n, &none) != 0 || hipDeviceSynchronize() != hipSuccess)) rc = ACG_EHIP;
         for (int r = -warmup; r < reps && rc == ACG_OK; ++r)
             for (int arm = 0; arm < 2 && rc == ACG_OK; ++arm) {
-                const AcgSinkPass sp = sink_pass(st[arm], lab.d_out, lab.d_oooi, lab.d_total(), (unsigned int)n, true);
+                AcgSinkPass sp = sink_pass(st[arm], lab.d_out, lab.d_oooi, lab.d_total(), (unsigned int)n, true);
+                sp.chmap = d_map;
+                sp.nmap = d_map ? (unsigned int)nch : 0u;
                 float t = 0.0f;
                 if (hipEventRecord(ev[0], nullptr) != hipSuccess || st[arm]->fmt->launch(&sp, nullptr) != 0 ||
                     hipEventRecord(ev[1], nullptr) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess ||
@@ -2581,6 +2664,7 @@ extern "C" int acg_lab_time_sink_passes(const acg_msg* in, int n, const acg_json
     }
     if (ev[0]) hipEventDestroy(ev[0]);
     if (ev[1]) hipEventDestroy(ev[1]);
+    hipFree(d_map);
     sink_destroy(st[0]);
     sink_destroy(st[1]);
     return rc;

@@ -231,6 +231,8 @@ struct AcgSinkPass {
     unsigned int* counters;     // [0] bytes, [1] records of this pass; [2] level guard (accumulates); [3] unused
     unsigned char* out;         // nmax * (the format's record bound) bytes, 16-byte aligned
     unsigned int out_cap;
+    unsigned int nmap;          // acg_set_channel_numbers: the number handed out for slot l is chmap[l], l < nmap; 0 / null: the slot's own.
+    const int* chmap;           // The key and the channel tokens take it; the frequency token stays the slot's
 };
 
 // ---- the flight table's text (flight_text.hip): printmonitor()'s screen (output.c:458-484) and routejson()'s line (output.c:428-456)

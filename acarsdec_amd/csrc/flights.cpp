@@ -35,6 +35,8 @@ struct AcgFlights {
     size_t r_cap = 0;
     // ---- one table for several contexts: this one exports its events (p.xq set) or takes in those of others
     int* d_chmap = nullptr;             // p.chmap, or null
+    const int* d_ctxmap = nullptr;      // the context's map (not owned): p.chmap while d_chmap is null
+    unsigned int n_ctxmap = 0;
     size_t xq_bound = 0;                // no more events than this can be queued for export
     std::deque<acg_flight_event> xpending;      // events already fetched, not yet handed out
     std::vector<acg_flight_event> imp_pending;  // imported, waiting for the next pass
@@ -224,14 +226,23 @@ int acg_fl_set_channels(AcgFlights* t, const int* chn, int nch)
     FLCHK(hipDeviceSynchronize());
     hipFree(t->d_chmap);
     t->d_chmap = nullptr;
-    t->p.chmap = nullptr;
-    t->p.nmap = 0;
+    t->p.chmap = t->d_ctxmap;                                         // no map of its own: the context's
+    t->p.nmap = t->n_ctxmap;
     if (!chn || nch <= 0) return ACG_OK;
     FLCHK(hipMalloc(&t->d_chmap, (size_t)nch * sizeof(int)));
     FLCHK(hipMemcpy(t->d_chmap, chn, (size_t)nch * sizeof(int), hipMemcpyHostToDevice));
     t->p.chmap = t->d_chmap;
     t->p.nmap = (unsigned int)nch;
     return ACG_OK;
+}
+
+void acg_fl_context_channels(AcgFlights* t, const int* d_chn, unsigned int n)
+{
+    t->d_ctxmap = d_chn;
+    t->n_ctxmap = d_chn ? n : 0;
+    if (t->d_chmap) return;                                           // a map of its own keeps precedence
+    t->p.chmap = t->d_ctxmap;
+    t->p.nmap = t->n_ctxmap;
 }
 
 int acg_fl_exporting(const AcgFlights* t) { return t->p.xq != nullptr; }

@@ -24,6 +24,9 @@ ACG_FL_WEAK int acg_fl_drain_routes(AcgFlights* t, void* stream, acg_route* out,
 // ---- one table for several contexts (acg_flights_set_channels / _export / _import of the public header)
 // the number recorded for local channel l: chn[nch], null = identity (the values are checked by the caller); synchronises
 ACG_FL_WEAK int acg_fl_set_channels(AcgFlights* t, const int* chn, int nch);
+// the context's own map (acg_set_channel_numbers): a device array the CONTEXT owns, null / 0 = identity.  The table follows it while
+// acg_fl_set_channels has given it none of its own; the caller has made sure no pass is in flight
+ACG_FL_WEAK void acg_fl_context_channels(AcgFlights* t, const int* d_chn, unsigned int n);
 // on: acg_fl_prepare's passes end behind the extraction and queue their events for acg_fl_drain_events.  Either way the table
 // and both event queues are emptied (acg_fl_reset, which keeps the switch and the channel map)
 ACG_FL_WEAK int acg_fl_export(AcgFlights* t, int on);

@@ -48,9 +48,9 @@ __device__ __forceinline__ unsigned int json_line(const unsigned char* R, unsign
     PUT_LIT("{\"timestamp\":");
     pos = pk_put_tok<W, B>(row, pos, jn_timestamp(cfg->t0_sec + q, (int)rem), lane);
     pos = pk_put_words<W, B>(row, pos, cfg->pre, cfg->pre_len, lane);                   // ,"station_id":".." or nothing
-    const int chn = r->chn;
+    const int chn = r->chn;                                                      // the slot: the frequency token's index
     PUT_LIT(",\"channel\":");
-    pos = pk_put_tok<W, B>(row, pos, jn_int(chn), lane);
+    pos = pk_put_tok<W, B>(row, pos, jn_int(pk_chn(p, chn)), lane);                   // the number handed out (acg_set_channel_numbers)
     PUT_LIT(",\"freq\":");
     if ((unsigned int)chn < (unsigned int)cfg->nch) {
         const unsigned long long ft = ((const unsigned long long*)p.freq)[chn];    // 7 characters and their count: one load

@@ -57,10 +57,17 @@ __device__ __forceinline__ void pk_load(unsigned char* R, const AcgMsgRec* recs,
     __builtin_amdgcn_wave_barrier();
 }
 
-// records the block repair dropped (none passes label.hip's filter) would sort last and render nothing
-__device__ __forceinline__ unsigned long long pk_key(const AcgMsgRec* r)
+// the number handed out for the record's channel (acg_set_channel_numbers; no map: the slot).  It goes into the sort key and the
+// channel tokens; whatever is a table per slot (the frequency token) keeps the slot.  A wave-uniform load, kept in a register.
+__device__ __forceinline__ int pk_chn(const AcgSinkPass& p, int slot)
 {
-    return r->valid ? (((unsigned long long)(unsigned int)r->chn & 0xfffffull) << 44) | ((unsigned long long)r->end_bit & ((1ull << 44) - 1ull)) : ~0ull;
+    return p.nmap && (unsigned int)slot < p.nmap ? p.chmap[slot] : slot;
+}
+
+// records the block repair dropped (none passes label.hip's filter) would sort last and render nothing
+__device__ __forceinline__ unsigned long long pk_key(const AcgMsgRec* r, const AcgSinkPass& p)
+{
+    return r->valid ? (((unsigned long long)(unsigned int)pk_chn(p, r->chn) & 0xfffffull) << 44) | ((unsigned long long)r->end_bit & ((1ull << 44) - 1ull)) : ~0ull;
 }
 
 // the float of acars.c:351 (or the record's own, lab entries).  *near_mid: the one inexact step -- another log10 may land on the
@@ -150,7 +157,7 @@ __device__ __forceinline__ void pk_keys(const AcgSinkPass& p)
 {
     const unsigned int i = blockIdx.x * PK_WG + threadIdx.x;
     if (i >= p.nmax || i >= *p.total) return;
-    p.key[i] = pk_key(p.recs + i);
+    p.key[i] = pk_key(p.recs + i, p);
     p.idx[i] = i;
 }
 

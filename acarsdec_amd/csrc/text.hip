@@ -122,7 +122,8 @@ __device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsi
     long long q = us / 1000000ll, rem = us % 1000000ll;
     if (rem < 0) { rem += 1000000ll; --q; }
     const TnDate date = tn_date(cfg->t0_sec + q, (int)rem);
-    const int chn = r->chn;
+    const int chn = r->chn;                                       // the slot: the "F:" token's index
+    const int num = pk_chn(p, chn);                               // the number handed out (acg_set_channel_numbers)
     *near_mid = false;
     const float lvl = format == ACG_TEXT_PP ? 0.0f : pk_level(r, p.lvl_from_rec, near_mid);
     int tl = r->txt_len;
@@ -134,7 +135,7 @@ __device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsi
 
     if (format == ACG_TEXT_ONELINE) {                             // output.c:338-344
         pos = tx_ch<W>(row, pos, '#', lane);
-        pos = pk_put_tok<W, TX_B>(row, pos, jn_int((long long)chn + 1), lane);
+        pos = pk_put_tok<W, TX_B>(row, pos, jn_int((long long)num + 1), lane);
         TX_LIT(" (L:");
         pos = tx_level<W>(row, pos, lvl, lane);
         TX_LIT(" E:");
@@ -157,7 +158,7 @@ __device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsi
     }
     if (format == ACG_TEXT_STD) {                                 // output.c:166-215
         TX_LIT("\n[#");
-        pos = pk_put_tok<W, TX_B>(row, pos, jn_int((long long)chn + 1), lane);
+        pos = pk_put_tok<W, TX_B>(row, pos, jn_int((long long)num + 1), lane);
         TX_LIT(" (");
         if (flags & ACG_TEXT_F_FREQ) {
             if ((unsigned int)chn < (unsigned int)cfg->nch) {
@@ -226,7 +227,7 @@ __device__ __forceinline__ unsigned int text_record(const unsigned char* R, unsi
     if (format == ACG_TEXT_SV) {
         pos = tx_words<W>(row, pos, cfg->station, cfg->station_len, lane);
         pos = tx_ch<W>(row, pos, ' ', lane);
-        pos = pk_put_tok<W, TX_B>(row, pos, jn_int((long long)chn + 1), lane);
+        pos = pk_put_tok<W, TX_B>(row, pos, jn_int((long long)num + 1), lane);
         pos = tx_ch<W>(row, pos, ' ', lane);
         pos = tx_date<W>(row, pos, date, TN_DATE_SV_LEN, lane);
         pos = tx_ch<W>(row, pos, ' ', lane);

@@ -455,6 +455,46 @@ class Decoder:
         out, self.route_lines_n = self._all_or_nothing(call, 64 * K.ROUTE_LINE_MAX)
         return out
 
+    # ---- sharded hosts: global channel numbers and the sinks' order keys (acg_set_channel_numbers, acg_sink_keys) ----------
+    def set_channel_numbers(self, chn=None):
+        """The number handed out for each local channel (slot) in frames, messages, JSON lines, text records, their order and
+        (unless set_flight_channels gave it a map of its own) the flight table; None: the slot's own, the default.  Distinct
+        values in 0 .. 2^20 - 1.  For `c mod N` sharding: shard.channel_numbers(nch, rank, world).  Per-slot tables (freqs_hz,
+        stats, state, taps) stay indexed by the slot.  Blocks already queued are numbered by the map in force when they are
+        handed out."""
+        if chn is None:
+            return self._chk(self.L.acg_set_channel_numbers(self.ctx, None))
+        arr = np.ascontiguousarray(np.asarray(chn, dtype=np.int32))
+        if arr.shape != (self.nch,):
+            raise ValueError("one channel number per local channel")
+        self._chk(self.L.acg_set_channel_numbers(self.ctx, arr.ctypes.data))
+
+    def _c_sink_keys(self, sink):
+        """acg_sink_keys: the keys of the records the sink's most recent C call handed out, a uint64 array"""
+        n = C.c_int(0)
+        buf = np.zeros(max(1, getattr(self, "_kbuf_n", 0)), dtype=np.uint64)
+        rc = self._chk(self.L.acg_sink_keys(self.ctx, sink, buf.ctypes.data, len(buf), C.byref(n)), allow=(K.EAGAIN,))
+        if rc == K.EAGAIN:
+            self._kbuf_n = n.value
+            buf = np.zeros(n.value, dtype=np.uint64)
+            self._chk(self.L.acg_sink_keys(self.ctx, sink, buf.ctypes.data, len(buf), C.byref(n)))
+        return buf[:n.value].copy()
+
+    def _keep_keys(self, kind, parts):
+        """a drain / collect that looped over several C calls keeps the keys of the earlier ones: sink_keys then covers them all"""
+        if not hasattr(self, "_keys_kept"):
+            self._keys_kept = {}
+        self._keys_kept[kind] = np.concatenate(parts + [self._c_sink_keys(K.SINK_JSON if kind == "json" else K.SINK_TEXT)]) if parts else None
+
+    def sink_keys(self, kind):
+        """The order keys (numpy uint64: channel number handed out << 44 | end_bit) of the records the most recent drain_json /
+        collect_json (kind "json") or drain_text / collect_text ("text") returned, one per record in their order.  Ascending
+        within a C call; several decoders' (keys, records) go to shard.merge_keyed.  Empty before any such call."""
+        if kind not in ("json", "text"):
+            raise ValueError("kind is 'json' or 'text'")
+        kept = getattr(self, "_keys_kept", {}).get(kind)
+        return kept if kept is not None else self._c_sink_keys(K.SINK_JSON if kind == "json" else K.SINK_TEXT)
+
     # ---- the JSON sink (acg_json_enable, acg_drain_json, acg_collect_json) -------------------------------------------------
     def enable_json(self, t0, station_id="", app_name="acarsdec", app_ver="", freqs_hz=None):
         """buildjson()'s lines (output.c:227-324, what -o 4 prints) rendered on the device from now on.  t0: wall clock of the
@@ -476,12 +516,15 @@ class Decoder:
             self._jbuf = C.create_string_buffer(cap)
             self._jbuf_cap = cap
         out = []
+        keys = []                                    # of the C calls that said "call again" (sink_keys)
         while True:
             nb, nl = C.c_size_t(0), C.c_int(0)
             rc = self._chk(fn(self.ctx, *lead, self._jbuf, self._jbuf_cap, C.byref(nb), C.byref(nl)), allow=(K.EAGAIN,))
             out.append(C.string_at(self._jbuf, nb.value))
             if rc == K.OK:
+                self._keep_keys("json", keys)
                 return b"".join(out)
+            keys.append(self._c_sink_keys(K.SINK_JSON))
 
     def drain_json(self, max_lines=4096):
         """The JSON lines of every block completed since the last drain (needs repair=True and enable_json), as bytes: one object
@@ -521,13 +564,16 @@ class Decoder:
             self._toffs = (C.c_uint * (n + 1))()
             self._tbuf_cap = cap
         out = []
+        keys = []                                    # as _json_call
         while True:
             nb, nr = C.c_size_t(0), C.c_int(0)
             rc = self._chk(fn(self.ctx, *lead, self._tbuf, self._tbuf_cap, C.byref(nb), self._toffs, n, C.byref(nr)), allow=(K.EAGAIN,))
             blob, offs = C.string_at(self._tbuf, nb.value), self._toffs[:nr.value + 1]
             out += [blob[offs[i]:offs[i + 1]] for i in range(nr.value)]
             if rc == K.OK:
+                self._keep_keys("text", keys)
                 return out
+            keys.append(self._c_sink_keys(K.SINK_TEXT))
 
     def drain_text(self, max_recs=4096):
         """The text records of every block completed since the last drain (needs repair=True and enable_text): a list of bytes, one

@@ -9,7 +9,8 @@ rank 0 (ONE BROADCAST of the whole table, 32 B per channel, from which every ran
 not an ncclSend/Recv scatter: 0.5 MB at 16 384 channels is not worth one), the barrier around the
 timed region and the reduction/gather of counts, timings and decoded blocks -- and, where ONE flight
 table is kept for all channels, each round's flight events (88 B per message that reaches addFlight())
-on their way to the rank that owns the table.
+on their way to the rank that owns the table, and each round's rendered records with their order keys (gather_keyed) on their
+way to the rank that writes the one output stream.
 """
 import numpy as np
 
@@ -87,10 +88,89 @@ def gather_scalars(x, world, dist=None, device=None):
     return [float(b.item()) for b in box]
 
 
-def flight_channel_map(nch_local, rank, world):
-    """The channel numbers a rank's flight table records (Decoder.set_flight_channels): local channel l of rank r is the global
-    channel l * world + r, the inverse of owned_channels."""
+def channel_numbers(nch_local, rank, world):
+    """The channel numbers a rank hands out (Decoder.set_channel_numbers; for the flight table alone: Decoder.set_flight_channels):
+    local channel l of rank r is the global channel l * world + r, the inverse of owned_channels."""
     return np.arange(int(nch_local), dtype=np.int32) * np.int32(world) + np.int32(rank)
+
+
+flight_channel_map = channel_numbers          # the name it had while only the flight table took a map
+
+
+def merge_keyed(parts):
+    """The records of several contexts as the ONE stream a single context over all channels hands out.  parts: [(keys, records), ...],
+    one pair per context and sink call -- keys as Decoder.sink_keys gives them (ascending within a part), records the lines /
+    text records / messages that belong to them, one per key.  Returns the records in ascending key order: a k-way merge of
+    inputs that are already sorted (heapq.merge, nothing is sorted again).  Raises ValueError on a part whose keys and records
+    differ in number or whose keys descend, and on a key that occurs twice (two contexts under one channel number)."""
+    import heapq
+
+    def walk(k, keys, recs):
+        for i, key in enumerate(keys):
+            yield int(key), k, i, recs[i]
+
+    runs = []
+    for k, (keys, recs) in enumerate(parts):
+        if len(keys) != len(recs):
+            raise ValueError("part %d: %d keys for %d records" % (k, len(keys), len(recs)))
+        if any(int(keys[i]) > int(keys[i + 1]) for i in range(len(keys) - 1)):
+            raise ValueError("part %d: its keys are not ascending" % k)
+        runs.append(walk(k, keys, recs))
+    out, last = [], None
+    for key, _, _, rec in heapq.merge(*runs):
+        if key == last:
+            raise ValueError("key %#x occurs twice: two records under one (channel number, end_bit)" % key)
+        last = key
+        out.append(rec)
+    return out
+
+
+def split_lines(buf):
+    """The JSON sink's packed lines as a list, each with its newline (a line holds no raw newline: cJSON escapes it)"""
+    return [l + b"\n" for l in bytes(buf).split(b"\n")[:-1]]
+
+
+def gather_keyed(keys, records, dst=0, dist=None, device=None):
+    """Every rank's (keys, records) of one round moved to `dst` and merged there (merge_keyed): the one stream of the round.
+    records: a list of bytes, one per key (JSON lines: split_lines(Decoder.drain_json()); text records as Decoder.drain_text gives
+    them).  The counts differ from rank to rank, so they are exchanged first (records, bytes: two int64 per rank); then ONE
+    gather carries, per rank and padded to the largest, the keys, the records' offsets and the packed bytes.  CPU tensors over
+    gloo, device tensors (device = the rank's GPU) over RCCL, as gather_flight_events.  Returns the merged list on `dst`, None
+    elsewhere."""
+    keys = np.ascontiguousarray(np.asarray(keys, dtype=np.uint64))
+    records = [bytes(r) for r in records]
+    if len(keys) != len(records):
+        raise ValueError("%d keys for %d records" % (len(keys), len(records)))
+    if dist is None:
+        return merge_keyed([(keys, records)])
+    import torch
+    rank, world = dist.get_rank(), dist.get_world_size()
+    blob = b"".join(records)
+    offs = np.zeros(len(records) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(r) for r in records], dtype=np.uint64)
+    mine = torch.tensor([len(records), len(blob)], dtype=torch.int64, device=device)
+    counts = [torch.zeros(2, dtype=torch.int64, device=device) for _ in range(world)]
+    dist.all_gather(counts, mine)
+    counts = [(int(c[0].item()), int(c[1].item())) for c in counts]
+    nmax, bmax = max(n for n, _ in counts), max(b for _, b in counts)
+    head = 8 * nmax + 8 * (nmax + 1)                                  # keys, then offsets
+    width = head + max(bmax, 1)
+    packed = np.zeros(width, dtype=np.uint8)
+    packed[: 8 * len(keys)] = keys.view(np.uint8)
+    packed[8 * nmax: 8 * nmax + 8 * len(offs)] = offs.view(np.uint8)
+    packed[head: head + len(blob)] = np.frombuffer(blob, dtype=np.uint8)
+    row = torch.from_numpy(packed).to(device) if device is not None else torch.from_numpy(packed)
+    box = [torch.zeros(width, dtype=torch.uint8, device=device) for _ in range(world)] if rank == dst else None
+    dist.gather(row, box, dst=dst)
+    if rank != dst:
+        return None
+    parts = []
+    for b, (n, _) in zip(box, counts):
+        raw = b.cpu().numpy().tobytes()
+        k = np.frombuffer(raw[: 8 * n], dtype=np.uint64)
+        o = np.frombuffer(raw[8 * nmax: 8 * nmax + 8 * (n + 1)], dtype=np.uint64)
+        parts.append((k, [raw[head + int(o[i]): head + int(o[i + 1])] for i in range(n)]))
+    return merge_keyed(parts)
 
 
 def gather_flight_events(events, dst=0, dist=None, device=None):

@@ -418,7 +418,8 @@ typedef struct {
  * key: chn[nch], or NULL for the identity.  It applies to the context's own table and to what it exports; for `c mod N` sharding
  * on rank r local channel l gets l * N + r.  ACG_EINVAL: a value outside 0 .. 2^20 - 1 (the key holds 20 bits); ACG_ESTATE: the
  * table is off.  acg_reset keeps the map; acg_flights_enable drops it with the table.
- * KNOWN FOLLOW-UP: acg_frame / acg_msg and the JSON and text sinks are untouched, their channel numbers stay local. */
+ * A host that numbers everything it hands out calls acg_set_channel_numbers (below, "sharded hosts") instead: the table follows the
+ * context's map while it has none of its own.  A map given HERE keeps precedence, for the table only. */
 int  acg_flights_set_channels(acg_ctx *ctx, const int *chn);
 /* on != 0: this context is a peer.  Its flight pass stops behind the extraction (after -A / -b, before -e, as ever): the events
  * of the blocks a message entry point consumes go to an export queue on the device, channel numbers applied, and the table stays
@@ -598,6 +599,41 @@ typedef struct {
 int  acg_text_enable(acg_ctx *ctx, const acg_text_config *cfg, const int *Fr_hz);
 int  acg_drain_text(acg_ctx *ctx, char *out, size_t cap, size_t *nbytes, unsigned int *offs, int max_recs, int *nrecs);
 int  acg_collect_text(acg_ctx *ctx, int lag, char *out, size_t cap, size_t *nbytes, unsigned int *offs, int max_recs, int *nrecs);
+
+/* ---- sharded hosts: global channel numbers in everything handed out, and the keys to merge by ---------------------------------
+ * A host that spreads its channels over N contexts (`c mod N`: slot l of rank r is channel l * N + r) gives every context the
+ * numbers of its slots once; from then on N contexts behind one host hand out exactly what ONE context over all channels hands
+ * out, byte for byte and -- merged by the keys below -- in its order.  Unused, nothing changes: no launch, no copy, no byte.
+ *
+ * acg_channel_numbers_check: ACG_OK when every one of the n values lies in 0 .. 2^20 - 1 (the sinks' order key holds 20 bits of
+ * channel) and the values are pairwise distinct (two slots under one number would make the order ambiguous), else ACG_EINVAL.
+ * n == 0 is ACG_OK.  Host arithmetic only, no context. */
+int  acg_channel_numbers_check(const int *chn, int n);
+/* chn[nch]: the number handed out for each local channel (slot); NULL = the identity, the default.  Checked with the function
+ * above: on ACG_EINVAL the map in force stays in force.  It takes effect with the NEXT entry point call, and blocks already queued
+ * are numbered by the map in force when they are HANDED OUT, not when they were decoded.  acg_reset keeps the map.
+ *   the number is used  in acg_frame.chn and acg_msg.chn, the JSON line's "channel", the channel tokens of the text formats
+ *                       (number + 1, as the reference prints chn + 1), in the order of every entry point -- "(chn, end_bit) order
+ *                       within the call" means the number handed out -- and in the sinks' order key (acg_sink_keys);
+ *                       by the flight table (events, first_chn, last_chn, chm, acg_route.chn, its order key) unless
+ *                       acg_flights_set_channels has given the table a map of its own;
+ *   the slot stays      the index of everything that is a table per slot: the Fr_hz of acg_json_enable / acg_text_enable (a line
+ *                       carries the number handed out and the frequency of its slot), acg_stats_read, acg_get_state /
+ *                       acg_set_state, acg_set_taps, acg_set_channel_streams, acg_read_bits. */
+int  acg_set_channel_numbers(acg_ctx *ctx, const int *chn);
+/* The order keys, (number handed out) << 44 | end_bit, of the records the most recent acg_drain_json / acg_collect_json call
+ * (sink == ACG_SINK_JSON) or acg_drain_text / acg_collect_text call (ACG_SINK_TEXT) handed out, in the order of its records:
+ * strictly ascending.  *n is their count: the call's *nlines / *nrecs, 0 before any call and after a call that handed out nothing.
+ * ACG_EAGAIN: max is too small, *n is the number needed.  Nothing is consumed either way; one copy of *n x 8 bytes, no kernel.
+ * ACG_ESTATE: that sink is off.
+ * THE MERGE.  Keys of different contexts are distinct when their channel numbers are, and each context's are ascending: after one
+ * sink call on every context over the same sample span, a k-way merge of (keys, records) by key is the one stream a single context
+ * would have handed out in that call.  JSON lines need no offset table for it (a line holds no raw '\n': cJSON escapes it), the
+ * text sink hands out its offsets.  As with the flight table's round, a call that returns ACG_EAGAIN has consumed an arbitrary
+ * oldest part of the queue: the merge then holds per call, so a host sizes its buffers for a round. */
+#define ACG_SINK_JSON  1
+#define ACG_SINK_TEXT  2
+int  acg_sink_keys(acg_ctx *ctx, int sink, unsigned long long *keys, int max, int *n);
 
 /* ---- per-channel reception statistics: what the reference says under -v, counted on the device --------------------------------
  * One record per channel, resident on the device across calls and updated in the round trips the entry points above already make

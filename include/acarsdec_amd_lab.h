@@ -132,7 +132,8 @@ int  acg_lab_text_level_guard(acg_ctx *ctx, unsigned int *near_midpoint);
 /* measurement: the device time of json.hip's passes and of text.hip's over the SAME n records (taken as the two self tests take
  * them, no filter), the label pass run once before; HIP events around each renderer's launches, `warmup` unrecorded rounds and
  * `reps` recorded ones, the two arms alternated within every round: ms[0 .. reps) = the JSON passes, ms[reps .. 2 reps) = the text
- * passes, milliseconds.  ACG_ENODEV: no GPU. */
+ * passes, milliseconds.  With the measurement switch ACG_SINK_MAP=1 (acg_tune) both renderers run under a channel map (slot l ->
+ * nch - 1 - l), as behind acg_set_channel_numbers.  ACG_ENODEV: no GPU. */
 int  acg_lab_time_sink_passes(const acg_msg *in, int n, const acg_json_config *jcfg, const acg_text_config *tcfg, int nch, int warmup, int reps,
 			      float *ms);
 
