@@ -54,6 +54,10 @@ MSK_FLAGS = ["-O3", "-ffp-contract=off", "-mllvm", "-amdgpu-sched-strategy=max-i
 # -0.7 % per bit without -disable-machine-sink, +4 % without max-ilp, +2 % without the structurizer switch, the others nil;
 # profiles/r06_msk_lean_builds_ab.txt)
 MSK_LEAN_FLAGS = [f for i, f in enumerate(MSK_FLAGS) if not (f == "-disable-machine-sink" or (f == "-mllvm" and MSK_FLAGS[i + 1] == "-disable-machine-sink"))]
+# The host side: the units that hold no kernel.  The host runtime (csrc/acg_ctx.h is what its units share) and the flight table's
+# host object in C++, the set-up arithmetic in C.
+HOST_UNITS = ["tune.cpp", "ctx.cpp", "process.cpp", "results.cpp", "sinks.cpp", "state.cpp", "lab.cpp", "flights.cpp"]
+HOST_C_UNITS = ["host_setup.c"]
 # unit -> (flags, in the product library?).  msk2.hip (the two-wave demodulator: bit-identical and slower) is lab only.
 UNITS = [("fir.hip", ["-O3"], True), ("fir_mm.hip", ["-O3"], True), ("msk.hip", MSK_FLAGS, True), ("msk_lean.hip", MSK_LEAN_FLAGS, True), ("msk2.hip", MSK_FLAGS, False), ("synth.hip", ["-O3"], True),
          ("blk.hip", ["-O3"], True), ("label.hip", ["-O3"], True), ("flight.hip", ["-O3"], True),
@@ -62,10 +66,19 @@ UNITS = [("fir.hip", ["-O3"], True), ("fir_mm.hip", ["-O3"], True), ("msk.hip", 
          ("flight_text.hip", ["-O3", "-ffp-contract=off"], True),   # text.hip's flags: the route line's time stamp is json.hip's double
          ("stats.hip", ["-O3", "-ffp-contract=off"], True),     # IEEE: the level ratio's double division is the host's
          ("pcm.hip", ["-O3"], True),        # a transpose: the int16 scale is exact, the f32 path moves words (nothing to contract)
-         ("flights.cpp", ["-O2"], True), ("acg_api.cpp", ["-O2"], True)]
-# which units see which define (the others are compiled once and shared between the libraries)
-SEES = {"-DACG_LAB": ("fir.hip", "msk2.hip", "acg_api.cpp"), "-DACG_MSK_STAMP": ("msk.hip", "msk2.hip", "acg_api.cpp"),
+         ] + [(u, ["-O2"], True) for u in HOST_UNITS]
+# which units see which define: those with a preprocessor line that tests it (tests/test_build_units.py); the others are compiled
+# once and shared between the libraries
+SEES = {"-DACG_LAB": ("fir.hip", "msk2.hip", "tune.cpp", "ctx.cpp", "process.cpp"), "-DACG_MSK_STAMP": ("msk.hip", "msk2.hip", "ctx.cpp", "lab.cpp"),
         "-DACG_MSK_SINCOS_POLY": ("msk.hip", "msk2.hip")}
+
+
+def headers():
+    """what every object depends on besides its source: the headers of csrc/ and include/, the lab-only kernel families fir.hip
+    includes (csrc/lab/), and this file (the flags live here)"""
+    return (sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) +
+            sorted(os.path.join(CSRC, "lab", f) for f in os.listdir(os.path.join(CSRC, "lab"))) +
+            sorted(os.path.join(INC, f) for f in os.listdir(INC) if f.endswith(".h")) + [os.path.abspath(__file__)])
 
 
 def build_lib(force=False, stamp=False, poly=False, lab=False):
@@ -85,9 +98,7 @@ def build_lib(force=False, stamp=False, poly=False, lab=False):
     os.makedirs(OBJDIR, exist_ok=True)
     defs = (["-DACG_LAB"] if (lab or stamp or poly) else []) + (["-DACG_MSK_STAMP"] if stamp else []) + (["-DACG_MSK_SINCOS_POLY"] if poly else [])
     out_lib = LIB_STAMP if stamp else LIB_POLY if poly else LIB_LAB if lab else LIB
-    hdrs = [os.path.join(CSRC, "acg_internal.h"), os.path.join(CSRC, "flights.h"), os.path.join(CSRC, "msk_common.h"), os.path.join(CSRC, "json_num.h"), os.path.join(CSRC, "text_num.h"), os.path.join(CSRC, "flight_text_num.h"), os.path.join(CSRC, "sink_pack.h"), os.path.join(CSRC, "sink_put.h"), os.path.join(CSRC, "msg_keep.h"), os.path.join(CSRC, "fir_mm_plan.h"), os.path.join(CSRC, "fir_plan.h"), os.path.join(INC, "acarsdec_amd.h"),
-            os.path.join(INC, "acarsdec_amd_lab.h"), os.path.abspath(__file__)]   # flags live here
-    hdrs += sorted(os.path.join(CSRC, "lab", f) for f in os.listdir(os.path.join(CSRC, "lab")))       # the lab-only kernel families fir.hip includes
+    hdrs = headers()
     objs = []
     hc = hipcc()
     for name, flags, in_product in UNITS:
@@ -100,15 +111,15 @@ def build_lib(force=False, stamp=False, poly=False, lab=False):
         if force or _newer([src] + hdrs, obj):
             _run([hc, "--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-I" + INC, "-I" + CSRC] + flags + mine + ["-c", src, "-o", obj])
         objs.append(obj)
-    src = os.path.join(CSRC, "host_setup.c")
-    obj = os.path.join(OBJDIR, "host_setup.o")
-    if force or _newer([src] + hdrs, obj):
-        _run(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-I" + INC, "-c", src, "-o", obj])
-    objs.append(obj)
+    for name in HOST_C_UNITS:
+        src = os.path.join(CSRC, name)
+        obj = os.path.join(OBJDIR, os.path.splitext(name)[0] + ".o")
+        if force or _newer([src] + hdrs, obj):
+            _run(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-I" + INC, "-c", src, "-o", obj])
+        objs.append(obj)
     # The library exports exactly what include/acarsdec_amd.h and include/acarsdec_amd_lab.h declare (a linker version script
     # made from the headers; the kernel launchers, the tuning look-ups and host_setup.c's helpers are local).  The stamp
     # build's two extra entry points are declared in the lab header and simply absent from the other builds.
-    vs = os.path.join(OBJDIR, "exports.map")
     vs = os.path.join(OBJDIR, "exports_stamp.map" if stamp else "exports.map")
     names = [n for n in declared_symbols() if stamp or n not in STAMP_ONLY]
     text = "{\n  global:\n" + "".join("    %s;\n" % n for n in names) + "  local: *;\n};\n"

@@ -1,5 +1,5 @@
 // flights.cpp -- host side of the flight table (flight.hip): the table and its work space in device memory, grown on demand
-// like the message staging of acg_api.cpp, the snapshot and the route hand-over; the channel map, the export queue and the import
+// like the message staging of results.cpp, the snapshot and the route hand-over; the channel map, the export queue and the import
 // queue of a table kept for the channels of several contexts.  Used by a context (acg_flights_enable) and, without one, by
 // acg_selftest_flights and acg_selftest_flights_sharded.
 #include <hip/hip_runtime.h>

@@ -12,6 +12,7 @@ import torch.multiprocessing as mp
 
 from acarsdec_amd import _capi as K
 from acarsdec_amd import shard
+import host_side
 from test_shard_gloo import free_port
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -121,7 +122,7 @@ def test_event_kernels_have_no_private_segment():
 
 def test_import_argument_checks_under_address_and_undefined_behaviour_sanitizers(tmp_path):
     """acg_flight_events_check -- what acg_flights_import runs on its events before it looks at the context -- and the NULL-context
-    answers of the new entry points, in the host units (acg_api.cpp, host_setup.c) built with -fsanitize=address,undefined and
+    answers of the new entry points, in the host units (host_side.py) built with -fsanitize=address,undefined and
     driven by tests/sanitize/flight_import_driver.c: every rule alone, the limits themselves, a bad record first, in the middle and
     last of 700 on the heap.  Any sanitizer report fails the test."""
     if not (shutil.which("g++") and os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h")):
@@ -129,14 +130,7 @@ def test_import_argument_checks_under_address_and_undefined_behaviour_sanitizers
     csrc = os.path.join(ROOT, "acarsdec_amd", "csrc")
     inc = ["-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__"]
     san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-O1", "-g", "-w"]
-    objs = []
-    for src, cc, std in ((os.path.join(csrc, "acg_api.cpp"), "g++", ["-std=c++17"]),
-                         (os.path.join(csrc, "host_setup.c"), "gcc", ["-ffp-contract=off"]),
-                         (os.path.join(ROOT, "tests", "sanitize", "flight_import_driver.c"), "gcc", [])):
-        obj = str(tmp_path / (os.path.basename(src) + ".o"))
-        r = subprocess.run([cc] + std + san + inc + ["-c", src, "-o", obj], capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-        objs.append(obj)
+    objs = host_side.compile_host_objects(tmp_path, "flight_import_driver.c", san + inc)
     exe = str(tmp_path / "flight_import_driver")
     libs = ["-L/opt/rocm/lib", "-lamdhip64", "-ldl", "-lm", "-Wl,-rpath,/opt/rocm/lib"]
     r = subprocess.run(["g++"] + san + objs + ["-o", exe] + libs, capture_output=True, text=True, timeout=600)

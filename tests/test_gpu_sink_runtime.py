@@ -1,4 +1,4 @@
-"""The one host runtime behind the JSON and the text sink (csrc/acg_api.cpp: AcgSinkState, sink_fetch, sink_reserve) where the two
+"""The one host runtime behind the JSON and the text sink (csrc/sinks.cpp: AcgSinkState, sink_fetch, sink_reserve) where the two
 sinks meet: both enabled in one context and drained in turn beside the message entry point, one of them re-enabled mid-run; and
 a work space that grows inside a live context, from sink_reserve's floor of 4096 records to a larger drain.  GPU box only."""
 import ctypes as C
