@@ -64,12 +64,15 @@ UNITS = [("fir.hip", ["-O3"], True), ("fir_mm.hip", ["-O3"], True), ("msk.hip", 
          ("json.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE, nothing fused: the level's float and the time stamp's double are computed here
          ("text.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE like json.hip: the same level float
          ("flight_text.hip", ["-O3", "-ffp-contract=off"], True),   # text.hip's flags: the route line's time stamp is json.hip's double
+         # text.hip's flags (the combined outputs pass launches its kernels and json.hip's); its own four small kernels as a compressed
+         # bundle, two pages of the library instead of five: the size rule of tests/test_host_logic.py (LEDGER, "Combined outputs")
+         ("outs.hip", ["-O3", "-ffp-contract=off", "--offload-compress"], True),
          ("stats.hip", ["-O3", "-ffp-contract=off"], True),     # IEEE: the level ratio's double division is the host's
          ("pcm.hip", ["-O3"], True),        # a transpose: the int16 scale is exact, the f32 path moves words (nothing to contract)
          ] + [(u, ["-O2"], True) for u in HOST_UNITS]
 # which units see which define: those with a preprocessor line that tests it (tests/test_build_units.py); the others are compiled
 # once and shared between the libraries
-SEES = {"-DACG_LAB": ("fir.hip", "msk2.hip", "tune.cpp", "ctx.cpp", "process.cpp"), "-DACG_MSK_STAMP": ("msk.hip", "msk2.hip", "ctx.cpp", "lab.cpp"),
+SEES = {"-DACG_LAB": ("fir.hip", "msk2.hip", "tune.cpp", "ctx.cpp", "process.cpp", "sinks.cpp"), "-DACG_MSK_STAMP": ("msk.hip", "msk2.hip", "ctx.cpp", "lab.cpp"),
         "-DACG_MSK_SINCOS_POLY": ("msk.hip", "msk2.hip")}
 
 

@@ -128,6 +128,26 @@ class JsonConfig(C.Structure):
                 ("app_ver", C.c_char * 17)]
 
 
+OUT_MSGS, OUT_JSON, OUT_LEGS_MAX = 0x10, 0x20, 4      # acg_out_leg.kind beside TEXT_*; SINK_OUTPUTS: acg_sink_keys
+SINK_OUTPUTS = 4
+
+
+class OutLeg(C.Structure):
+    """acg_out_leg: OUT_MSGS, OUT_JSON or a TEXT_* format, and the TEXT_F_* flags that format takes"""
+    _fields_ = [("kind", C.c_int), ("flags", C.c_uint)]
+
+
+class OutputsConfig(C.Structure):
+    """acg_outputs_config: the legs rendered from one take, one t0 and one station / app for all of them"""
+    _fields_ = [("nlegs", C.c_int), ("leg", OutLeg * OUT_LEGS_MAX), ("t0_sec", C.c_longlong), ("t0_usec", C.c_int), ("station_id", C.c_char * 33),
+                ("app_name", C.c_char * 17), ("app_ver", C.c_char * 17)]
+
+
+class OutBuf(C.Structure):
+    """acg_out_buf: one leg's buffers in an outputs call"""
+    _fields_ = [("out", C.c_void_p), ("cap", C.c_size_t), ("offs", C.c_void_p), ("oooi", C.c_void_p), ("nbytes", C.c_size_t)]
+
+
 class LaunchShape(C.Structure):
     """acg_lab_launch_shape: the down-converter launch the library makes for one launch of nblocks callbacks"""
     _fields_ = [("kernel", C.c_int), ("stages", C.c_int), ("cpr", C.c_int), ("ncu", C.c_int), ("device_cus", C.c_int),
@@ -199,6 +219,10 @@ SYMBOLS = {
     "acg_text_enable": (C.c_int, [C.c_void_p, C.POINTER(TextConfig), C.c_void_p]),
     "acg_drain_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "acg_collect_text": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "acg_outputs_config_check": (C.c_int, [C.POINTER(OutputsConfig)]),
+    "acg_outputs_enable": (C.c_int, [C.c_void_p, C.POINTER(OutputsConfig), C.c_void_p]),
+    "acg_drain_outputs": (C.c_int, [C.c_void_p, C.POINTER(OutBuf), C.c_int, C.POINTER(C.c_int)]),
+    "acg_collect_outputs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OutBuf), C.c_int, C.POINTER(C.c_int)]),
     "acg_channel_numbers_check": (C.c_int, [C.c_void_p, C.c_int]),
     "acg_set_channel_numbers": (C.c_int, [C.c_void_p, C.c_void_p]),
     "acg_sink_keys": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
@@ -254,6 +278,10 @@ LAB_SYMBOLS = {
     "acg_lab_text_level_guard": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint)]),
     "acg_lab_time_sink_passes": (C.c_int, [C.POINTER(Msg), C.c_int, C.POINTER(JsonConfig), C.POINTER(TextConfig), C.c_int, C.c_int, C.c_int,
                                            C.c_void_p]),
+    "acg_selftest_outputs": (C.c_int, [C.POINTER(Msg), C.c_int, C.POINTER(MsgFilter), C.POINTER(OutputsConfig), C.c_void_p, C.c_int,
+                                       C.POINTER(OutBuf), C.POINTER(C.c_int)]),
+    "acg_lab_outputs_level_guard": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint)]),
+    "acg_lab_time_output_passes": (C.c_int, [C.POINTER(Msg), C.c_int, C.POINTER(OutputsConfig), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "acg_lab_set_block_counter": (C.c_int, [C.c_void_p, C.c_uint]),
     "acg_lab_block_ring_size": (C.c_uint, [C.c_void_p]),
     "acg_lab_set_stream_counters": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong]),

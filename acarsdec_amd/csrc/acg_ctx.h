@@ -142,6 +142,7 @@ struct acg_ctx {
     // ---- sinks.cpp: the batch sinks
     struct AcgSinkState* text = nullptr;    // acg_text_enable: the text sink (text.hip), as json
     struct AcgSinkState* json = nullptr;    // acg_json_enable: the JSON sink (json.hip): configuration, work space, rendered lines
+    struct AcgOutputs* outs = nullptr;      // acg_outputs_enable: the legs rendered from one take (outs.hip), a state beside the two above
 };
 
 #define HIPCHK(ctx, call)                                                                  \
@@ -181,6 +182,8 @@ int label_filter_dev(const acg_msg_filter* f, AcgLabelFilter* d);
 
 // sinks.cpp: frees a sink (null: nothing)
 void sink_destroy(struct AcgSinkState* st);
+// sinks.cpp: frees the outputs (null: nothing)
+void outputs_destroy(struct AcgOutputs* o);
 
 
 // ---- what the lab entries below share: public records turned back into the device's form, staged, and label.hip's pass over them

@@ -235,6 +235,18 @@ struct AcgSinkPass {
     const int* chmap;           // The key and the channel tokens take it; the frequency token stays the slot's
 };
 
+// ---- the combined outputs pass (outs.hip): one take of kept records, ordered once, rendered into several legs
+#define ACG_OUTS_LEGS 4         // == ACG_OUT_LEGS_MAX of the public header
+struct AcgOutsPass {
+    AcgSinkPass order;          // recs, oooi, total, nmax, the channel map and key / idx / key_s / idx_s: the one order of all legs
+    unsigned int nrender;       // rendered legs (JSON, text); each names the same records and the same key_s / idx_s as `order`
+    int is_json[ACG_OUTS_LEGS]; // leg l: json.hip's kernels (1) or text.hip's (0)
+    AcgSinkPass leg[ACG_OUTS_LEGS];
+    AcgMsgRec* g_recs;          // the MSGS leg, or null: the records in sorted order, rank r at g_recs[r] ...
+    unsigned char* g_oooi;      // ... their acg_oooi ...
+    unsigned int* g_count;      // ... and how many were kept (they sort in front of dropped ones)
+};
+
 // ---- the flight table's text (flight_text.hip): printmonitor()'s screen (output.c:458-484) and routejson()'s line (output.c:428-456)
 #define ACG_FT_ROW_MAX 78       // == ACG_MONITOR_ROW_MAX of the public header (derived there)
 #define ACG_FT_LINE_MAX 363     // == ACG_ROUTE_LINE_MAX of the public header (derived there)
@@ -420,6 +432,15 @@ int acg_launch_sort_pairs(unsigned long long* ka, unsigned int* va, unsigned lon
 __attribute__((weak)) int acg_launch_json(const AcgSinkPass* p, void* stream);
 // text.hip: the same for the text formats (weak for the same reason)
 __attribute__((weak)) int acg_launch_text(const AcgSinkPass* p, void* stream);
+// json.hip, text.hip: pk_launch's tail for records somebody else has ordered (p->key_s / p->idx_s are filled): the measure
+// kernel (phase ACG_SORTED_MEASURE) or the render kernel (ACG_SORTED_RENDER); the scan between them is the caller's
+#define ACG_SORTED_MEASURE 0
+#define ACG_SORTED_RENDER 1
+int acg_launch_json_sorted(const AcgSinkPass* p, int phase, void* stream);
+int acg_launch_text_sorted(const AcgSinkPass* p, int phase, void* stream);
+// outs.hip: keys and sort once, every leg's measure, one scan over all legs, every leg's render, the MSGS leg's gather
+// (weak for the same reason: there acg_outputs_enable says ACG_ESTATE)
+__attribute__((weak)) int acg_launch_outs(const AcgOutsPass* o, void* stream);
 // stats.hip: the per-channel statistics of the blocks an entry point consumes (weak for the same reason: there acg_stats_enable
 // says ACG_ESTATE)
 __attribute__((weak)) int acg_launch_chan_stats(const AcgStatsPass* p, void* stream);

@@ -60,6 +60,8 @@ static void free_all(acg_ctx* c)
     c->json = nullptr;
     sink_destroy(c->text);
     c->text = nullptr;
+    outputs_destroy(c->outs);
+    c->outs = nullptr;
     hipFree(c->d_bits); hipFree(c->d_nbits); hipFree(c->d_stage[0]); hipFree(c->d_stage[1]); hipFree(c->d_work); hipFree(c->d_msk_done); std::free(c->h_stage); hipFree(c->d_crctab); hipFree(c->d_rep_upto);
     for (auto& p : c->fir_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& p : c->msk_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }

@@ -174,3 +174,8 @@ extern "C" int acg_launch_json(const AcgSinkPass* p, void* stream)
 {
     return pk_launch(p, stream, json_keys_kernel, json_measure_kernel, json_sum_kernel, json_offsets_kernel, json_render_kernel);
 }
+
+extern "C" int acg_launch_json_sorted(const AcgSinkPass* p, int phase, void* stream)
+{
+    return pk_launch_sorted(p, stream, phase, json_measure_kernel, json_render_kernel);
+}

@@ -207,3 +207,14 @@ static inline int pk_launch(const AcgSinkPass* p, void* stream, PkKernel keys, P
     hipLaunchKernelGGL(render, dim3(gw), dim3(64 * PK_WAVES), 0, s, *p);
     return (int)hipGetLastError();
 }
+
+// pk_launch's tail for records that are ordered already (outs.hip orders a take once for several formats): key_s / idx_s are
+// filled.  One of the unit's two wave-per-record kernels per call -- measure, then render -- because the scan between them runs
+// over all the caller's formats at once.
+static inline int pk_launch_sorted(const AcgSinkPass* p, void* stream, int phase, PkKernel measure, PkKernel render)
+{
+    if (p->nmax == 0) return 0;
+    const unsigned int gw = (p->nmax + PK_WAVES - 1) / PK_WAVES;
+    hipLaunchKernelGGL(phase == ACG_SORTED_MEASURE ? measure : render, dim3(gw), dim3(64 * PK_WAVES), 0, (hipStream_t)stream, *p);
+    return (int)hipGetLastError();
+}

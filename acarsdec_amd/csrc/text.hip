@@ -306,3 +306,8 @@ extern "C" int acg_launch_text(const AcgSinkPass* p, void* stream)
 {
     return pk_launch(p, stream, text_keys_kernel, text_measure_kernel, text_sum_kernel, text_offsets_kernel, text_render_kernel);
 }
+
+extern "C" int acg_launch_text_sorted(const AcgSinkPass* p, int phase, void* stream)
+{
+    return pk_launch_sorted(p, stream, phase, text_measure_kernel, text_render_kernel);
+}

@@ -484,16 +484,17 @@ class Decoder:
         """a drain / collect that looped over several C calls keeps the keys of the earlier ones: sink_keys then covers them all"""
         if not hasattr(self, "_keys_kept"):
             self._keys_kept = {}
-        self._keys_kept[kind] = np.concatenate(parts + [self._c_sink_keys(K.SINK_JSON if kind == "json" else K.SINK_TEXT)]) if parts else None
+        self._keys_kept[kind] = np.concatenate(parts + [self._c_sink_keys(SINK_KINDS[kind])]) if parts else None
 
     def sink_keys(self, kind):
         """The order keys (numpy uint64: channel number handed out << 44 | end_bit) of the records the most recent drain_json /
-        collect_json (kind "json") or drain_text / collect_text ("text") returned, one per record in their order.  Ascending
-        within a C call; several decoders' (keys, records) go to shard.merge_keyed.  Empty before any such call."""
-        if kind not in ("json", "text"):
-            raise ValueError("kind is 'json' or 'text'")
+        collect_json (kind "json"), drain_text / collect_text ("text") or drain_outputs / collect_outputs ("outputs": one list
+        for all legs) returned, one per record in their order.  Ascending within a C call; several decoders' (keys, records) go
+        to shard.merge_keyed.  Empty before any such call."""
+        if kind not in SINK_KINDS:
+            raise ValueError("kind is 'json', 'text' or 'outputs'")
         kept = getattr(self, "_keys_kept", {}).get(kind)
-        return kept if kept is not None else self._c_sink_keys(K.SINK_JSON if kind == "json" else K.SINK_TEXT)
+        return kept if kept is not None else self._c_sink_keys(SINK_KINDS[kind])
 
     # ---- the JSON sink (acg_json_enable, acg_drain_json, acg_collect_json) -------------------------------------------------
     def enable_json(self, t0, station_id="", app_name="acarsdec", app_ver="", freqs_hz=None):
@@ -590,6 +591,86 @@ class Decoder:
         self._chk(self.L.acg_lab_text_level_guard(self.ctx, C.byref(n)))
         return n.value
 
+    # ---- the outputs: every output of a message from one consumption (acg_outputs_enable, acg_drain_outputs) ----------------
+    def enable_outputs(self, legs, t0, station_id="", app_name="acarsdec", app_ver="", freqs_hz=None):
+        """Up to four legs rendered from the same kept records of one take, record i of every leg the same message: what the
+        reference's outputmsg() prints (-o) and sends (-n, -N, -j) from one msg.  legs: see outputs_config ("msgs", "json",
+        "oneline", "std", "pp", "sv", or (format, dict(date=.., freq=..))); t0, station_id, app_name, app_ver, freqs_hz as for
+        enable_json / enable_text, one of each for all legs."""
+        cfg = outputs_config(legs, t0, station_id, app_name, app_ver)
+        fr = None
+        if freqs_hz is not None:
+            fr = np.ascontiguousarray(freqs_hz, dtype=np.int32)
+            assert fr.size == self.nch
+        self._chk(self.L.acg_outputs_enable(self.ctx, C.byref(cfg), fr.ctypes.data if fr is not None else None))
+        self._out_kinds = [cfg.leg[l].kind for l in range(cfg.nlegs)]
+
+    def disable_outputs(self):
+        self._chk(self.L.acg_outputs_enable(self.ctx, None, None))
+        self._out_kinds = []
+
+    def _outputs_once(self, fn, max_recs, caps, *lead):
+        """one C call: (rc, nrecs, one list per leg).  caps: records of room per leg (None: max_recs for every leg)"""
+        kinds = getattr(self, "_out_kinds", [])
+        n = max(1, int(max_recs))
+        caps = [n] * len(kinds) if caps is None else [int(c) for c in caps]
+        bufs = (K.OutBuf * max(1, len(kinds)))()
+        keep = []
+        for l, kind in enumerate(kinds):
+            if kind == K.OUT_MSGS:
+                out, extra = (K.Msg * max(1, caps[l]))(), (K.Oooi * max(1, caps[l]))()
+                bufs[l].cap, bufs[l].oooi = caps[l] * C.sizeof(K.Msg), C.addressof(extra)
+            else:
+                rec_max = K.JSON_LINE_MAX if kind == K.OUT_JSON else K.TEXT_REC_MAX
+                out, extra = C.create_string_buffer(max(1, caps[l] * rec_max)), (C.c_uint * (n + 1))()
+                bufs[l].cap, bufs[l].offs = caps[l] * rec_max, C.addressof(extra)
+            bufs[l].out = C.addressof(out)
+            keep.append((out, extra))
+        nr = C.c_int(0)
+        rc = self._chk(fn(self.ctx, *lead, bufs, n, C.byref(nr)), allow=(K.EAGAIN,))
+        legs = []
+        for l, kind in enumerate(kinds):
+            out, extra = keep[l]
+            if kind == K.OUT_MSGS:
+                assert bufs[l].nbytes == nr.value * C.sizeof(K.Msg)
+                legs.append([(K.Msg.from_buffer_copy(out[i]), K.Oooi.from_buffer_copy(extra[i])) for i in range(nr.value)])
+            else:
+                blob, offs = C.string_at(out, bufs[l].nbytes), extra[:nr.value + 1]
+                assert offs[0] == 0 and offs[nr.value] == bufs[l].nbytes
+                legs.append([blob[offs[i]:offs[i + 1]] for i in range(nr.value)])
+        return rc, nr.value, legs
+
+    def _outputs_call(self, fn, max_recs, caps, *lead):
+        out = [[] for _ in getattr(self, "_out_kinds", [])]
+        keys = []                                    # as _json_call
+        while True:
+            rc, _, legs = self._outputs_once(fn, max_recs, caps, *lead)
+            for acc, leg in zip(out, legs):
+                acc += leg
+            if rc == K.OK:
+                self._keep_keys("outputs", keys)
+                return out
+            keys.append(self._c_sink_keys(K.SINK_OUTPUTS))
+
+    def drain_outputs(self, max_recs=4096, caps=None):
+        """Every leg of every block completed since the last drain (needs repair=True and enable_outputs), consumed once: one
+        list per leg in the order of enable_outputs' legs -- bytes records (JSON, text) or (K.Msg, K.Oooi) pairs (msgs) -- all
+        of one length, record i of each the same message, in (chn, end_bit) order per C call; loops while the C side says
+        ACG_EAGAIN.  caps (a test aid: the binding bound of a take) gives each leg's buffer room for that many records instead of
+        max_recs."""
+        return self._outputs_call(self.L.acg_drain_outputs, max_recs, caps)
+
+    def drain_outputs_once(self, max_recs=4096, caps=None):
+        """A test aid, not part of the interface: (more, nrecs, legs) of ONE acg_drain_outputs call; more: the C side said
+        ACG_EAGAIN"""
+        rc, n, legs = self._outputs_once(self.L.acg_drain_outputs, max_recs, caps)
+        self._keep_keys("outputs", [])               # sink_keys("outputs"): this call's
+        return rc == K.EAGAIN, n, legs
+
+    def collect_outputs(self, lag=1, max_recs=4096, caps=None):
+        """Streaming variant (acg_collect_outputs): the legs of all calls but the `lag` newest"""
+        return self._outputs_call(self.L.acg_collect_outputs, max_recs, caps, lag)
+
     def bits(self, ch):
         vo = np.zeros(self.bit_cap, dtype=np.float32)
         lvl = np.zeros(self.bit_cap, dtype=np.float32)
@@ -671,6 +752,29 @@ def text_config(fmt, t0, date=False, freq=False, station_id=""):
         raise ValueError("station_id holds 32 characters")
     flags = (K.TEXT_F_DATE if date else 0) | (K.TEXT_F_FREQ if freq else 0)
     return K.TextConfig(TEXT_FORMATS.get(fmt, fmt), flags, int(sec), int(usec), station_id)
+
+
+SINK_KINDS = {"json": K.SINK_JSON, "text": K.SINK_TEXT, "outputs": K.SINK_OUTPUTS}      # Decoder.sink_keys
+OUT_KINDS = dict(TEXT_FORMATS, msgs=K.OUT_MSGS, json=K.OUT_JSON)
+
+
+def outputs_config(legs, t0, station_id="", app_name="acarsdec", app_ver=""):
+    """K.OutputsConfig for acg_outputs_enable / acg_selftest_outputs.  legs: one entry per leg -- a name of OUT_KINDS ("msgs",
+    "json", "oneline", "std", "pp", "sv"), a (name, dict(date=.., freq=..)) pair for a text format with flags, or a (kind, flags)
+    pair of integers as the C side takes them; t0 and the strings as json_config"""
+    j = json_config(t0, station_id, app_name, app_ver)
+    legs = list(legs)
+    if len(legs) > K.OUT_LEGS_MAX:
+        raise ValueError("at most %d legs" % K.OUT_LEGS_MAX)
+    cfg = K.OutputsConfig()
+    cfg.nlegs = len(legs)
+    for l, leg in enumerate(legs):
+        kind, flags = leg if isinstance(leg, tuple) else (leg, 0)
+        if isinstance(flags, dict):
+            flags = (K.TEXT_F_DATE if flags.get("date") else 0) | (K.TEXT_F_FREQ if flags.get("freq") else 0)
+        cfg.leg[l].kind, cfg.leg[l].flags = OUT_KINDS.get(kind, kind), int(flags)
+    cfg.t0_sec, cfg.t0_usec, cfg.station_id, cfg.app_name, cfg.app_ver = j.t0_sec, j.t0_usec, j.station_id, j.app_name, j.app_ver
+    return cfg
 
 
 # oooi_t field -> the reference JSON's key (output.c:280-295, in the order buildjson adds them)

@@ -600,6 +600,65 @@ int  acg_text_enable(acg_ctx *ctx, const acg_text_config *cfg, const int *Fr_hz)
 int  acg_drain_text(acg_ctx *ctx, char *out, size_t cap, size_t *nbytes, unsigned int *offs, int max_recs, int *nrecs);
 int  acg_collect_text(acg_ctx *ctx, int lag, char *out, size_t cap, size_t *nbytes, unsigned int *offs, int max_recs, int *nrecs);
 
+/* ---- the outputs: every output of a message from ONE consumption ---------------------------------------------------------------
+ * The reference's outputmsg() prints the format -o selects AND sends the packet -n / -N / -j selects, both from the same msg
+ * (output.c:665-701).  The entry points above each consume the blocks they hand out, so a block rendered as a JSON line is gone
+ * before the text sink sees it.  acg_drain_outputs / acg_collect_outputs consume a take of blocks ONCE and hand out up to
+ * ACG_OUT_LEGS_MAX "legs" rendered from the same kept records in the same order: record i of every leg is the same message.
+ * Off by default; with it off nothing is allocated or launched and every entry point above hands out the bytes it hands out
+ * without this section.
+ *   Legs.    1 <= nlegs <= ACG_OUT_LEGS_MAX, the kinds pairwise distinct: at most one ACG_OUT_MSGS leg and one ACG_OUT_JSON leg,
+ *            and two or three different text formats are allowed (-o 1 beside -n: ONELINE and SV).  -o 4 -j is ONE JSON leg, which
+ *            the host writes and sends, like the reference's one jsonbuf.  A text leg's kind is its ACG_TEXT_* format and its
+ *            flags are the ACG_TEXT_F_* that format takes; the other kinds take no flag.
+ *   Errors.  acg_outputs_config_check (host arithmetic only, no context) and acg_outputs_enable say ACG_EINVAL for nlegs out of
+ *            range, an unknown kind, a flag the kind does not take, duplicate kinds, t0_sec outside [10^9, 4 * 10^9), t0_usec
+ *            outside 0..999999, an unterminated string: the conditions of acg_json_enable and acg_text_enable, through the same
+ *            checks.  ACG_ESTATE: context without ACG_F_REPAIR.  cfg == NULL: off, everything freed.  acg_reset keeps the
+ *            configuration, acg_destroy frees it.  Fr_hz as for acg_json_enable / acg_text_enable, one table for all legs.
+ *   Take.    A call looks at the oldest min(max_recs, min over legs of cap / recmax) queued blocks (recmax: ACG_JSON_LINE_MAX,
+ *            ACG_TEXT_REC_MAX, sizeof(acg_msg)) and consumes exactly those, ONCE, for all legs.  More queued: ACG_EAGAIN -- call
+ *            again, nothing is lost and nothing is rendered twice.  ACG_EINVAL: a leg's cap below its recmax, a missing buffer or
+ *            table, max_recs < 1.  ACG_ESTATE: no ACG_F_REPAIR, or the outputs are not enabled.
+ *   Order.   Every leg hands out *nrecs records in ascending key order -- the (chn, end_bit) order of every other entry point,
+ *            numbered by acg_set_channel_numbers' map when one is set.  JSON and text legs hand out offs[0 .. *nrecs] (the JSON
+ *            leg too, so that all legs index alike); acg_sink_keys(.., ACG_SINK_OUTPUTS, ..) hands out ONE key list for all legs.
+ *   Bytes.   Each leg is byte for byte what its own entry point hands out for the same blocks: acg_drain_json; acg_drain_text
+ *            with that format and those flags; acg_drain_msgs_oooi (lvl, soh_sample, the reserved words zero, the number handed
+ *            out in chn).
+ *   Once.    The filters, the flight table's pass, the statistics pass and (in a call that consumes nothing) the commit of imported
+ *            flight events happen once per take, whatever the number of legs.  -o 3 / -o 5 stay acg_flight_monitor_text /
+ *            acg_drain_routes_json, called after the outputs call: that call has updated the table.
+ * The individually enabled JSON and text sinks are separate states and keep working beside the outputs; each entry point consumes
+ * the blocks it hands out. */
+#define ACG_OUT_MSGS      0x10   /* acg_msg + acg_oooi records, as acg_drain_msgs_oooi hands them out */
+#define ACG_OUT_JSON      0x20   /* buildjson()'s line, as acg_drain_json */
+/* text legs use ACG_TEXT_ONELINE / _STD / _PP / _SV as their kind */
+#define ACG_OUT_LEGS_MAX  4
+typedef struct {
+	int kind;                     /* ACG_OUT_MSGS, ACG_OUT_JSON or an ACG_TEXT_* format */
+	unsigned int flags;           /* the ACG_TEXT_F_* the kind takes, else 0 */
+} acg_out_leg;
+typedef struct {
+	int nlegs;
+	acg_out_leg leg[ACG_OUT_LEGS_MAX];
+	long long t0_sec;             /* one epoch for all legs: tv = t0 + soh_sample / 12500 s, in integers */
+	int t0_usec;                  /* 0 .. 999999 */
+	char station_id[33], app_name[17], app_ver[17];   /* as acg_json_config's; station_id also SV's "%8s" */
+} acg_outputs_config;
+typedef struct {
+	void *out;                    /* JSON and text legs: the packed records; MSGS leg: an acg_msg array */
+	size_t cap;                   /* bytes of out (MSGS leg too) */
+	unsigned int *offs;           /* JSON and text legs: max_recs + 1 entries of room; MSGS leg: NULL */
+	acg_oooi *oooi;               /* MSGS leg only: cap / sizeof(acg_msg) entries; else NULL */
+	size_t nbytes;                /* out: bytes written to this leg */
+} acg_out_buf;
+int  acg_outputs_config_check(const acg_outputs_config *cfg);
+int  acg_outputs_enable(acg_ctx *ctx, const acg_outputs_config *cfg, const int *Fr_hz);
+/* bufs[nlegs], in the order of the configuration's legs */
+int  acg_drain_outputs(acg_ctx *ctx, acg_out_buf *bufs, int max_recs, int *nrecs);
+int  acg_collect_outputs(acg_ctx *ctx, int lag, acg_out_buf *bufs, int max_recs, int *nrecs);
+
 /* ---- sharded hosts: global channel numbers in everything handed out, and the keys to merge by ---------------------------------
  * A host that spreads its channels over N contexts (`c mod N`: slot l of rank r is channel l * N + r) gives every context the
  * numbers of its slots once; from then on N contexts behind one host hand out exactly what ONE context over all channels hands
@@ -630,9 +689,12 @@ int  acg_set_channel_numbers(acg_ctx *ctx, const int *chn);
  * sink call on every context over the same sample span, a k-way merge of (keys, records) by key is the one stream a single context
  * would have handed out in that call.  JSON lines need no offset table for it (a line holds no raw '\n': cJSON escapes it), the
  * text sink hands out its offsets.  As with the flight table's round, a call that returns ACG_EAGAIN has consumed an arbitrary
- * oldest part of the queue: the merge then holds per call, so a host sizes its buffers for a round. */
+ * oldest part of the queue: the merge then holds per call, so a host sizes its buffers for a round.
+ * ACG_SINK_OUTPUTS: the keys of the most recent acg_drain_outputs / acg_collect_outputs call, ONE list for all its legs (the merge
+ * is applied per leg with it); ACG_ESTATE: the outputs are off. */
 #define ACG_SINK_JSON  1
 #define ACG_SINK_TEXT  2
+#define ACG_SINK_OUTPUTS  4      /* (3 stays what it was: ACG_EINVAL) */
 int  acg_sink_keys(acg_ctx *ctx, int sink, unsigned long long *keys, int max, int *n);
 
 /* ---- per-channel reception statistics: what the reference says under -v, counted on the device --------------------------------

@@ -137,6 +137,31 @@ int  acg_lab_text_level_guard(acg_ctx *ctx, unsigned int *near_midpoint);
 int  acg_lab_time_sink_passes(const acg_msg *in, int n, const acg_json_config *jcfg, const acg_text_config *tcfg, int nch, int warmup, int reps,
 			      float *ms);
 
+/* The three entries of the outputs below are compiled into the LAB library only (libacarsdec_amd_lab.so); the product library
+ * exports their names and says ACG_ESTATE.
+ *
+ * diagnostics: the combined outputs pass (label.hip's filter and compaction, then outs.hip's one order and every leg of cfg) on n
+ * caller-supplied records, exactly as acg_selftest_msg_json / _text take them (level = in[i].lvl as it stands, time, dropped
+ * records, Fr_hz, the ACG_EINVAL conditions).  bufs[cfg->nlegs] as acg_drain_outputs takes them (offs: n + 1 entries of room); a
+ * JSON or text leg is what its own self test hands out, the MSGS leg the kept records in key order (equal keys: input order) with
+ * lvl as given, the reserved words zero and their acg_oooi.  *nrecs: the records of every leg.
+ * ACG_EAGAIN: a leg's cap < the bytes it needs (every leg's nbytes says how many; nothing is written); ACG_ENODEV: no GPU;
+ * ACG_ESTATE: the entry's own check found the legs not indexing alike -- the first *nrecs sorted keys the pass left on the device
+ * are real and ascending (equal keys: input order) over distinct kept records, every table starts at 0, ascends strictly and ends
+ * at its leg's bytes, and record i of the MSGS leg carries key i. */
+int  acg_selftest_outputs(const acg_msg *in, int n, const acg_msg_filter *f, const acg_outputs_config *cfg, const int *Fr_hz, int nch,
+			  acg_out_buf *bufs, int *nrecs);
+/* diagnostics: acg_lab_json_level_guard / acg_lab_text_level_guard for leg `leg` of the outputs (a JSON or text leg) of a context
+ * of the lab library */
+int  acg_lab_outputs_level_guard(acg_ctx *ctx, int leg, unsigned int *near_midpoint);
+/* measurement: as acg_lab_time_sink_passes, two arms over the SAME n records alternated within every round, each bracketed by HIP
+ * events on one stream.  cfg: exactly one JSON leg and one text leg.  Arm A, ms[0 .. reps): json.hip's passes followed by
+ * text.hip's, the launchers of acg_drain_json and acg_drain_text; arm B, ms[reps .. 2 reps): the combined pass over those two
+ * legs (one keys launch, one sort and two scan launches fewer).  ACG_SINK_MAP=1 (acg_tune): both arms under a channel map, as
+ * there.  ACG_ESTATE: what arm B left on the device is not, leg by leg, what arm A left (counters, offset table, bytes): the
+ * figures are refused.  ACG_ENODEV: no GPU. */
+int  acg_lab_time_output_passes(const acg_msg *in, int n, const acg_outputs_config *cfg, int nch, int warmup, int reps, float *ms);
+
 /* Test hook (the block ring across the wrap of its 32-bit counters): right after acg_reset, with nothing queued,
  * sets the device's block counter, the repair pass's mark and the host's consumer mark to `value`, as if that many blocks had
  * been produced and consumed already.  ACG_ESTATE if calls have been issued since the reset. */
