@@ -41,6 +41,7 @@ struct acg_ctx {
     size_t dm_pitch = 0;
     int bit_cap = 0;
     unsigned int frame_cap = 0;
+    unsigned int per_call = 0;      // most blocks one process call can queue (what frame_cap was sized from)
     int msk_lpc = 8;                // lanes per channel in the MSK kernel
     int msk_high_prio = 1;
     int msk_split = 0;              // demodulator as wave pairs (msk2.hip)
@@ -163,10 +164,17 @@ int stats_zero(acg_ctx* ctx);
 
 // results.cpp: a drain's `lag`
 static constexpr int DRAIN = -1;
+// results.cpp: what ring_upto finds and ring_claim works on
+struct RingSpan {
+    unsigned int upto = 0;          // where this collect / drain ends
+    unsigned int live = 0;          // the device's count with every issued call finished, where ring_upto has waited for that (a drain; a
+                                    // collect that may have been lapped); otherwise upto: nothing newer can have reached the consumer
+    bool any = false;               // false: a collect with nothing pending (it returns ACG_OK at once)
+};
 // results.cpp: where a collect / drain ends
-int ring_upto(acg_ctx* ctx, int lag, unsigned int* upto, bool* any);
-// results.cpp: claims the oldest min(pending, max) blocks
-int ring_claim(acg_ctx* ctx, unsigned int upto, int max, unsigned int* pending, unsigned int* take);
+int ring_upto(acg_ctx* ctx, int lag, RingSpan* span);
+// results.cpp: accounts what the device overwrote, then claims the oldest min(pending, max) blocks
+int ring_claim(acg_ctx* ctx, const RingSpan& span, int max, unsigned int* pending, unsigned int* take);
 // results.cpp: what the call returns once the claimed records are out
 int ring_result(acg_ctx* ctx, int rc, unsigned int pending, unsigned int take, const char* again);
 // results.cpp: the split's records, device and host, grown on demand

@@ -187,6 +187,7 @@ extern "C" int acg_create(acg_ctx** out, const acg_config* cfg)
         }
         if (cap2 > 0x80000000ull) { delete c; return ACG_EINVAL; }
         c->frame_cap = (unsigned int)cap2;
+        c->per_call = (unsigned int)per_call;                                         // (results.cpp: how far the newest calls can be ahead of a collect's mark)
         c->lag_max = (int)std::min<unsigned long long>(acg_ctx::NCALL - 2, cap2 / per_call - 1);
     }
     c->exact_fir = (cfg->flags & ACG_F_EXACT_FIR) != 0;

@@ -8,44 +8,72 @@
 // the oldest min(pending, max) records of [consumed, upto), ordered by (chn, end_bit) within the call.  What does not fit
 // STAYS queued (ACG_EAGAIN: call again, nothing lost); only a ring that the device has lapped loses blocks (ACG_EOVERFLOW,
 // the count is in acg_last_error).
+//
+// The rule (include/acarsdec_amd.h, ACG_EOVERFLOW; tests/ring_model.py restates it, tests/test_gpu_ring_laps.py holds every entry
+// point to it).  With live = the device's count once every ISSUED call has finished:
+//     lost    = max(0, live - cap - consumed), consumed += lost       -- ACG_EOVERFLOW iff lost > 0
+//     pending = max(0, upto - consumed)                               -- a collect's mark may lie behind the consumer
+//     take    = min(pending, max), the blocks [consumed, consumed + take) go out, consumed += take
+// The loss is judged against `live`, not against a collect's own mark: the calls newer than that mark write into the ring whether
+// the host has waited for them or not, and what they overwrote is gone for this collect as well.
 
-// *upto: where this collect / drain ends; *any = false: a collect with nothing pending (it returns ACG_OK at once)
-int ring_upto(acg_ctx* ctx, int lag, unsigned int* upto, bool* any)
+// Where this collect / drain ends (RingSpan, acg_ctx.h), and the device's live count where only that can tell what was overwritten
+int ring_upto(acg_ctx* ctx, int lag, RingSpan* span)
 {
-    *any = false;
+    *span = RingSpan{};
     if (lag != DRAIN && lag > ctx->lag_max) return fail(ctx, ACG_EINVAL, "lag above acg_max_lag(): the block queue of this context holds fewer calls");
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     if (lag == DRAIN) {
         HIPCHK(ctx, hipDeviceSynchronize());
-        HIPCHK(ctx, hipMemcpy(upto, ctx->d_frame_count, sizeof(*upto), hipMemcpyDeviceToHost));
-        *any = true;
+        HIPCHK(ctx, hipMemcpy(&span->upto, ctx->d_frame_count, sizeof(span->upto), hipMemcpyDeviceToHost));
+        span->live = span->upto;
+        span->any = true;
         return ACG_OK;
     }
     if (ctx->call_seq <= (unsigned long long)lag) return ACG_OK;              // nothing old enough yet
     const unsigned long long call = ctx->call_seq - 1 - (unsigned long long)lag;
     const int slot = (int)(call % acg_ctx::NCALL);
     HIPCHK(ctx, hipEventSynchronize(ctx->call_done[slot]));                   // only that call, not newer ones
-    *upto = ctx->h_call_count[slot];
+    span->upto = span->live = ctx->h_call_count[slot];
     // (a drain may already have handed out more than that call had queued: its mark then lies BEHIND the consumer -- nothing
     //  is pending; the counters are monotonic and wrap, so the comparison is a signed difference)
-    *any = (int)(*upto - ctx->consumed) > 0;
+    const long long behind = (int)(span->upto - ctx->consumed);
+    // The `lag` newer calls have queued at most per_call blocks each behind that mark: live <= upto + lag * per_call.  While that
+    // bound stays inside the ring they cannot have reached the consumer, whether they have run yet or not, and nothing more is
+    // waited for or read (`upto` stands for the live count).  A host that collects after every call is always here: the ring
+    // holds (lag_max + 1) * per_call.
+    if (behind + (long long)lag * (long long)ctx->per_call <= (long long)ctx->frame_cap) {
+        span->any = behind > 0;
+        return ACG_OK;
+    }
+    // A host that fell behind (it skipped collects, or left a remainder through a small buffer): the newest calls may have
+    // overwritten what it has not consumed.  Only the device's count tells, once everything issued has finished -- the same
+    // outcome whether the newest call had run yet or not; the loss is ring_claim's to account.
+    // (one error text for both steps: the product library has no room for HIPCHK's two, tests/test_host_logic.py's size rule)
+    if (hipEventSynchronize(ctx->call_done[(int)((ctx->call_seq - 1) % acg_ctx::NCALL)]) != hipSuccess ||
+        hipMemcpy(&span->live, ctx->d_frame_count, sizeof(span->live), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(ctx, ACG_EHIP, "block queue: the live count could not be read");
+    span->any = true;
     return ACG_OK;
 }
 
-// Claims the oldest min(pending, max) blocks of [consumed, upto); ACG_EOVERFLOW when the device lapped the host
-int ring_claim(acg_ctx* ctx, unsigned int upto, int max, unsigned int* pending, unsigned int* take)
+// Accounts what the device has overwritten (ACG_EOVERFLOW), then claims the oldest min(pending, max) blocks of [consumed, upto)
+int ring_claim(acg_ctx* ctx, const RingSpan& span, int max, unsigned int* pending, unsigned int* take)
 {
     int rc = ACG_OK;
-    *pending = upto - ctx->consumed;                              // monotonic counters, wrap-safe
-    if (*pending > ctx->frame_cap) {                              // the device lapped the host: oldest lost
+    unsigned int queued = span.live - ctx->consumed;              // monotonic counters, wrap-safe
+    if (queued > ctx->frame_cap) {                                // the device lapped the host: oldest lost
+        const unsigned int lost = queued - ctx->frame_cap;
         char msg[96];
-        std::snprintf(msg, sizeof(msg), "block queue lapped: the %u oldest blocks are lost", *pending - ctx->frame_cap);
+        std::snprintf(msg, sizeof(msg), "block queue lapped: the %u oldest blocks are lost", lost);
         ctx->err = msg;
-        if (ctx->d_stats) ctx->lost_blocks += *pending - ctx->frame_cap;   // (they belong to no channel: their records are gone)
-        ctx->consumed = upto - ctx->frame_cap;
-        *pending = ctx->frame_cap;
+        if (ctx->d_stats) ctx->lost_blocks += lost;               // (they belong to no channel: their records are gone)
+        ctx->consumed += lost;
+        queued = ctx->frame_cap;
         rc = ACG_EOVERFLOW;
     }
+    *pending = span.upto - ctx->consumed;
+    if (*pending > queued) *pending = 0;                          // a collect's mark behind the consumer (the loss moved it there)
     *take = std::min(*pending, (unsigned int)std::max(0, max));
     return rc;
 }
@@ -90,11 +118,11 @@ static void order_by_channel(std::vector<unsigned int>& order, const Rec* rec)
 
 static int fetch_frames(acg_ctx* ctx, int lag, acg_frame* out, int max_frames, int* nframes)
 {
-    unsigned int upto = 0, pending = 0, take = 0;
-    bool any = false;
-    int rc = ring_upto(ctx, lag, &upto, &any);
-    if (rc != ACG_OK || !any) return rc;
-    rc = ring_claim(ctx, upto, max_frames, &pending, &take);
+    unsigned int pending = 0, take = 0;
+    RingSpan span;
+    int rc = ring_upto(ctx, lag, &span);
+    if (rc != ACG_OK || !span.any) return rc;
+    rc = ring_claim(ctx, span, max_frames, &pending, &take);
     if (take > ctx->h_stage_cap) {                                // host staging, grown on demand
         // Pageable on purpose: with a pinned destination (one SDMA transfer) the same copy, issued while the
         // down-converter saturates HBM, made every step 0.9 ms slower at 16 384 channels (10.3 -> 11.2 ms);
@@ -226,16 +254,16 @@ int launch_split(acg_ctx* ctx, unsigned int take, bool labels, unsigned int** d_
 
 static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
 {
-    unsigned int upto = 0, pending = 0, take = 0;
-    bool any = false;
-    int rc = ring_upto(ctx, lag, &upto, &any);
+    unsigned int pending = 0, take = 0;
+    RingSpan span;
+    int rc = ring_upto(ctx, lag, &span);
     if (rc != ACG_OK) return rc;
-    if (!any) return commit_imports(ctx);
+    if (!span.any) return commit_imports(ctx);
     if (!ctx->d_crctab) return fail(ctx, ACG_ESTATE, "context created without ACG_F_REPAIR");
     // A call splits and copies the oldest min(pending, max_msgs) blocks only (a block yields at most one message, so they
     // all fit) and consumes exactly those: draining a long queue through a small buffer costs what it hands out, not the
     // square of it, and the staging follows the caller's buffer, not the ring.
-    rc = ring_claim(ctx, upto, max_msgs, &pending, &take);
+    rc = ring_claim(ctx, span, max_msgs, &pending, &take);
     if (const int gr = grow_msg_stage(ctx, take)) return gr;
     // label.hip's pass (filters, label decoding, compaction) runs when a filter is set, the labels are asked for or the flight
     // table is on (its pass hangs on this one and shares its round trip); without all three the call launches and copies exactly

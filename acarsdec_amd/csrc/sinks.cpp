@@ -178,12 +178,12 @@ static int sink_fetch(acg_ctx* ctx, const AcgSinkFormat* fmt, AcgSinkState* st, 
     if (!st) return fail(ctx, ACG_ESTATE, fmt->is_off);
     st->last_nrecs = 0;
     const size_t fit = std::min<size_t>(std::min<size_t>(cap / fmt->rec_max, (size_t)max_recs), fmt->max_take);
-    unsigned int upto = 0, pending = 0, take = 0;
-    bool any = false;
-    int rc = ring_upto(ctx, lag, &upto, &any);
+    unsigned int pending = 0, take = 0;
+    RingSpan span;
+    int rc = ring_upto(ctx, lag, &span);
     if (rc != ACG_OK) return rc;
-    if (!any) return commit_imports(ctx);
-    rc = ring_claim(ctx, upto, (int)fit, &pending, &take);
+    if (!span.any) return commit_imports(ctx);
+    rc = ring_claim(ctx, span, (int)fit, &pending, &take);
     if (!take) {
         if (const int cr = commit_imports(ctx)) return cr;
         return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
@@ -884,12 +884,12 @@ static int outputs_fetch(acg_ctx* ctx, int lag, acg_out_buf* bufs, int max_recs,
         fit = std::min(fit, bufs[l].cap / leg_rec_max(o->cfg.leg[l].kind));
         if (o->st[l]) fit = std::min<size_t>(fit, o->st[l]->fmt->max_take);
     }
-    unsigned int upto = 0, pending = 0, take = 0;
-    bool any = false;
-    int rc = ring_upto(ctx, lag, &upto, &any);
+    unsigned int pending = 0, take = 0;
+    RingSpan span;
+    int rc = ring_upto(ctx, lag, &span);
     if (rc != ACG_OK) return rc;
-    if (!any) return commit_imports(ctx);
-    rc = ring_claim(ctx, upto, (int)std::min<size_t>(fit, INT_MAX), &pending, &take);
+    if (!span.any) return commit_imports(ctx);
+    rc = ring_claim(ctx, span, (int)std::min<size_t>(fit, INT_MAX), &pending, &take);
     if (!take) {
         if (const int cr = commit_imports(ctx)) return cr;
         return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");

@@ -39,7 +39,15 @@ extern "C" {
 #define ACG_EOVERFLOW  -5   /* results were LOST: the device lapped the block queue (the host collected too rarely), or a per-bit
                                log was longer than its buffer; what could be handed out has been.  From acg_drain_* /
                                acg_collect_* it reports the loss ONCE and may still leave blocks queued (the caller's buffer was
-                               smaller than what survived): call again -- the next call returns ACG_OK or ACG_EAGAIN */
+                               smaller than what survived): call again -- the next call returns ACG_OK or ACG_EAGAIN.
+                               The rule, for every acg_drain_* / acg_collect_* (cap = the queue's length in blocks, consumed = the
+                               blocks handed out or declared lost so far, live = the blocks queued by ALL process calls issued so
+                               far, upto = live for a drain, the queue's length at the end of the call `lag` calls back for a
+                               collect):  lost = max(0, live - cap - consumed) blocks, the oldest, are gone (their count is in
+                               acg_last_error and goes to acg_stats_read's lost_blocks); then the oldest
+                               min(max(0, upto - consumed), what the caller's buffer holds) blocks that remain are handed out.
+                               ACG_EOVERFLOW iff lost > 0.  The loss is judged against `live` for a collect as well: the calls
+                               newer than its mark write into the queue whether the host has waited for them or not */
 #define ACG_ESTATE     -6   /* call sequence error */
 #define ACG_EAGAIN     -7   /* drain/collect: the caller's buffer is full and more results are queued -- nothing is lost,
                                call again */
@@ -251,7 +259,12 @@ int  acg_host_unregister(void *p);
 int  acg_drain_frames(acg_ctx *ctx, acg_frame *out, int max_frames, int *nframes);
 /* Streaming variant: hands over the blocks of every process call except the `lag` most recent
  * ones and waits only for those older calls, so that the newest call(s) keep the GPU busy
- * (lag = 1: classic double buffering; lag = 0: wait for the last call only).  0 <= lag <= acg_max_lag(). */
+ * (lag = 1: classic double buffering; lag = 0: wait for the last call only).  0 <= lag <= acg_max_lag().
+ * With fewer than lag + 1 calls issued it hands out nothing.  A host that collects after every call is never lapped and
+ * never waits for a newer call.  One that fell behind -- it skipped collects, or left a remainder through a small buffer,
+ * so that what it has not consumed plus the worst case of the `lag` newer calls no longer fits the queue -- gets the rule
+ * of ACG_EOVERFLOW applied to the queue as it stands once every issued call has finished: such a collect (and only such a
+ * one) waits for the newest call too, reports what was overwritten, and hands out what is left up to its own mark. */
 int  acg_collect_frames(acg_ctx *ctx, int lag, acg_frame *out, int max_frames, int *nframes);
 /* Largest lag this context accepts: its block queue is sized for the worst case (a 56-bit block every 291 samples on
  * every channel) of acg_max_lag() + 1 calls, so a host that collects after every call cannot be lapped.
