@@ -59,7 +59,10 @@ MSK_LEAN_FLAGS = [f for i, f in enumerate(MSK_FLAGS) if not (f == "-disable-mach
 HOST_UNITS = ["tune.cpp", "ctx.cpp", "process.cpp", "results.cpp", "sinks.cpp", "state.cpp", "lab.cpp", "flights.cpp"]
 HOST_C_UNITS = ["host_setup.c"]
 # unit -> (flags, in the product library?).  msk2.hip (the two-wave demodulator: bit-identical and slower) is lab only.
-UNITS = [("fir.hip", ["-O3"], True), ("fir_mm.hip", ["-O3"], True), ("msk.hip", MSK_FLAGS, True), ("msk_lean.hip", MSK_LEAN_FLAGS, True), ("msk2.hip", MSK_FLAGS, False), ("synth.hip", ["-O3"], True),
+UNITS = [("fir.hip", ["-O3"], True),
+         # the recordings' sample formats and the matrix-pipe kernels (six of them the int8 format's) as compressed bundles, outs.hip's
+         # way: the size rule of tests/test_host_logic.py (LEDGER, "Complex int8 and complex float32")
+         ("fir_iq.hip", ["-O3", "--offload-compress"], True), ("fir_mm.hip", ["-O3", "--offload-compress"], True), ("msk.hip", MSK_FLAGS, True), ("msk_lean.hip", MSK_LEAN_FLAGS, True), ("msk2.hip", MSK_FLAGS, False), ("synth.hip", ["-O3"], True),
          ("blk.hip", ["-O3"], True), ("label.hip", ["-O3"], True), ("flight.hip", ["-O3"], True),
          ("json.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE, nothing fused: the level's float and the time stamp's double are computed here
          ("text.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE like json.hip: the same level float

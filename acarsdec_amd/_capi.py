@@ -14,6 +14,9 @@ F_BITLOG, F_TIMING, F_REPAIR, F_EXACT_FIR, F_PRECISE_MIXER = 1, 2, 4, 8, 16
 INTRATE, BLOCK, MAXDECIM, FLEN, TXTMAX = 12500, 1024, 320, 11, 250
 MAXDECIM_SAMPLES = 1024
 FMT_CS16, FMT_S16_SPLIT, FMT_F32_REAL = 1, 2, 3
+FMT_CS8, FMT_CF32 = 4, 5                   # SigMF ci8 / cf32_le
+# acg_lab_samples_launch.family
+FIR_STREAMING, FIR_WORKGROUP, FIR_MATRIX, FIR_SHARED_VECTOR = 1, 2, 3, 4
 PCM_S16, PCM_F32 = 1, 2
 
 
@@ -155,6 +158,12 @@ class LaunchShape(C.Structure):
                 ("runs", C.c_uint), ("wave_slots", C.c_uint), ("workgroups", C.c_uint), ("waves", C.c_uint)]
 
 
+class SamplesLaunch(C.Structure):
+    """acg_lab_samples_launch: the kernel family one launch of a sample format takes, and the streaming kernel's tile geometry"""
+    _fields_ = [("family", C.c_int), ("tile_windows", C.c_int), ("stages", C.c_int), ("waves_per_workgroup", C.c_int),
+                ("bodies_per_run", C.c_int), ("chunk_blocks", C.c_int), ("runs", C.c_uint), ("waves", C.c_uint)]
+
+
 assert C.sizeof(ChanStats) == 88
 assert C.sizeof(Flight) == 120 and C.sizeof(Route) == 56 and C.sizeof(FlightEvent) == 88
 
@@ -286,6 +295,7 @@ LAB_SYMBOLS = {
     "acg_lab_block_ring_size": (C.c_uint, [C.c_void_p]),
     "acg_lab_set_stream_counters": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong]),
     "acg_lab_fir_launch_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(LaunchShape)]),
+    "acg_lab_samples_launch_shape": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(SamplesLaunch)]),
     "acg_lab_pcm_deinterleave": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_float]),
 }
 # declared in acarsdec_amd_lab.h, present in the stamp build only (-DACG_MSK_STAMP)

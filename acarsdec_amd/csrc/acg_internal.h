@@ -301,6 +301,8 @@ struct FirArgs {
     const int4* groups;         // shared-stream kernel: {stream, first index into group_ch, channel count (<= 8), 0}
     const int* group_ch;        // shared-stream kernel: channel ids ordered by stream
     int ngroups;
+    int s8;                     // host side only: the bytes are int8 I,Q (ACG_FMT_CS8) and the launchers take the u8 kernels' signed
+                                // twins.  (It fills the padding behind ngroups: no other member moves, no kernel reads it.)
     const float* gtaps;         // shared-stream kernel: taps regrouped [group][step][channel][16]
     int wg_per_cu;              // resident down-converter workgroups per CU (0 = as many as fit, at most 5)
     int ncu;                    // CUs the launch may use (0 = the whole device; fewer on a CU-masked stream)
@@ -382,7 +384,26 @@ size_t acg_fir_mm1_image_bytes(int decim, int nch);                  // fir_mm.h
 int acg_fir_mm1_takes(const FirArgs* a);
 int acg_launch_fir_mm1_prep(const FirArgs* a, void* stream);
 int acg_launch_fir_mm1(const FirArgs* a, void* stream);
-int acg_launch_fir_fmt(const FirArgs* a, int fmt, void* stream);     // fmt: 1 CS16, 2 split int16 planes, 3 real f32
+int acg_launch_fir_fmt(const FirArgs* a, int fmt, void* stream);     // fmt: 1 CS16, 2 split int16 planes, 3 real f32, 5 complex f32
+// fir_iq.hip: the recordings' formats, reached through the launchers above (a->s8 / fmt 5), never from the host runtime
+int acg_launch_fir_s8(const FirArgs* a, void* stream);               // int8 I,Q, one stream per channel
+int acg_launch_fir_shared_s8(const FirArgs* a, long long grid, size_t lds, void* stream);   // ... several channels per stream, vector pipe
+int acg_launch_fir_cf32(const FirArgs* a, void* stream);             // complex float32
+// fir.hip: the kernel family a launch of sample format fmt (1 .. 5; 4 = int8 I,Q on the u8 kernels' signed twins, a->s8) takes,
+// and the streaming kernel's tile geometry.  A weak reference, as the sinks' launchers below: the host runtime is also linked
+// without the device units, where the lab entry that reports this says ACG_ESTATE.
+#define ACG_FIR_FAM_STREAMING 1     // wave-private streaming kernel (fir_u8_direct / fir_s8_direct / fir_fmt_direct)
+#define ACG_FIR_FAM_WORKGROUP 2     // workgroup-granular fallback (fir_u8_persist / fir_s8_persist / fir_fmt_kernel)
+#define ACG_FIR_FAM_MATRIX 3        // matrix pipe (fir_mm.hip)
+#define ACG_FIR_FAM_SHARED 4        // shared-stream vector kernel
+struct FirChoice {
+    int family;
+    int tile_win;               // streaming kernel: windows per tile (W)
+    long long runs;             // ... dispensed runs of the launch
+    long long waves;            // ... waves launched
+    int wpg, pairs;             // ... waves per workgroup, two-tile bodies per run
+};
+__attribute__((weak)) int acg_fir_choice(const FirArgs* a, int fmt, FirChoice* out);
 size_t acg_fir_lds_bytes(const FirArgs* a);
 // fir.hip: per-device launch state of every down-converter unit (not exported: the version script lists the public headers' names)
 int acg_fir_device_cus(int* num_cu);                                 // CUs of the current device; returns a HIP error or 0

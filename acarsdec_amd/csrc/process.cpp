@@ -131,7 +131,8 @@ static FirU8Kernel fir_u8_kernel(const acg_ctx* c, FirArgs& a)
     const acg_config& g = c->cfg;
     a.nseg = 1;
     // verification mode: rtl.c:335-353 in the reference's own order of operations (fir.hip, fir_u8_generic_kernel)
-    if (c->exact_fir || !c->tile_path) return FIR_U8_GENERIC;
+    // (ACG_FMT_CS8, a.s8: the exact-order kernel restates rtl.c's u8 loop and does not apply; fmt_args has checked decim % 8)
+    if (!a.s8 && (c->exact_fir || !c->tile_path)) return FIR_U8_GENERIC;
     a.cpr = a.row_bytes / 16;
     a.row_stride = (a.cpr & 1) ? a.row_bytes : a.row_bytes + 16;
     a.cpr_magic = ((1u << 20) + (unsigned int)a.cpr - 1) / (unsigned int)a.cpr;
@@ -146,7 +147,7 @@ static FirU8Kernel fir_u8_kernel(const acg_ctx* c, FirArgs& a)
     a.mm_img = c->d_mm_img;
     a.mm_chan = c->d_mm_chan;
     // one stream per channel: the exact contraction with K = 1 takes the arithmetic off the vector pipe (fir_u8_mm1_kernel)
-    if (c->ngroups == 0 && acg_tune_get("ACG_FIR_MM1", ACG_FIR_MM1_DEFAULT) && acg_fir_mm1_image_bytes(g.decim, 1) != 0) {
+    if (!a.s8 && c->ngroups == 0 && acg_tune_get("ACG_FIR_MM1", ACG_FIR_MM1_DEFAULT) && acg_fir_mm1_image_bytes(g.decim, 1) != 0) {
         // (its images are made at the first launch that wants them, launch_fir_u8: whether the kernel takes the shape does not
         //  depend on where they lie)
         FirArgs t = a;
@@ -668,17 +669,41 @@ extern "C" int acg_lab_pcm_deinterleave(acg_ctx* ctx, int fmt, const void* frame
 
 // ------------------------------------------------------------------------------------------
 // The other front ends' sample formats: soapy.c (CS16), sdrplay.c (split int16),
-// air.c (real f32).  Same tile kernel, 4 bytes per input sample.
+// air.c (real f32), and the recordings' (SigMF ci8, cf32_le).  Same tile kernel; bytes per sample and plane by format.
+static size_t fmt_sample_bytes(int fmt)
+{
+    return fmt == ACG_FMT_CS8 || fmt == ACG_FMT_S16_SPLIT ? 2 : fmt == ACG_FMT_CF32 ? 8 : 4;
+}
+
+// The limits of a sample format on a context of window length decim with ntaps_pad padded taps: NULL, or the rule broken.
+// Host arithmetic only (acg_lab_samples_launch_shape reports the same answer without launching).
+static const char* fmt_limits(int fmt, int decim, int ntaps_pad)
+{
+    if (fmt < ACG_FMT_CS16 || fmt > ACG_FMT_CF32) return "unknown sample format";
+    if (fmt == ACG_FMT_CS8)
+        return decim % 8 ? "int8 I/Q samples need decim % 8 == 0 (a 16-byte chunk is 8 samples)"
+               : decim > ACG_MAXDECIM ? "int8 I/Q samples: decim above ACG_MAXDECIM (the u8 kernels' window limit)" : nullptr;
+    if (fmt == ACG_FMT_CF32)
+        return decim % 2 ? "complex float32 samples need decim % 2 == 0 (a 16-byte chunk is 2 samples)"
+               : decim > ACG_MAXDECIM_SAMPLES ? "complex float32 samples: decim above ACG_MAXDECIM_SAMPLES"
+               : ntaps_pad % 2 ? "complex float32 samples need ntaps % 2 == 0 when decim % 8 != 0" : nullptr;
+    if (decim % (fmt == ACG_FMT_S16_SPLIT ? 8 : 4) || (fmt == ACG_FMT_S16_SPLIT && decim > 208))
+        return "this sample format needs decim % 4 == 0 (split planes: % 8 and <= 208)";
+    if (ntaps_pad % (fmt == ACG_FMT_S16_SPLIT ? 8 : 4)) return "this sample format needs ntaps % 4 == 0 when decim % 8 != 0";
+    return nullptr;
+}
+
 static int fmt_args(acg_ctx* ctx, int fmt, FirArgs* a)
 {
     const acg_config& g = ctx->cfg;
-    if (fmt < ACG_FMT_CS16 || fmt > ACG_FMT_F32_REAL) return fail(ctx, ACG_EINVAL, "unknown sample format");
-    if (g.decim % (fmt == ACG_FMT_S16_SPLIT ? 8 : 4) || (fmt == ACG_FMT_S16_SPLIT && g.decim > 208))
-        return fail(ctx, ACG_EINVAL, "this sample format needs decim % 4 == 0 (split planes: % 8 and <= 208)");
-    if (ctx->ntaps_pad % (fmt == ACG_FMT_S16_SPLIT ? 8 : 4))
-        return fail(ctx, ACG_EINVAL, "this sample format needs ntaps % 4 == 0 when decim % 8 != 0");
+    if (const char* broken = fmt_limits(fmt, g.decim, ctx->ntaps_pad)) return fail(ctx, ACG_EINVAL, broken);
+    if (fmt == ACG_FMT_CS8) {                           // the u8 window and the u8 kernel choice, signed (iq, pitch: the caller)
+        *a = u8_args(ctx, nullptr, 0);
+        a->s8 = 1;
+        return ACG_OK;
+    }
     *a = fir_args(ctx);
-    a->row_bytes = 4 * g.decim;
+    a->row_bytes = (fmt == ACG_FMT_S16_SPLIT ? 2 : 1) * (int)fmt_sample_bytes(fmt) * g.decim;      // a window's bytes, both planes
     a->cpr_total = a->row_bytes / 16;
     a->kseg = (a->cpr_total + 51) / 52;                 // LDS slice <= 52 chunks per window (Airspy: 480 -> 3 x 40, 800 -> 4 x 50)
     a->cpr = (a->cpr_total + a->kseg - 1) / a->kseg;
@@ -689,10 +714,18 @@ static int fmt_args(acg_ctx* ctx, int fmt, FirArgs* a)
     return ACG_OK;
 }
 
-// pipeline chunk of the formats: 4-byte samples, half the callbacks per ~2 GB
-static int fmt_chunk_win(const acg_ctx* ctx)
+// pipeline chunk of the formats: the u8 path's bytes per launch (2-byte samples: its callbacks; 4-byte samples: half of them;
+// 8-byte samples: a quarter)
+static int fmt_chunk_win(const acg_ctx* ctx, int fmt)
 {
-    return (ctx->pipe_blocks > 0 ? (ctx->pipe_blocks + 1) / 2 : ctx->cfg.max_blocks) * ACG_BLOCK;
+    const int per = fmt == ACG_FMT_CS8 ? 1 : fmt == ACG_FMT_CF32 ? 4 : 2;
+    return (ctx->pipe_blocks > 0 ? (ctx->pipe_blocks + per - 1) / per : ctx->cfg.max_blocks) * ACG_BLOCK;
+}
+
+// the format's down-converter launch (see fir_launch)
+static auto fmt_launch(int fmt)
+{
+    return [fmt](acg_ctx* c, FirArgs& f, hipStream_t s) { return fmt == ACG_FMT_CS8 ? launch_fir_u8(c, f, s) : acg_launch_fir_fmt(&f, fmt, s); };
 }
 
 extern "C" int acg_process_samples_dev(acg_ctx* ctx, int fmt, const void* dev, size_t pitch_bytes, size_t plane_bytes,
@@ -708,9 +741,9 @@ extern "C" int acg_process_samples_dev(acg_ctx* ctx, int fmt, const void* dev, s
     a.iq = (const uint8_t*)dev;
     a.pitch = pitch_bytes;
     a.plane = plane_bytes;
-    const size_t win_bytes = (size_t)ctx->cfg.decim * (fmt == ACG_FMT_S16_SPLIT ? 2 : 4);      // of one plane
-    return run_pipeline(ctx, hip_stream ? (hipStream_t)hip_stream : ctx->stream, a, win_bytes, nblocks * ACG_BLOCK, fmt_chunk_win(ctx),
-                        [fmt](acg_ctx*, FirArgs& f, hipStream_t s) { return acg_launch_fir_fmt(&f, fmt, s); });
+    const size_t win_bytes = (size_t)ctx->cfg.decim * fmt_sample_bytes(fmt);                   // of one plane
+    return run_pipeline(ctx, hip_stream ? (hipStream_t)hip_stream : ctx->stream, a, win_bytes, nblocks * ACG_BLOCK, fmt_chunk_win(ctx, fmt),
+                        fmt_launch(fmt));
 }
 
 // Host feed with carry: windows may straddle feeds of any size (soapy.c:232-254, sdrplay.c:215-236,
@@ -727,7 +760,7 @@ extern "C" int acg_feed_samples_host(acg_ctx* ctx, int fmt, const void* p0, cons
     if (ctx->feed_fmt != fmt) { ctx->feed_fmt = fmt; ctx->feed_fill = 0; }
     const acg_config& g = ctx->cfg;
     const size_t M = (size_t)g.decim;
-    const size_t bps = fmt == ACG_FMT_S16_SPLIT ? 2 : 4;                     // bytes per sample per plane
+    const size_t bps = fmt_sample_bytes(fmt);                                 // bytes per sample per plane
     const size_t cap = (size_t)ctx->max_len * M;                              // samples a staging row holds (<= max_len windows per launch)
     const size_t plane = ((cap * bps) + 15) & ~(size_t)15;
     const size_t rowb = fmt == ACG_FMT_S16_SPLIT ? 2 * plane : plane;
@@ -756,8 +789,7 @@ extern "C" int acg_feed_samples_host(acg_ctx* ctx, int fmt, const void* p0, cons
             a.iq = base;
             a.pitch = rowb;
             a.plane = plane;
-            if ((r = run_pipeline(ctx, s, a, M * bps, (int)nwin, fmt_chunk_win(ctx),
-                                  [fmt](acg_ctx*, FirArgs& f, hipStream_t st) { return acg_launch_fir_fmt(&f, fmt, st); })) != ACG_OK) {
+            if ((r = run_pipeline(ctx, s, a, M * bps, (int)nwin, fmt_chunk_win(ctx, fmt), fmt_launch(fmt))) != ACG_OK) {
                 (void)hipEventSynchronize(ctx->h2d_done);   // the copy may still be reading the caller's buffers: not after we return
                 return r;
             }
@@ -877,5 +909,49 @@ extern "C" int acg_lab_fir_launch_shape(acg_ctx* ctx, int nblocks, acg_lab_launc
     out->wave_slots = p.wave_slots;
     out->workgroups = p.workgroups;
     out->waves = p.waves;
+    return ACG_OK;
+}
+
+// ---- lab: the kernel family one launch of `nblocks` callbacks of sample format fmt takes on this context -----------------------
+extern "C" int acg_lab_samples_launch_shape(acg_ctx* ctx, int fmt, int nblocks, acg_lab_samples_launch* out)
+{
+    if (!ctx || !out) return ACG_EINVAL;
+    if (nblocks < 1 || nblocks > ctx->cfg.max_blocks) return fail(ctx, ACG_EINVAL, "nblocks out of range");
+    if (!acg_fir_choice) return fail(ctx, ACG_ESTATE, "this build has no down-converter unit");
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    std::memset(out, 0, sizeof *out);
+    FirArgs a;
+    int r = fmt_args(ctx, fmt, &a);
+    if (r != ACG_OK) return r;
+    a.nwin = nblocks * ACG_BLOCK;
+    if (ctx->fir_stream) a.ncu = ctx->fir_ncu;
+    out->chunk_blocks = fmt_chunk_win(ctx, fmt) / ACG_BLOCK;
+    if (fmt == ACG_FMT_CS8) {
+        const FirU8Kernel k = fir_u8_kernel(ctx, a);
+        if (k == FIR_U8_MM || k == FIR_U8_SHARED) {
+            out->family = k == FIR_U8_MM ? ACG_LAB_FIR_MATRIX : ACG_LAB_FIR_SHARED_VECTOR;
+            if (k == FIR_U8_MM) {
+                int cus = 0;
+                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->cfg.device);
+                const MmPlan p = acg_fir_mm_plan(&a, cus);
+                out->tile_windows = 32;
+                out->stages = p.stages;
+                out->runs = p.runs;
+                out->waves = p.waves;
+            }
+            return ACG_OK;
+        }
+    }
+    FirChoice ch;
+    if (int e = acg_fir_choice(&a, fmt, &ch)) {
+        ctx->err = std::string("acg_lab_samples_launch_shape: ") + hipGetErrorString((hipError_t)e);
+        return ACG_EHIP;
+    }
+    out->family = ch.family;
+    out->tile_windows = ch.tile_win;
+    out->runs = (unsigned int)ch.runs;
+    out->waves = (unsigned int)ch.waves;
+    out->waves_per_workgroup = ch.wpg;
+    out->bodies_per_run = ch.pairs;
     return ACG_OK;
 }

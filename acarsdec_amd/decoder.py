@@ -148,8 +148,17 @@ class Decoder:
             self._chk(self.L.acg_process_iq_u8_host(self.ctx, p, pitch, nblocks))
 
     def feed(self, fmt, samples, q_plane=None):
-        """Host samples of any length (the SDR drivers' shape): [nstreams, n] int16 pairs / planes / float32."""
-        if fmt == K.FMT_CS16:
+        """Host samples of any length (the SDR drivers' shape): [nstreams, n] int16 pairs / planes / float32; the recordings'
+        formats: int8 pairs (FMT_CS8), float32 pairs or complex64 (FMT_CF32)."""
+        if fmt == K.FMT_CS8:
+            a = np.ascontiguousarray(samples, dtype=np.int8).reshape(self.nstreams, -1)
+            n, pitch = a.shape[1] // 2, a.shape[1] // 2
+        elif fmt == K.FMT_CF32:
+            a = np.asarray(samples)
+            a = np.ascontiguousarray(a, dtype=np.complex64 if np.iscomplexobj(a) else np.float32).reshape(self.nstreams, -1)
+            a = a.view(np.float32)
+            n, pitch = a.shape[1] // 2, a.shape[1] // 2
+        elif fmt == K.FMT_CS16:
             a = np.ascontiguousarray(samples, dtype=np.int16).reshape(self.nstreams, -1)
             n, pitch = a.shape[1] // 2, a.shape[1] // 2
         elif fmt == K.FMT_S16_SPLIT:
@@ -185,6 +194,13 @@ class Decoder:
         K.LaunchShape: kernel (0 vector pipe, 1 fir_u8_mm_kernel, 2 fir_u8_mm1_kernel), stages, runs, tiles_per_run, waves ..."""
         s = K.LaunchShape()
         self._chk(self.L.acg_lab_fir_launch_shape(self.ctx, int(nblocks), C.byref(s)))
+        return s
+
+    def samples_launch(self, fmt, nblocks):
+        """The kernel family one launch of nblocks callbacks of sample format fmt takes (acg_lab_samples_launch_shape), as a
+        K.SamplesLaunch: family (K.FIR_STREAMING / FIR_WORKGROUP / FIR_MATRIX / FIR_SHARED_VECTOR), tile_windows, runs, waves ..."""
+        s = K.SamplesLaunch()
+        self._chk(self.L.acg_lab_samples_launch_shape(self.ctx, int(fmt), int(nblocks), C.byref(s)))
         return s
 
     def set_stream_counters(self, nsamp_total, nbit_total, ch0=0, n=None):

@@ -206,6 +206,20 @@ def iq_s16_from_envelopes(envs, M, offsets_hz, phases=None, scale=0.25, noise=0.
     return out
 
 
+def iq_s8_from_envelopes(envs, M, offsets_hz, phases=None, scale=0.25, noise=0.0, rng=None):
+    """CS8 interleaved I,Q (SigMF ci8, what a HackRF delivers): int8 = rint(127 x), clipped."""
+    x = iq_complex_from_envelopes(envs, M, offsets_hz, phases, scale, noise, rng)
+    out = np.empty(x.size * 2, dtype=np.int8)
+    out[0::2] = np.clip(np.rint(127.0 * x.real), -128, 127).astype(np.int8)
+    out[1::2] = np.clip(np.rint(127.0 * x.imag), -128, 127).astype(np.int8)
+    return out
+
+
+def iq_cf32_from_envelopes(envs, M, offsets_hz, phases=None, scale=0.25, noise=0.0, rng=None):
+    """CF32 interleaved I,Q (SigMF cf32_le, GNU Radio's .cfile): iq_complex_from_envelopes as complex64."""
+    return iq_complex_from_envelopes(envs, M, offsets_hz, phases, scale, noise, rng).astype(np.complex64)
+
+
 def real_f32_from_envelopes(envs, M, offsets_hz, phases=None, scale=0.25, noise=0.0, rng=None):
     """Real float32 samples at INTRATE*M (what an Airspy in FLOAT32_REAL mode delivers, air.c:195,314):
     carriers at offsets_hz from 0 Hz of the REAL spectrum (air.c tunes so that channels sit around Fs/4)."""

@@ -209,6 +209,9 @@ int  acg_sync(acg_ctx *ctx);
 #define ACG_FMT_CS16       1   /* interleaved int16 I,Q: soapy.c:238-241 (dm = |D| with the /32768 of soapy.c:241) */
 #define ACG_FMT_S16_SPLIT  2   /* int16 I plane + int16 Q plane: sdrplay.c:219-225 (dm = |D|/4) */
 #define ACG_FMT_F32_REAL   3   /* real float32 samples, complex taps: air.c:314-324 */
+/* the recordings' formats: soapy.c:232-254's loop with only the sample type changed; taps as acg_soapy_taps makes them */
+#define ACG_FMT_CS8        4   /* interleaved int8 I,Q (SigMF ci8, HackRF):                    dm = |D| / 128 */
+#define ACG_FMT_CF32       5   /* interleaved float32 I,Q (SigMF cf32_le, .cfile, Soapy CF32): dm = |D|       */
 /* soapy.c:163-166 oscillator table ([decim][2]); ch->Fr is a float in that front end */
 int  acg_soapy_taps(float Fr_hz, int freq_hz, int decim, float *taps_out);
 /* sdrplay.c:160-164 (fixed rate multiplier 160) */
@@ -216,15 +219,20 @@ int  acg_sdrplay_taps(float Fr_hz, unsigned int Fc_hz, float *taps_out);
 /* air.c:62 centre frequency (no IF-filter branch) and air.c:278-285 taps; inrate = 12500*decim */
 unsigned int acg_airspy_choose_fc(unsigned int minF_hz, unsigned int maxF_hz);
 int  acg_airspy_taps(int Fr_hz, int Fc_hz, unsigned int inrate, float *taps_out);
-/* Window-aligned device input: [nstreams] rows of nblocks*1024*decim samples (4 bytes per sample;
- * ACG_FMT_S16_SPLIT: I plane at the row start, Q plane plane_bytes further).  decim % 4 == 0
- * and decim <= ACG_MAXDECIM_SAMPLES (split planes: decim % 8 == 0, decim <= 208).  Same asynchronous
- * contract and FIR/demodulator stream pipeline as acg_process_iq_u8_dev. */
+/* Window-aligned device input: [nstreams] rows of nblocks*1024*decim samples.  Bytes per sample: 4 (ACG_FMT_CS16,
+ * ACG_FMT_F32_REAL), 2 per plane (ACG_FMT_S16_SPLIT: I plane at the row start, Q plane plane_bytes further), 2 (ACG_FMT_CS8),
+ * 8 (ACG_FMT_CF32); plane_bytes is 0 for every format but split planes.  decim % 4 == 0 and decim <= ACG_MAXDECIM_SAMPLES
+ * (split planes: decim % 8 == 0, decim <= 208; ACG_FMT_CS8: decim % 8 == 0, decim <= ACG_MAXDECIM; ACG_FMT_CF32:
+ * decim % 2 == 0); base, pitch and plane 16-byte aligned; anything else is ACG_EINVAL before a launch.  Several channels of a
+ * stream (acg_set_channel_streams) each read it; ACG_FMT_CS8 at decim 160 / 192 / 200 then takes the matrix-pipe kernel of the
+ * u8 path (exact integer sums, one rounding).  Same asynchronous contract and FIR/demodulator stream pipeline as
+ * acg_process_iq_u8_dev. */
 int  acg_process_samples_dev(acg_ctx *ctx, int fmt, const void *dev, size_t pitch_bytes, size_t plane_bytes,
 			     int nblocks, void *hip_stream);
 /* Host input of ANY length per call, as the SDR drivers deliver it: windows may straddle calls (the
  * reference carries D / its index across buffers: soapy.c:232-254, sdrplay.c:215-236, air.c:299-338).
- * p0 = samples (I plane for ACG_FMT_S16_SPLIT), p1 = Q plane or NULL; rows pitch_samples apart.  Same return contract
+ * p0 = samples (I plane for ACG_FMT_S16_SPLIT), p1 = Q plane or NULL (every other format); rows pitch_samples apart; a
+ * sample is the format's bytes per sample as above (lengths and the pitch count samples, never bytes).  Same return contract
  * and the same two staging buffers as acg_process_iq_u8_host: the copy of feed i+1 runs beside the kernels of feed i. */
 int  acg_feed_samples_host(acg_ctx *ctx, int fmt, const void *p0, const void *p1, size_t pitch_samples,
 			   size_t nsamples);

@@ -196,6 +196,27 @@ typedef struct acg_lab_launch_shape {
 } acg_lab_launch_shape;
 int  acg_lab_fir_launch_shape(acg_ctx *ctx, int nblocks, acg_lab_launch_shape *out);
 
+/* diagnostics: which down-converter kernel family ONE launch of `nblocks` callbacks of sample format fmt (ACG_FMT_*) takes on this
+ * context, as the launchers themselves decide it, and the streaming kernel's tile geometry.  A call of acg_process_samples_dev is
+ * one such launch per pipeline chunk (chunk_blocks callbacks); acg_feed_samples_host launches the windows a feed completes.
+ * Reads the tuning switches as a launch at this moment would; launches nothing.  ACG_EINVAL: nblocks outside 1..max_blocks, or a
+ * format the context's window length does not admit (acg_last_error names the rule, as acg_process_samples_dev would). */
+#define ACG_LAB_FIR_STREAMING     1	/* wave-private streaming kernel */
+#define ACG_LAB_FIR_WORKGROUP     2	/* workgroup-granular fallback */
+#define ACG_LAB_FIR_MATRIX        3	/* matrix pipe: several channels per stream (ACG_FMT_CS8 at decim 160 / 192 / 200) */
+#define ACG_LAB_FIR_SHARED_VECTOR 4	/* shared-stream vector kernel (ACG_FMT_CS8 at other lengths or with ACG_FIR_MM=0) */
+typedef struct acg_lab_samples_launch {
+	int family;			/* ACG_LAB_FIR_* */
+	int tile_windows;		/* streaming kernel: windows per tile (W); matrix pipe: 32 */
+	int stages;			/* matrix pipe: tiles in flight per wave */
+	int waves_per_workgroup;	/* streaming kernel */
+	int bodies_per_run;		/* streaming kernel: two-tile bodies per dispensed run */
+	int chunk_blocks;		/* the format's pipeline chunk in callbacks */
+	unsigned int runs;		/* streaming kernel, matrix pipe: dispensed runs of the launch */
+	unsigned int waves;		/* ... and waves launched: runs beyond these are handed out by ticket */
+} acg_lab_samples_launch;
+int  acg_lab_samples_launch_shape(acg_ctx *ctx, int fmt, int nblocks, acg_lab_samples_launch *out);
+
 /* diagnostics: ONLY the de-interleave kernel of acg_process_pcm_dev (pcm.hip) on nframes host frames of the context's nch channels:
  * dm_host, an image of nch rows of pitch_floats words, is filled with `fill`, goes to the device, the kernel writes columns
  * [0, nframes) of its rows, and the WHOLE image comes back -- every word outside those columns must still be `fill`.  The input
