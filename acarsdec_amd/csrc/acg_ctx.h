@@ -141,9 +141,10 @@ struct acg_ctx {
     unsigned long long lost_blocks = 0;     // ... and the blocks lost to a lapped ring since the table was zeroed
 
     // ---- sinks.cpp: the batch sinks
-    struct AcgSinkState* text = nullptr;    // acg_text_enable: the text sink (text.hip), as json
-    struct AcgSinkState* json = nullptr;    // acg_json_enable: the JSON sink (json.hip): configuration, work space, rendered lines
-    struct AcgOutputs* outs = nullptr;      // acg_outputs_enable: the legs rendered from one take (outs.hip), a state beside the two above
+    // three independent instances of one type: configuration, order, work space and what the legs rendered (outs.hip's sequence)
+    struct AcgOutputs* text = nullptr;      // acg_text_enable: the text sink, one leg (text.hip)
+    struct AcgOutputs* json = nullptr;      // acg_json_enable: the JSON sink, one leg (json.hip)
+    struct AcgOutputs* outs = nullptr;      // acg_outputs_enable: up to ACG_OUT_LEGS_MAX legs rendered from one take
 };
 
 #define HIPCHK(ctx, call)                                                                  \
@@ -188,9 +189,7 @@ int launch_split(acg_ctx* ctx, unsigned int take, bool labels, unsigned int** d_
 // results.cpp: the device form of a message filter
 int label_filter_dev(const acg_msg_filter* f, AcgLabelFilter* d);
 
-// sinks.cpp: frees a sink (null: nothing)
-void sink_destroy(struct AcgSinkState* st);
-// sinks.cpp: frees the outputs (null: nothing)
+// sinks.cpp: frees a sink or the outputs (null: nothing)
 void outputs_destroy(struct AcgOutputs* o);
 
 

@@ -447,20 +447,17 @@ int acg_launch_flight_route_text(const AcgFlightTextPass* p, unsigned int n, voi
 // (a device word) or n_fixed; the result lies in (kb, vb)
 int acg_launch_sort_pairs(unsigned long long* ka, unsigned int* va, unsigned long long* kb, unsigned int* vb, const unsigned int* n_ptr,
                           unsigned int n_fixed, void* stream);
-// json.hip: order, measure, scan and render the kept records of one label pass into p->out; p->counters says how much.
-// A WEAK reference, as flights.h's: the host runtime is also linked without the device units (the sanitizer build of
-// tests/test_host_logic.py, which stubs the launchers it knows); there the JSON sink is absent and acg_json_enable says ACG_ESTATE.
-__attribute__((weak)) int acg_launch_json(const AcgSinkPass* p, void* stream);
-// text.hip: the same for the text formats (weak for the same reason)
-__attribute__((weak)) int acg_launch_text(const AcgSinkPass* p, void* stream);
-// json.hip, text.hip: pk_launch's tail for records somebody else has ordered (p->key_s / p->idx_s are filled): the measure
-// kernel (phase ACG_SORTED_MEASURE) or the render kernel (ACG_SORTED_RENDER); the scan between them is the caller's
+// json.hip, text.hip: a unit's part of outs.hip's sequence, over records that are ordered (p->key_s / p->idx_s are filled): the
+// measure kernel (phase ACG_SORTED_MEASURE) or the render kernel (ACG_SORTED_RENDER); the scan between them is the caller's
 #define ACG_SORTED_MEASURE 0
 #define ACG_SORTED_RENDER 1
 int acg_launch_json_sorted(const AcgSinkPass* p, int phase, void* stream);
 int acg_launch_text_sorted(const AcgSinkPass* p, int phase, void* stream);
-// outs.hip: keys and sort once, every leg's measure, one scan over all legs, every leg's render, the MSGS leg's gather
-// (weak for the same reason: there acg_outputs_enable says ACG_ESTATE)
+// outs.hip: keys and sort once, every leg's measure, one scan over all legs, every leg's render, the MSGS leg's gather; each
+// leg's counters say how much.  The one launch sequence of the JSON sink, the text sink (one leg each) and the outputs.
+// A WEAK reference, as flights.h's: the host runtime is also linked without the device units (the sanitizer build of
+// tests/test_host_logic.py, which stubs the launchers it knows); there the sinks are absent and acg_json_enable, acg_text_enable
+// and acg_outputs_enable say ACG_ESTATE.
 __attribute__((weak)) int acg_launch_outs(const AcgOutsPass* o, void* stream);
 // stats.hip: the per-channel statistics of the blocks an entry point consumes (weak for the same reason: there acg_stats_enable
 // says ACG_ESTATE)

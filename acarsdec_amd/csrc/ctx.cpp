@@ -56,9 +56,9 @@ static void free_all(acg_ctx* c)
     hipFree(c->d_kmsgs); hipFree(c->d_oooi); hipFree(c->d_kwork); std::free(c->h_oooi);
     if (c->flights) acg_fl_destroy(c->flights);
     c->flights = nullptr;
-    sink_destroy(c->json);
+    outputs_destroy(c->json);
     c->json = nullptr;
-    sink_destroy(c->text);
+    outputs_destroy(c->text);
     c->text = nullptr;
     outputs_destroy(c->outs);
     c->outs = nullptr;

@@ -19,8 +19,8 @@
 // House style as json.hip / text.hip: lane j computes character j (flight_text_num.h, text_num.h, json_num.h); a C string's end
 // is a ballot and a find-first; "%-8s", "%-7s", "%4s" and "%3d" pad and never cut; measure and render run the SAME function
 // (ft_row / ft_line <false / true>); no scratch, no per-byte global traffic of whole records.  sink_pack.h's pieces are used as
-// they are (PkLit, pk_sum, pk_offsets, pk_flush_row).  Its pk_measure / pk_render / pk_launch are written over AcgSinkPass and a
-// message record, so this unit has loop bodies of its own.  The row writers and the escape's rules (cJSON.c:858-877) are the
+// they are (PkLit, pk_sum, pk_offsets, pk_flush_row).  Its pk_measure / pk_render are written over AcgSinkPass and a message
+// record, so this unit has loop bodies and a launch sequence of its own.  The row writers and the escape's rules (cJSON.c:858-877) are the
 // sinks' own, sink_put.h; what only the monitor row uses ("%-Ns", the OOOI field, printtime()) is here and stores through pk_st,
 // and so is the one round a route's short strings need (ft_str_json, over the shared classes and escaped byte).
 #include "sink_put.h"

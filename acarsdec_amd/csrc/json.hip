@@ -3,25 +3,22 @@
 // label.hip kept and compacted for one drain / collect.  What leaves is what `-o 4` prints: one JSON object per message, each
 // ended by '\n', packed back to back in (chn, end_bit) order; the host copies bytes and two counters, no records.
 //
-// The passes, all on the stream of the label pass they hang on:
-//   json_keys_kernel     a thread per kept record: the sort key (chn << 44 | end_bit) and the record's index;
-//   flight_sort_kernel   flight.hip's one-workgroup radix sort (acg_launch_sort_pairs) puts them in (chn, end_bit) order;
-//   json_measure_kernel  one WAVE per record: the line's length.  The escape class of every string byte is decided by the lanes
-//                        in parallel (the text: four rounds of 64 lanes), a C string's end is a ballot and a find-first, the
-//                        length is popcounts;
-//   json_sum_kernel / json_offsets_kernel   the exclusive scan of the lengths in sorted order (label.hip's two-launch count /
-//                        base scheme): every line's byte offset, the pass's bytes and lines;
-//   json_render_kernel   one wave per record: the line assembled in a per-wave LDS row, then stored to its packed offset.
+// This unit's two kernels, launched by outs.hip's sequence (acg_launch_outs: keys, sort, measure, scan, render -- the JSON sink
+// is that sequence with one leg) through acg_launch_json_sorted, on the stream of the label pass they hang on:
+//   json_measure_kernel  one WAVE per record, in sorted order: the line's length.  The escape class of every string byte is
+//                        decided by the lanes in parallel (the text: four rounds of 64 lanes), a C string's end is a ballot and a
+//                        find-first, the length is popcounts;
+//   json_render_kernel   one wave per record: the line assembled in a per-wave LDS row, then stored to the packed offset the
+//                        scan between the two gave it.
 //
 // A string byte's place in the line is its index + the two-character escapes before it + 5 x the \u00xx escapes before it: two
 // ballots and two popcounts, never a lane walking the text.  Numbers are integer arithmetic (json_num.h): lane j computes the
 // j-th character of a token.  Measure and render run the SAME function (json_line<false / true>): the length a line was given
 // room for is the length it is rendered with.
 //
-// THE SEAM, the scan, the record load, the level's float, the bodies of the keys / measure / render kernels and the launch sequence
-// are shared with the text renderer (text.hip): sink_pack.h.  The row writers (bounded store, literal, number token, dword copy,
-// the string escape) are shared with text.hip and flight_text.hip: sink_put.h.  This unit supplies json_line and keeps its kernels
-// as wrappers.
+// THE SEAM, the record load, the level's float and the bodies of the measure / render kernels are shared with the text renderer
+// (text.hip): sink_pack.h.  The row writers (bounded store, literal, number token, dword copy, the string escape) are shared with
+// text.hip and flight_text.hip: sink_put.h.  This unit supplies json_line and keeps its two kernels as wrappers.
 //
 // No scratch (no indexed private array: a record's fields are read out of LDS, digits are computed, not stored), no per-byte
 // global traffic (a record comes in as 80 + 10 dword loads, the constant stretches as dwords, a line leaves as 16-byte stores and < 30 byte stores), two
@@ -136,8 +133,6 @@ struct JsonFmt {
 };
 
 // the passes (sink_pack.h): the kernels and their LDS are this unit's own
-__global__ __launch_bounds__(PK_WG) void json_keys_kernel(AcgSinkPass p) { pk_keys(p); }
-
 __global__ __launch_bounds__(64 * PK_WAVES) void json_measure_kernel(AcgSinkPass p)
 {
     __shared__ __attribute__((aligned(16))) unsigned char recs[PK_WAVES][PK_REC];
@@ -150,29 +145,11 @@ __global__ __launch_bounds__(64 * PK_WAVES) void json_measure_kernel(AcgSinkPass
     pk_measure<JsonFmt>(recs, p, r);
 }
 
-__global__ __launch_bounds__(PK_WG) void json_sum_kernel(AcgSinkPass p)
-{
-    __shared__ unsigned int sum_s;
-    pk_sum(&sum_s, p.len, p.wg_sum, p.wg_cnt, p.nmax, p.total);
-}
-
-__global__ __launch_bounds__(PK_WG) void json_offsets_kernel(AcgSinkPass p)
-{
-    __shared__ unsigned int base_s, cnt_s;
-    __shared__ unsigned int wave_n[PK_WG / 64];
-    pk_offsets(&base_s, &cnt_s, wave_n, p.len, p.off, p.wg_sum, p.wg_cnt, p.counters, p.nmax, p.total);
-}
-
 __global__ __launch_bounds__(64 * PK_WAVES) void json_render_kernel(AcgSinkPass p)
 {
     __shared__ __attribute__((aligned(16))) unsigned char recs[PK_WAVES][PK_REC];
     __shared__ __attribute__((aligned(16))) unsigned char rows[PK_WAVES][JsonFmt::REC_MAX + 16];
     pk_render<JsonFmt>(recs, rows, p);
-}
-
-extern "C" int acg_launch_json(const AcgSinkPass* p, void* stream)
-{
-    return pk_launch(p, stream, json_keys_kernel, json_measure_kernel, json_sum_kernel, json_offsets_kernel, json_render_kernel);
 }
 
 extern "C" int acg_launch_json_sorted(const AcgSinkPass* p, int phase, void* stream)

@@ -1,5 +1,7 @@
-// outs.hip -- the combined outputs pass (acg_drain_outputs / acg_collect_outputs): the kept records of ONE take rendered into
-// up to ACG_OUTS_LEGS legs, record i of every leg the same message.
+// outs.hip -- the one launch sequence of the batch sinks: the kept records of ONE take rendered into up to ACG_OUTS_LEGS legs,
+// record i of every leg the same message (acg_drain_outputs / acg_collect_outputs).  The JSON sink and the text sink
+// (acg_drain_json / acg_drain_text and their collects) are this sequence with one rendered leg, launch for launch what a
+// sequence of their own would be.
 //   outs_keys_kernel      the (chn, end_bit) keys of the take (sink_pack.h pk_keys), once for all legs;
 //   flight_sort_kernel    flight.hip's one-workgroup radix sort (acg_launch_sort_pairs), once: the serial part of a sink pass;
 //   <unit>_measure_kernel json.hip's / text.hip's own kernel per rendered leg (acg_launch_json_sorted / _text_sorted): unchanged;

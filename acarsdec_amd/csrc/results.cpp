@@ -191,7 +191,7 @@ extern "C" int acg_drain_frames(acg_ctx* ctx, acg_frame* out, int max_frames, in
 // ------------------------------------------------------------------------------------------
 // the claimed blocks through the device-side field split (blk.hip msg_split_kernel)
 static_assert(sizeof(AcgMsgRec) == sizeof(acg_msg), "device record and public record must have one layout");
-// the message entry points' staging (fetch_msgs, sink_fetch), grown on demand: the split's records, device and host ...
+// the message entry points' staging (fetch_msgs, outputs_fetch), grown on demand: the split's records, device and host ...
 int grow_msg_stage(acg_ctx* ctx, unsigned int take)
 {
     if (take <= ctx->msgs_cap) return ACG_OK;

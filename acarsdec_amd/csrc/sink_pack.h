@@ -1,22 +1,24 @@
 // sink_pack.h -- what the device renderers of the batch sink (json.hip, text.hip) have in common: a record and its acg_oooi into a
 // wave's LDS, the (chn, end_bit) sort key, the level's float and its guard, the two-launch exclusive scan of the record lengths
 // in sorted order, the seam-safe flush of a wave's LDS row to its packed place in the output, and the skeleton of the passes.
-// Every device function is inlined into the kernels of the unit that includes it, so each unit keeps kernels of its own.
+// Every device function is inlined into the kernels of the unit that includes it, so each unit keeps kernels of its own: json.hip
+// and text.hip a measure and a render kernel each; outs.hip the keys kernel and the scan's two, which it launches around them
+// (acg_launch_outs, the one launch sequence of the sinks and the outputs); flight_text.hip scan kernels over its own pass.
 //
 // THE SEAM.  Records are packed without padding, so two neighbours share a 16-byte chunk where they meet, and another wave writes
 // the neighbour.  No chunk is ever read back and merged: the row holds the record at the same offset mod 16 as its place in the
 // output, the first bytes up to the next 16-byte boundary and the last bytes behind the last one leave as BYTE stores, and only
 // chunks that lie wholly inside the record leave as 16-byte stores (LDS 16-byte reads, both sides aligned).
 //
-// THE SKELETON.  The bodies of the keys, measure and render kernels and the launch sequence are here too (pk_keys, pk_measure<F>,
-// pk_render<F>, pk_launch), written once over a format F that supplies
+// THE SKELETON.  The bodies of the keys, measure and render kernels are here too (pk_keys, pk_measure<F>, pk_render<F>), written
+// once over a format F that supplies
 //   F::REC_MAX                                   the longest record, a multiple of 64;
 //   F::record<W>(R, row, pass, lane, &near_mid)  the record's length; with W, its bytes at row (json_line, text_record);
 //   F::row_at(rows, wv, off)                     rows[wv] + off % 16: where wave wv's record starts in its row.  The same two
 //                                                operations in every unit; the order they are written in decides the order of two
 //                                                independent instructions of the render kernel, and each unit keeps its own.
-// A unit keeps its five __global__ kernels as thin wrappers (and with them its own names and __shared__ footprint; the measure
-// kernel also its two early-outs, see pk_measure) and its extern "C" launcher.
+// A unit keeps its two __global__ kernels as thin wrappers (and with them its own names and __shared__ footprint; the measure
+// kernel also its two early-outs, see pk_measure) and its extern "C" launcher (pk_launch_sorted).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "acg_internal.h"
@@ -191,26 +193,10 @@ __device__ __forceinline__ void pk_render(unsigned char (*recs)[PK_REC], unsigne
     pk_flush_row(rows[wv], p.out, off, len, lane);
 }
 
-// the launch sequence over a unit's five kernels, all on the stream of the label pass they hang on
+// A unit's part of the launch sequence (outs.hip, acg_launch_outs, which has ordered the take once for all its formats: key_s /
+// idx_s are filled), on the stream of the label pass it hangs on.  One of the unit's two wave-per-record kernels per call --
+// measure, then render -- because the scan between them runs over all the caller's formats at once.
 typedef void (*PkKernel)(AcgSinkPass);
-static inline int pk_launch(const AcgSinkPass* p, void* stream, PkKernel keys, PkKernel measure, PkKernel sum, PkKernel offsets, PkKernel render)
-{
-    if (p->nmax == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned int g = (p->nmax + PK_WG - 1) / PK_WG, gw = (p->nmax + PK_WAVES - 1) / PK_WAVES;
-    hipLaunchKernelGGL(keys, dim3(g), dim3(PK_WG), 0, s, *p);
-    int e = acg_launch_sort_pairs(p->key, p->idx, p->key_s, p->idx_s, p->total, 0u, stream);
-    if (e) return e;
-    hipLaunchKernelGGL(measure, dim3(gw), dim3(64 * PK_WAVES), 0, s, *p);
-    hipLaunchKernelGGL(sum, dim3(g), dim3(PK_WG), 0, s, *p);
-    hipLaunchKernelGGL(offsets, dim3(g), dim3(PK_WG), 0, s, *p);
-    hipLaunchKernelGGL(render, dim3(gw), dim3(64 * PK_WAVES), 0, s, *p);
-    return (int)hipGetLastError();
-}
-
-// pk_launch's tail for records that are ordered already (outs.hip orders a take once for several formats): key_s / idx_s are
-// filled.  One of the unit's two wave-per-record kernels per call -- measure, then render -- because the scan between them runs
-// over all the caller's formats at once.
 static inline int pk_launch_sorted(const AcgSinkPass* p, void* stream, int phase, PkKernel measure, PkKernel render)
 {
     if (p->nmax == 0) return 0;

@@ -7,13 +7,13 @@
 // What leaves is the records' bytes packed back to back in (chn, end_bit) order and the table of their offsets: a record may hold
 // any byte ("%1c" of a NUL mode, a '\n' inside a text), so there is nothing to split it by.
 //
-// The passes are json.hip's, on the stream of the label pass they hang on: text_keys_kernel + flight.hip's sort, text_measure_kernel
-// (one WAVE per record: its length), text_sum_kernel / text_offsets_kernel (the exclusive scan in sorted order = the offset table),
-// text_render_kernel (one wave per record: the record assembled in a per-wave LDS row, flushed seam-safe).  Scan, flush, record
-// load, sort key, the level's float, the kernels' bodies and the launch sequence are shared with json.hip (sink_pack.h), the row
-// writers (bounded store, literal, fill, number token) with json.hip and flight_text.hip (sink_put.h); this unit supplies
-// text_record, keeps its kernels as wrappers and what only these formats use (tx_*).  Measure and render run the SAME function
-// (text_record<false / true>).
+// This unit's two kernels are launched as json.hip's, by outs.hip's sequence (acg_launch_outs; the text sink is that sequence with
+// one leg) through acg_launch_text_sorted, on the stream of the label pass they hang on: text_measure_kernel (one WAVE per record:
+// its length) and, behind the scan in sorted order that makes the offset table, text_render_kernel (one wave per record: the
+// record assembled in a per-wave LDS row, flushed seam-safe).  Flush, record load, the level's float and the kernels' bodies are
+// shared with json.hip (sink_pack.h), the row writers (bounded store, literal, fill, number token) with json.hip and
+// flight_text.hip (sink_put.h); this unit supplies text_record, keeps its kernels as wrappers and what only these formats use
+// (tx_*).  Measure and render run the SAME function (text_record<false / true>).
 //
 // "%Ns" is a ballot and a find-first (the C string's end) and max(0, N - len) spaces in front; the text is four rounds of 64 lanes,
 // byte i at place i; lane j computes character j of a number or of the date (json_num.h, text_num.h).  No lane walks anything, no
@@ -268,8 +268,6 @@ struct TextFmt {
 };
 
 // the passes (sink_pack.h): the kernels and their LDS are this unit's own
-__global__ __launch_bounds__(PK_WG) void text_keys_kernel(AcgSinkPass p) { pk_keys(p); }
-
 __global__ __launch_bounds__(64 * PK_WAVES) void text_measure_kernel(AcgSinkPass p)
 {
     __shared__ __attribute__((aligned(16))) unsigned char recs[PK_WAVES][PK_REC];
@@ -282,29 +280,11 @@ __global__ __launch_bounds__(64 * PK_WAVES) void text_measure_kernel(AcgSinkPass
     pk_measure<TextFmt>(recs, p, r);
 }
 
-__global__ __launch_bounds__(PK_WG) void text_sum_kernel(AcgSinkPass p)
-{
-    __shared__ unsigned int sum_s;
-    pk_sum(&sum_s, p.len, p.wg_sum, p.wg_cnt, p.nmax, p.total);
-}
-
-__global__ __launch_bounds__(PK_WG) void text_offsets_kernel(AcgSinkPass p)
-{
-    __shared__ unsigned int base_s, cnt_s;
-    __shared__ unsigned int wave_n[PK_WG / 64];
-    pk_offsets(&base_s, &cnt_s, wave_n, p.len, p.off, p.wg_sum, p.wg_cnt, p.counters, p.nmax, p.total);
-}
-
 __global__ __launch_bounds__(64 * PK_WAVES) void text_render_kernel(AcgSinkPass p)
 {
     __shared__ __attribute__((aligned(16))) unsigned char recs[PK_WAVES][PK_REC];
     __shared__ __attribute__((aligned(16))) unsigned char rows[PK_WAVES][TextFmt::REC_MAX + 16];
     pk_render<TextFmt>(recs, rows, p);
-}
-
-extern "C" int acg_launch_text(const AcgSinkPass* p, void* stream)
-{
-    return pk_launch(p, stream, text_keys_kernel, text_measure_kernel, text_sum_kernel, text_offsets_kernel, text_render_kernel);
 }
 
 extern "C" int acg_launch_text_sorted(const AcgSinkPass* p, int phase, void* stream)

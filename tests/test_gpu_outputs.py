@@ -202,11 +202,13 @@ def test_designed_records_equal_the_sinks_own_lab_entries(D):
     with the acg_oooi acg_selftest_msg_labels decodes.  Asserted over the set: kept records under ONE (chn, end_bit) key that are
     neighbours in rank, inside a 256-rank workgroup and across two; every text length of 0, 1, 58 .. 65, 241, 242 among the kept
     records.  The legs differ in length per record, so each meets its seams at other alignments: over the set every offset mod 16
-    occurs in each rendered kind."""
+    occurs in each rendered kind, in every configuration that renders it.  The one-leg configurations are what a sink of its own
+    runs: a JSON leg alone, a text leg alone, and the MSGS leg alone (no rendered leg: no scan is launched)."""
     from acarsdec_amd import _capi as K
     L = K.load(lab=True)                                         # (the outputs' lab entries live in the lab library only)
     fr = np.random.default_rng(5).integers(118000000, 137000000, NCH_LAB).astype(np.int32)
-    configs = [["msgs", "json", ("oneline", dict(date=True)), ("std", dict(date=True, freq=True))], ["pp", "sv", "json", "msgs"]]
+    configs = [["msgs", "json", ("oneline", dict(date=True)), ("std", dict(date=True, freq=True))], ["pp", "sv", "json", "msgs"],
+               ["json"], ["sv"], ["msgs"]]     # one leg: what a sink of its own runs; ["msgs"] renders nothing (nrender == 0)
     seams, lens, inside, across = {}, set(), 0, 0
     for n in SIZES:
         recs = lab_records(np.random.default_rng(4000 + n), n, K)
@@ -247,9 +249,11 @@ def test_designed_records_equal_the_sinks_own_lab_entries(D):
                                                        table.ctypes.data, C.byref(nr)) == K.OK
                         blob, offs = out[:nb.value].tobytes(), table[:nr.value + 1].tolist()
                     assert nr.value == nrecs and mine[1] == offs and mine[0] == blob, (n, fkw, leg)
-                    seams.setdefault(str(leg), set()).update(o % 16 for o in offs)
+                    seams.setdefault((configs.index(legs), str(leg)), set()).update(o % 16 for o in offs)
     assert inside > 100 and across >= 2 and set(TEXT_LENS_WANTED) <= lens, (inside, across, sorted(lens))
-    assert len(seams) == 5 and all(s == set(range(16)) for s in seams.values()), {k: sorted(v) for k, v in seams.items()}
+    rendered = [(c, str(leg)) for c, legs in enumerate(configs) for leg in legs if leg != "msgs"]
+    assert len({k for _, k in rendered}) == 5 and sorted(seams) == sorted(rendered)     # five kinds; every rendered leg of every configuration
+    assert all(s == set(range(16)) for s in seams.values()), {k: sorted(v) for k, v in seams.items()}
 
 
 def test_lab_entry_says_again_with_every_legs_size_and_writes_nothing(D):

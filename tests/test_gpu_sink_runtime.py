@@ -1,6 +1,6 @@
-"""The one host runtime behind the JSON and the text sink (csrc/sinks.cpp: AcgSinkState, sink_fetch, sink_reserve) where the two
+"""The one host runtime behind the JSON and the text sink (csrc/sinks.cpp: AcgOutputs, outputs_fetch, outputs_reserve) where the two
 sinks meet: both enabled in one context and drained in turn beside the message entry point, one of them re-enabled mid-run; and
-a work space that grows inside a live context, from sink_reserve's floor of 4096 records to a larger drain.  GPU box only."""
+a work space that grows inside a live context, from outputs_reserve's floor of 4096 records to a larger drain.  GPU box only."""
 import ctypes as C
 import os
 import re
@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 T0 = (1792301725, 269667)
 CHUNK = 4096
-FLOOR = 4096                                                     # sink_reserve's smallest work space, in records
+FLOOR = 4096                                                     # outputs_reserve's smallest work space, in records
 
 
 @pytest.fixture(scope="module")

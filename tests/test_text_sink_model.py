@@ -289,12 +289,13 @@ def test_text_kernels_use_no_scratch():
                        flags + ["-S", "-o", "-", os.path.join(csrc, "text.hip")], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     names = re.findall(r"^\s*\.amdhsa_kernel (\S+)", r.stdout, flags=re.M)
-    assert sorted(n.split("text_")[1].split("_kernel")[0] for n in names) == ["keys", "measure", "offsets", "render", "sum"], names
+    # (the unit's own two: keys and scan are outs.hip's, tests/test_outputs_host.py)
+    assert sorted(n.split("text_")[1].split("_kernel")[0] for n in names) == ["measure", "render"], names
     scratch = [int(v) for v in re.findall(r"\.amdhsa_private_segment_fixed_size (\d+)", r.stdout)]
     vgpr = [int(v) for v in re.findall(r"\.amdhsa_next_free_vgpr (\d+)", r.stdout)]
     lds = [int(v) for v in re.findall(r"\.amdhsa_group_segment_fixed_size (\d+)", r.stdout)]
     print("text.hip kernels:", list(zip(names, vgpr, lds, scratch)))
-    assert len(scratch) == 5 and not any(scratch), scratch
+    assert len(scratch) == 2 and not any(scratch), scratch
     assert "scratch_" not in r.stdout
     assert max(lds) <= 2 * (384 + TM.REC_MAX + 16), lds
     assert max(vgpr) <= 128, vgpr
