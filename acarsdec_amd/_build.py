@@ -62,7 +62,9 @@ HOST_C_UNITS = ["host_setup.c"]
 UNITS = [("fir.hip", ["-O3"], True),
          # the recordings' sample formats and the matrix-pipe kernels (six of them the int8 format's) as compressed bundles, outs.hip's
          # way: the size rule of tests/test_host_logic.py (LEDGER, "Complex int8 and complex float32")
-         ("fir_iq.hip", ["-O3", "--offload-compress"], True), ("fir_mm.hip", ["-O3", "--offload-compress"], True), ("msk.hip", MSK_FLAGS, True), ("msk_lean.hip", MSK_LEAN_FLAGS, True), ("msk2.hip", MSK_FLAGS, False), ("synth.hip", ["-O3"], True),
+         ("fir_iq.hip", ["-O3", "--offload-compress"], True), ("fir_mm.hip", ["-O3", "--offload-compress"], True),
+         ("fir_rate.hip", ["-O3", "--offload-compress"], True),    # any input rate: four format instantiations, the same way
+         ("msk.hip", MSK_FLAGS, True), ("msk_lean.hip", MSK_LEAN_FLAGS, True), ("msk2.hip", MSK_FLAGS, False), ("synth.hip", ["-O3"], True),
          ("blk.hip", ["-O3"], True), ("label.hip", ["-O3"], True), ("flight.hip", ["-O3"], True),
          ("json.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE, nothing fused: the level's float and the time stamp's double are computed here
          ("text.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE like json.hip: the same level float

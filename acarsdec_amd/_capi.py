@@ -15,6 +15,7 @@ INTRATE, BLOCK, MAXDECIM, FLEN, TXTMAX = 12500, 1024, 320, 11, 250
 MAXDECIM_SAMPLES = 1024
 FMT_CS16, FMT_S16_SPLIT, FMT_F32_REAL = 1, 2, 3
 FMT_CS8, FMT_CF32 = 4, 5                   # SigMF ci8 / cf32_le
+FMT_CU8 = 6                                # rtl_sdr files, SigMF cu8: on the rate entry points only
 # acg_lab_samples_launch.family
 FIR_STREAMING, FIR_WORKGROUP, FIR_MATRIX, FIR_SHARED_VECTOR = 1, 2, 3, 4
 PCM_S16, PCM_F32 = 1, 2
@@ -195,6 +196,13 @@ SYMBOLS = {
     "acg_airspy_taps": (C.c_int, [C.c_int, C.c_int, C.c_uint, C.c_void_p]),
     "acg_process_samples_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]),
     "acg_feed_samples_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]),
+    "acg_rate_decim": (C.c_int, [C.c_uint]),
+    "acg_rate_window_starts": (C.c_int, [C.c_uint, C.c_ulonglong, C.c_int, C.c_void_p]),
+    "acg_rate_taps": (C.c_int, [C.c_uint, C.c_double, C.c_int, C.c_void_p]),
+    "acg_set_input_rate": (C.c_int, [C.c_void_p, C.c_uint]),
+    "acg_process_rate_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_int),
+                                       C.POINTER(C.c_size_t)]),
+    "acg_feed_rate_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t]),
     "acg_process_pcm_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "acg_feed_pcm_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "acg_host_alloc": (C.c_void_p, [C.c_size_t]),

@@ -71,6 +71,13 @@ struct acg_ctx {
     unsigned long long* d_stamp = nullptr;   // measurement build (ACG_MSK_STAMP): per-wave phase cycle sums of the last demodulator launch
     std::vector<int> chnum;                 // acg_set_channel_numbers: the number handed out for each slot; empty = the slot's own
     int* d_chnum = nullptr;                 // ... on the device, for the sinks' passes and the flight table; null = identity
+    // acg_set_input_rate: the rational window grid (fir_rate.h).  rate_hz == 0: integer windows, none of this is used
+    unsigned int rate_hz = 0, rate_P = 0, rate_Q = 0;
+    unsigned long long rate_k = 0;          // windows since acg_reset / acg_set_input_rate
+    std::vector<unsigned int> rate_grid;    // floor(r P / Q), r <= Q ...
+    unsigned int* d_rate_grid = nullptr;    // ... and on the device
+    float* d_rate_tapsum = nullptr;         // [nch][4]: the taps' sums over [0, decim - 1) and [0, decim), re and im
+    const struct FirRateArgs* rate_call = nullptr;   // the rate call being issued: what its chunks' launches share (process.cpp)
 
     // ---- process.cpp: streams and events of the pipeline, call slots, dm buffers and guards, host staging, launch timing
     hipStream_t stream = nullptr;
@@ -158,10 +165,19 @@ struct acg_ctx {
 
 // ctx.cpp: the error text of a context, and the code handed back
 int fail(acg_ctx* ctx, int code, const char* msg);
+// ctx.cpp: HIPCHK's text and code out of line, for units with many calls to check (HIPCHK builds its string at every site)
+int hip_fail(acg_ctx* ctx, hipError_t e, const char* call);
+#define HIPCHK_OL(ctx, call)                                                               \
+    do {                                                                                   \
+        const hipError_t e__ = (call);                                                     \
+        if (e__ != hipSuccess) return hip_fail((ctx), e__, #call);                         \
+    } while (0)
 // ctx.cpp: zero device memory and make sure it has happened before any later launch on any stream
 int zero_sync(acg_ctx* c, void* p, size_t bytes);
 // ctx.cpp: the statistics table as acg_stats_enable (results.cpp) and acg_reset leave it
 int stats_zero(acg_ctx* ctx);
+// ctx.cpp: the text every window-aligned entry point refuses with while a rate is set
+extern const char* const RATE_SET_MSG;
 
 // results.cpp: a drain's `lag`
 static constexpr int DRAIN = -1;

@@ -10,6 +10,12 @@ int fail(acg_ctx* ctx, int code, const char* msg)
     return code;
 }
 
+int hip_fail(acg_ctx* ctx, hipError_t e, const char* call)
+{
+    ctx->err = std::string(call) + ": " + hipGetErrorString(e);
+    return ACG_EHIP;
+}
+
 // zero device memory and make sure it has happened before any later launch on any stream
 int zero_sync(acg_ctx* c, void* p, size_t bytes)
 {
@@ -52,6 +58,7 @@ static void free_all(acg_ctx* c)
     hipFree(c->d_stamp);
     hipFree(c->d_stats);
     hipFree(c->d_chnum);
+    hipFree(c->d_rate_grid); hipFree(c->d_rate_tapsum);
     hipFree(c->d_msgs); std::free(c->h_msgs);
     hipFree(c->d_kmsgs); hipFree(c->d_oooi); hipFree(c->d_kwork); std::free(c->h_oooi);
     if (c->flights) acg_fl_destroy(c->flights);
@@ -372,6 +379,7 @@ extern "C" int acg_reset(acg_ctx* ctx)
     ctx->last_guard = nullptr;
     ctx->feed_fill = 0;
     ctx->feed_cur = 0;
+    ctx->rate_k = 0;                                     // the grid restarts at window 0
     ctx->stage_seq = 0;
     ctx->stage_free_valid[0] = ctx->stage_free_valid[1] = false;
     std::fill(ctx->msk_done_owner.begin(), ctx->msk_done_owner.end(), -1);
@@ -393,6 +401,26 @@ extern "C" int acg_reset(acg_ctx* ctx)
     return ACG_OK;
 }
 
+// The u8 / int8 constant of the rate kernel: sum (x - c) t = sum x t - c (1 + j) sum_{i < L} t[i] needs the taps' sum for both
+// window lengths, L = decim - 1 and decim.  Made from the table as the device holds it, in double, whenever taps or rate change.
+static int rate_tapsums(acg_ctx* ctx)
+{
+    if (!ctx->d_rate_tapsum) return ACG_OK;
+    const size_t nch = (size_t)ctx->cfg.nch, pad = (size_t)ctx->ntaps_pad, n = (size_t)ctx->cfg.decim;
+    std::vector<float> t(nch * pad * 2), sums(nch * 4);
+    HIPCHK_OL(ctx, hipMemcpy(t.data(), ctx->d_taps, t.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < nch; ++c) {
+        double sr = 0, si = 0;
+        for (size_t i = 0; i + 1 < n; ++i) { sr += t[(c * pad + i) * 2]; si += t[(c * pad + i) * 2 + 1]; }
+        sums[4 * c] = (float)sr;
+        sums[4 * c + 1] = (float)si;
+        sums[4 * c + 2] = (float)(sr + t[(c * pad + n - 1) * 2]);
+        sums[4 * c + 3] = (float)(si + t[(c * pad + n - 1) * 2 + 1]);
+    }
+    HIPCHK_OL(ctx, hipMemcpy(ctx->d_rate_tapsum, sums.data(), sums.size() * sizeof(float), hipMemcpyHostToDevice));
+    return ACG_OK;
+}
+
 extern "C" int acg_set_taps(acg_ctx* ctx, int ch0, int n, const float* taps)
 {
     if (!ctx || !taps || ch0 < 0 || n < 1 || ch0 + n > ctx->cfg.nch) return ACG_EINVAL;
@@ -405,6 +433,36 @@ extern "C" int acg_set_taps(acg_ctx* ctx, int ch0, int n, const float* taps)
     ctx->gtaps_dirty = true;
     ctx->mm_dirty = true;
     ctx->mm1_dirty = true;
+    return ctx->rate_hz ? rate_tapsums(ctx) : ACG_OK;
+}
+
+// ---- any input rate: the window grid of the context (include/acarsdec_amd.h; the kernel: fir_rate.hip) --------------------
+const char* const RATE_SET_MSG = "an input rate is set (acg_set_input_rate): this entry point takes whole windows of decim samples, use acg_process_rate_dev / acg_feed_rate_host";
+
+extern "C" int acg_set_input_rate(acg_ctx* ctx, unsigned int rate_hz)
+{
+    if (!ctx) return ACG_EINVAL;
+    if (ctx->feed_fill) return fail(ctx, ACG_ESTATE, "the input rate cannot change while a host feed carries samples (acg_reset drops them)");
+    if (rate_hz != 0 && (acg_rate_decim(rate_hz) != ctx->cfg.decim || ctx->cfg.ntaps != ctx->cfg.decim))
+        return fail(ctx, ACG_EINVAL, "input rate: the context needs decim == ntaps == acg_rate_decim(rate_hz)");
+    HIPCHK_OL(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK_OL(ctx, hipDeviceSynchronize());                 // down-converter launches that read the grid run on the callers' streams
+    ctx->rate_k = 0;
+    ctx->rate_hz = 0;
+    if (rate_hz == 0) return ACG_OK;
+    unsigned int g = rate_hz, b = ACG_INTRATE;
+    while (b) { const unsigned int r = g % b; g = b; b = r; }
+    const unsigned int P = rate_hz / g, Q = ACG_INTRATE / g;
+    ctx->rate_grid.resize((size_t)Q + 1);
+    for (unsigned int r = 0; r <= Q; ++r) ctx->rate_grid[r] = (unsigned int)((unsigned long long)r * P / Q);
+    if (!ctx->d_rate_grid) HIPCHK_OL(ctx, hipMalloc(&ctx->d_rate_grid, ((size_t)ACG_INTRATE + 1) * sizeof(unsigned int)));
+    if (!ctx->d_rate_tapsum) HIPCHK_OL(ctx, hipMalloc(&ctx->d_rate_tapsum, (size_t)ctx->cfg.nch * 4 * sizeof(float)));
+    HIPCHK_OL(ctx, hipMemcpy(ctx->d_rate_grid, ctx->rate_grid.data(), ctx->rate_grid.size() * sizeof(unsigned int), hipMemcpyHostToDevice));
+    const int r = rate_tapsums(ctx);
+    if (r != ACG_OK) return r;
+    ctx->rate_P = P;
+    ctx->rate_Q = Q;
+    ctx->rate_hz = rate_hz;
     return ACG_OK;
 }
 

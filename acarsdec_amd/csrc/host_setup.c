@@ -226,3 +226,51 @@ int acg_airspy_taps(int Fr_hz, int Fc_hz, unsigned int inrate, float *taps_out)
 	}
 	return ACG_OK;
 }
+
+/* ---- any input rate: the window grid s_k = floor(k P / Q), P / Q = rate / 12500 in lowest terms -------------------------- */
+static unsigned int rate_gcd(unsigned int a, unsigned int b)
+{
+	while (b) {
+		const unsigned int t = a % b;
+		a = b;
+		b = t;
+	}
+	return a;
+}
+
+int acg_rate_decim(unsigned int rate_hz)
+{
+	if (rate_hz < 2u * ACG_INTRATE || rate_hz > (unsigned int)ACG_INTRATE * ACG_MAXDECIM)
+		return ACG_EINVAL;
+	return (int)((rate_hz + ACG_INTRATE - 1) / ACG_INTRATE);
+}
+
+int acg_rate_window_starts(unsigned int rate_hz, unsigned long long k0, int n, unsigned long long *starts)
+{
+	unsigned int g;
+	unsigned long long P, Q;
+	int i;
+	if (acg_rate_decim(rate_hz) < 0 || !starts || n < 0)
+		return ACG_EINVAL;
+	g = rate_gcd(rate_hz, ACG_INTRATE);
+	P = rate_hz / g;
+	Q = ACG_INTRATE / g;
+	for (i = 0; i <= n; i++)
+		starts[i] = (unsigned long long)((unsigned __int128)(k0 + (unsigned long long)i) * P / Q);
+	return ACG_OK;
+}
+
+int acg_rate_taps(unsigned int rate_hz, double offset_hz, int n, float *taps_out)
+{
+	int i;
+	if (acg_rate_decim(rate_hz) < 0 || !taps_out || n < 1 || n > ACG_MAXDECIM)
+		return ACG_EINVAL;
+	for (i = 0; i < n; i++) {
+		/* the fractional turn, so that the argument of cos / sin stays in [0, 2 pi) whatever the offset */
+		const double turns = offset_hz * (double)i / (double)rate_hz;
+		const double ph = 2.0 * M_PI * (turns - floor(turns));
+		taps_out[2 * i] = (float)cos(ph);
+		taps_out[2 * i + 1] = (float)-sin(ph);
+	}
+	return ACG_OK;
+}

@@ -7,6 +7,7 @@
 
 #include "acg_ctx.h"
 #include "fir_mm_plan.h"
+#include "fir_rate.h"
 
 namespace {
 
@@ -303,6 +304,7 @@ static int launch_msk(acg_ctx* c, const float* dm_dev, size_t pitch_floats, int 
 static int check_iq_args(acg_ctx* ctx, const void* p, size_t pitch, int nblocks)
 {
     if (!ctx || !p) return ACG_EINVAL;
+    if (ctx->rate_hz) return fail(ctx, ACG_ESTATE, RATE_SET_MSG);
     if (nblocks < 1 || nblocks > ctx->cfg.max_blocks) return fail(ctx, ACG_EINVAL, "nblocks out of range");
     if (ctx->cfg.decim > ACG_MAXDECIM) return fail(ctx, ACG_EINVAL, "u8 I/Q path: decim above RTLMULTMAX (rtl.c:39)");
     const size_t row = (size_t)nblocks * ACG_BLOCK * ctx->cfg.decim * 2;
@@ -732,6 +734,7 @@ extern "C" int acg_process_samples_dev(acg_ctx* ctx, int fmt, const void* dev, s
                                        int nblocks, void* hip_stream)
 {
     if (!ctx || !dev) return ACG_EINVAL;
+    if (ctx->rate_hz) return fail(ctx, ACG_ESTATE, RATE_SET_MSG);
     if (nblocks < 1 || nblocks > ctx->cfg.max_blocks) return fail(ctx, ACG_EINVAL, "nblocks out of range");
     if ((((uintptr_t)dev | pitch_bytes | plane_bytes) & 15)) return fail(ctx, ACG_EINVAL, "base, pitch and plane must be 16-byte aligned");
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
@@ -753,6 +756,7 @@ extern "C" int acg_feed_samples_host(acg_ctx* ctx, int fmt, const void* p0, cons
                                      size_t nsamples)
 {
     if (!ctx || !p0 || (fmt == ACG_FMT_S16_SPLIT && !p1)) return ACG_EINVAL;
+    if (ctx->rate_hz) return fail(ctx, ACG_ESTATE, RATE_SET_MSG);
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     FirArgs a;
     int r = fmt_args(ctx, fmt, &a);
@@ -814,6 +818,172 @@ extern "C" int acg_feed_samples_host(acg_ctx* ctx, int fmt, const void* p0, cons
             ctx->feed_fill = have;
         }
         HIPCHK(ctx, hipEventSynchronize(ctx->h2d_done));   // the caller's buffers may be reused after return
+    }
+    return ACG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Any input rate (acg_set_input_rate): windows on the grid s_k = floor(k P / Q).  The kernel is fir_rate.hip's; the CU partition
+// and the FIR/demodulator stream pipeline are run_pipeline's, with no bytes per window: a chunk's launch finds its windows from
+// the chunk's first window, which is where its dm begins.
+static int rate_fmt(acg_ctx* ctx, int fmt, FirRateArgs* r)
+{
+    if (!ctx->rate_hz) return fail(ctx, ACG_ESTATE, "no input rate is set (acg_set_input_rate)");
+    if (!acg_launch_fir_rate) return fail(ctx, ACG_ESTATE, "this build has no rate down-converter unit");
+    float scale;
+    switch (fmt) {
+    case ACG_FMT_CU8: r->fmt = RATE_CU8; scale = 1.0f / 127.5f; break;
+    case ACG_FMT_CS8: r->fmt = RATE_CS8; scale = 1.0f / 128.0f; break;
+    case ACG_FMT_CS16: r->fmt = RATE_CS16; scale = 1.0f / 32768.0f; break;
+    case ACG_FMT_CF32: r->fmt = RATE_CF32; scale = 1.0f; break;
+    case ACG_FMT_S16_SPLIT:
+    case ACG_FMT_F32_REAL:
+        return fail(ctx, ACG_EINVAL, "split planes and real float32 belong to front ends that fix their own rates: the rate entry points take "
+                                     "ACG_FMT_CU8, ACG_FMT_CS8, ACG_FMT_CS16 and ACG_FMT_CF32");
+    default: return fail(ctx, ACG_EINVAL, "unknown sample format");
+    }
+    const acg_config& g = ctx->cfg;
+    r->stream_of = ctx->d_stream_of;
+    r->taps = ctx->d_taps;
+    r->tapsum = ctx->d_rate_tapsum;
+    r->grid = ctx->d_rate_grid;
+    r->dm_pitch = ctx->dm_pitch;
+    r->P = ctx->rate_P;
+    r->Q = ctx->rate_Q;
+    r->r0 = (unsigned int)(ctx->rate_k % ctx->rate_Q);
+    r->nch = g.nch;
+    r->decim = g.decim;
+    r->scale_long = (float)((double)scale / g.decim);
+    r->scale_short = (float)((double)scale / (g.decim - 1));
+    acg_fir_rate_plan(r);
+    return ACG_OK;
+}
+
+// s_(k0 + n) - s_k0 on the context's grid
+static unsigned long long rate_span(const acg_ctx* ctx, unsigned long long n)
+{
+    const unsigned long long r0 = ctx->rate_k % ctx->rate_Q, i = r0 + n;
+    return i / ctx->rate_Q * ctx->rate_P + ctx->rate_grid[(size_t)(i % ctx->rate_Q)] - ctx->rate_grid[(size_t)r0];
+}
+
+// the whole windows that fit into nsamples from the context's current window start, at most max_len
+static int rate_windows_fit(const acg_ctx* ctx, size_t nsamples)
+{
+    unsigned long long n = (unsigned long long)((unsigned __int128)nsamples * ctx->rate_Q / ctx->rate_P);     // within one of the answer
+    n = std::min<unsigned long long>(n, (unsigned long long)ctx->max_len);
+    while (n < (unsigned long long)ctx->max_len && rate_span(ctx, n + 1) <= nsamples) ++n;
+    while (n > 0 && rate_span(ctx, n) > nsamples) --n;
+    return (int)n;
+}
+
+// One chunk's launch of a rate call (see fir_launch).  A plain function of launch_fir_u8's type, so that the pipeline is the
+// instantiation the u8 path already has; what the chunks share waits in the context while the call is issued.
+static int launch_fir_rate_chunk(acg_ctx* c, FirArgs& f, hipStream_t st)
+{
+    FirRateArgs b = *c->rate_call;
+    b.dm = f.dm;
+    b.win0 = (unsigned int)(f.dm - c->d_dm);                     // the chunk's first window
+    b.nwin = f.nwin;
+    b.ncu = f.ncu;
+    return acg_launch_fir_rate(&b, st);
+}
+
+// nwin windows of the rows at dev (nsamples presented each) through the pipeline; advances the grid
+static int rate_run(acg_ctx* ctx, FirRateArgs& r, const void* dev, size_t pitch, size_t nsamples, int nwin, hipStream_t s)
+{
+    r.in = (const uint8_t*)dev;
+    r.pitch = pitch;
+    r.valid_bytes = ((unsigned long long)nsamples * r.bps + 15) & ~15ull;
+    FirArgs a = fir_args(ctx);
+    a.iq = r.in;
+    a.pitch = pitch;
+    const int per = r.bps == 2 ? 1 : r.bps == 4 ? 2 : 4;         // the formats' pipeline chunk (fmt_chunk_win): the u8 path's bytes per launch
+    const int chunk = (ctx->pipe_blocks > 0 ? (ctx->pipe_blocks + per - 1) / per : ctx->cfg.max_blocks) * ACG_BLOCK;
+    ctx->rate_call = &r;
+    const int rc = run_pipeline(ctx, s, a, 0, nwin, chunk, launch_fir_rate_chunk);
+    ctx->rate_call = nullptr;
+    if (rc == ACG_OK) ctx->rate_k += (unsigned long long)nwin;
+    return rc;
+}
+
+extern "C" int acg_process_rate_dev(acg_ctx* ctx, int fmt, const void* dev, size_t pitch_bytes, size_t nsamples, void* hip_stream,
+                                    int* nwin, size_t* consumed)
+{
+    if (!ctx || !dev || !nwin || !consumed) return ACG_EINVAL;
+    *nwin = 0;
+    *consumed = 0;
+    FirRateArgs r{};
+    int rc = rate_fmt(ctx, fmt, &r);
+    if (rc != ACG_OK) return rc;
+    if ((((uintptr_t)dev | pitch_bytes) & 15)) return fail(ctx, ACG_EINVAL, "base and pitch must be 16-byte aligned");
+    if (pitch_bytes < (((unsigned long long)nsamples * r.bps + 15) & ~15ull))
+        return fail(ctx, ACG_EINVAL, "pitch smaller than a row: nsamples * bytes per sample, rounded up to 16");
+    if (ctx->feed_fill) return fail(ctx, ACG_ESTATE, "acg_feed_rate_host is carrying a partial window (acg_reset drops it)");
+    HIPCHK_OL(ctx, hipSetDevice(ctx->cfg.device));
+    const int n = rate_windows_fit(ctx, nsamples);
+    if (n == 0) return ACG_OK;
+    const unsigned long long span = rate_span(ctx, (unsigned long long)n);
+    rc = rate_run(ctx, r, dev, pitch_bytes, nsamples, n, hip_stream ? (hipStream_t)hip_stream : ctx->stream);
+    if (rc != ACG_OK) return rc;
+    *nwin = n;
+    *consumed = (size_t)span;
+    return ACG_OK;
+}
+
+// acg_feed_samples_host's scheme with variable windows: the samples behind the last whole window wait at the head of the other
+// staging row -- always a window start -- and the copy of feed i + 1 runs beside the kernels of feed i.
+extern "C" int acg_feed_rate_host(acg_ctx* ctx, int fmt, const void* samples, size_t pitch_samples, size_t nsamples)
+{
+    if (!ctx || !samples) return ACG_EINVAL;
+    FirRateArgs r{};
+    int rc = rate_fmt(ctx, fmt, &r);
+    if (rc != ACG_OK) return rc;
+    HIPCHK_OL(ctx, hipSetDevice(ctx->cfg.device));
+    if (ctx->feed_fmt != fmt) { ctx->feed_fmt = fmt; ctx->feed_fill = 0; }
+    const acg_config& g = ctx->cfg;
+    const size_t bps = (size_t)r.bps;
+    const size_t cap = (size_t)ctx->max_len * (size_t)g.decim;                // samples a staging row holds: max_len windows always fit
+    const size_t rowb = ((cap * bps) + 15) & ~(size_t)15;
+    if ((rc = ensure_stage(ctx, rowb * (size_t)g.nstreams)) != ACG_OK) return rc;
+    hipStream_t s = ctx->stream, hs = ctx->h2d_stream;
+    size_t done = 0;
+    for (;;) {
+        const size_t take = std::min(nsamples - done, cap - ctx->feed_fill);
+        const int cur = ctx->feed_cur;
+        unsigned char* base = (unsigned char*)ctx->d_stage[cur];
+        // new samples behind the carried ones, on the copy stream (which already waits for the last reader of this buffer and
+        // carries the copy of the carried samples); no new ones: a round for whole windows the last launch left behind
+        if (take)
+            HIPCHK_OL(ctx, hipMemcpy2DAsync(base + ctx->feed_fill * bps, rowb, (const unsigned char*)samples + done * bps,
+                                         (g.nstreams > 1 ? pitch_samples : nsamples) * bps, take * bps, (size_t)g.nstreams,
+                                         hipMemcpyHostToDevice, hs));
+        HIPCHK_OL(ctx, hipEventRecord(ctx->h2d_done, hs));
+        done += take;
+        const size_t have = ctx->feed_fill + take;
+        const int nwin = rate_windows_fit(ctx, have);
+        if (nwin == 0) {
+            ctx->feed_fill = have;
+            HIPCHK_OL(ctx, hipEventSynchronize(ctx->h2d_done));
+            break;                                                          // (have < cap here: the input is used up)
+        }
+        const size_t used = (size_t)rate_span(ctx, (unsigned long long)nwin);
+        HIPCHK_OL(ctx, hipStreamWaitEvent(s, ctx->h2d_done, 0));
+        r.r0 = (unsigned int)(ctx->rate_k % ctx->rate_Q);
+        if ((rc = rate_run(ctx, r, base, rowb, have, nwin, s)) != ACG_OK) {
+            (void)hipEventSynchronize(ctx->h2d_done);           // the copy may still be reading the caller's buffer: not after we return
+            return rc;
+        }
+        HIPCHK_OL(ctx, hipEventRecord(ctx->stage_free[cur], s));      // behind the last down-converter launch that reads `cur`
+        ctx->stage_free_valid[cur] = true;
+        const int nxt = cur ^ 1;
+        const size_t left = have - used;
+        if (ctx->stage_free_valid[nxt]) HIPCHK_OL(ctx, hipStreamWaitEvent(hs, ctx->stage_free[nxt], 0));
+        if (left)
+            HIPCHK_OL(ctx, hipMemcpy2DAsync(ctx->d_stage[nxt], rowb, base + used * bps, rowb, left * bps, (size_t)g.nstreams,
+                                         hipMemcpyDeviceToDevice, hs));
+        ctx->feed_fill = left;
+        ctx->feed_cur = nxt;
+        HIPCHK_OL(ctx, hipEventSynchronize(ctx->h2d_done));   // the caller's buffer may be reused after return
     }
     return ACG_OK;
 }

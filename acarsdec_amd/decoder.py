@@ -58,6 +58,30 @@ def airspy_choose_fc(freqs_hz):
     return int(K.load().acg_airspy_choose_fc(int(min(freqs_hz)), int(max(freqs_hz))))
 
 
+def rate_decim(rate_hz):
+    """ceil(rate / 12500): the decim (== ntaps) of a Decoder that takes input at rate_hz (acg_rate_decim)"""
+    m = K.load().acg_rate_decim(int(rate_hz))
+    if m < 0:
+        raise K.AcgError(m, "acg_rate_decim(%d)" % int(rate_hz))
+    return m
+
+
+def rate_taps(rate_hz, offset_hz, n=None):
+    """The bare oscillator of a channel offset_hz above the centre at input rate rate_hz, float32 [n, 2] (n: rate_decim):
+    (cos, -sin) of 2 pi frac(offset_hz i / rate_hz).  The rate kernel divides by the window's own length."""
+    n = rate_decim(rate_hz) if n is None else int(n)
+    out = np.zeros((n, 2), dtype=np.float32)
+    _chk(None, K.load().acg_rate_taps(int(rate_hz), float(offset_hz), n, out.ctypes.data))
+    return out
+
+
+def rate_window_starts(rate_hz, k0, n):
+    """s_k0 .. s_(k0 + n) of the window grid s_k = floor(k P / Q), P / Q = rate_hz / 12500: uint64 [n + 1]"""
+    out = np.zeros(int(n) + 1, dtype=np.uint64)
+    _chk(None, K.load().acg_rate_window_starts(int(rate_hz), int(k0), int(n), out.ctypes.data))
+    return out
+
+
 def parse_freq_mhz(s):
     """rtl.c:245-247: command-line MHz string -> Hz rounded to the 12.5 kHz raster."""
     return (int(1000000 * float(s) + K.INTRATE / 2) // K.INTRATE) * K.INTRATE
@@ -170,6 +194,31 @@ class Decoder:
             n, pitch = a.shape[1], a.shape[1]
         self._chk(self.L.acg_feed_samples_host(self.ctx, fmt, a.ctypes.data,
                                                      q_plane.ctypes.data if q_plane is not None else None, pitch, n))
+
+    # ---- any input rate (acg_set_input_rate, acg_process_rate_dev, acg_feed_rate_host) ------------------------------------
+    _RATE_DTYPES = {K.FMT_CU8: np.uint8, K.FMT_CS8: np.int8, K.FMT_CS16: np.int16, K.FMT_CF32: np.float32}
+
+    def set_input_rate(self, rate_hz):
+        """Input at rate_hz from now on, windows on the grid s_k = floor(k rate / 12500) (needs decim == ntaps ==
+        rate_decim(rate_hz) and taps as rate_taps makes them); 0: whole windows of decim samples again.  Restarts the grid."""
+        self._chk(self.L.acg_set_input_rate(self.ctx, int(rate_hz)))
+
+    def process_rate(self, fmt, dev_tensor, nsamples, pitch, stream=None):
+        """Device rows of nsamples samples that begin at the current window start; pitch in bytes.  Returns (nwin, consumed): the
+        whole windows run and the samples they covered -- present the rest again at the head of the next call."""
+        nwin, used = C.c_int(0), C.c_size_t(0)
+        self._chk(self.L.acg_process_rate_dev(self.ctx, int(fmt), dev_tensor.data_ptr(), int(pitch), int(nsamples), stream,
+                                              C.byref(nwin), C.byref(used)))
+        return nwin.value, used.value
+
+    def feed_rate(self, fmt, samples):
+        """Host samples of any length at the rate set: [nstreams, n] pairs of uint8 (FMT_CU8), int8, int16, float32 (or
+        complex64 for FMT_CF32)."""
+        a = np.asarray(samples)
+        dt = np.complex64 if (fmt == K.FMT_CF32 and np.iscomplexobj(a)) else self._RATE_DTYPES[fmt]
+        a = np.ascontiguousarray(a, dtype=dt).reshape(self.nstreams, -1)
+        n = a.shape[1] if dt is np.complex64 else a.shape[1] // 2
+        self._chk(self.L.acg_feed_rate_host(self.ctx, int(fmt), a.ctypes.data, n, n))
 
     def process_samples(self, fmt, dev_tensor, nblocks, pitch, plane=0, stream=None):
         self._chk(self.L.acg_process_samples_dev(self.ctx, fmt, dev_tensor.data_ptr(), pitch, plane, nblocks, stream))

@@ -240,6 +240,64 @@ def real_f32_from_envelopes(envs, M, offsets_hz, phases=None, scale=0.25, noise=
     return x.astype(np.float32)
 
 
+# ------------------------------------------------------------------ any input rate: windows on the grid floor(k R / 12500)
+def rate_window_starts(rate_hz, k0, n):
+    """s_k0 .. s_(k0 + n) in Python integers: s_k = floor(k P / Q) with P / Q = rate_hz / 12500 in lowest terms"""
+    from math import gcd
+    g = gcd(int(rate_hz), INTRATE)
+    P, Q = int(rate_hz) // g, INTRATE // g
+    return [(int(k0) + i) * P // Q for i in range(int(n) + 1)]
+
+
+def iq_complex_at_rate(envs, rate_hz, offsets_hz, phases=None, scale=0.25, noise=0.0, rng=None, k0=0):
+    """iq_complex_from_envelopes at any input rate: sample n (counted from the start of window k0) carries envs[:, k] for the
+    window k with s_k <= n < s_(k+1) -- membership by the grid, not floor(n Q / P), which leaks one sample per window -- on
+    carriers of phase 2 pi frac(f n / R) + phi, n counted from sample s_k0.  complex128 [s_(k0 + nout) - s_k0]."""
+    envs = np.atleast_2d(np.asarray(envs, dtype=np.float64))
+    nc, nout = envs.shape
+    offsets_hz = np.asarray(offsets_hz, dtype=np.float64).reshape(nc)
+    phases = np.zeros(nc) if phases is None else np.asarray(phases, dtype=np.float64).reshape(nc)
+    rng = rng or np.random.default_rng(0)
+    s = np.array(rate_window_starts(rate_hz, k0, nout), dtype=np.int64)
+    lens = np.diff(s)
+    n = np.arange(int(s[-1] - s[0]), dtype=np.float64)
+    x = np.zeros(n.size, dtype=np.complex128)
+    for c in range(nc):
+        turns = np.mod(offsets_hz[c] * n / float(rate_hz), 1.0)
+        x += np.repeat(envs[c], lens) * np.exp(1j * (2 * np.pi * turns + phases[c]))
+    x *= scale
+    if noise > 0:
+        x += rng.normal(0, noise, size=x.shape) + 1j * rng.normal(0, noise, size=x.shape)
+    return x
+
+
+def _pairs(x, dtype, gain, lo, hi, offset=0.0):
+    out = np.empty(x.size * 2, dtype=dtype)
+    out[0::2] = np.clip(np.rint(offset + gain * x.real), lo, hi).astype(dtype)
+    out[1::2] = np.clip(np.rint(offset + gain * x.imag), lo, hi).astype(dtype)
+    return out
+
+
+def iq_u8_at_rate(envs, rate_hz, offsets_hz, **kw):
+    """CU8 interleaved I,Q (an rtl_sdr file, SigMF cu8): u8 = clip(rint(127.37 + 127.5 x)), the rtl.c:338-339 convention"""
+    return _pairs(iq_complex_at_rate(envs, rate_hz, offsets_hz, **kw), np.uint8, 127.5, 0, 255, 127.37)
+
+
+def iq_s8_at_rate(envs, rate_hz, offsets_hz, **kw):
+    """CS8 interleaved I,Q (SigMF ci8): int8 = rint(127 x), clipped"""
+    return _pairs(iq_complex_at_rate(envs, rate_hz, offsets_hz, **kw), np.int8, 127.0, -128, 127)
+
+
+def iq_s16_at_rate(envs, rate_hz, offsets_hz, full_scale=0.9, **kw):
+    """CS16 interleaved I,Q: int16 = rint(32767 full_scale x), clipped"""
+    return _pairs(iq_complex_at_rate(envs, rate_hz, offsets_hz, **kw), np.int16, 32767.0 * full_scale, -32768, 32767)
+
+
+def iq_cf32_at_rate(envs, rate_hz, offsets_hz, **kw):
+    """CF32 interleaved I,Q (SigMF cf32_le): iq_complex_at_rate as complex64"""
+    return iq_complex_at_rate(envs, rate_hz, offsets_hz, **kw).astype(np.complex64)
+
+
 def pad_blocks(x, block=1024, fill=0.0):
     """Pad the last axis to a multiple of `block` (rtl.c:49 RTLOUTBUFSZ) with `fill`."""
     x = np.asarray(x)

@@ -237,6 +237,43 @@ int  acg_process_samples_dev(acg_ctx *ctx, int fmt, const void *dev, size_t pitc
 int  acg_feed_samples_host(acg_ctx *ctx, int fmt, const void *p0, const void *p1, size_t pitch_samples,
 			   size_t nsamples);
 
+/* ---- any input sample rate: the down-converter's windows on a rational grid ---------------- */
+/* The reference's down-converter (rtl.c:344-354, soapy.c:232-254: one window per 12.5 kHz output, a per-window oscillator
+ * table that restarts at index 0, |D|) with only the window grid generalised.  R = the input rate in Hz, g = gcd(R, 12500),
+ * P = R / g, Q = 12500 / g.  Window k, counted per context from acg_reset, covers input samples [s_k, s_(k+1)) with
+ * s_k = floor(k P / Q) in exact integer arithmetic, so its length L_k is floor(P / Q) or ceil(P / Q), and
+ *     dm_c[k] = scale_fmt / L_k * | sum_{i < L_k} v[s_k + i] * t_c[i] |
+ * with t_c the decim = ntaps = ceil(P / Q) taps of channel c -- the bare oscillator (acg_rate_taps): the 1 / L_k differs from
+ * window to window and is the kernel's -- and scale_fmt = 1/32768 (ACG_FMT_CS16), 1/128 (ACG_FMT_CS8), 1 (ACG_FMT_CF32),
+ * 1/127.5 for ACG_FMT_CU8 whose sample is (I - 127.37) + j (Q - 127.37) (rtl.c:338-339).  Q == 1 is the integer case.  The
+ * outputs are 12 500 per second on average and each is displaced by less than one input sample: end_sample, soh_sample and the
+ * time stamps keep their meaning.  All streams of a context share one rate. */
+#define ACG_FMT_CU8        6   /* interleaved u8 I,Q (rtl_sdr files, SigMF cu8): on the acg_*_rate_* entry points only */
+/* ceil(rate / 12500) = what acg_config.decim (== ntaps) must be, or ACG_EINVAL outside 25 000 <= rate_hz <= 12500 * ACG_MAXDECIM */
+int  acg_rate_decim(unsigned int rate_hz);
+/* s_k0 .. s_(k0 + n): n + 1 values of the grid above */
+int  acg_rate_window_starts(unsigned int rate_hz, unsigned long long k0, int n, unsigned long long *starts);
+/* [n][2]: (float)cos, (float)-sin of 2 pi frac(offset_hz * i / rate_hz), i = 0 .. n - 1, evaluated in double */
+int  acg_rate_taps(unsigned int rate_hz, double offset_hz, int n, float *taps_out);
+/* The context's input rate; 0 = integer windows again (the default).  ACG_EINVAL unless cfg.decim == cfg.ntaps ==
+ * acg_rate_decim(rate_hz); ACG_ESTATE while either host feed carries samples.  Sets the window counter to 0, as acg_reset
+ * does.  While a rate is set the window-aligned entry points (acg_process_iq_u8_*, acg_fir_only_dev, acg_process_samples_dev,
+ * acg_feed_samples_host) return ACG_ESTATE and launch nothing; acg_process_dm_* and the PCM entry points do not care. */
+int  acg_set_input_rate(acg_ctx *ctx, unsigned int rate_hz);
+/* Device input at the rate set: each of the [nstreams] rows holds nsamples samples (ACG_FMT_CU8, _CS8, _CS16 or _CF32; 2, 2, 4,
+ * 8 bytes each) that begin at the context's current window start.  Base and pitch 16-byte aligned, pitch_bytes >= nsamples *
+ * bytes per sample rounded up to 16 (a 16-byte read that covers a row's last sample stays inside the row's pitch).  Runs the
+ * whole windows that fit, at most max_blocks * 1024 of them, and the demodulator on them, under the asynchronous contract of
+ * acg_process_samples_dev; reports *nwin and *consumed = s_(k0 + nwin) - s_k0 and advances the context by that much: the
+ * caller presents the rest again at the head of the next call.  ACG_ESTATE while acg_feed_rate_host carries samples or no
+ * rate is set; split planes and real f32 belong to front ends that fix their own rates: ACG_EINVAL. */
+int  acg_process_rate_dev(acg_ctx *ctx, int fmt, const void *dev, size_t pitch_bytes, size_t nsamples,
+			  void *hip_stream, int *nwin, size_t *consumed);
+/* Host input of ANY length at the rate set: acg_feed_samples_host's scheme with variable windows -- the incomplete window's
+ * samples wait at the head of the other staging row (always a window start), the copy of feed i+1 runs beside the kernels of
+ * feed i.  Rows pitch_samples apart. */
+int  acg_feed_rate_host(acg_ctx *ctx, int fmt, const void *samples, size_t pitch_samples, size_t nsamples);
+
 /* ---- the 12.5 kHz front ends' own shape: interleaved PCM frames (soundfile.c, alsa.c) ------- */
 #define ACG_PCM_S16 1   /* interleaved int16 frames, x/32768: what sf_read_float makes of a PCM16 file (soundfile.c:65) */
 #define ACG_PCM_F32 2   /* interleaved float32 frames: sf_read_float's own output, alsa.c:66,114 */
