@@ -65,7 +65,10 @@ UNITS = [("fir.hip", ["-O3"], True),
          ("fir_iq.hip", ["-O3", "--offload-compress"], True), ("fir_mm.hip", ["-O3", "--offload-compress"], True),
          ("fir_rate.hip", ["-O3", "--offload-compress"], True),    # any input rate: four format instantiations, the same way
          ("msk.hip", MSK_FLAGS, True), ("msk_lean.hip", MSK_LEAN_FLAGS, True), ("msk2.hip", MSK_FLAGS, False), ("synth.hip", ["-O3"], True),
-         ("blk.hip", ["-O3"], True), ("label.hip", ["-O3"], True), ("flight.hip", ["-O3"], True),
+         ("blk.hip", ["-O3"], True), ("label.hip", ["-O3"], True),
+         # the two resident tables (flight.hip's sort serves both) as compressed bundles, outs.hip's way: the size rule of
+         # tests/test_host_logic.py (LEDGER, "Multi-block reassembly")
+         ("flight.hip", ["-O3", "--offload-compress"], True), ("reasm.hip", ["-O3", "--offload-compress"], True),
          ("json.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE, nothing fused: the level's float and the time stamp's double are computed here
          ("text.hip", ["-O3", "-ffp-contract=off"], True),      # IEEE like json.hip: the same level float
          ("flight_text.hip", ["-O3", "-ffp-contract=off"], True),   # text.hip's flags: the route line's time stamp is json.hip's double

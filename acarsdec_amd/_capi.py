@@ -93,6 +93,24 @@ FLIGHT_EVENT_DTYPE = [("end_sample", "<i8"), ("soh_sample", "<i8"), ("sec", "<i8
                       ("fid", "S7"), ("e_ok", "u1"), ("oooi", "V40")]
 
 
+class ReasmConfig(C.Structure):
+    """acg_reasm_config: t0 of the sample clock, the table's capacity (0 = 1024 chains), the longest text (0 = 3584 bytes)"""
+    _fields_ = [("t0_sec", C.c_longlong), ("t0_usec", C.c_int), ("max_msgs", C.c_int), ("max_text", C.c_int)]
+
+
+class ReasmMsg(C.Structure):
+    """acg_reasm_msg: one completed multi-block message; its text lies at text_off of the same call's text buffer"""
+    _fields_ = [("chn", C.c_int), ("nfrag", C.c_int), ("end_bit", C.c_longlong), ("end_sample", C.c_longlong), ("soh_sample", C.c_longlong),
+                ("first_soh_sample", C.c_longlong), ("text_off", C.c_ulonglong), ("text_len", C.c_uint), ("down", C.c_char),
+                ("addr", C.c_char * 8), ("label", C.c_char * 3), ("msn", C.c_char * 4), ("reserved", C.c_char * 12)]
+
+
+REASM_UNKNOWN, REASM_COMPLETE, REASM_IN_PROGRESS, REASM_SKIPPED, REASM_DUPLICATE, REASM_OUT_OF_SEQUENCE, REASM_ARGS_INVALID, REASM_OVERFLOW = range(8)
+# the same record as a numpy structured dtype (Decoder.drain_reassembled hands out arrays of it)
+REASM_MSG_DTYPE = [("chn", "<i4"), ("nfrag", "<i4"), ("end_bit", "<i8"), ("end_sample", "<i8"), ("soh_sample", "<i8"), ("first_soh_sample", "<i8"),
+                   ("text_off", "<u8"), ("text_len", "<u4"), ("down", "u1"), ("addr", "S8"), ("label", "S3"), ("msn", "S4"), ("reserved", "V12")]
+
+
 class FlightTextConfig(C.Structure):
     """acg_flight_text_config: the monitor's mask columns (the reference's nbch) and the route line's station id"""
     _fields_ = [("nbch", C.c_int), ("station_id", C.c_char * 33)]
@@ -166,6 +184,7 @@ class SamplesLaunch(C.Structure):
 
 
 assert C.sizeof(ChanStats) == 88
+assert C.sizeof(ReasmMsg) == 80 and C.sizeof(ReasmConfig) == 24
 assert C.sizeof(Flight) == 120 and C.sizeof(Route) == 56 and C.sizeof(FlightEvent) == 88
 
 BIT_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_float, C.c_float)
@@ -226,6 +245,12 @@ SYMBOLS = {
     "acg_flight_events_check": (C.c_int, [C.c_void_p, C.c_int]),
     "acg_flights_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "acg_flights_commit": (C.c_int, [C.c_void_p]),
+    "acg_reasm_enable": (C.c_int, [C.c_void_p, C.POINTER(ReasmConfig)]),
+    "acg_drain_msgs_reasm": (C.c_int, [C.c_void_p, C.POINTER(Msg), C.POINTER(Oooi), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "acg_collect_msgs_reasm": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Msg), C.POINTER(Oooi), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "acg_drain_reassembled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_int)]),
+    "acg_reasm_status_name": (C.c_char_p, [C.c_int]),
     "acg_flight_text_enable": (C.c_int, [C.c_void_p, C.POINTER(FlightTextConfig)]),
     "acg_flight_monitor_text": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                           C.POINTER(C.c_int)]),
@@ -284,6 +309,8 @@ LAB_SYMBOLS = {
     "acg_selftest_flights_sharded": (C.c_int, [C.POINTER(Msg), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(FlightConfig), C.POINTER(MsgFilter),
                                                C.POINTER(Flight), C.c_int, C.POINTER(C.c_int), C.POINTER(Route), C.c_int, C.POINTER(C.c_int),
                                                C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "acg_selftest_reasm": (C.c_int, [C.POINTER(Msg), C.POINTER(C.c_int), C.c_int, C.POINTER(ReasmConfig), C.POINTER(MsgFilter), C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "acg_selftest_flight_text": (C.c_int, [C.POINTER(Flight), C.c_int, C.POINTER(Route), C.c_int, C.POINTER(FlightConfig),
                                            C.POINTER(FlightTextConfig), C.c_longlong, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                            C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),

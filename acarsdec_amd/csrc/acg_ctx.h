@@ -144,6 +144,7 @@ struct acg_ctx {
     unsigned int* d_kwork = nullptr;        // [kmsgs_cap / 256 + 1] per-workgroup counts, then the total
     size_t kmsgs_cap = 0;
     AcgFlights* flights = nullptr;          // acg_flights_enable: the flight table (flights.cpp), updated by every message entry point
+    AcgReasm* reasm = nullptr;              // acg_reasm_enable: the reassembly table (reasm.hip), fed by every message entry point
     AcgChanStats* d_stats = nullptr;        // acg_stats_enable: the per-channel statistics (stats.hip), [nch]; null = off
     unsigned long long lost_blocks = 0;     // ... and the blocks lost to a lapped ring since the table was zeroed
 
@@ -200,7 +201,7 @@ int grow_msg_stage(acg_ctx* ctx, unsigned int take);
 int grow_label_stage(acg_ctx* ctx, unsigned int take);
 // results.cpp: the flight table's pass over the imported events alone
 int commit_imports(acg_ctx* ctx);
-// results.cpp: the split of the `take` oldest blocks, label.hip's pass and the flight table's behind it
+// results.cpp: the split of the `take` oldest blocks, label.hip's pass, the flight table's and the reassembly table's behind it
 int launch_split(acg_ctx* ctx, unsigned int take, bool labels, unsigned int** d_total);
 // results.cpp: the device form of a message filter
 int label_filter_dev(const acg_msg_filter* f, AcgLabelFilter* d);

@@ -186,6 +186,75 @@ struct AcgFlightPass {
     unsigned int xq_cap;        // acg_flight_event records xq holds
 };
 
+// ---- multi-block reassembly (reasm.hip, flights.cpp): the reference's call site of la_reasm_fragment_add() (output.c:33-101,
+// 579-626) over a call's split records; the table's rule is tests/reasm_model.py
+#define ACG_RS_PREV_NONE 0x7fffffff
+#define ACG_RS_F_DOWN 1u            // AcgReasmEv::flags: a downlink (sequence from no[3], first = 0, no wrap)
+#define ACG_RS_F_FINAL 2u           // be != ETB
+#define ACG_RS_F_CREATES 4u         // not final and (an uplink or seq == 0): the event can create an entry
+#define ACG_RS_WRAP_SHIFT 8         // bits 8-15: the wrap (0 none, 23, 26)
+// One event = one record that reaches the table, extracted by reasm_extract_kernel (compacted; any order)
+struct AcgReasmEv {
+    unsigned long long k0;      // addr (7 bytes, a C string) | label[0] << 56
+    unsigned long long k1;      // label[1] | msn[0..2] << 8 (a downlink's; C strings) | 1 << 63: never 0 (an unused slot)
+    long long tv_us;            // t0_us + 80 * soh_sample
+    long long soh_sample;
+    unsigned int rec;           // index of its record in the pass
+    int seq;
+    unsigned int flags;
+    unsigned int txt_len;       // clamped to the record's row
+};
+
+// One slot of the open-addressing table; its text row is rows + slot * max_text
+struct AcgReasmSlot {
+    unsigned long long k0, k1;  // k1 == 0: never used; an idle entry keeps its key (its own tombstone)
+    long long first_us, timeout_us, first_soh;
+    int prev;                   // ACG_RS_PREV_NONE: no fragment yet
+    unsigned int text_len, nfrag;
+    unsigned int tail;          // the bytes of the row's last, incomplete dword (text_len & 3 of them), so that an append writes whole dwords
+    unsigned int touch;         // the pass that last used or claimed the slot
+    unsigned int live;          // 0: idle (removed)
+};
+
+struct AcgReasmState {
+    long long G;                // the largest tv_us any event of an EARLIER pass carried
+    long long Gnext;            // ... and of this pass so far
+    unsigned int m, nseg;       // events and segments of the pass in flight
+    unsigned int ndone;         // completed messages queued
+    unsigned int dropped;       // (call, key) pairs whose key found no slot
+    unsigned long long tbytes;  // bytes of their texts queued (each text starts on a 16-byte boundary)
+    unsigned int qfull;         // completions that did not fit a queue (the host sizes them so that this stays 0)
+    unsigned int pad_;
+};
+
+struct AcgReasmDone {
+    unsigned long long tkey;    // the final fragment's time key (end_sample << 20 | chn) ...
+    unsigned int pass, pad_;    // ... and its pass: the host's final order
+    unsigned char r[80];        // acg_reasm_msg; text_off = the text's place in the device queue
+};
+
+struct AcgReasmPass {
+    long long t0_us;
+    unsigned int pass, cap;     // this pass; table slots (a power of two)
+    unsigned int max_text;      // bytes per row, a multiple of 16
+    unsigned int done_cap;      // records `done` holds
+    unsigned long long text_cap;    // bytes `texts` holds
+    AcgReasmSlot* slots;
+    unsigned char* rows;
+    AcgReasmState* st;
+    AcgReasmDone* done;
+    unsigned char* texts;
+    // per-pass work space, each for at least the pass's n records
+    AcgReasmEv* ev;
+    unsigned long long *ka, *kb;
+    unsigned int *va, *vb;
+    uint2* segs;
+    unsigned int* status;       // [n]: ACG_REASM_* per record of the pass (a word each: no byte stores)
+    unsigned char* keep;        // [n]: the label pass's decision per record (AcgLabelPass::keep_out), for the host's index map
+    const int* chmap;           // or null: the channel number recorded for local channel l, [nmap]
+    unsigned int nmap;
+};
+
 // ---- the JSON line renderer (json.hip): buildjson() + cJSON_PrintPreallocated (output.c:227-324) over a call's kept records ----
 #define ACG_JS_LINE_MAX 2496    // == ACG_JSON_LINE_MAX of the public header (derived there)
 #define ACG_JS_PRE_MAX 224      // ,"station_id":"<escaped>"            (15 + 32 * 6 + 1 = 208)
@@ -447,6 +516,8 @@ int acg_launch_flight_route_text(const AcgFlightTextPass* p, unsigned int n, voi
 // (a device word) or n_fixed; the result lies in (kb, vb)
 int acg_launch_sort_pairs(unsigned long long* ka, unsigned int* va, unsigned long long* kb, unsigned int* vb, const unsigned int* n_ptr,
                           unsigned int n_fixed, void* stream);
+// reasm.hip: extraction, the three sorts, heads, segment walk and table update for the n records of one pass (-A / -b of f decide)
+int acg_launch_reasm_pass(const AcgMsgRec* recs, unsigned int n, const AcgLabelFilter* f, const AcgReasmPass* p, void* stream);
 // json.hip, text.hip: a unit's part of outs.hip's sequence, over records that are ordered (p->key_s / p->idx_s are filled): the
 // measure kernel (phase ACG_SORTED_MEASURE) or the render kernel (ACG_SORTED_RENDER); the scan between them is the caller's
 #define ACG_SORTED_MEASURE 0

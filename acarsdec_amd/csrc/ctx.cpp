@@ -63,6 +63,8 @@ static void free_all(acg_ctx* c)
     hipFree(c->d_kmsgs); hipFree(c->d_oooi); hipFree(c->d_kwork); std::free(c->h_oooi);
     if (c->flights) acg_fl_destroy(c->flights);
     c->flights = nullptr;
+    if (c->reasm) acg_rs_destroy(c->reasm);
+    c->reasm = nullptr;
     outputs_destroy(c->json);
     c->json = nullptr;
     outputs_destroy(c->text);
@@ -397,6 +399,7 @@ extern "C" int acg_reset(acg_ctx* ctx)
     ctx->last_len = 0;
     ctx->last_had_demod = false;
     if (ctx->flights && acg_fl_reset(ctx->flights) != ACG_OK) return fail(ctx, ACG_EHIP, "flight table reset");
+    if (ctx->reasm && acg_rs_reset(ctx->reasm) != ACG_OK) return fail(ctx, ACG_EHIP, "reassembly table reset");
     if (ctx->d_stats) return stats_zero(ctx);
     return ACG_OK;
 }

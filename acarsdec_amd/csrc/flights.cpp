@@ -1,7 +1,7 @@
 // flights.cpp -- host side of the flight table (flight.hip): the table and its work space in device memory, grown on demand
 // like the message staging of results.cpp, the snapshot and the route hand-over; the channel map, the export queue and the import
 // queue of a table kept for the channels of several contexts.  Used by a context (acg_flights_enable) and, without one, by
-// acg_selftest_flights and acg_selftest_flights_sharded.
+// acg_selftest_flights and acg_selftest_flights_sharded.  Behind it, the same for the reassembly table (reasm.hip): AcgReasm.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -549,4 +549,194 @@ int acg_fl_load_designed(AcgFlights* t, const acg_flight* in, int n, const acg_r
     FLCHK(hipDeviceSynchronize());
     t->route_bound = (size_t)nr;
     return ACG_OK;
+}
+
+// ---- the reassembly table (reasm.hip): the table, its rows and work space in device memory, the two queues of completed messages
+// (fixed records; texts, each on a 16-byte boundary) grown on demand like the route queue, and their hand-over in final order ----
+struct AcgReasm {
+    AcgReasmPass p{};
+    size_t work_cap = 0;                // records the per-pass work space holds
+    void* work = nullptr;               // one allocation behind p.ev ... p.keep
+    size_t done_bound = 0;              // no more completed records than this can be queued on the device ...
+    unsigned long long text_bound = 0;  // ... and no more bytes of text
+    unsigned long long in_table = 0;    // no more bytes than this lie in the table's rows
+    std::vector<acg_reasm_msg> pending; // fetched and ordered, not yet handed out: [pend_head, size), text_off into pend_text
+    std::vector<char> pend_text;
+    size_t pend_head = 0;
+};
+
+void acg_rs_destroy(AcgReasm* t)
+{
+    if (!t) return;
+    hipFree(t->work);
+    hipFree(t->p.slots); hipFree(t->p.rows); hipFree(t->p.st); hipFree(t->p.done); hipFree(t->p.texts);
+    delete t;
+}
+
+int acg_rs_reset(AcgReasm* t)
+{
+    AcgReasmState st{};
+    st.G = st.Gnext = LLONG_MIN;
+    FLCHK(hipDeviceSynchronize());
+    FLCHK(hipMemset(t->p.slots, 0, (size_t)t->p.cap * sizeof(AcgReasmSlot)));
+    FLCHK(hipMemcpy(t->p.st, &st, sizeof(st), hipMemcpyHostToDevice));
+    FLCHK(hipDeviceSynchronize());
+    t->p.pass = 0;
+    t->done_bound = 0;
+    t->text_bound = t->in_table = 0;
+    t->pending.clear();
+    t->pend_text.clear();
+    t->pend_head = 0;
+    return ACG_OK;
+}
+
+int acg_rs_create(AcgReasm** out, const acg_reasm_config* cfg)
+{
+    *out = nullptr;
+    acg_reasm_config c;
+    if (!acg_rs_config_ok(cfg, &c)) return ACG_EINVAL;
+    AcgReasm* t = new (std::nothrow) AcgReasm;
+    if (!t) return ACG_ENOMEM;
+    unsigned int cap = 1;
+    while (cap < (unsigned int)c.max_msgs) cap <<= 1;
+    t->p.t0_us = c.t0_sec * 1000000ll + c.t0_usec;
+    t->p.cap = cap;
+    t->p.max_text = (unsigned int)c.max_text;
+    t->p.done_cap = 1024;
+    t->p.text_cap = (unsigned long long)std::max(c.max_text, 1 << 18);
+    const bool ok = hipMalloc(&t->p.slots, (size_t)cap * sizeof(AcgReasmSlot)) == hipSuccess &&
+                    hipMalloc(&t->p.rows, (size_t)cap * (size_t)c.max_text) == hipSuccess && hipMalloc(&t->p.st, sizeof(AcgReasmState)) == hipSuccess &&
+                    hipMalloc(&t->p.done, (size_t)t->p.done_cap * sizeof(AcgReasmDone)) == hipSuccess &&
+                    hipMalloc(&t->p.texts, (size_t)t->p.text_cap) == hipSuccess;
+    const int rc = ok ? acg_rs_reset(t) : ACG_ENOMEM;
+    if (rc != ACG_OK) {
+        acg_rs_destroy(t);
+        return rc;
+    }
+    *out = t;
+    return ACG_OK;
+}
+
+int acg_rs_prepare(AcgReasm* t, unsigned int n, void* stream, const int* chmap, unsigned int nmap, const AcgReasmPass** pass)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (n > (1u << 30)) return ACG_ENOMEM;
+    if (n > t->work_cap) {
+        FLCHK(hipStreamSynchronize(s));                               // an earlier pass may still use the old buffers
+        hipFree(t->work);
+        t->work = nullptr;
+        t->work_cap = 0;
+        const size_t want = std::max<size_t>(n, 4096);
+        const size_t b_ev = up256(want * sizeof(AcgReasmEv)), b_64 = up256(want * 8), b_32 = up256(want * 4);
+        FLCHK(hipMalloc(&t->work, b_ev + 3 * b_64 + 3 * b_32 + up256(want)));
+        unsigned char* w = (unsigned char*)t->work;
+        t->p.ev = (AcgReasmEv*)w; w += b_ev;
+        t->p.ka = (unsigned long long*)w; w += b_64;
+        t->p.kb = (unsigned long long*)w; w += b_64;
+        t->p.segs = (uint2*)w; w += b_64;
+        t->p.va = (unsigned int*)w; w += b_32;
+        t->p.vb = (unsigned int*)w; w += b_32;
+        t->p.status = (unsigned int*)w; w += b_32;
+        t->p.keep = w;
+        t->work_cap = want;
+    }
+    // a pass of n records completes at most n messages ...
+    void* dq = t->p.done;
+    int rc = queue_room(&dq, &t->p.done_cap, sizeof(AcgReasmDone), &t->done_bound, &t->p.st->ndone, n, s);
+    t->p.done = (AcgReasmDone*)dq;
+    if (rc != ACG_OK) return rc;
+    // ... whose texts hold what lay in the rows and what the pass appends (242 bytes a record), each rounded up to 16 bytes
+    const unsigned long long row = t->p.max_text;
+    t->in_table = std::min<unsigned long long>(t->in_table + 242ull * n, row * t->p.cap);
+    const unsigned long long need = std::min<unsigned long long>(row * n, t->in_table + 16ull * n);
+    if (t->text_bound + need > t->p.text_cap) {                        // as queue_room: what is really queued, before the queue grows
+        unsigned long long queued = 0;
+        FLCHK(hipMemcpyAsync(&queued, &t->p.st->tbytes, sizeof(queued), hipMemcpyDeviceToHost, s));
+        FLCHK(hipStreamSynchronize(s));
+        t->text_bound = std::min(queued, t->p.text_cap);
+    }
+    if (t->text_bound + need > t->p.text_cap) {
+        const unsigned long long want = std::max(2 * t->p.text_cap, t->text_bound + need);
+        if (want > (1ull << 40)) return ACG_ENOMEM;
+        void* bigger = nullptr;
+        FLCHK(hipMalloc(&bigger, (size_t)want));
+        FLCHK(hipMemcpyAsync(bigger, t->p.texts, (size_t)t->text_bound, hipMemcpyDeviceToDevice, s));
+        FLCHK(hipStreamSynchronize(s));
+        hipFree(t->p.texts);
+        t->p.texts = (unsigned char*)bigger;
+        t->p.text_cap = want;
+    }
+    t->text_bound += need;
+    t->p.chmap = chmap;
+    t->p.nmap = chmap ? nmap : 0;
+    t->p.pass += 1;
+    *pass = &t->p;
+    return ACG_OK;
+}
+
+int acg_rs_launch(AcgReasm* t, const AcgMsgRec* recs, unsigned int n, const AcgLabelFilter* f, void* stream)
+{
+    return acg_launch_reasm_pass(recs, n, f, &t->p, stream) == 0 ? ACG_OK : ACG_EHIP;
+}
+
+int acg_rs_fetch_status(AcgReasm* t, void* stream, unsigned int n, unsigned char* status, unsigned char* keep)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (n > t->work_cap) return ACG_ESTATE;
+    std::vector<unsigned int> w(n);
+    if (n) FLCHK(hipMemcpyAsync(w.data(), t->p.status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (n && keep) FLCHK(hipMemcpyAsync(keep, t->p.keep, n, hipMemcpyDeviceToHost, s));
+    FLCHK(hipStreamSynchronize(s));
+    for (unsigned int i = 0; i < n; ++i) status[i] = (unsigned char)w[i];
+    return ACG_OK;
+}
+
+int acg_rs_drain(AcgReasm* t, void* stream, acg_reasm_msg* out, int max, int* n, char* text, size_t cap, size_t* nbytes, int* dropped)
+{
+    hipStream_t s = (hipStream_t)stream;
+    AcgReasmState st{};
+    FLCHK(hipMemcpyAsync(&st, t->p.st, sizeof(st), hipMemcpyDeviceToHost, s));
+    FLCHK(hipStreamSynchronize(s));
+    if (st.qfull || st.ndone > t->p.done_cap || st.tbytes > t->p.text_cap) return ACG_EHIP;     // (the queues are sized so that this cannot happen)
+    if (dropped) *dropped = (int)st.dropped;
+    if (t->pend_head == t->pending.size()) {                          // everything fetched earlier has been handed out
+        t->pending.clear();
+        t->pend_text.clear();
+        t->pend_head = 0;
+    }
+    if (st.ndone) {
+        std::vector<AcgReasmDone> h(st.ndone);
+        const size_t t0 = t->pend_text.size();
+        t->pend_text.resize(t0 + (size_t)st.tbytes);
+        FLCHK(hipMemcpyAsync(h.data(), t->p.done, (size_t)st.ndone * sizeof(AcgReasmDone), hipMemcpyDeviceToHost, s));
+        if (st.tbytes) FLCHK(hipMemcpyAsync(t->pend_text.data() + t0, t->p.texts, (size_t)st.tbytes, hipMemcpyDeviceToHost, s));
+        FLCHK(hipMemsetAsync(&t->p.st->ndone, 0, sizeof(unsigned int), s));
+        FLCHK(hipMemsetAsync(&t->p.st->tbytes, 0, sizeof(unsigned long long), s));
+        FLCHK(hipStreamSynchronize(s));
+        // the waves queued them in the order they got there: by (pass, time key of the final fragment) they are in the order of
+        // their final fragments
+        std::sort(h.begin(), h.end(), [](const AcgReasmDone& a, const AcgReasmDone& b) { return a.pass != b.pass ? a.pass < b.pass : a.tkey < b.tkey; });
+        for (const AcgReasmDone& d : h) {
+            acg_reasm_msg x;
+            std::memcpy(&x, d.r, sizeof(x));
+            if (x.text_off + x.text_len > st.tbytes) return ACG_EHIP;
+            x.text_off += t0;
+            t->pending.push_back(x);
+        }
+    }
+    t->done_bound = 0;
+    t->text_bound = 0;
+    int k = 0;
+    size_t used = 0;
+    while (k < max && t->pend_head < t->pending.size() && used + t->pending[t->pend_head].text_len <= cap) {
+        const acg_reasm_msg& x = t->pending[t->pend_head++];
+        out[k] = x;
+        out[k].text_off = used;
+        if (x.text_len) std::memcpy(text + used, t->pend_text.data() + x.text_off, x.text_len);
+        used += x.text_len;
+        ++k;
+    }
+    *n = k;
+    *nbytes = used;
+    return t->pend_head == t->pending.size() ? ACG_OK : ACG_EAGAIN;
 }

@@ -45,3 +45,27 @@ ACG_FL_WEAK int acg_fl_monitor_text(AcgFlights* t, void* stream, long long hdr_s
 ACG_FL_WEAK int acg_fl_routes_json(AcgFlights* t, void* stream, char* out, size_t cap, size_t* nbytes, int* nlines);   // ACG_ESTATE: routes pending on the host
 // lab: the table's content replaced by n designed entries (in[0] the latest update; cap >= n) and nr designed routes
 ACG_FL_WEAK int acg_fl_load_designed(AcgFlights* t, const acg_flight* in, int n, const acg_route* rt, int nr);
+
+// ---- the reassembly table's host object (flights.cpp; reasm.hip), the same way: weak references, absent without flights.cpp
+struct AcgReasm;
+// the configuration with its defaults filled in (max_msgs 0 = 1024, max_text 0 = 3584); 0: a value out of range
+static inline int acg_rs_config_ok(const acg_reasm_config* cfg, acg_reasm_config* eff)
+{
+    if (!cfg) return 0;
+    *eff = *cfg;
+    if (eff->max_msgs == 0) eff->max_msgs = 1024;
+    if (eff->max_text == 0) eff->max_text = 3584;
+    return eff->t0_usec >= 0 && eff->t0_usec <= 999999 && eff->max_msgs >= 1 && eff->max_msgs <= (1 << 20) && eff->max_text >= 16 &&
+           eff->max_text <= 65536 && eff->max_text % 16 == 0;
+}
+ACG_FL_WEAK int acg_rs_create(AcgReasm** out, const acg_reasm_config* cfg);         // an empty table on the current device
+ACG_FL_WEAK void acg_rs_destroy(AcgReasm* t);
+ACG_FL_WEAK int acg_rs_reset(AcgReasm* t);                                           // empties table, queues and pending messages (synchronises)
+// before a pass over n records on `stream`: grows the work space and the two queues, numbers the pass.  chmap / nmap: the channel
+// numbers recorded (a device array the caller owns, null = the slots' own)
+ACG_FL_WEAK int acg_rs_prepare(AcgReasm* t, unsigned int n, void* stream, const int* chmap, unsigned int nmap, const AcgReasmPass** pass);
+// the pass itself over recs[n] (device), behind acg_rs_prepare
+ACG_FL_WEAK int acg_rs_launch(AcgReasm* t, const AcgMsgRec* recs, unsigned int n, const AcgLabelFilter* f, void* stream);
+// the last pass's statuses (and with `keep` the label pass's decisions: AcgReasmPass::keep) of its n records; waits for the stream
+ACG_FL_WEAK int acg_rs_fetch_status(AcgReasm* t, void* stream, unsigned int n, unsigned char* status, unsigned char* keep);
+ACG_FL_WEAK int acg_rs_drain(AcgReasm* t, void* stream, acg_reasm_msg* out, int max, int* n, char* text, size_t cap, size_t* nbytes, int* dropped);

@@ -238,22 +238,32 @@ int commit_imports(acg_ctx* ctx)
 
 // The split of the `take` oldest blocks into d_msgs on the copy stream (it writes every byte of a record, text tail zeroed, so
 // nothing stale crosses the ABI); with `labels`, label.hip's pass behind it into d_kmsgs / d_oooi (the caller has grown the label
-// stage) and, the flight table on, its pass.  *d_total: the label pass's count of kept records, a device word.
+// stage) and, the flight table on, its pass; the reassembly table on, its pass over the split's records behind them.  *d_total: the
+// label pass's count of kept records, a device word.
 int launch_split(acg_ctx* ctx, unsigned int take, bool labels, unsigned int** d_total)
 {
     *d_total = ctx->d_kwork + ctx->kmsgs_cap / 256 + 1;
     AcgLabelPass pass{&ctx->msg_filter, ctx->d_kwork, ctx->d_kmsgs, ctx->d_oooi, *d_total, nullptr, nullptr};
+    const AcgReasmPass* rp = nullptr;
+    if (ctx->reasm) {                                             // the same blocks through the reassembly table, behind the label pass
+        const int rr = acg_rs_prepare(ctx->reasm, take, ctx->copy_stream, ctx->d_chnum, (unsigned int)ctx->cfg.nch, &rp);
+        if (rr != ACG_OK) return fail(ctx, rr, "reassembly table: work space");
+        pass.keep_out = rp->keep;                                 // (which records the label pass kept: the statuses' way to them)
+    }
     if (ctx->flights) {                                           // over exactly the blocks this call consumes, before -e drops any
         const int fr = acg_fl_prepare(ctx->flights, take, ctx->copy_stream, &pass.flights);
         if (fr != ACG_OK) return fail(ctx, fr, "flight table: work space");
     }
     if (acg_launch_msg_split(ctx->d_frames, ctx->frame_cap, ctx->consumed, take, ctx->d_msgs, ctx->copy_stream, labels ? &pass : nullptr) != 0)
         return fail(ctx, ACG_EHIP, "message split launch failed");
+    if (rp && acg_rs_launch(ctx->reasm, ctx->d_msgs, take, &ctx->msg_filter, ctx->copy_stream) != ACG_OK)
+        return fail(ctx, ACG_EHIP, "reassembly pass launch failed");
     return launch_stats(ctx, take, true);
 }
 
-static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs)
+static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int max_msgs, int* nmsgs, unsigned char* status = nullptr)
 {
+    if (status && !ctx->reasm) return fail(ctx, ACG_ESTATE, "reassembly is off (acg_reasm_enable first)");
     unsigned int pending = 0, take = 0;
     RingSpan span;
     int rc = ring_upto(ctx, lag, &span);
@@ -290,6 +300,17 @@ static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int m
     } else if (const int cr = commit_imports(ctx)) {
         return cr;
     }
+    // the statuses are per consumed block: kept record j is the j-th block the label pass kept
+    std::vector<unsigned char> rs_status;                         // [take] statuses, [take] keep
+    std::vector<unsigned int> rs_block;
+    if (status && take) {
+        rs_status.resize(2 * (size_t)take);
+        if (acg_rs_fetch_status(ctx->reasm, ctx->copy_stream, take, rs_status.data(), labels ? rs_status.data() + take : nullptr) != ACG_OK)
+            return fail(ctx, ACG_EHIP, "reassembly: statuses");
+        for (unsigned int i = 0; i < take; ++i)
+            if (!labels || rs_status[take + i]) rs_block.push_back(i);
+        if (rs_block.size() != nrec) return fail(ctx, ACG_EHIP, "reassembly: statuses");
+    }
     number_channels(ctx, ctx->h_msgs, nrec);
     const AcgMsgRec* rec = ctx->h_msgs;
     ctx->consumed += take;
@@ -308,6 +329,7 @@ static int fetch_msgs(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, int m
         m.reserved2 = 0;
         m.reserved3 = 0;
         if (oooi) oooi[kept - 1] = ctx->h_oooi[i];
+        if (status) status[kept - 1] = rs_status[rs_block[i]];
     }
     *nmsgs = (int)kept;
     return ring_result(ctx, rc, pending, take, "more messages queued than fit: call again");
@@ -341,6 +363,22 @@ extern "C" int acg_drain_msgs_oooi(acg_ctx* ctx, acg_msg* out, acg_oooi* oooi, i
     *nmsgs = 0;
     acg_oooi none;
     return fetch_msgs(ctx, DRAIN, out, oooi ? oooi : &none, max_msgs, nmsgs);
+}
+
+extern "C" int acg_collect_msgs_reasm(acg_ctx* ctx, int lag, acg_msg* out, acg_oooi* oooi, unsigned char* status, int max_msgs, int* nmsgs)
+{
+    if (!ctx || !nmsgs || (max_msgs > 0 && (!out || !status)) || lag < 0 || lag >= acg_ctx::NCALL - 1) return ACG_EINVAL;
+    *nmsgs = 0;
+    unsigned char none;
+    return fetch_msgs(ctx, lag, out, oooi, max_msgs, nmsgs, status ? status : &none);
+}
+
+extern "C" int acg_drain_msgs_reasm(acg_ctx* ctx, acg_msg* out, acg_oooi* oooi, unsigned char* status, int max_msgs, int* nmsgs)
+{
+    if (!ctx || !nmsgs || (max_msgs > 0 && (!out || !status))) return ACG_EINVAL;
+    *nmsgs = 0;
+    unsigned char none;
+    return fetch_msgs(ctx, DRAIN, out, oooi, max_msgs, nmsgs, status ? status : &none);
 }
 
 // ---- the sink's filters (label.c:9-23 build_label_filter, acarsdec.c -A / -b / -e) --------------------------------------
@@ -433,6 +471,39 @@ extern "C" int acg_drain_routes(acg_ctx* ctx, acg_route* out, int max, int* n)
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     const int rc = acg_fl_drain_routes(ctx->flights, ctx->copy_stream, out, max, n);
     return rc == ACG_OK ? rc : fail(ctx, rc, rc == ACG_EAGAIN ? "more routes queued than fit: call again" : "route hand-over failed");
+}
+
+// ---- reassembly of multi-block messages (reasm.hip; host side: flights.cpp) ------------------------------------------------
+extern "C" int acg_reasm_enable(acg_ctx* ctx, const acg_reasm_config* cfg)
+{
+    acg_reasm_config eff;
+    if (!ctx || (cfg && !acg_rs_config_ok(cfg, &eff))) return ACG_EINVAL;
+    // (one text for each code: the product library has no room for more, tests/test_host_logic.py's size rule)
+    if (hipSetDevice(ctx->cfg.device) != hipSuccess || (ctx->reasm && hipStreamSynchronize(ctx->copy_stream) != hipSuccess)) return fail(ctx, ACG_EHIP, "reassembly: device");
+    if (ctx->reasm) acg_rs_destroy(ctx->reasm);
+    ctx->reasm = nullptr;
+    if (!cfg) return ACG_OK;
+    if (!acg_rs_create || !ctx->d_crctab) return fail(ctx, ACG_ESTATE, "reassembly: context created without ACG_F_REPAIR");
+    if (ctx->cfg.nch > (1 << 20)) return fail(ctx, ACG_EINVAL, "reassembly: more than 2^20 channels");
+    const int rc = acg_rs_create(&ctx->reasm, cfg);
+    return rc == ACG_OK ? rc : fail(ctx, rc, "reassembly: allocation failed");
+}
+
+extern "C" int acg_drain_reassembled(acg_ctx* ctx, acg_reasm_msg* out, int max, int* n, char* text, size_t cap, size_t* nbytes, int* dropped)
+{
+    if (!ctx || !n || !nbytes || max < 0 || (max > 0 && !out) || (cap > 0 && !text)) return ACG_EINVAL;
+    *n = 0;
+    *nbytes = 0;
+    if (!ctx->reasm) return fail(ctx, ACG_ESTATE, "reassembly is off");
+    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return fail(ctx, ACG_EHIP, "reassembly: device");
+    const int rc = acg_rs_drain(ctx->reasm, ctx->copy_stream, out, max, n, text, cap, nbytes, dropped);
+    return rc == ACG_OK ? rc : fail(ctx, rc, rc == ACG_EAGAIN ? "more completed messages queued than fit: call again" : "reassembly: hand-over");
+}
+
+extern "C" const char* acg_reasm_status_name(int status)
+{
+    static const char* const name[8] = {"unknown", "complete", "in progress", "skipped", "duplicate", "out of sequence", "invalid args", "overflow"};
+    return name[status >= 0 && status < 8 ? status : 0];
 }
 
 // ---- one flight table for the channels of several contexts: events leave the peers and enter the owner ---------------------

@@ -869,7 +869,63 @@ extern "C" int acg_lab_outputs_level_guard(acg_ctx*, int, unsigned int*) { retur
 extern "C" int acg_selftest_outputs(const acg_msg*, int, const acg_msg_filter*, const acg_outputs_config*, const int*, int, acg_out_buf*, int*) { return ACG_ESTATE; }
 
 extern "C" int acg_lab_time_output_passes(const acg_msg*, int, const acg_outputs_config*, int, int, int, float*) { return ACG_ESTATE; }
+
+// (the reassembly table's self test: the same rule)
+extern "C" int acg_selftest_reasm(const acg_msg*, const int*, int, const acg_reasm_config*, const acg_msg_filter*, unsigned char*, acg_reasm_msg*, int, char*, size_t,
+                                  int*, int*, float*) { return ACG_ESTATE; }
 #else
+extern "C" int acg_selftest_reasm(const acg_msg* in, const int* batch, int nbatch, const acg_reasm_config* cfg, const acg_msg_filter* f, unsigned char* status,
+                                  acg_reasm_msg* done, int done_cap, char* text, size_t text_cap, int* ndone, int* dropped, float* pass_ms)
+{
+    acg_reasm_config eff;
+    if (nbatch < 0 || !acg_rs_config_ok(cfg, &eff) || done_cap < 0 || !ndone || (nbatch > 0 && !batch) || (done_cap > 0 && !done) || (text_cap > 0 && !text))
+        return ACG_EINVAL;
+    AcgLabelFilter d;
+    if (label_filter_dev(f, &d) != ACG_OK) return ACG_EINVAL;
+    size_t total = 0, biggest = 0;
+    for (int b = 0; b < nbatch; ++b) {
+        if (batch[b] < 0) return ACG_EINVAL;
+        total += (size_t)batch[b];
+        biggest = std::max(biggest, (size_t)batch[b]);
+    }
+    if (total > 0 && (!in || !status)) return ACG_EINVAL;
+    *ndone = 0;
+    int ndev = 0;
+    if (!acg_rs_create || hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ACG_ENODEV;
+    AcgReasm* t = nullptr;
+    int rc = acg_rs_create(&t, cfg);
+    if (rc != ACG_OK) return rc;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (pass_ms && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) rc = ACG_EHIP;
+    if (rc == ACG_OK) {
+        LabStage lab(biggest);
+        if (!lab.ok()) rc = ACG_ENOMEM;
+        size_t at = 0;
+        for (int b = 0; b < nbatch && rc == ACG_OK; ++b) {
+            const unsigned int n = (unsigned int)batch[b];
+            if (pass_ms) pass_ms[b] = 0.f;
+            if (!n) continue;
+            lab.stage(in + at, n, false, true);
+            const AcgReasmPass* rp = nullptr;
+            if (lab.upload(n) != 0) rc = ACG_EHIP;
+            if (rc == ACG_OK) rc = acg_rs_prepare(t, n, nullptr, nullptr, 0, &rp);
+            if (rc == ACG_OK && pass_ms && hipEventRecord(ev0, nullptr) != hipSuccess) rc = ACG_EHIP;
+            if (rc == ACG_OK) rc = acg_rs_launch(t, lab.d_in, n, &d, nullptr);
+            if (rc == ACG_OK && pass_ms &&
+                (hipEventRecord(ev1, nullptr) != hipSuccess || hipEventSynchronize(ev1) != hipSuccess || hipEventElapsedTime(&pass_ms[b], ev0, ev1) != hipSuccess))
+                rc = ACG_EHIP;
+            if (rc == ACG_OK) rc = acg_rs_fetch_status(t, nullptr, n, status + at, nullptr);
+            at += n;
+        }
+        size_t nbytes = 0;
+        if (rc == ACG_OK) rc = acg_rs_drain(t, nullptr, done, done_cap, ndone, text, text_cap, &nbytes, dropped);
+    }
+    acg_rs_destroy(t);
+    if (ev0) hipEventDestroy(ev0);
+    if (ev1) hipEventDestroy(ev1);
+    return rc;
+}
+
 extern "C" int acg_lab_outputs_level_guard(acg_ctx* ctx, int leg, unsigned int* near_midpoint)
 {
     if (!ctx || !near_midpoint) return ACG_EINVAL;

@@ -318,12 +318,16 @@ class Decoder:
             self._mbuf_cap = max_msgs
         return self._mbuf
 
-    def drain_msgs(self, max_msgs=4096, oooi=False):
+    def drain_msgs(self, max_msgs=4096, oooi=False, reasm=False):
         """outputmsg()'s field split of every block completed since the last drain (needs repair=True): K.Msg records.
         The C side hands out the oldest messages that fit and says ACG_EAGAIN ("call again, nothing lost") while more are
         queued: this wrapper calls again until the queue is empty, so the list is complete whatever max_msgs is (per call the
         records are ordered by (chn, end_bit); across calls the order is completion order).
-        oooi=True: (K.Msg, K.Oooi) pairs from acg_drain_msgs_oooi (the labels decoded on the device)."""
+        oooi=True: (K.Msg, K.Oooi) pairs from acg_drain_msgs_oooi (the labels decoded on the device).
+        reasm=True (after reasm_enable): (K.Msg, status) pairs from acg_drain_msgs_reasm, status one of K.REASM_*; with oooi=True
+        (K.Msg, K.Oooi, status) triples."""
+        if reasm:
+            return self._msgs_reasm(self.L.acg_drain_msgs_reasm, max_msgs, oooi)
         if oooi:
             return self._msgs_oooi(self.L.acg_drain_msgs_oooi, max_msgs)
         buf = self._msg_buf(max(1, max_msgs))
@@ -350,9 +354,11 @@ class Decoder:
         rc = self._chk(self.L.acg_collect_msgs(self.ctx, lag, buf, self._mbuf_cap, C.byref(n)), allow=(K.EAGAIN,))
         return n.value, buf, rc == K.EAGAIN
 
-    def collect_msgs(self, lag=1, max_msgs=4096, oooi=False):
+    def collect_msgs(self, lag=1, max_msgs=4096, oooi=False, reasm=False):
         """list of K.Msg of all calls but the `lag` newest (loops while the C side says "call again"); oooi=True: (K.Msg, K.Oooi)
-        pairs from acg_collect_msgs_oooi"""
+        pairs from acg_collect_msgs_oooi; reasm=True: as drain_msgs, from acg_collect_msgs_reasm"""
+        if reasm:
+            return self._msgs_reasm(self.L.acg_collect_msgs_reasm, max_msgs, oooi, lag)
         if oooi:
             return self._msgs_oooi(self.L.acg_collect_msgs_oooi, max_msgs, lag)
         out = []
@@ -445,6 +451,61 @@ class Decoder:
             out += [K.Route.from_buffer_copy(buf[i]) for i in range(n.value)]
             if rc == K.OK:
                 return out
+
+    # ---- reassembly of multi-block messages (acg_reasm_enable, acg_*_msgs_reasm, acg_drain_reassembled) ----------------------
+    def reasm_enable(self, t0=0.0, max_msgs=0, max_text=0):
+        """The reassembly table (ETB chains, libacars' assstat) on the device for every message entry point from now on.  t0 as
+        in enable_flights; max_msgs: chains in progress the table holds (0: 1024); max_text: bytes of a complete text, a multiple of
+        16 (0: 3584).  The table starts empty."""
+        sec, usec = t0 if isinstance(t0, tuple) else (int(t0 // 1), int(round((t0 - t0 // 1) * 1e6)))
+        if usec >= 1000000:
+            sec, usec = sec + 1, usec - 1000000
+        cfg = K.ReasmConfig(int(sec), int(usec), int(max_msgs), int(max_text))
+        self._chk(self.L.acg_reasm_enable(self.ctx, C.byref(cfg)))
+        self._reasm_text = int(max_text) or 3584
+        self.reasm_dropped = 0
+
+    def reasm_disable(self):
+        self._chk(self.L.acg_reasm_enable(self.ctx, None))
+
+    def _msgs_reasm(self, fn, max_msgs, oooi, *lead):
+        max_msgs = max(1, int(max_msgs))
+        buf = self._msg_buf(max_msgs)
+        cap = self._mbuf_cap
+        obuf = (K.Oooi * cap)() if oooi else None
+        st = (C.c_ubyte * cap)()
+        out = []
+        while True:
+            n = C.c_int(0)
+            rc = self._chk(fn(self.ctx, *lead, buf, obuf, st, cap, C.byref(n)), allow=(K.EAGAIN,))
+            for i in range(n.value):
+                m = K.Msg.from_buffer_copy(buf[i])
+                out.append((m, K.Oooi.from_buffer_copy(obuf[i]), int(st[i])) if oooi else (m, int(st[i])))
+            if rc == K.OK:
+                return out
+
+    def drain_reassembled(self, max_msgs=1024, cap=None):
+        """The completed messages so far, in the order of their final fragments: a list of (K.ReasmMsg, text bytes);
+        self.reasm_dropped = chains that found no slot since enable / reset.  cap: bytes of text taken per call of the C side
+        (default max_msgs texts of the longest kind; at least one always fits)."""
+        max_msgs = max(1, int(max_msgs))
+        cap = max(int(cap) if cap is not None else max_msgs * self._reasm_text, self._reasm_text)
+        buf = (K.ReasmMsg * max_msgs)()
+        text = C.create_string_buffer(cap)
+        out = []
+        while True:
+            n, dropped, nbytes = C.c_int(0), C.c_int(0), C.c_size_t(0)
+            rc = self._chk(self.L.acg_drain_reassembled(self.ctx, buf, max_msgs, C.byref(n), text, cap, C.byref(nbytes), C.byref(dropped)), allow=(K.EAGAIN,))
+            self.reasm_dropped = dropped.value
+            for i in range(n.value):
+                r = K.ReasmMsg.from_buffer_copy(buf[i])
+                out.append((r, text.raw[r.text_off:r.text_off + r.text_len]))
+            if rc == K.OK:
+                return out
+
+    def reasm_status_name(self, status):
+        """libacars' name of a K.REASM_* value ("in progress", "complete", ...), what the reference prints as assstat"""
+        return self.L.acg_reasm_status_name(int(status)).decode()
 
     # ---- one flight table for the channels of several decoders (acg_flights_set_channels / _export / _import / _commit) -----
     def set_flight_channels(self, chn=None):

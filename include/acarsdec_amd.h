@@ -556,6 +556,77 @@ int  acg_flight_monitor_text(acg_ctx *ctx, long long hdr_soh_sample, char *out, 
  * the host -- a host uses one of the two, or switches only behind an ACG_OK. */
 int  acg_drain_routes_json(acg_ctx *ctx, char *out, size_t cap, size_t *nbytes, int *nlines);
 
+/* ---- reassembly of multi-block messages: the reference's call site of la_reasm_fragment_add() (output.c:33-101,579-626) ------
+ * An ACARS message longer than about 220 characters travels as a chain of blocks, every block but the last ending in ETB; the
+ * reference built with libacars reports per block "assstat" and hands the complete text on.  Off by default; with it off every
+ * entry point launches, allocates, copies and returns exactly what it does without this section.  When enabled, every message
+ * entry point, the sinks and the outputs take the blocks they consume through ONE table on the device, resident across calls like
+ * the flight table, and by the flight table's three rules:
+ *   which messages   those that passed -A / -b, downlinks and uplinks alike, BEFORE -e (output.c:537-540,650);
+ *   time             tv_us = t0_us + 80 * soh_sample, in integers;
+ *   ORDER            within one drain / collect call ascending (end_sample, chn); across calls, call order.
+ * The table's rule, for a message m (tests/reasm_model.py is this text as a plain dict walk; it follows libacars' documented
+ * behaviour from the reference's call site outward and HAS NOT BEEN RUN AGAINST libacars):
+ *   bs == ETX or bid == 0 (a squitter)                SKIPPED, the table is not touched
+ *   key    (addr, label, msn) as C strings; msn = no[0..2] of a downlink ('0' <= bid <= '9'), "" of an uplink
+ *   seq    (signed char)no[3] - 'A' of a downlink, whose first fragment has 0; bid - 'A' of an uplink, which has no first and
+ *          wraps (after 'Z' in mode '2', after 'W' otherwise, comes 'A')
+ *   an entry whose FIRST fragment is more than its time-out older than m (strictly; VGT4 = 660 s for a chain begun by a
+ *   downlink, VAT4 = 90 s by an uplink) is gone.  Then, without an entry: a downlink with seq != 0 is OUT_OF_SEQUENCE, a block
+ *   that does not end in ETB is SKIPPED (a single-block message), anything else begins an entry.  With one: seq == the previous
+ *   is a DUPLICATE (entry untouched); seq != previous + 1 is OUT_OF_SEQUENCE and the entry is gone; a text that would pass
+ *   max_text bytes is an OVERFLOW and the entry is gone; otherwise m.txt (txt_len bytes) is appended, and the entry is
+ *   IN_PROGRESS while m ends in ETB, else COMPLETE, handed to acg_drain_reassembled and gone.
+ * The fragment data is acg_msg.txt: the H1 sublabel / MFI prefix that libacars strips per fragment is NOT stripped.
+ * "assstat" and the complete text are not spliced into the JSON / text sinks' rendered bytes: a host does that by (chn, end_bit). */
+#define ACG_REASM_UNKNOWN          0   /* a chain's first block found no slot in the table (counted in `dropped`) */
+#define ACG_REASM_COMPLETE         1
+#define ACG_REASM_IN_PROGRESS      2
+#define ACG_REASM_SKIPPED          3
+#define ACG_REASM_DUPLICATE        4
+#define ACG_REASM_OUT_OF_SEQUENCE  5
+#define ACG_REASM_ARGS_INVALID     6   /* libacars' value; never produced */
+#define ACG_REASM_OVERFLOW         7   /* ours: the one bound a fixed table needs */
+typedef struct {
+	long long t0_sec;             /* wall clock of the channels' first sample since acg_reset */
+	int t0_usec;                  /* 0 .. 999999 */
+	int max_msgs;                 /* chains in progress the table holds, >= 1 (rounded up to a power of two), <= 2^20; 0 = 1024 */
+	int max_text;                 /* bytes of a complete text: a multiple of 16, 16 .. 65536; 0 = 3584 (16 blocks of 224) */
+} acg_reasm_config;
+
+/* One completed message.  Every byte is defined (strings are NUL padded). */
+typedef struct {
+	int chn;                      /* of the FINAL fragment, as chn, end_bit, end_sample, soh_sample: they name the handed-out */
+	int nfrag;                    /* message (or sink line) this text replaces.  nfrag: fragments appended */
+	long long end_bit, end_sample, soh_sample;
+	long long first_soh_sample;   /* soh_sample of the chain's first fragment */
+	unsigned long long text_off;  /* the text: text_len bytes at text + text_off of the same acg_drain_reassembled call */
+	unsigned int text_len;
+	char down;                    /* the final fragment is a downlink */
+	char addr[8];
+	char label[3];
+	char msn[4];                  /* "" for an uplink */
+	char reserved[12];            /* 0 */
+} acg_reasm_msg;
+
+/* Switches the table on (cfg) or off and frees it (NULL).  Enabling an enabled table replaces it by an empty one.  ACG_EINVAL: a
+ * value outside the ranges above; ACG_ESTATE: context without ACG_F_REPAIR.  acg_reset() empties the table and the completed
+ * messages not yet drained. */
+int  acg_reasm_enable(acg_ctx *ctx, const acg_reasm_config *cfg);
+/* acg_drain_msgs_oooi / acg_collect_msgs_oooi plus the reassembly status: status[i] (ACG_REASM_*) belongs to out[i]; oooi may be
+ * NULL here.  The records are byte-identical to the plain pair's.  ACG_ESTATE: the table is off. */
+int  acg_drain_msgs_reasm(acg_ctx *ctx, acg_msg *out, acg_oooi *oooi, unsigned char *status, int max_msgs, int *nmsgs);
+int  acg_collect_msgs_reasm(acg_ctx *ctx, int lag, acg_msg *out, acg_oooi *oooi, unsigned char *status, int max_msgs, int *nmsgs);
+/* The completed messages in the order of their final fragments, texts packed back to back into text (cap bytes, *nbytes used).
+ * Whole records only: ACG_EAGAIN when more are queued than max or cap take, the rest stay queued (a text longer than cap never
+ * fits: cap >= max_text always makes progress).  *dropped (may be NULL) counts, since enable / reset, every (call, key) pair in
+ * which a key that could begin an entry found no slot within 128 of its place (see acg_flight_snapshot); its creating blocks
+ * carry ACG_REASM_UNKNOWN.  Waits for the passes issued so far.  ACG_ESTATE: the table is off. */
+int  acg_drain_reassembled(acg_ctx *ctx, acg_reasm_msg *out, int max, int *n, char *text, size_t cap, size_t *nbytes, int *dropped);
+/* "unknown", "complete", "in progress", "skipped", "duplicate", "out of sequence", "invalid args", "overflow": libacars' names in
+ * libacars' order, for a host that prints assstat; anything else: "unknown". */
+const char *acg_reasm_status_name(int status);
+
 /* ---- the JSON sink: buildjson() (output.c:227-324), what -o 4 prints, -j sends and the MQTT sink publishes ------------------
  * Off by default; with it off every entry point launches, copies and returns exactly what it does without this section.
  * acg_drain_json / acg_collect_json are message entry points like acg_drain_msgs / acg_collect_msgs (ACG_F_REPAIR, the filters

@@ -93,6 +93,17 @@ int  acg_selftest_flights_sharded(const acg_msg *in, const int *batch, int nbatc
 				  const acg_msg_filter *f, acg_flight *snaps, int snap_cap, int *snap_n, acg_route *routes, int route_cap,
 				  int *nroutes, int *dropped, float *pass_ms);
 
+/* diagnostics: the reassembly table (reasm.hip) on caller-supplied records, without a demodulator: acg_selftest_flights' shape.
+ * in holds sum(batch[0..nbatch)) records as acg_drain_msgs hands them out; batch b is taken through one pass (filter f, NULL =
+ * none; order (end_sample, chn) within the batch) of a table made from cfg.  status[i] (ACG_REASM_*) belongs to in[i].  The
+ * completed messages of all batches go to done (done_cap records) and text (text_cap bytes) as acg_drain_reassembled hands them
+ * out, *ndone of them; *dropped as there.  pass_ms (nbatch entries, or NULL): the device time of batch b's pass in milliseconds,
+ * HIP events around it (the records' way to the device is outside).  ACG_EAGAIN: done or text too small; ACG_ENODEV: no GPU;
+ * ACG_ESTATE: the product library (the entry is compiled into the lab library only). */
+int  acg_selftest_reasm(const acg_msg *in, const int *batch, int nbatch, const acg_reasm_config *cfg, const acg_msg_filter *f,
+			unsigned char *status, acg_reasm_msg *done, int done_cap, char *text, size_t text_cap, int *ndone, int *dropped,
+			float *pass_ms);
+
 /* diagnostics: the flight table's text (flight_text.hip) on caller-supplied entries and routes, without traffic: a table made
  * from cfg (at least n slots) holds in[0 .. n) as its live entries, in[0] the latest update, and its queue holds rt[0 .. nr),
  * stored in a shuffled order under tags that ascend with their index; then exactly what acg_flight_monitor_text (tcfg,
