@@ -64,6 +64,7 @@ UNITS = [("fir.hip", ["-O3"], True),
          # way: the size rule of tests/test_host_logic.py (LEDGER, "Complex int8 and complex float32")
          ("fir_iq.hip", ["-O3", "--offload-compress"], True), ("fir_mm.hip", ["-O3", "--offload-compress"], True),
          ("fir_rate.hip", ["-O3", "--offload-compress"], True),    # any input rate: four format instantiations, the same way
+         ("fir_long.hip", ["-O3", "--offload-compress"], True),    # channel filters over several windows: one instantiation per sample size
          ("msk.hip", MSK_FLAGS, True), ("msk_lean.hip", MSK_LEAN_FLAGS, True), ("msk2.hip", MSK_FLAGS, False), ("synth.hip", ["-O3"], True),
          ("blk.hip", ["-O3"], True), ("label.hip", ["-O3"], True),
          # the two resident tables (flight.hip's sort serves both) as compressed bundles, outs.hip's way: the size rule of

@@ -222,6 +222,8 @@ SYMBOLS = {
     "acg_process_rate_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_int),
                                        C.POINTER(C.c_size_t)]),
     "acg_feed_rate_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t]),
+    "acg_set_channel_filter": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "acg_channel_filter_taps": (C.c_int, [C.c_uint, C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "acg_process_pcm_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "acg_feed_pcm_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "acg_host_alloc": (C.c_void_p, [C.c_size_t]),

@@ -78,6 +78,17 @@ struct acg_ctx {
     unsigned int* d_rate_grid = nullptr;    // ... and on the device
     float* d_rate_tapsum = nullptr;         // [nch][4]: the taps' sums over [0, decim - 1) and [0, decim), re and im
     const struct FirRateArgs* rate_call = nullptr;   // the rate call being issued: what its chunks' launches share (process.cpp)
+    // acg_set_channel_filter: taps over long_nseg windows (fir_long.h).  long_nseg == 0: off, none of this is used or allocated
+    int long_nseg = 0;
+    float* d_long_taps = nullptr;           // [nch][long_nseg * decim + 8][2], the last 8 of a channel zeros
+    unsigned char* d_long_hist[2] = {};     // [nstreams] rows of the long_nseg - 1 windows before the next call's first sample, raw;
+    size_t long_hist_pitch = 0;             // ... a call reads long_hist_cur and writes the other one behind its last launch
+    int long_hist_cur = 0;
+    int long_have = 0;                      // windows of that history that exist (0 after acg_reset / a change of rate, filter or format)
+    int long_fmt = -1;                      // the format the history is in
+    hipEvent_t long_hist_ev = nullptr;      // the history is written: the next call's launches wait for it, whatever their stream
+    bool long_hist_ev_valid = false;
+    const struct FirLongArgs* long_call = nullptr;   // as rate_call, while a filter is on
 
     // ---- process.cpp: streams and events of the pipeline, call slots, dm buffers and guards, host staging, launch timing
     hipStream_t stream = nullptr;

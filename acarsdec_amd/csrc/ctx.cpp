@@ -3,6 +3,7 @@
 // fails with ACG_ENODEV.
 #include "acg_ctx.h"
 #include "fir_mm_plan.h"
+#include "fir_long.h"
 
 int fail(acg_ctx* ctx, int code, const char* msg)
 {
@@ -59,6 +60,8 @@ static void free_all(acg_ctx* c)
     hipFree(c->d_stats);
     hipFree(c->d_chnum);
     hipFree(c->d_rate_grid); hipFree(c->d_rate_tapsum);
+    hipFree(c->d_long_taps); hipFree(c->d_long_hist[0]); hipFree(c->d_long_hist[1]);
+    if (c->long_hist_ev) hipEventDestroy(c->long_hist_ev);
     hipFree(c->d_msgs); std::free(c->h_msgs);
     hipFree(c->d_kmsgs); hipFree(c->d_oooi); hipFree(c->d_kwork); std::free(c->h_oooi);
     if (c->flights) acg_fl_destroy(c->flights);
@@ -382,6 +385,7 @@ extern "C" int acg_reset(acg_ctx* ctx)
     ctx->feed_fill = 0;
     ctx->feed_cur = 0;
     ctx->rate_k = 0;                                     // the grid restarts at window 0
+    ctx->long_have = 0;                                  // ... and a channel filter, which stays on, has nothing before it
     ctx->stage_seq = 0;
     ctx->stage_free_valid[0] = ctx->stage_free_valid[1] = false;
     std::fill(ctx->msk_done_owner.begin(), ctx->msk_done_owner.end(), -1);
@@ -452,6 +456,8 @@ extern "C" int acg_set_input_rate(acg_ctx* ctx, unsigned int rate_hz)
     HIPCHK_OL(ctx, hipDeviceSynchronize());                 // down-converter launches that read the grid run on the callers' streams
     ctx->rate_k = 0;
     ctx->rate_hz = 0;
+    ctx->long_nseg = 0;                                     // a channel filter belongs to the rate it was made for: off
+    ctx->long_have = 0;
     if (rate_hz == 0) return ACG_OK;
     unsigned int g = rate_hz, b = ACG_INTRATE;
     while (b) { const unsigned int r = g % b; g = b; b = r; }
@@ -466,6 +472,50 @@ extern "C" int acg_set_input_rate(acg_ctx* ctx, unsigned int rate_hz)
     ctx->rate_P = P;
     ctx->rate_Q = Q;
     ctx->rate_hz = rate_hz;
+    return ACG_OK;
+}
+
+// ---- channel filters over several windows (include/acarsdec_amd.h; the kernel: fir_long.hip) -----------------------------
+extern "C" int acg_set_channel_filter(acg_ctx* ctx, int nseg, const float* taps)
+{
+    if (!ctx) return ACG_EINVAL;
+    const bool off = nseg == 0 || !taps;
+    if (!ctx->rate_hz) return fail(ctx, ACG_ESTATE, "channel filter: no input rate is set (acg_set_input_rate)");
+    if (ctx->rate_Q != 1) return fail(ctx, ACG_EINVAL, "channel filter: the input rate must be a multiple of 12 500 Hz");
+    if (!off && (nseg < 2 || nseg > ACG_MAXSEG)) return fail(ctx, ACG_EINVAL, "channel filter: nseg outside 2 .. ACG_MAXSEG (0 = off)");
+    if (ctx->feed_fill) return fail(ctx, ACG_ESTATE, "the channel filter cannot change while a host feed carries samples (acg_reset drops them)");
+    if (!off && !acg_launch_fir_long) return fail(ctx, ACG_ESTATE, "this build has no channel-filter unit");
+    HIPCHK_OL(ctx, hipSetDevice(ctx->cfg.device));
+    HIPCHK_OL(ctx, hipDeviceSynchronize());                 // down-converter launches that read the table run on the callers' streams
+    ctx->rate_k = 0;
+    ctx->long_have = 0;
+    ctx->long_hist_ev_valid = false;
+    if (off) {
+        ctx->long_nseg = 0;
+        return ACG_OK;
+    }
+    const acg_config& g = ctx->cfg;
+    // a channel's table on the device: its nseg * decim taps and 8 zeros (fir_long.h: what a window's last chunk reads past a segment)
+    const size_t tap_bytes = (size_t)nseg * g.decim * 2 * sizeof(float), tap_pitch = tap_bytes + 8 * 2 * sizeof(float);
+    if (nseg != ctx->long_nseg || !ctx->d_long_taps) {
+        ctx->long_nseg = 0;
+        hipFree(ctx->d_long_taps); hipFree(ctx->d_long_hist[0]); hipFree(ctx->d_long_hist[1]);
+        ctx->d_long_taps = nullptr;
+        ctx->d_long_hist[0] = ctx->d_long_hist[1] = nullptr;
+        // the history in the widest format (8 bytes per sample), a chunk of room behind it: every aligned 16-byte read of a
+        // row stays inside its pitch
+        ctx->long_hist_pitch = (((size_t)(nseg - 1) * g.decim * 8 + 15) & ~(size_t)15) + 16;
+        HIPCHK_OL(ctx, hipMalloc(&ctx->d_long_taps, (size_t)g.nch * tap_pitch));
+        HIPCHK_OL(ctx, hipMemset(ctx->d_long_taps, 0, (size_t)g.nch * tap_pitch));
+        for (auto& h : ctx->d_long_hist) {
+            HIPCHK_OL(ctx, hipMalloc(&h, ctx->long_hist_pitch * (size_t)g.nstreams));
+            HIPCHK_OL(ctx, hipMemset(h, 0, ctx->long_hist_pitch * (size_t)g.nstreams));
+        }
+        if (!ctx->long_hist_ev) HIPCHK_OL(ctx, hipEventCreateWithFlags(&ctx->long_hist_ev, hipEventDisableTiming));
+    }
+    HIPCHK_OL(ctx, hipMemcpy2D(ctx->d_long_taps, tap_pitch, taps, tap_bytes, tap_bytes, (size_t)g.nch, hipMemcpyHostToDevice));
+    HIPCHK_OL(ctx, hipDeviceSynchronize());
+    ctx->long_nseg = nseg;
     return ACG_OK;
 }
 

@@ -274,3 +274,53 @@ int acg_rate_taps(unsigned int rate_hz, double offset_hz, int n, float *taps_out
 	}
 	return ACG_OK;
 }
+
+/* ---- channel filters over several windows: a Kaiser-windowed sinc times the channel's oscillator -------------------------- */
+/* the modified Bessel function of the first kind, order 0, as its power series sum ((x / 2)^2)^k / (k!)^2 (glibc has none) */
+static double bessel_i0(double x)
+{
+	const double q = 0.25 * x * x;
+	double term = 1.0, sum = 1.0;
+	int k;
+	for (k = 1; k < 500; k++) {
+		term *= q / ((double)k * (double)k);
+		sum += term;
+		if (term < 1e-18 * sum)
+			break;
+	}
+	return sum;
+}
+
+int acg_channel_filter_taps(unsigned int rate_hz, double offset_hz, int nseg, double cutoff_hz, double beta, float *taps_out)
+{
+	int i, n;
+	double alpha, norm = 0.0, i0b;
+	double *h;
+	if (acg_rate_decim(rate_hz) < 0 || rate_hz % ACG_INTRATE || nseg < 2 || nseg > ACG_MAXSEG || !taps_out)
+		return ACG_EINVAL;
+	if (!(cutoff_hz > 0.0) || !(cutoff_hz < 0.5 * (double)rate_hz) || !(beta >= 0.0))
+		return ACG_EINVAL;
+	n = nseg * (int)(rate_hz / ACG_INTRATE);
+	h = (double *)malloc((size_t)n * sizeof(double));
+	if (!h)
+		return ACG_ENOMEM;
+	alpha = 0.5 * (double)(n - 1);
+	i0b = bessel_i0(beta);
+	for (i = 0; i < n; i++) {
+		/* the ideal low-pass of that cut-off, sin(pi x) / (pi x) with x = 2 fc / R (i - alpha), under the Kaiser window */
+		const double r = ((double)i - alpha) / alpha;
+		const double x = 2.0 * cutoff_hz / (double)rate_hz * ((double)i - alpha);
+		const double y = M_PI * (x == 0.0 ? 1e-20 : x);
+		h[i] = sin(y) / y * (bessel_i0(beta * sqrt(1.0 - r * r)) / i0b);
+		norm += h[i];
+	}
+	for (i = 0; i < n; i++) {
+		const double turns = offset_hz * (double)i / (double)rate_hz;
+		const double ph = 2.0 * M_PI * (turns - floor(turns));
+		const double g = h[i] / norm;
+		taps_out[2 * i] = (float)(g * cos(ph));
+		taps_out[2 * i + 1] = (float)(g * -sin(ph));
+	}
+	free(h);
+	return ACG_OK;
+}

@@ -8,6 +8,7 @@
 #include "acg_ctx.h"
 #include "fir_mm_plan.h"
 #include "fir_rate.h"
+#include "fir_long.h"
 
 namespace {
 
@@ -830,6 +831,7 @@ static int rate_fmt(acg_ctx* ctx, int fmt, FirRateArgs* r)
 {
     if (!ctx->rate_hz) return fail(ctx, ACG_ESTATE, "no input rate is set (acg_set_input_rate)");
     if (!acg_launch_fir_rate) return fail(ctx, ACG_ESTATE, "this build has no rate down-converter unit");
+    if (ctx->long_nseg && !acg_launch_fir_long) return fail(ctx, ACG_ESTATE, "this build has no channel-filter unit");
     float scale;
     switch (fmt) {
     case ACG_FMT_CU8: r->fmt = RATE_CU8; scale = 1.0f / 127.5f; break;
@@ -880,6 +882,14 @@ static int rate_windows_fit(const acg_ctx* ctx, size_t nsamples)
 // instantiation the u8 path already has; what the chunks share waits in the context while the call is issued.
 static int launch_fir_rate_chunk(acg_ctx* c, FirArgs& f, hipStream_t st)
 {
+    if (c->long_call) {                                          // a channel filter is on: the same chunk, fir_long.hip's kernel
+        FirLongArgs b = *c->long_call;
+        b.dm = f.dm;
+        b.win0 = (int)(f.dm - c->d_dm);
+        b.nwin = f.nwin;
+        b.ncu = f.ncu;
+        return acg_launch_fir_long(&b, st);
+    }
     FirRateArgs b = *c->rate_call;
     b.dm = f.dm;
     b.win0 = (unsigned int)(f.dm - c->d_dm);                     // the chunk's first window
@@ -899,10 +909,54 @@ static int rate_run(acg_ctx* ctx, FirRateArgs& r, const void* dev, size_t pitch,
     a.pitch = pitch;
     const int per = r.bps == 2 ? 1 : r.bps == 4 ? 2 : 4;         // the formats' pipeline chunk (fmt_chunk_win): the u8 path's bytes per launch
     const int chunk = (ctx->pipe_blocks > 0 ? (ctx->pipe_blocks + per - 1) / per : ctx->cfg.max_blocks) * ACG_BLOCK;
+    FirLongArgs l{};
+    if (ctx->long_nseg) {
+        // A channel filter (acg_set_channel_filter): the rows and the chunks are the same, the kernel is fir_long.hip's, and the
+        // nseg - 1 windows before the call's first sample come from the context's history -- written behind the last launch of
+        // the call before, on that call's stream: this call's launches wait for it, whatever their stream.
+        if (ctx->long_fmt != r.fmt) { ctx->long_fmt = r.fmt; ctx->long_have = 0; }
+        if (ctx->long_hist_ev_valid) HIPCHK_OL(ctx, hipStreamWaitEvent(s, ctx->long_hist_ev, 0));
+        l.in = r.in;
+        l.pitch = pitch;
+        l.valid_bytes = r.valid_bytes;
+        l.hist = ctx->d_long_hist[ctx->long_hist_cur];
+        l.hist_pitch = ctx->long_hist_pitch;
+        l.stream_of = r.stream_of;
+        l.taps = ctx->d_long_taps;
+        l.tap_pitch = ((size_t)ctx->long_nseg * r.decim + 8) * 2;
+        l.dm_pitch = r.dm_pitch;
+        l.nch = r.nch;
+        l.decim = r.decim;
+        l.nseg = ctx->long_nseg;
+        l.fmt = r.fmt;
+        l.nprev = ctx->long_have;
+        l.scale = r.fmt == RATE_CU8 ? 1.0f / 127.5f : r.fmt == RATE_CS8 ? 1.0f / 128.0f : r.fmt == RATE_CS16 ? 1.0f / 32768.0f : 1.0f;
+        acg_fir_long_plan(&l);
+        ctx->long_call = &l;
+    }
     ctx->rate_call = &r;
     const int rc = run_pipeline(ctx, s, a, 0, nwin, chunk, launch_fir_rate_chunk);
     ctx->rate_call = nullptr;
+    ctx->long_call = nullptr;
     if (rc == ACG_OK) ctx->rate_k += (unsigned long long)nwin;
+    if (rc == ACG_OK && ctx->long_nseg) {
+        // The history of the next call: the last nseg - 1 windows of (this call's history, this call's windows), into the other
+        // buffer (the launches just issued read this one), on the caller's stream, which run_pipeline has ordered behind the
+        // call's last down-converter launch.  A call of fewer windows than that shifts what there was.
+        const int keep = ctx->long_nseg - 1, nxt = ctx->long_hist_cur ^ 1;
+        const size_t wb = (size_t)r.decim * r.bps, ns = (size_t)ctx->cfg.nstreams;
+        unsigned char* dst = ctx->d_long_hist[nxt];
+        if (nwin >= keep) {
+            HIPCHK_OL(ctx, hipMemcpy2DAsync(dst, l.hist_pitch, r.in + (size_t)(nwin - keep) * wb, pitch, keep * wb, ns, hipMemcpyDeviceToDevice, s));
+        } else {
+            HIPCHK_OL(ctx, hipMemcpy2DAsync(dst, l.hist_pitch, l.hist + (size_t)nwin * wb, l.hist_pitch, (keep - nwin) * wb, ns, hipMemcpyDeviceToDevice, s));
+            HIPCHK_OL(ctx, hipMemcpy2DAsync(dst + (keep - nwin) * wb, l.hist_pitch, r.in, pitch, nwin * wb, ns, hipMemcpyDeviceToDevice, s));
+        }
+        HIPCHK_OL(ctx, hipEventRecord(ctx->long_hist_ev, s));
+        ctx->long_hist_ev_valid = true;
+        ctx->long_hist_cur = nxt;
+        ctx->long_have = std::min(keep, ctx->long_have + nwin);
+    }
     return rc;
 }
 

@@ -75,6 +75,17 @@ def rate_taps(rate_hz, offset_hz, n=None):
     return out
 
 
+def channel_filter_taps(rate_hz, offset_hz, nseg, cutoff_hz=6250.0, beta=7.0):
+    """A channel filter over nseg windows for Decoder.set_channel_filter, float32 [nseg * decim, 2]: a Kaiser-windowed sinc (-6 dB
+    at cutoff_hz, DC gain 1) times the oscillator of a channel offset_hz above the centre; rate_hz a multiple of 12 500
+    (acg_channel_filter_taps)."""
+    if int(rate_hz) % K.INTRATE:
+        raise K.AcgError(K.EINVAL, "channel_filter_taps: the rate must be a multiple of 12 500 Hz")
+    out = np.zeros((max(int(nseg), 0) * (int(rate_hz) // K.INTRATE), 2), dtype=np.float32)
+    _chk(None, K.load().acg_channel_filter_taps(int(rate_hz), float(offset_hz), int(nseg), float(cutoff_hz), float(beta), out.ctypes.data))
+    return out
+
+
 def rate_window_starts(rate_hz, k0, n):
     """s_k0 .. s_(k0 + n) of the window grid s_k = floor(k P / Q), P / Q = rate_hz / 12500: uint64 [n + 1]"""
     out = np.zeros(int(n) + 1, dtype=np.uint64)
@@ -202,6 +213,17 @@ class Decoder:
         """Input at rate_hz from now on, windows on the grid s_k = floor(k rate / 12500) (needs decim == ntaps ==
         rate_decim(rate_hz) and taps as rate_taps makes them); 0: whole windows of decim samples again.  Restarts the grid."""
         self._chk(self.L.acg_set_input_rate(self.ctx, int(rate_hz)))
+
+    def set_channel_filter(self, taps):
+        """A channel filter over several windows on the rate path (rate a multiple of 12 500 Hz): float32 [nch, nseg * decim, 2] as
+        channel_filter_taps makes them, index 0 for the oldest sample, nseg = 2 .. 4 from the shape; None: off.  Restarts the
+        grid and empties the history.  The filter's centre lies (nseg - 1) / 2 output samples earlier than the boxcar's."""
+        if taps is None:
+            self._chk(self.L.acg_set_channel_filter(self.ctx, 0, None))
+            return
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        assert taps.ndim == 3 and taps.shape[0] == self.nch and taps.shape[2] == 2 and taps.shape[1] % self.decim == 0, taps.shape
+        self._chk(self.L.acg_set_channel_filter(self.ctx, taps.shape[1] // self.decim, taps.ctypes.data))
 
     def process_rate(self, fmt, dev_tensor, nsamples, pitch, stream=None):
         """Device rows of nsamples samples that begin at the current window start; pitch in bytes.  Returns (nwin, consumed): the

@@ -274,6 +274,35 @@ int  acg_process_rate_dev(acg_ctx *ctx, int fmt, const void *dev, size_t pitch_b
  * feed i.  Rows pitch_samples apart. */
 int  acg_feed_rate_host(acg_ctx *ctx, int fmt, const void *samples, size_t pitch_samples, size_t nsamples);
 
+/* ---- channel filters: taps over several windows (overlapped FIR) ---------------------------- */
+/* The definition above is a boxcar of one output period: a sinc with side lobes at -13 dB, -18 dB, ... that folds every
+ * neighbour into the 12.5 kHz output.  On a wide-band recording, where the neighbours are not on the 12.5 kHz raster, a
+ * context whose rate is a multiple of 12 500 Hz (Q == 1, M = decim = rate / 12500, window k = samples [k M, (k + 1) M)) can
+ * be given a filter of J = nseg windows, 2 <= J <= ACG_MAXSEG, with J M complex taps t_c[n] per channel:
+ *     dm_c[k] = scale_fmt * | sum_{n < J M} v[(k - J + 1) M + n] * t_c[n] |
+ * v[i] = 0 before the context's first sample since acg_reset / acg_set_input_rate / acg_set_channel_filter; k counts windows
+ * as the rate path does; scale_fmt is the rate path's and there is no 1 / L: the taps carry the gain (DC gain 1 reproduces the
+ * boxcar's level).  The ACG_FMT_CU8 sample is ((float)I - 127.37f) + j ((float)Q - 127.37f), each rounded once; the constant
+ * is not folded out of the sum.  Output k exists as soon as window k is complete: acg_process_rate_dev and acg_feed_rate_host
+ * deliver the same nwin and consumed as without a filter, in any split of the input the same bits, and every record field
+ * keeps its meaning.  The filter's centre lies (J - 1) / 2 output samples earlier than the boxcar's: a host that cares
+ * subtracts (J - 1) / 25000 s from its t0.  The down-converter's history (the J - 1 windows before the next call) belongs to
+ * the context, not to a channel: acg_get_state / acg_set_state do not carry it, a channel moved between contexts starts with
+ * J - 1 windows of zeros. */
+#define ACG_MAXSEG 4
+/* taps: [nch][nseg * decim][2], index 0 multiplies the OLDEST sample.  nseg == 0 or taps == NULL: off, the rate path is
+ * bit for bit what it was.  ACG_ESTATE unless a rate is set, ACG_EINVAL when that rate is no multiple of 12 500 Hz or nseg
+ * is outside 2 .. ACG_MAXSEG, ACG_ESTATE while acg_feed_rate_host carries samples.  Zeroes the window counter and the
+ * history, as acg_set_input_rate does; acg_set_input_rate (any value) switches the filter off; acg_reset keeps the filter
+ * and empties the history, and so does a change of sample format between calls; acg_set_taps keeps setting the one-window
+ * table, which is unused while a filter is on. */
+int  acg_set_channel_filter(acg_ctx *ctx, int nseg, const float *taps);
+/* Kaiser-windowed sinc of nseg * decim taps (decim = rate_hz / 12500), -6 dB at cutoff_hz, DC gain 1, times the oscillator
+ * exp(-j 2 pi frac(offset_hz n / rate_hz)); everything evaluated in double, rounded once to float.  [nseg * decim][2].
+ * ACG_EINVAL unless rate_hz is a multiple of 12 500 that acg_rate_decim takes, 2 <= nseg <= ACG_MAXSEG,
+ * 0 < cutoff_hz < rate_hz / 2 and beta >= 0. */
+int  acg_channel_filter_taps(unsigned int rate_hz, double offset_hz, int nseg, double cutoff_hz, double beta, float *taps_out);
+
 /* ---- the 12.5 kHz front ends' own shape: interleaved PCM frames (soundfile.c, alsa.c) ------- */
 #define ACG_PCM_S16 1   /* interleaved int16 frames, x/32768: what sf_read_float makes of a PCM16 file (soundfile.c:65) */
 #define ACG_PCM_F32 2   /* interleaved float32 frames: sf_read_float's own output, alsa.c:66,114 */
