@@ -71,14 +71,14 @@ struct acg_ctx {
     unsigned long long* d_stamp = nullptr;   // measurement build (ACG_MSK_STAMP): per-wave phase cycle sums of the last demodulator launch
     std::vector<int> chnum;                 // acg_set_channel_numbers: the number handed out for each slot; empty = the slot's own
     int* d_chnum = nullptr;                 // ... on the device, for the sinks' passes and the flight table; null = identity
-    // acg_set_input_rate: the rational window grid (fir_rate.h).  rate_hz == 0: integer windows, none of this is used
+    // acg_set_input_rate: the rational window grid (fir_grid.h).  rate_hz == 0: integer windows, none of this is used
     unsigned int rate_hz = 0, rate_P = 0, rate_Q = 0;
     unsigned long long rate_k = 0;          // windows since acg_reset / acg_set_input_rate
     std::vector<unsigned int> rate_grid;    // floor(r P / Q), r <= Q ...
     unsigned int* d_rate_grid = nullptr;    // ... and on the device
     float* d_rate_tapsum = nullptr;         // [nch][4]: the taps' sums over [0, decim - 1) and [0, decim), re and im
     const struct FirRateArgs* rate_call = nullptr;   // the rate call being issued: what its chunks' launches share (process.cpp)
-    // acg_set_channel_filter: taps over long_nseg windows (fir_long.h).  long_nseg == 0: off, none of this is used or allocated
+    // acg_set_channel_filter: taps over long_nseg windows (fir_grid.h).  long_nseg == 0: off, none of this is used or allocated
     int long_nseg = 0;
     float* d_long_taps = nullptr;           // [nch][long_nseg * decim + 8][2], the last 8 of a channel zeros
     unsigned char* d_long_hist[2] = {};     // [nstreams] rows of the long_nseg - 1 windows before the next call's first sample, raw;

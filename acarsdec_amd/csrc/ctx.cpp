@@ -3,7 +3,7 @@
 // fails with ACG_ENODEV.
 #include "acg_ctx.h"
 #include "fir_mm_plan.h"
-#include "fir_long.h"
+#include "fir_grid.h"
 
 int fail(acg_ctx* ctx, int code, const char* msg)
 {
@@ -495,7 +495,7 @@ extern "C" int acg_set_channel_filter(acg_ctx* ctx, int nseg, const float* taps)
         return ACG_OK;
     }
     const acg_config& g = ctx->cfg;
-    // a channel's table on the device: its nseg * decim taps and 8 zeros (fir_long.h: what a window's last chunk reads past a segment)
+    // a channel's table on the device: its nseg * decim taps and 8 zeros (fir_grid.h: what a window's last chunk reads past a segment)
     const size_t tap_bytes = (size_t)nseg * g.decim * 2 * sizeof(float), tap_pitch = tap_bytes + 8 * 2 * sizeof(float);
     if (nseg != ctx->long_nseg || !ctx->d_long_taps) {
         ctx->long_nseg = 0;

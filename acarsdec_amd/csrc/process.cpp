@@ -7,8 +7,7 @@
 
 #include "acg_ctx.h"
 #include "fir_mm_plan.h"
-#include "fir_rate.h"
-#include "fir_long.h"
+#include "fir_grid.h"
 
 namespace {
 
@@ -832,12 +831,11 @@ static int rate_fmt(acg_ctx* ctx, int fmt, FirRateArgs* r)
     if (!ctx->rate_hz) return fail(ctx, ACG_ESTATE, "no input rate is set (acg_set_input_rate)");
     if (!acg_launch_fir_rate) return fail(ctx, ACG_ESTATE, "this build has no rate down-converter unit");
     if (ctx->long_nseg && !acg_launch_fir_long) return fail(ctx, ACG_ESTATE, "this build has no channel-filter unit");
-    float scale;
     switch (fmt) {
-    case ACG_FMT_CU8: r->fmt = RATE_CU8; scale = 1.0f / 127.5f; break;
-    case ACG_FMT_CS8: r->fmt = RATE_CS8; scale = 1.0f / 128.0f; break;
-    case ACG_FMT_CS16: r->fmt = RATE_CS16; scale = 1.0f / 32768.0f; break;
-    case ACG_FMT_CF32: r->fmt = RATE_CF32; scale = 1.0f; break;
+    case ACG_FMT_CU8: r->fmt = RATE_CU8; break;
+    case ACG_FMT_CS8: r->fmt = RATE_CS8; break;
+    case ACG_FMT_CS16: r->fmt = RATE_CS16; break;
+    case ACG_FMT_CF32: r->fmt = RATE_CF32; break;
     case ACG_FMT_S16_SPLIT:
     case ACG_FMT_F32_REAL:
         return fail(ctx, ACG_EINVAL, "split planes and real float32 belong to front ends that fix their own rates: the rate entry points take "
@@ -855,6 +853,7 @@ static int rate_fmt(acg_ctx* ctx, int fmt, FirRateArgs* r)
     r->r0 = (unsigned int)(ctx->rate_k % ctx->rate_Q);
     r->nch = g.nch;
     r->decim = g.decim;
+    const float scale = ACG_FIR_GRID_FMT[r->fmt].scale;
     r->scale_long = (float)((double)scale / g.decim);
     r->scale_short = (float)((double)scale / (g.decim - 1));
     acg_fir_rate_plan(r);
@@ -882,19 +881,19 @@ static int rate_windows_fit(const acg_ctx* ctx, size_t nsamples)
 // instantiation the u8 path already has; what the chunks share waits in the context while the call is issued.
 static int launch_fir_rate_chunk(acg_ctx* c, FirArgs& f, hipStream_t st)
 {
-    if (c->long_call) {                                          // a channel filter is on: the same chunk, fir_long.hip's kernel
-        FirLongArgs b = *c->long_call;
+    auto chunk = [&](FirGridArgs& b) {
         b.dm = f.dm;
-        b.win0 = (int)(f.dm - c->d_dm);
+        b.win0 = (int)(f.dm - c->d_dm);                          // the chunk's first window
         b.nwin = f.nwin;
         b.ncu = f.ncu;
+    };
+    if (c->long_call) {                                          // a channel filter is on: the same chunk, fir_long.hip's kernel
+        FirLongArgs b = *c->long_call;
+        chunk(b);
         return acg_launch_fir_long(&b, st);
     }
     FirRateArgs b = *c->rate_call;
-    b.dm = f.dm;
-    b.win0 = (unsigned int)(f.dm - c->d_dm);                     // the chunk's first window
-    b.nwin = f.nwin;
-    b.ncu = f.ncu;
+    chunk(b);
     return acg_launch_fir_rate(&b, st);
 }
 
@@ -916,21 +915,14 @@ static int rate_run(acg_ctx* ctx, FirRateArgs& r, const void* dev, size_t pitch,
         // the call before, on that call's stream: this call's launches wait for it, whatever their stream.
         if (ctx->long_fmt != r.fmt) { ctx->long_fmt = r.fmt; ctx->long_have = 0; }
         if (ctx->long_hist_ev_valid) HIPCHK_OL(ctx, hipStreamWaitEvent(s, ctx->long_hist_ev, 0));
-        l.in = r.in;
-        l.pitch = pitch;
-        l.valid_bytes = r.valid_bytes;
+        static_cast<FirGridArgs&>(l) = r;                        // the same rows, channels and windows
         l.hist = ctx->d_long_hist[ctx->long_hist_cur];
         l.hist_pitch = ctx->long_hist_pitch;
-        l.stream_of = r.stream_of;
         l.taps = ctx->d_long_taps;
         l.tap_pitch = ((size_t)ctx->long_nseg * r.decim + 8) * 2;
-        l.dm_pitch = r.dm_pitch;
-        l.nch = r.nch;
-        l.decim = r.decim;
         l.nseg = ctx->long_nseg;
-        l.fmt = r.fmt;
         l.nprev = ctx->long_have;
-        l.scale = r.fmt == RATE_CU8 ? 1.0f / 127.5f : r.fmt == RATE_CS8 ? 1.0f / 128.0f : r.fmt == RATE_CS16 ? 1.0f / 32768.0f : 1.0f;
+        l.scale = ACG_FIR_GRID_FMT[r.fmt].scale;
         acg_fir_long_plan(&l);
         ctx->long_call = &l;
     }

@@ -16,7 +16,7 @@ over the J M samples of output k.  The worst-case bound for 2 J M products added
 the variant "last tap of each segment omitted" stays under the bar at 16 % of the outputs at M = 320 (test_long_ref.py wants a
 wrong kernel over it at 90 %), so the constant is shortened to what the contract's FIXED order of additions allows.  A product
 passes through as many roundings as there are additions between it and the result (the products are fused, the operands exact):
-  * its wave's accumulator chain: the window's ceil(M b / 16) chunks go through in K slices (csrc/fir_long.h: at most 35 chunks
+  * its wave's accumulator chain: the window's ceil(M b / 16) chunks go through in K slices (csrc/fir_grid.h: at most 35 chunks
     and a third of a CU's LDS each), a wave takes at most ceil(chunks of the slice / 4) of them, so with S samples per chunk the
     chain is at most M / 4 + S / 4 + 3 K S / 4 <= M / 4 + 14 samples long for every format at M <= 320 (K S <= 16: two slices
     of 8-sample chunks for the 1-byte formats, three of 4, five of 2);

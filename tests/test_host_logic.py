@@ -358,6 +358,27 @@ def test_wave_private_launch_plan_keeps_what_the_kernels_assume(tmp_path):
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-2000:]
 
 
+def test_grid_plan_is_the_two_plans_it_replaced(tmp_path):
+    """csrc/fir_grid.h has one launch plan for the rate kernel and the channel filter (fir_rate.hip, fir_long.hip).
+    tests/fir_grid_plan_check.cpp compiles the header for the host, under the address and undefined-behaviour sanitizers, and
+    sweeps decim 2 .. ACG_MAXDECIM_SAMPLES x four formats x nseg 1 .. 4 (1: the rate plan): every plan field and the LDS size
+    equal the literal restatement of the two earlier plans, the slices hold the window, cpr <= 51 (rate) / 35 (filter), the row
+    stride is an odd number of 16-byte slots, ld_magic is the division for every load slot, and the filter's LDS stays within a
+    third of a CU's unless a slice is one chunk."""
+    import shutil
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "a host C++ compiler"
+    exe = str(tmp_path / "fir_grid_plan_check")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] +
+                       ([] if "clang" in os.path.basename(cxx) else ["-static-libasan", "-static-libubsan"]) +      # (clang links them statically anyway)
+                       ["-I" + os.path.join(ROOT, "acarsdec_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, "tests", "fir_grid_plan_check.cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.stdout[-2000:], r.stderr[-2000:])
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-2000:]
+
+
 def test_demodulator_loop_keeps_its_state_in_registers():
     """The demodulator's per-bit loop is one long dependent chain compiled with a recipe (_build.MSK_FLAGS) under which the
     register allocator sits close to a cliff: round 5 added ONE 32-bit field to the state the loop carries and the product
