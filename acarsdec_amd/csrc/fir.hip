@@ -14,6 +14,10 @@
 //     through scalar loads (SGPRs), not VGPRs or LDS;
 //   * the 4 waves split the tap range; partial sums meet in LDS; wave 0 takes |D| and writes 64
 //     consecutive floats of dm.
+// That is the tile family (fir_tile_kernel.h: fir_u8_persist_kernel, fir_u8_shared_kernel, fir_fmt_kernel, and the parts they
+// are made of); the default for whole callbacks at the documented rates is the wave-private streaming family (fir_kernels.h).
+// This unit instantiates both for u8 I/Q and the front ends' sample formats, holds the per-device launch state, the launchers
+// (their grid: fir_plan.h) and the exact-order kernel.
 #include <hip/hip_runtime.h>
 #include <map>
 #include <mutex>
@@ -22,9 +26,10 @@
 #include <type_traits>
 #include "acg_internal.h"
 #include "fir_plan.h"
-#include "fir_kernels.h"        // the kernel templates (shared with fir_iq.hip)
+#include "fir_tile_kernel.h"    // the tile kernels described above, and the parts they are made of ...
+#include "fir_kernels.h"        // ... and the wave-private streaming kernels (both shared with fir_iq.hip)
 
-// (the tap regrouping of the shared-stream kernel: fir_kernels.h, FIR_KC)
+// (the tap regrouping of the shared-stream kernel: fir_tile_kernel.h, FIR_KC)
 __global__ void regroup_taps_kernel(const float* __restrict__ taps, float* __restrict__ gtaps,
                                     const int4* __restrict__ groups, const int* __restrict__ group_ch, int ntaps_pad)
 {
@@ -112,7 +117,6 @@ extern "C" int acg_fir_lds_optin(const void* kernel, size_t bytes)
 extern "C" int acg_launch_fir_fmt(const FirArgs* a, int fmt, void* stream)
 {
     if (fmt == FMT_CF32) return acg_launch_fir_cf32(a, stream);            // the recordings' formats: fir_iq.hip
-    const size_t lds = (size_t)ACG_TILE_WIN * a->row_stride + 4 * 64 * sizeof(float4);
     int num_cu = 0;
     if (int e = acg_fir_device_cus(&num_cu)) return e;
     // the wave-private streaming kernel where it is instantiated for the window length and the launch is whole runs
@@ -125,17 +129,10 @@ extern "C" int acg_launch_fir_fmt(const FirArgs* a, int fmt, void* stream)
         FIRX_LIST(FIRX_TRY)
 #undef FIRX_TRY
     }
-    if (lds > 64 * 1024) return (int)hipErrorInvalidValue;
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 4) per_cu = 4;
-    const long long ntile = (a->nwin + ACG_TILE_WIN - 1) / ACG_TILE_WIN;
-    const long long G = (long long)a->nch * ntile;
-    long long grid = (long long)(a->ncu > 0 ? a->ncu : num_cu) * per_cu;
-    if (grid > G) grid = G;
     switch (fmt) {
-    case FMT_CS16: return launch_fmt<FMT_CS16>(a, grid, lds, (hipStream_t)stream);
-    case FMT_SPLIT: return launch_fmt<FMT_SPLIT>(a, grid, lds, (hipStream_t)stream);
-    case FMT_F32R: return launch_fmt<FMT_F32R>(a, grid, lds, (hipStream_t)stream);
+    case FMT_CS16: return launch_fmt<FMT_CS16>(a, num_cu, (hipStream_t)stream);
+    case FMT_SPLIT: return launch_fmt<FMT_SPLIT>(a, num_cu, (hipStream_t)stream);
+    case FMT_F32R: return launch_fmt<FMT_F32R>(a, num_cu, (hipStream_t)stream);
     }
     return (int)hipErrorInvalidValue;
 }
@@ -175,7 +172,7 @@ __global__ void fir_u8_generic_kernel(const FirArgs a)
 
 extern "C" size_t acg_fir_lds_bytes(const FirArgs* a)
 {
-    return (size_t)ACG_TILE_WIN * a->row_stride + 4 * 64 * sizeof(float4) + 16;
+    return fir_persist_lds(*a);
 }
 
 // wave-private streaming kernel: whole tiles, runs inside one channel, a rate it is instantiated for
@@ -228,12 +225,8 @@ extern "C" int acg_launch_fir(const FirArgs* a, void* stream)
         return launch_mfma<25>(a, num_cu, (hipStream_t)stream);
 #endif
     if ((variant == 5 || (variant >= 50 && variant <= 56)) && acg_fir_u8_wave_takes(a)) {
-        switch (a->cpr) {
-        // (dm is stored write-through: beside the streaming reads a write-back line costs more, DESIGN 4)
-        case 20: return launch_direct<20, 0, 0, true, true>(a, num_cu, (hipStream_t)stream);
-        case 24: return launch_direct<24, 0, 0, true, true>(a, num_cu, (hipStream_t)stream);
-        case 25:
 #ifdef ACG_LAB    // 50..54: measurement knobs (staging slots, burst length, 127.37 per sample)
+        if (a->cpr == 25) {
             if (variant == 50) return launch_direct<25, 10, 1>(a, num_cu, (hipStream_t)stream);
             if (variant == 51) return launch_direct<25, 25, 5>(a, num_cu, (hipStream_t)stream);
             if (variant == 52) return launch_direct<25, 25, 10>(a, num_cu, (hipStream_t)stream);
@@ -241,10 +234,12 @@ extern "C" int acg_launch_fir(const FirArgs* a, void* stream)
             if (variant == 54) return launch_direct<25, 0, 0, false>(a, num_cu, (hipStream_t)stream);      // 127.37 subtracted per sample
             if (variant == 56) return launch_direct<25, 0, 0, true, true, true>(a, num_cu, (hipStream_t)stream);   // measurement: no arithmetic (dm is garbage)
             if (variant == 55) return launch_direct<25>(a, num_cu, (hipStream_t)stream);                    // dm stored write-back (round 2a)
-#endif
-            return launch_direct<25, 0, 0, true, true>(a, num_cu, (hipStream_t)stream);
-        default: break;
         }
+#endif
+        // (dm is stored write-through: beside the streaming reads a write-back line costs more, DESIGN 4)
+#define FIRD_TRY(C_) if (a->cpr == C_) return launch_direct<C_, 0, 0, true, true>(a, num_cu, (hipStream_t)stream);
+        FIRD_LIST(FIRD_TRY)
+#undef FIRD_TRY
     }
 #ifdef ACG_LAB
     if (variant == 0) {
@@ -257,32 +252,18 @@ extern "C" int acg_launch_fir(const FirArgs* a, void* stream)
         const size_t tile = (size_t)ACG_TILE_WIN * a->row_bytes;
         const size_t lds2 = 2 * tile + 2 * 4 * 64 * sizeof(float4) + 16;
         if (lds2 <= 96 * 1024) {
-            int per = (int)((160 * 1024) / lds2);
-            if (per > 4) per = 4;
-            per = env_int("ACG_FIR_WG_PER_CU", per);
-            const long long ntile4 = (a->nwin + ACG_TILE_WIN - 1) / ACG_TILE_WIN;
-            const long long G4 = (long long)a->nch * ntile4;
-            const long long nrun4 = (G4 + FIR_RUN - 1) / FIR_RUN;
-            long long grid4 = (long long)num_cu * per;
-            if (grid4 > nrun4) grid4 = nrun4;
+            const long long grid4 = acg_fir_tile_grid(num_cu, lds2, 4, 0, true, acg_fir_tile_units(a->nch, a->nwin, ACG_TILE_WIN), FIR_RUN);
             FIR_LAUNCH(fir_u8_dma_kernel, dim3((unsigned int)grid4), dim3(ACG_WG_FIR), lds2, (hipStream_t)stream,
                                *a, a->iq, a->taps, a->stream_of, a->dm);
             return (int)hipGetLastError();
         }
     }
 #endif
-    // resident workgroups: LDS-limited (160 KiB per CU), at most 5 (VGPR budget of 4-wave workgroups)
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 5) per_cu = 5;
-    if (a->wg_per_cu > 0 && per_cu > a->wg_per_cu) per_cu = a->wg_per_cu;
-    if (per_cu < 1) per_cu = 1;
-    per_cu = env_int("ACG_FIR_WG_PER_CU", per_cu);
-    const long long ntile = (a->nwin + ACG_TILE_WIN - 1) / ACG_TILE_WIN;
-    const long long G = (long long)a->nch * ntile;
-    long long grid = (long long)(a->ncu > 0 ? a->ncu : num_cu) * per_cu;
-    if (grid > G) grid = G;
     FirArgs b = *a;
 #ifdef ACG_LAB
+    // variants 1 and 2, the static partition: resident workgroups, LDS-limited (160 KiB per CU), at most 5 (VGPR budget of 4-wave
+    // workgroups), one per (channel, tile) at most
+    const long long grid = acg_fir_tile_grid(a->ncu > 0 ? a->ncu : num_cu, lds, 5, a->wg_per_cu, true, acg_fir_tile_units(a->nch, a->nwin, ACG_TILE_WIN));
     const bool nocompute = acg_tune_has("ACG_FIR_DEBUG_NOCOMPUTE") != 0;   // measurement aid: loads + LDS staging only
     if (nocompute) b.ntaps_pad = 0;
     if (variant == 1) {
@@ -296,42 +277,22 @@ extern "C" int acg_launch_fir(const FirArgs* a, void* stream)
         return (int)hipGetLastError();
     }
 #endif
-    const long long nrun = (G + FIR_RUN - 1) / FIR_RUN;
-    if (grid > nrun) grid = nrun;
-    if (G >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    if (a->nwin % ACG_TILE_WIN == 0)      // whole callbacks: every tile is complete
-        FIR_LAUNCH((fir_u8_persist_kernel<true, true, true>), dim3((unsigned int)grid), dim3(ACG_WG_FIR), lds,
-                           (hipStream_t)stream, b, a->iq, a->taps, a->stream_of, a->dm);
-    else
-        FIR_LAUNCH((fir_u8_persist_kernel<true, true, false>), dim3((unsigned int)grid), dim3(ACG_WG_FIR), lds,
-                           (hipStream_t)stream, b, a->iq, a->taps, a->stream_of, a->dm);
-    return (int)hipGetLastError();
+    return launch_persist<false>(b, a, num_cu, (hipStream_t)stream);
 }
 
 extern "C" int acg_launch_fir_shared(const FirArgs* a, void* stream)
 {
-    const size_t lds = (size_t)ACG_TILE_WIN * a->row_stride + 16 * 64 * sizeof(float4) + 16;
+    const size_t lds = fir_shared_lds(*a);
     int num_cu = 0;
     if (int e = acg_fir_device_cus(&num_cu)) return e;
     if (lds > 64 * 1024) return (int)hipErrorInvalidValue;
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 4) per_cu = 4;
-    if (per_cu < 1) per_cu = 1;
-    per_cu = env_int("ACG_FIR_WG_PER_CU", per_cu);
-    const long long ntile = (a->nwin + ACG_TILE_WIN - 1) / ACG_TILE_WIN;
-    const long long G = (long long)a->ngroups * ntile;
-    const long long nrun = (G + FIR_RUN - 1) / FIR_RUN;
-    long long grid = (long long)(a->ncu > 0 ? a->ncu : num_cu) * per_cu;
-    if (grid > nrun) grid = nrun;
+    const long long G = acg_fir_tile_units(a->ngroups, a->nwin, ACG_TILE_WIN);
     if (G >= (1ll << 31)) return (int)hipErrorInvalidValue;
+    // four workgroups per CU at most (the K-channel register block)
+    const long long grid = acg_fir_tile_grid(a->ncu > 0 ? a->ncu : num_cu, lds, 4, 0, true, G, FIR_RUN);
     if (a->s8) return acg_launch_fir_shared_s8(a, grid, lds, stream);      // (fir_iq.hip)
-    if (a->nwin % ACG_TILE_WIN == 0)
-        FIR_LAUNCH(fir_u8_shared_kernel<true>, dim3((unsigned int)grid), dim3(ACG_WG_FIR), lds, (hipStream_t)stream, *a,
-                           a->iq, a->gtaps, a->groups, a->group_ch, a->dm);
-    else
-        FIR_LAUNCH(fir_u8_shared_kernel<false>, dim3((unsigned int)grid), dim3(ACG_WG_FIR), lds, (hipStream_t)stream, *a,
-                           a->iq, a->gtaps, a->groups, a->group_ch, a->dm);
-    return (int)hipGetLastError();
+    return launch_whole_or_ragged(fir_u8_shared_kernel<true>, fir_u8_shared_kernel<false>, a->nwin, grid, lds, (hipStream_t)stream, *a, a->iq, a->gtaps,
+                                  a->groups, a->group_ch, a->dm);
 }
 
 extern "C" int acg_launch_regroup_taps(const FirArgs* a, void* stream)
@@ -362,11 +323,13 @@ extern "C" int acg_fir_choice(const FirArgs* a, int fmt, FirChoice* out)
     int W = 0;
     if (fmt == FMT_CS8) {
         if (variant != 3 && acg_fir_u8_wave_takes(a)) {
-            W = ACG_TILE_WIN;
-            if (a->cpr == 20) p = acg_fir_wave_plan(a, num_cu, FirD<20>::WAVE_LDS, W, 8);
-            else if (a->cpr == 24) p = acg_fir_wave_plan(a, num_cu, FirD<24>::WAVE_LDS, W, 8);
-            else if (a->cpr == 25) p = acg_fir_wave_plan(a, num_cu, FirD<25>::WAVE_LDS, W, 8);
-            else W = 0;
+#define FIRD_PLAN(C_) \
+            if (a->cpr == C_) { \
+                W = ACG_TILE_WIN; \
+                p = acg_fir_wave_plan(a, num_cu, FirD<C_>::WAVE_LDS, W, 8); \
+            }
+            FIRD_LIST(FIRD_PLAN)
+#undef FIRD_PLAN
         }
     } else if (variant >= 5) {
         const int cprw = a->cpr_total;

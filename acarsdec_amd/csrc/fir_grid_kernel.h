@@ -1,8 +1,9 @@
-// fir_grid_kernel.h -- what the kernels of fir_rate.hip and fir_long.hip are both made of.  The siblings of fir_fmt_kernel
-// (fir_kernels.h): a tile of ACG_TILE_WIN windows goes through LDS one padded row per window, lane = window, the four waves split
-// the taps, partial sums meet in LDS, windows longer than a slice go through in column slices; a workgroup walks a static
-// contiguous share of the (channel, tile) space and fetches unit u + 1 into registers while it computes unit u.  What the grid
-// adds is that a row -- a window -- begins at any sample of its stream:
+// fir_grid_kernel.h -- what the kernels of fir_rate.hip and fir_long.hip are both made of, on top of the tile family's common parts
+// (fir_tile_kernel.h; the siblings of its fir_fmt_kernel): a tile of ACG_TILE_WIN windows goes through LDS one padded row per
+// window, lane = window, the four waves split the taps, partial sums meet in LDS, windows longer than a slice go through in column
+// slices; a workgroup walks a static contiguous share of the (channel, tile) space and fetches unit u + 1 into registers while
+// it computes unit u.  The ids, the static share, the slot decode, the wave split, the sample conversions, the multiply-add, the
+// four waves' sum and the launchers' grid are the family's.  What the grid adds is that a row -- a window -- begins at any sample of its stream:
 //   * the rows are fetched in ALIGNED 16-byte non-temporal chunks, per row from its start rounded down to 16 bytes, so a chunk
 //     that two windows share is fetched for both (it hits L2 the second time): one aligned chunk more per row than the window has
 //     (grid_fetch; fir_grid.h's plan counts it);
@@ -19,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include "acg_internal.h"
 #include "fir_grid.h"
-#include "fir_kernels.h"
+#include "fir_tile_kernel.h"
 
 // one row of a tile, as grid_fetch is told of it
 struct GridRow {
@@ -29,10 +30,12 @@ struct GridRow {
     bool exists;                    // a window of the launch (and of the context)
 };
 
-// A workgroup's share of the launch and its walk over it: units (channel ch, tile t, slice k), slices innermost.
-struct GridWalk {
+// A workgroup's share of the launch (the family's static share) and its walk over it: units (channel ch, tile t, slice k), slices
+// innermost.  The walk is SliceWalk's, spelled out: derived from it, fir_long_kernel compiles to other text and its shared-stream
+// arm runs 0.3 % slower, outside the parent's spread (profiles/LEDGER.md, "Tile down-converters on one skeleton").
+struct GridWalk : TileIds {
     const FirGridArgs& a;
-    int tid, lane, wave, ntile;
+    int ntile;
     int cprl, slots, nld;           // aligned chunks loaded per row and slice (one more than it holds), load slots of a slice, per thread
     int win_bytes;
     long long u1;                   // the units of this workgroup
@@ -42,13 +45,9 @@ struct GridWalk {
     // tile_out: outputs per tile; bps: the instantiation's bytes per sample
     __device__ __forceinline__ GridWalk(const FirGridArgs& a_, int tile_out, int bps) : a(a_)
     {
-        tid = threadIdx.x;
-        lane = tid & 63;
-        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         ntile = (a.nwin + tile_out - 1) / tile_out;
-        const long long G = (long long)a.nch * ntile;
-        const long long g0 = G * blockIdx.x / gridDim.x;
-        const long long g1 = G * (blockIdx.x + 1) / gridDim.x;
+        long long g0, g1;
+        tile_static_share((long long)a.nch * ntile, g0, g1);
         cprl = a.cpr + 1;
         slots = ACG_TILE_WIN * cprl;
         nld = (slots + ACG_WG_FIR - 1) / ACG_WG_FIR;
@@ -59,11 +58,7 @@ struct GridWalk {
         k = 0;
     }
     // load slot c of a slice -> its row and its aligned chunk in the row's slice
-    __device__ __forceinline__ void slot(int c, int& r, int& col) const
-    {
-        r = (int)(((unsigned int)c * a.ld_magic) >> 20);
-        col = c - r * cprl;
-    }
+    __device__ __forceinline__ void slot(int c, int& r, int& col) const { tile_slot(c, a.ld_magic, cprl, r, col); }
     // the successor of the unit in LDS (round -1, !live: the first unit itself); true: it begins another tile
     __device__ __forceinline__ bool successor(bool live)
     {
@@ -75,16 +70,14 @@ struct GridWalk {
     }
     __device__ __forceinline__ void advance() { ch = nch, t = nt, k = nk; }
     // this slice's chunks, split over the 4 waves
-    __device__ __forceinline__ void wave_chunks(int& c0, int& c1) const
-    {
-        const int nstep = max(0, min(a.cpr, a.cpr_total - k * a.cpr));
-        c0 = nstep * wave / 4;
-        c1 = nstep * (wave + 1) / 4;
-    }
+    __device__ __forceinline__ void wave_chunks(int& c0, int& c1) const { tile_wave_steps(max(0, min(a.cpr, a.cpr_total - k * a.cpr)), wave, c0, c1); }
 };
 
 // The loads of slice w.nk of the successor's tile into the staging registers; row_of(r) -> GridRow.  A slot is loaded if its row
 // exists and the chunk holds samples of the window and lies inside what may be read; the others stage zeros.
+// (In its own words, not through the family's tile_fetch_slots: with the predicate behind a functor the compiler spills 20 fewer
+// SGPRs and the kernels run 1-3 % slower -- rate-cu8 1.077 -> 1.110 ms, the filter at J = 4 cs16 2.66 -> 2.74 ms; profiles/LEDGER.md,
+// "Tile down-converters on one skeleton".)
 template <int MAXLD, class RowOf>
 __device__ __forceinline__ void grid_fetch(const GridWalk& w, uint4 (&stage)[MAXLD], RowOf row_of)
 {
@@ -152,44 +145,12 @@ __device__ __forceinline__ void grid_read_chunk(const unsigned char* rowp, int c
     }
 }
 
-// sample j of a chunk as (I, Q): BPS 2 the bytes as they are, unsigned (the kernels treat the offset); 4 int16; 8 float32
+// the family's sample conversion, multiply-add and four-wave sum under the names the grid kernels call them by
 template <int BPS>
-__device__ __forceinline__ f2 grid_sample(const unsigned int (&qq)[4], int j)
-{
-    f2 x;
-    if (BPS == 2) {
-        const unsigned int word = qq[j >> 1];
-        const unsigned int sh = (j & 1) * 16;
-        x.x = (float)((word >> sh) & 0xffu);                        // rtl.c:338-339
-        x.y = (float)((word >> (sh + 8)) & 0xffu);
-    } else if (BPS == 4) {
-        x.x = (float)(short)(qq[j] & 0xffffu);                      // soapy.c:238
-        x.y = (float)((int)qq[j] >> 16);                            // soapy.c:239
-    } else {
-        x.x = __uint_as_float(qq[2 * j]);
-        x.y = __uint_as_float(qq[2 * j + 1]);
-    }
-    return x;
-}
-
-// a chunk's samples times the taps tw[SPC][2] into the lane's accumulators (sum r*wr, sum g*wi) and (sum r*wi, sum g*wr)
+__device__ __forceinline__ f2 grid_sample(const unsigned int (&qq)[4], int j) { return tile_sample<BPS>(qq, j); }
 template <int SPC>
-__device__ __forceinline__ void grid_mac(const f2 (&x)[SPC], const float* __restrict__ tw, f2& accA, f2& accB)
-{
-#pragma unroll
-    for (int j = 0; j < SPC; ++j) {
-        accA = __builtin_elementwise_fma(x[j], f2{tw[2 * j], tw[2 * j + 1]}, accA);
-        accB = __builtin_elementwise_fma(x[j], f2{tw[2 * j + 1], tw[2 * j]}, accB);
-    }
-}
-
-// The four waves' partial sums (sum r*wr, sum g*wi, sum r*wi, sum g*wr) of one row, wave_stride float4 apart, as (re, im): per
-// component (w0 + w1) + (w2 + w3), re and im from those
-__device__ __forceinline__ f2 grid_wave_sum(const float4* red, int wave_stride, int row)
-{
-    const float4 r0 = red[row], r1 = red[wave_stride + row], r2 = red[2 * wave_stride + row], r3 = red[3 * wave_stride + row];
-    return {((r0.x + r1.x) + (r2.x + r3.x)) - ((r0.y + r1.y) + (r2.y + r3.y)), ((r0.z + r1.z) + (r2.z + r3.z)) + ((r0.w + r1.w) + (r2.w + r3.w))};
-}
+__device__ __forceinline__ void grid_mac(const f2 (&x)[SPC], const float* __restrict__ tw, f2& accA, f2& accB) { tile_mac(x, tw, accA, accB); }
+__device__ __forceinline__ f2 grid_wave_sum(const float4* red, int wave_stride, int row) { return tile_wave_sum(red, wave_stride, row); }
 
 // The launchers' grid: as many workgroups as stay resident (per_cu_max of them on a CU, or fewer by their LDS), at most one per
 // (channel, tile).
@@ -197,11 +158,6 @@ static inline int grid_resident_blocks(const FirGridArgs* a, size_t lds, int per
 {
     int num_cu = 0;
     if (int e = acg_fir_device_cus(&num_cu)) return e;
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > per_cu_max) per_cu = per_cu_max;
-    const long long ntile = (a->nwin + tile_out - 1) / tile_out;
-    const long long G = (long long)a->nch * ntile;
-    *grid = (long long)(a->ncu > 0 ? a->ncu : num_cu) * per_cu;
-    if (*grid > G) *grid = G;
+    *grid = acg_fir_tile_grid(a->ncu > 0 ? a->ncu : num_cu, lds, per_cu_max, 0, false, acg_fir_tile_units(a->nch, a->nwin, tile_out));
     return 0;
 }

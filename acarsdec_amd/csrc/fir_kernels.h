@@ -1,398 +1,19 @@
-// fir_kernels.h -- the down-converter's kernel templates and the launch helpers its units share.  fir.hip instantiates the u8 I/Q
-// kernels and the front ends' sample formats, fir_iq.hip the recordings' formats (complex int8 on the u8 kernels' signed switch,
-// complex float32 on the format kernels); a template is compiled where it is launched.  Not a unit of its own.
+// fir_kernels.h -- the wave-private streaming down-converter kernels (fir_u8_direct_kernel, fir_s8_direct_kernel,
+// fir_fmt_direct_kernel) and the launch helpers of their units.  fir.hip instantiates the u8 I/Q kernels and the front ends' sample
+// formats, fir_iq.hip the recordings' formats (complex int8 on the u8 kernels' signed switch, complex float32 on the format
+// kernels); a template is compiled where it is launched.  The tile kernels, the fallbacks of every format and window length, are
+// fir_tile_kernel.h; what both families reach is fir_common.h.  Not a unit of its own.
 #ifndef ACG_FIR_KERNELS_H
 #define ACG_FIR_KERNELS_H
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "acg_internal.h"
 #include "fir_plan.h"
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-#define FIR_MAXLD 10   // 64 rows * 640 B (M=320) / 16 B / 256 threads
-#define FIR_RUN 4      // tiles per dynamically scheduled run (>= 2)
-
-extern __shared__ __attribute__((aligned(16))) unsigned char fir_smem[];
-
-// The run dispenser is an atomic whose result is needed a whole tile later.  Written as a compiler
-// intrinsic it is waited for on the spot (it sits in divergent control flow), which stalls the
-// requesting wave -- and at the next barrier the whole workgroup -- for a full device-scope round
-// trip per run.  As inline asm the compiler does not track it; take_ticket() is the matching wait
-// (vmcnt retires in order, and it is called where no newer load is outstanding).
-__device__ __forceinline__ void request_ticket(unsigned int* counter, unsigned int& ticket)
-{
-    const unsigned int one = 1u;
-    asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(ticket) : "v"(counter), "v"(one) : "memory");
-}
-__device__ __forceinline__ unsigned int take_ticket(unsigned int& ticket)
-{
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(ticket) : : "memory");
-    return ticket;
-}
-// The dispenser is two words, {tickets handed out, workgroups finished}, both zero between launches:
-// run ids are gridDim.x + ticket (the first run of a workgroup is its own id), and the last workgroup
-// to leave re-arms the pair, so no memset launch precedes the kernel.  A workgroup's own request has
-// been performed before it signs off (take_ticket), so no ticket atomic can land after the reset.
-__device__ __forceinline__ void dispenser_sign_off(unsigned int* counter, unsigned int& pending)
-{
-    (void)take_ticket(pending);
-    const unsigned int d = atomicAdd(counter + 1, 1u);
-    if (d == gridDim.x - 1) {
-        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(counter + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-
-__device__ __forceinline__ float cabs_like_glibc(float re, float im)
-{
-    // glibc 2.35 cabsf/hypotf == (float)sqrt((double)x*x + (double)y*y) (checked on 2e8 inputs);
-    // products are exact in double, one rounding in the sum, correctly rounded sqrt, one narrowing.
-    double d = (double)re * (double)re + (double)im * (double)im;
-    return (float)__dsqrt_rn(d);
-}
-
-// Persistent variant: the grid is exactly the number of workgroups the chip holds at once and the
-// (channel, tile) space is cut into equal contiguous runs, one per workgroup, so that all workgroups
-// finish together (no partial last wave of workgroups).  A run may cross channel boundaries; the
-// stream/tap base pointers follow.  NT selects non-temporal loads for the input, which is read once.
-// S8: ACG_FMT_CS8's bytes (int8): xor 0x80 per word, then (u8 - 128) is the sample, exactly; |D| / 128.
-// (ACG_FMT_CS8 at the window lengths without a streaming kernel, and its ragged launches from the host feed.)
-template <bool NT, bool DYN, bool FULL, bool S8 = false>
-__global__ __launch_bounds__(ACG_WG_FIR) void fir_u8_persist_kernel(const FirArgs a,
-                                                                     const uint8_t* __restrict__ iq_base,
-                                                                     const float* __restrict__ taps_base,
-                                                                     const int* __restrict__ stream_of,
-                                                                     float* __restrict__ dm_base)
-{
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ntile = (a.nwin + ACG_TILE_WIN - 1) / ACG_TILE_WIN;
-    const long long G = (long long)a.nch * ntile;
-    // static: equal contiguous runs.  dynamic: runs of FIR_RUN tiles handed out by an atomic counter
-    // (zeroed by the launcher), so that workgroups slowed by co-running demodulator waves simply
-    // take fewer runs instead of stretching the kernel's tail.
-    const long long nrun = (G + FIR_RUN - 1) / FIR_RUN;
-    long long run = blockIdx.x;                       // first run: own id (the counter starts at gridDim.x)
-    long long g0 = DYN ? run * FIR_RUN : G * blockIdx.x / gridDim.x;
-    long long g1 = DYN ? (g0 + FIR_RUN < G ? g0 + FIR_RUN : G) : G * (blockIdx.x + 1) / gridDim.x;
-    if (g0 >= g1) return;
-    int* s_next = (int*)(fir_smem + ACG_TILE_WIN * a.row_stride + 4 * 64 * sizeof(float4));
-
-    const int cpr = a.cpr;
-    const int tile_chunks = ACG_TILE_WIN * cpr;
-    const int total_chunks = a.nwin * cpr;
-    const int pad = a.row_stride - a.row_bytes;
-    const unsigned int magic = a.cpr_magic;
-    unsigned char* tileL = fir_smem;
-    float4* red = (float4*)(fir_smem + ACG_TILE_WIN * a.row_stride);
-    const int nck = a.ntaps_pad >> 3;
-    const int c0 = nck * wave / 4;
-    const int c1 = nck * (wave + 1) / 4;
-
-    int ch = (int)(g0 / ntile);
-    int t = (int)(g0 - (long long)ch * ntile);
-    uint4 stage[FIR_MAXLD];
-
-    // A tile is 64*cpr chunks and a wave owns 64 consecutive chunks per pass, so "chunk inside the tile"
-    // is a whole-wave property (wave + 4*i < cpr): scalar branches, no per-lane predicates, and the
-    // address is one uniform base per pass + a per-thread constant offset (global_load ... saddr form:
-    // no vector address arithmetic at all).  FULL = every tile lies completely inside the row
-    // (nwin % 64 == 0, always true for whole callbacks), which removes the last per-lane bound.
-    const unsigned int voff = (unsigned int)tid << 4;
-    const size_t tile_bytes = (size_t)tile_chunks << 4;
-    // the row base follows the channel; looked up only when the channel changes (a dependent scalar
-    // load in front of every tile's loads would leave the workgroup without loads in flight meanwhile)
-    int row_ch = -1;
-    const uint8_t* __restrict__ row_base = iq_base;
-    auto fetch = [&](int fch, int ft) {
-        if (fch != row_ch) {
-            row_base = iq_base + (size_t)stream_of[fch] * a.pitch;
-            row_ch = fch;
-        }
-        const uint8_t* __restrict__ tb = row_base + (size_t)ft * tile_bytes;
-        const int base = ft * tile_chunks;
-        typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int i = 0; i < FIR_MAXLD; ++i) {
-            if (wave + 4 * i < cpr) {
-                if (FULL || base + tid + i * ACG_WG_FIR < total_chunks) {
-                    const u4v* p = (const u4v*)(tb + (size_t)i * (ACG_WG_FIR * 16) + (size_t)voff);
-                    const u4v x = NT ? __builtin_nontemporal_load(p) : *p;
-                    stage[i] = make_uint4(x.x, x.y, x.z, x.w);
-                } else {
-                    stage[i] = make_uint4(0, 0, 0, 0);
-                }
-            }
-        }
-    };
-
-    fetch(ch, t);
-    unsigned int pending_next = 0;        // thread 0: id of the next run (valid one barrier after the request)
-    for (long long g = g0;;) {
-#pragma unroll
-        for (int i = 0; i < FIR_MAXLD; ++i) {
-            if (wave + 4 * i < cpr) {
-                const int c = tid + i * ACG_WG_FIR;
-                const int r = (int)(((unsigned int)c * magic) >> 20);
-                *(uint4*)(tileL + (c << 4) + r * pad) = stage[i];
-            }
-        }
-        if (DYN) {
-            // first tile of a run: ask for the next run; the answer is published at this barrier
-            // one tile later and read when the last tile of the run prefetches across the run boundary
-            if (g == g0 && tid == 0) request_ticket(a.work_counter, pending_next);
-            if (g == g0 + 1 && tid == 0) *s_next = (int)(gridDim.x + take_ticket(pending_next));
-        }
-        __syncthreads();
-
-        // where does the stream go next?
-        int nch_ = ch, nt_ = t + 1;
-        if (nt_ == ntile) { nt_ = 0; ++nch_; }
-        bool more = g + 1 < g1;
-        long long ng0 = g0, ng1 = g1, ng = g + 1;
-        if (DYN && !more) {
-            // (runs are >= 2 tiles except possibly the very last one, which has no successor anyway)
-            const long long nr = (g1 - g0 >= 2) ? (long long)*s_next : nrun;
-            if (nr < nrun) {
-                ng0 = nr * FIR_RUN;
-                ng1 = ng0 + FIR_RUN < G ? ng0 + FIR_RUN : G;
-                ng = ng0;
-                nch_ = (int)((unsigned int)ng0 / (unsigned int)ntile);      // G < 2^31 (launcher)
-                nt_ = (int)((unsigned int)ng0 - (unsigned int)nch_ * (unsigned int)ntile);
-                more = true;
-            }
-        }
-        if (more) fetch(nch_, nt_);
-
-        const float* __restrict__ taps = taps_base + (size_t)ch * a.ntaps_pad * 2;
-        f2 accA = {0.f, 0.f};
-        f2 accB = {0.f, 0.f};
-        const unsigned char* rowp = tileL + lane * a.row_stride;
-        for (int c = c0; c < c1; ++c) {
-            const uint4 q = *(const uint4*)(rowp + (c << 4));
-            const float* __restrict__ w = taps + (c << 4);
-            const unsigned int sx = S8 ? 0x80808080u : 0u;
-            const float off = S8 ? 128.0f : 127.37f;
-            const unsigned int qq[4] = {q.x ^ sx, q.y ^ sx, q.z ^ sx, q.w ^ sx};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const unsigned int word = qq[j >> 1];
-                const unsigned int sh = (j & 1) * 16;
-                f2 tt;
-                tt.x = (float)((word >> sh) & 0xffu) - off;
-                tt.y = (float)((word >> (sh + 8)) & 0xffu) - off;
-                const f2 wv = {w[2 * j], w[2 * j + 1]};
-                const f2 ws = {w[2 * j + 1], w[2 * j]};
-                accA = __builtin_elementwise_fma(tt, wv, accA);
-                accB = __builtin_elementwise_fma(tt, ws, accB);
-            }
-        }
-        red[wave * 64 + lane] = make_float4(accA.x, accA.y, accB.x, accB.y);
-        __syncthreads();
-
-        if (wave == 0) {
-            const float4 r0 = red[lane], r1 = red[64 + lane], r2 = red[128 + lane], r3 = red[192 + lane];
-            const float Dr = ((r0.x + r1.x) + (r2.x + r3.x)) - ((r0.y + r1.y) + (r2.y + r3.y));
-            const float Di = ((r0.z + r1.z) + (r2.z + r3.z)) + ((r0.w + r1.w) + (r2.w + r3.w));
-            const int m = t * ACG_TILE_WIN + lane;
-            if (m < a.nwin) dm_base[(size_t)ch * a.dm_pitch + m] = S8 ? cabs_like_glibc(Dr, Di) * (1.0f / 128.0f) : cabs_like_glibc(Dr, Di);             // rtl.c:353
-        }
-        if (!more) break;
-        ch = nch_;
-        t = nt_;
-        g = ng;
-        g0 = ng0;
-        g1 = ng1;
-    }
-    if (DYN && tid == 0) dispenser_sign_off(a.work_counter, pending_next);
-}
-
-// Shared-stream variant -- rtl.c's own shape: one dongle's stream feeds several channels (up to 16,
-// acarsdec.h:30).  A work unit is (group of <= FIR_KC channels of ONE stream, tile): the tile is loaded
-// and converted u8 -> f32 once and every channel of the group takes its taps to the same registers.
-// Per 8 complex samples: 1 ds_read_b128 + 24 conversion ops shared, 16 v_pk_fma_f32 per channel, so the
-// kernel is VALU-bound at (2 + 3/K) lane-ops per channel-sample instead of HBM/fabric-bound at 5.
-// The arithmetic per channel (tap split over the 4 waves, reduction order) is that of
-// fir_u8_persist_kernel: both give bit-identical dm.  Partial sums meet in LDS four channels at a
-// time; wave w finishes channel 4r + w.  Dynamic run dispenser as above.
-// Taps come from a regrouped copy of the tap table, [group][8-sample step][channel of the group][16 floats]
-// (regroup_taps_kernel), so that one scalar base + immediate offsets reaches all channels of a step.
-#define FIR_KC 8
-
-// S8: ACG_FMT_CS8 with several channels per stream where the matrix kernel does not take the launch (or ACG_FIR_MM=0).
-template <bool FULL, bool S8 = false>
-__global__ __launch_bounds__(ACG_WG_FIR) void fir_u8_shared_kernel(const FirArgs a,
-                                                                    const uint8_t* __restrict__ iq_base,
-                                                                    const float* __restrict__ taps_base,
-                                                                    const int4* __restrict__ groups,
-                                                                    const int* __restrict__ group_ch,
-                                                                    float* __restrict__ dm_base)
-{
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ntile = (a.nwin + ACG_TILE_WIN - 1) / ACG_TILE_WIN;
-    const long long G = (long long)a.ngroups * ntile;
-    const long long nrun = (G + FIR_RUN - 1) / FIR_RUN;
-    long long g0 = (long long)blockIdx.x * FIR_RUN;
-    long long g1 = g0 + FIR_RUN < G ? g0 + FIR_RUN : G;
-    if (g0 >= g1) return;
-    int* s_next = (int*)(fir_smem + ACG_TILE_WIN * a.row_stride + 16 * 64 * sizeof(float4));
-
-    const int cpr = a.cpr;
-    const int tile_chunks = ACG_TILE_WIN * cpr;
-    const int total_chunks = a.nwin * cpr;
-    const int pad = a.row_stride - a.row_bytes;
-    const unsigned int magic = a.cpr_magic;
-    unsigned char* tileL = fir_smem;
-    float4* red = (float4*)(fir_smem + ACG_TILE_WIN * a.row_stride);      // [4 channels][4 waves][64]
-    const int nck = a.ntaps_pad >> 3;
-    const int c0 = nck * wave / 4;
-    const int c1 = nck * (wave + 1) / 4;
-
-    int grp = (int)(g0 / ntile);
-    int t = (int)(g0 - (long long)grp * ntile);
-    uint4 stage[FIR_MAXLD];
-
-    // wave-granular tile loads from one uniform base per pass, as in fir_u8_persist_kernel
-    const unsigned int voff = (unsigned int)tid << 4;
-    const size_t tile_bytes = (size_t)tile_chunks << 4;
-    int row_grp = -1;
-    const uint8_t* __restrict__ row_base = iq_base;
-    auto fetch = [&](int fgrp, int ft) {
-        if (fgrp != row_grp) {
-            row_base = iq_base + (size_t)groups[fgrp].x * a.pitch;
-            row_grp = fgrp;
-        }
-        const uint8_t* __restrict__ tb = row_base + (size_t)ft * tile_bytes;
-        const int base = ft * tile_chunks;
-        typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int i = 0; i < FIR_MAXLD; ++i) {
-            if (wave + 4 * i < cpr) {
-                if (FULL || base + tid + i * ACG_WG_FIR < total_chunks) {
-                    const u4v x = __builtin_nontemporal_load((const u4v*)(tb + (size_t)i * (ACG_WG_FIR * 16) + (size_t)voff));
-                    stage[i] = make_uint4(x.x, x.y, x.z, x.w);
-                } else {
-                    stage[i] = make_uint4(0, 0, 0, 0);
-                }
-            }
-        }
-    };
-
-    fetch(grp, t);
-    unsigned int pending_next = 0;
-    for (long long g = g0;;) {
-#pragma unroll
-        for (int i = 0; i < FIR_MAXLD; ++i) {
-            if (wave + 4 * i < cpr) {
-                const int c = tid + i * ACG_WG_FIR;
-                const int r = (int)(((unsigned int)c * magic) >> 20);
-                *(uint4*)(tileL + (c << 4) + r * pad) = stage[i];
-            }
-        }
-        if (g == g0 && tid == 0) request_ticket(a.work_counter, pending_next);
-        if (g == g0 + 1 && tid == 0) *s_next = (int)(gridDim.x + take_ticket(pending_next));
-        __syncthreads();
-
-        int ngrp = grp, nt_ = t + 1;
-        if (nt_ == ntile) { nt_ = 0; ++ngrp; }
-        bool more = g + 1 < g1;
-        long long ng0 = g0, ng1 = g1, ng = g + 1;
-        if (!more) {
-            const long long nr = (g1 - g0 >= 2) ? (long long)*s_next : nrun;
-            if (nr < nrun) {
-                ng0 = nr * FIR_RUN;
-                ng1 = ng0 + FIR_RUN < G ? ng0 + FIR_RUN : G;
-                ng = ng0;
-                ngrp = (int)((unsigned int)ng0 / (unsigned int)ntile);      // G < 2^31 (launcher)
-                nt_ = (int)((unsigned int)ng0 - (unsigned int)ngrp * (unsigned int)ntile);
-                more = true;
-            }
-        }
-        if (more) fetch(ngrp, nt_);
-
-        const int4 gi = groups[grp];                                        // wave-uniform
-        const int kc = gi.z;
-        const float* __restrict__ gt = taps_base + (size_t)gi.y * a.ntaps_pad * 2;
-        f2 accA[FIR_KC], accB[FIR_KC];
-#pragma unroll
-        for (int k = 0; k < FIR_KC; ++k) {
-            accA[k] = {0.f, 0.f};
-            accB[k] = {0.f, 0.f};
-        }
-        const unsigned char* rowp = tileL + lane * a.row_stride;
-        auto taps_pass = [&](auto full) {
-            constexpr bool ALLK = decltype(full)::value;
-            const int kcc = ALLK ? FIR_KC : kc;
-            for (int c = c0; c < c1; ++c) {
-                const float* __restrict__ wc = gt + (size_t)(c * kcc) * 16;
-                const uint4 q = *(const uint4*)(rowp + (c << 4));
-                const unsigned int sx = S8 ? 0x80808080u : 0u;          // ACG_FMT_CS8: int8 -> the sample + 128 as u8
-                const float off = S8 ? 128.0f : 127.37f;
-                const unsigned int qq[4] = {q.x ^ sx, q.y ^ sx, q.z ^ sx, q.w ^ sx};
-                f2 x[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const unsigned int word = qq[j >> 1];
-                    const unsigned int sh = (j & 1) * 16;
-                    x[j].x = (float)((word >> sh) & 0xffu) - off;
-                    x[j].y = (float)((word >> (sh + 8)) & 0xffu) - off;
-                }
-#pragma unroll
-                for (int k = 0; k < FIR_KC; ++k) {
-                    if (ALLK || k < kc) {
-                        const float* __restrict__ w = wc + k * 16;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const f2 wv = {w[2 * j], w[2 * j + 1]};
-                            const f2 ws = {w[2 * j + 1], w[2 * j]};
-                            accA[k] = __builtin_elementwise_fma(x[j], wv, accA[k]);
-                            accB[k] = __builtin_elementwise_fma(x[j], ws, accB[k]);
-                        }
-                    }
-                }
-            }
-        };
-        if (kc == FIR_KC) taps_pass(std::true_type{});
-        else taps_pass(std::false_type{});
-
-        const int m = t * ACG_TILE_WIN + lane;
-#pragma unroll
-        for (int r = 0; r < FIR_KC / 4; ++r) {
-            if (4 * r < kc) {                                               // uniform
-                if (r > 0) __syncthreads();                                 // round r-1's reads are done
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk)
-                    red[(kk * 4 + wave) * 64 + lane] = make_float4(accA[4 * r + kk].x, accA[4 * r + kk].y,
-                                                                   accB[4 * r + kk].x, accB[4 * r + kk].y);
-                __syncthreads();
-                if (4 * r + wave < kc) {
-                    const float4* rr = red + (wave * 4) * 64 + lane;
-                    const float4 r0 = rr[0], r1 = rr[64], r2 = rr[128], r3 = rr[192];
-                    const float Dr = ((r0.x + r1.x) + (r2.x + r3.x)) - ((r0.y + r1.y) + (r2.y + r3.y));
-                    const float Di = ((r0.z + r1.z) + (r2.z + r3.z)) + ((r0.w + r1.w) + (r2.w + r3.w));
-                    const int mych = group_ch[gi.y + 4 * r + wave];          // wave-uniform
-                    if (m < a.nwin) dm_base[(size_t)mych * a.dm_pitch + m] = S8 ? cabs_like_glibc(Dr, Di) * (1.0f / 128.0f) : cabs_like_glibc(Dr, Di);
-                }
-            }
-        }
-        if (!more) break;
-        grp = ngrp;
-        t = nt_;
-        g = ng;
-        g0 = ng0;
-        g1 = ng1;
-    }
-    if (tid == 0) dispenser_sign_off(a.work_counter, pending_next);
-}
+#include "fir_common.h"
 
 // ---------------------------------------------------------------------------------------------------
 // Wave-private streaming variant -- the default for whole callbacks at the documented rates
-// (rtlMult 160 / 192 / 200, rtl.c:244-262).  What the workgroup-granular kernels above pay for is
+// (rtlMult 160 / 192 / 200, rtl.c:244-262).  What the workgroup-granular kernels (fir_tile_kernel.h) pay for is
 // structure, not arithmetic: two barriers per tile, a partial-sum exchange between the four
 // waves and a single finishing wave.  Here a wave owns its tiles outright and never talks to another wave:
 //   * the input never passes through LDS: a tile (64 windows x 2M bytes = CPR KiB, contiguous in HBM) is
@@ -496,24 +117,8 @@ struct RunDisp {
     }
 };
 
-// The ticket for the run after the current one is requested by lane 0 a whole tile before it is looked at.
-// As a compiler builtin the atomic is waited for on the spot (the uniform-address atomic optimiser wants
-// its result at once); as inline asm the compiler does not know about it.  Returns are in issue order, so
-// once at most `younger` vector-memory operations are outstanding the (older) atomic has returned:
-// ticket_take waits for exactly that and costs nothing when U later loads have long been consumed.
-// tests/test_host_logic.py disassembles the kernel and checks that nothing touches the ticket register
-// between the two statements.
-__device__ __forceinline__ void ticket_request(unsigned int* counter, unsigned int& ticket)
-{
-    const unsigned int one = 1u;
-    asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(ticket) : "v"(counter), "v"(one) : "memory");
-}
-template <int YOUNGER>
-__device__ __forceinline__ unsigned int ticket_take(unsigned int& ticket)
-{
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(ticket) : "i"(YOUNGER) : "memory");
-    return (unsigned int)__builtin_amdgcn_readfirstlane((int)ticket);
-}
+// (the ticket for the run after the current one is requested by lane 0 a whole tile before it is looked at: ticket_request /
+//  ticket_take, fir_common.h; the U loads and the store in flight are all younger than it)
 
 // one tile: CPR steps.  A step is fenced off from its neighbours with scheduling barriers -- left alone, the scheduler
 // delays the loads to shorten live ranges (the pipeline then runs dry at the end of a tile) or bunches them up at
@@ -704,7 +309,7 @@ __device__ __forceinline__ void fird_body(const FirArgs& a, const uint8_t* __res
             const uint8_t* nbase = base + run_bytes;                // the next body of this run ...
             if (j + 1 == pairs) {                                   // ... or the first body of the next run
                 // (U loads and a store are in flight, all younger than the ticket)
-                nrun_ = disp.run_of_ticket(s, ticket_take<F::U + 1>(tk));
+                nrun_ = disp.run_of_ticket(s, (unsigned int)__builtin_amdgcn_readfirstlane((int)ticket_take<F::U + 1>(tk)));
                 if (nrun_ == NONE) nrun_ = disp.probe_after(s);
                 has_next = nrun_ != NONE;
                 nbase = base;
@@ -747,196 +352,6 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_s8_direct_kernel(const FirArgs
                                                                     float* __restrict__ dm_base)
 {
     fird_body<CPR, 0, 0, true, true, false, true>(a, iq_base, taps_base, stream_of, dm_base);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The other front ends' sample formats: same tile scheme, 4 bytes per input sample (FMT_CF32: 8).
-//   FMT_CS16   interleaved int16 I,Q        soapy.c:238-241   (x/32768 folded into the output scale)
-//   FMT_SPLIT  int16 I plane + int16 Q plane sdrplay.c:219-223 (cabsf(D)/4 = output scale)
-//   FMT_F32R   real float32 samples          air.c:314-324     (complex tap x real sample)
-//   FMT_CF32   interleaved float32 I,Q       soapy.c:232-254's loop on floats (SigMF cf32_le, SoapySDR CF32; scale 1)
-// (FMT_CS8 = 4, interleaved int8 I,Q, runs on the u8 kernels' signed twins above: its window is the u8 window.)
-// A row (one window) is 4*M bytes in LDS (FMT_CF32: 8*M); for FMT_SPLIT it is [I half | Q half]; windows longer than
-// 52 chunks go through LDS in column slices.  Static contiguous partition of the (channel, tile)
-// space, non-temporal loads, taps through scalar loads.
-#define FMT_CS16 1
-#define FMT_SPLIT 2
-#define FMT_F32R 3
-#define FMT_CS8 4
-#define FMT_CF32 5
-#define FMT_MAXLD 14   // 64 rows * 52 chunks (one slice) / 256 threads
-
-template <int FMT>
-__global__ __launch_bounds__(ACG_WG_FIR) void fir_fmt_kernel(const FirArgs a,
-                                                              const uint8_t* __restrict__ in_base,
-                                                              const float* __restrict__ taps_base,
-                                                              const int* __restrict__ stream_of,
-                                                              float* __restrict__ dm_base)
-{
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ntile = (a.nwin + ACG_TILE_WIN - 1) / ACG_TILE_WIN;
-    const long long G = (long long)a.nch * ntile;
-    const long long g0 = G * blockIdx.x / gridDim.x;
-    const long long g1 = G * (blockIdx.x + 1) / gridDim.x;
-    if (g0 >= g1) return;
-
-    // A window longer than 52 chunks (Airspy: 480 / 800 samples) passes through LDS in K column
-    // slices of cpr chunks; the partial sums stay in registers across the slices of one tile.
-    const int K = a.kseg;
-    const int cpr = a.cpr;                              // 16-byte chunks per LDS row (one slice)
-    const int half = cpr >> 1;                          // FMT_SPLIT: chunks per plane row (K == 1)
-    const int tile_chunks = ACG_TILE_WIN * cpr;
-    const int pad = a.row_stride - (cpr << 4);
-    const unsigned int magic = a.cpr_magic;
-    unsigned char* tileL = fir_smem;
-    float4* red = (float4*)(fir_smem + ACG_TILE_WIN * a.row_stride);
-    constexpr int SPC = (FMT == FMT_SPLIT) ? 8 : (FMT == FMT_CF32) ? 2 : 4;     // samples (taps) per inner step
-    const int nstep_total = a.ntaps_pad / SPC;
-    const int nld = (tile_chunks + ACG_WG_FIR - 1) / ACG_WG_FIR;
-
-    int ch = (int)(g0 / ntile);
-    int t = (int)(g0 - (long long)ch * ntile);
-    int k = 0;
-    uint4 stage[FMT_MAXLD];
-
-    auto fetch = [&](int fch, int ft, int fk) {
-        const uint8_t* __restrict__ src = in_base + (size_t)stream_of[fch] * a.pitch;
-        typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-        const int col0 = fk * cpr;
-#pragma unroll
-        for (int i = 0; i < FMT_MAXLD; ++i) {
-            if (i < nld) {
-                const int c = tid + i * ACG_WG_FIR;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (c < tile_chunks) {
-                    const int r = (int)(((unsigned int)c * magic) >> 20);
-                    const int col = c - r * cpr;
-                    const int win = ft * ACG_TILE_WIN + r;
-                    if (win < a.nwin && col0 + col < a.cpr_total) {
-                        size_t off;
-                        if (FMT == FMT_SPLIT)           // I plane, then Q plane a.plane bytes further
-                            off = (col < half) ? (size_t)win * (a.row_bytes >> 1) + ((size_t)col << 4)
-                                               : a.plane + (size_t)win * (a.row_bytes >> 1) + ((size_t)(col - half) << 4);
-                        else
-                            off = (size_t)win * a.row_bytes + ((size_t)(col0 + col) << 4);
-                        const u4v x = __builtin_nontemporal_load((const u4v*)(src + off));
-                        v = make_uint4(x.x, x.y, x.z, x.w);
-                    }
-                }
-                stage[i] = v;
-            }
-        }
-    };
-
-    f2 accA = {0.f, 0.f};       // CS16/SPLIT: (sum r*wr, sum g*wi)   F32R: (sum s*wr, sum s*wi)
-    f2 accB = {0.f, 0.f};       // CS16/SPLIT: (sum r*wi, sum g*wr)
-    const long long u1 = (g1 - g0) * K;
-    fetch(ch, t, 0);
-    for (long long u = 0; u < u1; ++u) {
-#pragma unroll
-        for (int i = 0; i < FMT_MAXLD; ++i) {
-            if (i < nld) {
-                const int c = tid + i * ACG_WG_FIR;
-                if (c < tile_chunks) {
-                    const int r = (int)(((unsigned int)c * magic) >> 20);
-                    *(uint4*)(tileL + (c << 4) + r * pad) = stage[i];
-                }
-            }
-        }
-        __syncthreads();
-        int nch_ = ch, nt_ = t, nk_ = k + 1;
-        if (nk_ == K) {
-            nk_ = 0;
-            if (++nt_ == ntile) { nt_ = 0; ++nch_; }
-        }
-        if (u + 1 < u1) fetch(nch_, nt_, nk_);
-
-        // this slice's inner steps, split over the 4 waves
-        const int nstep = (FMT == FMT_SPLIT) ? nstep_total : max(0, min(cpr, nstep_total - k * cpr));
-        const int c0 = nstep * wave / 4;
-        const int c1 = nstep * (wave + 1) / 4;
-        const float* __restrict__ taps = taps_base + (size_t)ch * a.ntaps_pad * 2 + (size_t)k * cpr * SPC * 2;
-        const unsigned char* rowp = tileL + lane * a.row_stride;
-        for (int c = c0; c < c1; ++c) {
-            const float* __restrict__ w = taps + c * SPC * 2;                  // wave-uniform
-            if (FMT == FMT_CS16) {
-                const uint4 q = *(const uint4*)(rowp + (c << 4));
-                const unsigned int qq[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f2 tt;
-                    tt.x = (float)(short)(qq[j] & 0xffffu);                    // soapy.c:238
-                    tt.y = (float)((int)qq[j] >> 16);                          // soapy.c:239
-                    const f2 wv = {w[2 * j], w[2 * j + 1]};
-                    const f2 ws = {w[2 * j + 1], w[2 * j]};
-                    accA = __builtin_elementwise_fma(tt, wv, accA);
-                    accB = __builtin_elementwise_fma(tt, ws, accB);
-                }
-            } else if (FMT == FMT_SPLIT) {
-                const uint4 qi = *(const uint4*)(rowp + (c << 4));
-                const uint4 qq_ = *(const uint4*)(rowp + ((c + half) << 4));
-                const unsigned int xi[4] = {qi.x, qi.y, qi.z, qi.w};
-                const unsigned int xq[4] = {qq_.x, qq_.y, qq_.z, qq_.w};
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    f2 tt;
-                    tt.x = (j & 1) ? (float)((int)xi[j >> 1] >> 16) : (float)(short)(xi[j >> 1] & 0xffffu);   // sdrplay.c:219
-                    tt.y = (j & 1) ? (float)((int)xq[j >> 1] >> 16) : (float)(short)(xq[j >> 1] & 0xffffu);   // sdrplay.c:220
-                    const f2 wv = {w[2 * j], w[2 * j + 1]};
-                    const f2 ws = {w[2 * j + 1], w[2 * j]};
-                    accA = __builtin_elementwise_fma(tt, wv, accA);
-                    accB = __builtin_elementwise_fma(tt, ws, accB);
-                }
-            } else if (FMT == FMT_CF32) {
-                const float4 q = *(const float4*)(rowp + (c << 4));
-                const float sv[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const f2 tt = {sv[2 * j], sv[2 * j + 1]};                  // soapy.c:238-239 without the conversion
-                    const f2 wv = {w[2 * j], w[2 * j + 1]};
-                    const f2 ws = {w[2 * j + 1], w[2 * j]};
-                    accA = __builtin_elementwise_fma(tt, wv, accA);
-                    accB = __builtin_elementwise_fma(tt, ws, accB);
-                }
-            } else {
-                const float4 q = *(const float4*)(rowp + (c << 4));
-                const float sv[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f2 tt = {sv[j], sv[j]};                              // air.c:315-316: wf[i] * S
-                    const f2 wv = {w[2 * j], w[2 * j + 1]};
-                    accA = __builtin_elementwise_fma(tt, wv, accA);
-                }
-            }
-        }
-        if (nk_ == 0) {                                 // last slice of this tile: reduce the 4 waves, emit |D|
-            red[wave * 64 + lane] = make_float4(accA.x, accA.y, accB.x, accB.y);
-            accA = {0.f, 0.f};
-            accB = {0.f, 0.f};
-            __syncthreads();
-            if (wave == 0) {
-                const float4 r0 = red[lane], r1 = red[64 + lane], r2 = red[128 + lane], r3 = red[192 + lane];
-                float Dr, Di;
-                if (FMT == FMT_F32R) {
-                    Dr = (r0.x + r1.x) + (r2.x + r3.x);
-                    Di = (r0.y + r1.y) + (r2.y + r3.y);
-                } else {
-                    Dr = ((r0.x + r1.x) + (r2.x + r3.x)) - ((r0.y + r1.y) + (r2.y + r3.y));
-                    Di = ((r0.z + r1.z) + (r2.z + r3.z)) + ((r0.w + r1.w) + (r2.w + r3.w));
-                }
-                const int m = t * ACG_TILE_WIN + lane;
-                // power-of-two output scale (1/32768 soapy.c:241, 1/4 sdrplay.c:225): exact, commutes with cabsf
-                if (m < a.nwin) dm_base[(size_t)ch * a.dm_pitch + m] = cabs_like_glibc(Dr, Di) * a.out_scale;
-            }
-        } else {
-            __syncthreads();                            // the slice in LDS is overwritten next round
-        }
-        ch = nch_;
-        t = nt_;
-        k = nk_;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1190,7 +605,7 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_fmt_direct_kernel(const FirArg
             // second tile of the body: where does the stream go next -- the next body of this run, or the next run's first
             const uint8_t* nbase = base + run_bytes;
             if (j + 1 == pairs) {
-                nrun_ = disp.run_of_ticket(s, ticket_take<F::NLD * F::U + 1>(tk));
+                nrun_ = disp.run_of_ticket(s, (unsigned int)__builtin_amdgcn_readfirstlane((int)ticket_take<F::NLD * F::U + 1>(tk)));
                 if (nrun_ == NONE) nrun_ = disp.probe_after(s);
                 has_next = nrun_ != NONE;
                 nbase = base;
@@ -1215,17 +630,6 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_fmt_direct_kernel(const FirArg
 }
 
 // ---- launch helpers ----------------------------------------------------------------------------------------------------
-#define FIR_LAUNCH(K_, grid_, blk_, lds_, stream_, ...)                                            \
-    do {                                                                                           \
-        if (int oe_ = acg_fir_lds_optin((const void*)(K_), (size_t)(lds_))) return oe_;            \
-        hipLaunchKernelGGL((K_), grid_, blk_, lds_, stream_, __VA_ARGS__);                         \
-    } while (0)
-
-// measurement / layout switches: one table, filled from the environment once per process (acg_api.cpp)
-extern "C" int acg_tune_get(const char* name, int dflt);
-extern "C" int acg_tune_has(const char* name);
-static inline int env_int(const char* name, int dflt) { return acg_tune_get(name, dflt); }
-
 // a wave-private kernel's launch: the plan's shape (fir_plan.h), its run length in the arguments
 typedef void (*FirWaveKernel)(const FirArgs, const uint8_t*, const float*, const int*, float*);
 static inline int launch_planned(FirWaveKernel kernel, const FirWavePlan& p, const FirArgs& a, hipStream_t stream)
@@ -1244,14 +648,8 @@ static int launch_fmt_direct(const FirArgs* a, int num_cu, hipStream_t stream)
     return launch_planned(fir_fmt_direct_kernel<FMT, CPR, W>, p, *a, stream);
 }
 
-// the workgroup-granular format kernel
-template <int FMT>
-static int launch_fmt(const FirArgs* a, long long grid, size_t lds, hipStream_t stream)
-{
-    FIR_LAUNCH(fir_fmt_kernel<FMT>, dim3((unsigned int)grid), dim3(ACG_WG_FIR), lds, stream, *a, a->iq, a->taps, a->stream_of, a->dm);
-    return (int)hipGetLastError();
-}
-
+// the window lengths fir_u8_direct_kernel and fir_s8_direct_kernel are instantiated for: 16-byte chunks per window (rtlMult 160 / 192 / 200)
+#define FIRD_LIST(X) X(20) X(24) X(25)
 // the instantiations of fir_fmt_direct_kernel: (format, chunks per window and plane, windows per tile)
 #define FIRX_LIST(X) \
     X(FMT_CS16, 40, 32) X(FMT_CS16, 48, 32) X(FMT_CS16, 50, 32) \
@@ -1259,23 +657,5 @@ static int launch_fmt(const FirArgs* a, long long grid, size_t lds, hipStream_t 
     X(FMT_SPLIT, 20, 64)
 // ... and the recordings' (fir_iq.hip launches these)
 #define FIRX_LIST_IQ(X) X(FMT_CF32, 80, 16) X(FMT_CF32, 96, 16) X(FMT_CF32, 100, 16)
-
-// the workgroup-granular kernel's grid as acg_launch_fir sizes it (the signed twin's launch in fir_iq.hip takes the same)
-static inline int persist_grid(const FirArgs* a, size_t lds, int num_cu, long long* grid_out)
-{
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 5) per_cu = 5;
-    if (a->wg_per_cu > 0 && per_cu > a->wg_per_cu) per_cu = a->wg_per_cu;
-    if (per_cu < 1) per_cu = 1;
-    per_cu = env_int("ACG_FIR_WG_PER_CU", per_cu);
-    const long long ntile = (a->nwin + ACG_TILE_WIN - 1) / ACG_TILE_WIN;
-    const long long G = (long long)a->nch * ntile;
-    const long long nrun = (G + FIR_RUN - 1) / FIR_RUN;
-    long long grid = (long long)(a->ncu > 0 ? a->ncu : num_cu) * per_cu;
-    if (grid > nrun) grid = nrun;
-    if (G >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    *grid_out = grid;
-    return 0;
-}
 
 #endif /* ACG_FIR_KERNELS_H */

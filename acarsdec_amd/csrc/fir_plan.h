@@ -68,4 +68,27 @@ static inline bool acg_fir_fmt_wave_takes(const FirArgs* a, int tile_win)
     return a->nwin > 0 && (long long)a->nch * a->nwin < (1ll << 31) && a->nwin % (tile_win * FIRD_R) == 0;
 }
 
+// ---- the tile kernels (fir_tile_kernel.h, fir_grid_kernel.h): a grid of resident workgroups ------------------------------------
+// the (unit, tile) space of a launch: nunits channels or groups, tiles of tile_out outputs
+static inline long long acg_fir_tile_units(int nunits, int nwin, int tile_out)
+{
+    return (long long)nunits * ((nwin + tile_out - 1) / tile_out);
+}
+
+// As many workgroups as stay resident: on each of `cus` CUs (the context's partition, else the device's) what the LDS bytes of a
+// workgroup allow, `cap` at most (the kernel's VGPR budget), and no more than there are runs of `run` units.  tunable: the u8
+// kernels' -- the context's wg_per_cu (0: none) bounds it too, never below one, and ACG_FIR_WG_PER_CU overrides the lot.
+static inline long long acg_fir_tile_grid(int cus, size_t lds, int cap, int wg_per_cu, bool tunable, long long units, int run = 1)
+{
+    int per_cu = (int)(FIR_CU_LDS / lds);
+    if (per_cu > cap) per_cu = cap;
+    if (tunable) {
+        if (wg_per_cu > 0 && per_cu > wg_per_cu) per_cu = wg_per_cu;
+        if (per_cu < 1) per_cu = 1;
+        per_cu = acg_tune_get("ACG_FIR_WG_PER_CU", per_cu);
+    }
+    const long long grid = (long long)cus * per_cu, nrun = (units + run - 1) / run;
+    return grid > nrun ? nrun : grid;
+}
+
 #endif /* ACG_FIR_PLAN_H */

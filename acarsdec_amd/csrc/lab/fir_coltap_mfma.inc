@@ -244,7 +244,7 @@ __device__ __forceinline__ void firc_body(const FirArgs& a, const uint8_t* __res
             const uint8_t* nbase = base + run_bytes;                // the next body of this run ...
             if (j + 1 == pairs) {                                   // ... or the first body of the next run
                 // (U loads and a store are in flight, all younger than the ticket)
-                nrun_ = disp.run_of_ticket(s, ticket_take<F::U + 1>(tk));
+                nrun_ = disp.run_of_ticket(s, (unsigned int)__builtin_amdgcn_readfirstlane((int)ticket_take<F::U + 1>(tk)));
                 if (nrun_ == NONE) nrun_ = disp.probe_after(s);
                 has_next = nrun_ != NONE;
                 nbase = base;

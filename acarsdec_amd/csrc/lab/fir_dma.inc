@@ -4,36 +4,26 @@
 // LDS-DMA variant (rows that are an odd number of 16-byte slots, e.g. M = 200: no padding needed, so the
 // LDS image of a tile is the linear image of its bytes in HBM).  `global_load_lds_dwordx4 ... nt` moves
 // 1 KiB per wave-instruction straight into LDS: no staging VGPRs, no ds_write pass, one barrier per
-// tile.  Two tile buffers: the DMA of tile t+1 lands while tile t is computed.  Same run dispenser as
-// the register-staged kernel.  LDS: 2 tiles + 2 reduction buffers -> 2 workgroups per CU.
+// tile.  Two tile buffers: the DMA of tile t+1 lands while tile t is computed.  The run walk of
+// the register-staged kernel (RunWalk).  LDS: 2 tiles + 2 reduction buffers -> 2 workgroups per CU.
 __global__ __launch_bounds__(ACG_WG_FIR) void fir_u8_dma_kernel(const FirArgs a,
                                                                  const uint8_t* __restrict__ iq_base,
                                                                  const float* __restrict__ taps_base,
                                                                  const int* __restrict__ stream_of,
                                                                  float* __restrict__ dm_base)
 {
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ntile = (a.nwin + ACG_TILE_WIN - 1) / ACG_TILE_WIN;
-    const long long G = (long long)a.nch * ntile;
-    const long long nrun = (G + FIR_RUN - 1) / FIR_RUN;
-    long long g0 = (long long)blockIdx.x * FIR_RUN;
-    long long g1 = g0 + FIR_RUN < G ? g0 + FIR_RUN : G;
-    if (g0 >= g1) return;
-
+    const TileIds id;
+    const int lane = id.lane, wave = id.wave;
     const int cpr = a.cpr;                               // odd
     const int tile_bytes = ACG_TILE_WIN * a.row_bytes;   // = cpr KiB
     const int total_chunks = a.nwin * cpr;
     unsigned char* buf0 = fir_smem;
     float4* red = (float4*)(fir_smem + 2 * tile_bytes);  // [2][4][64]
-    int* s_next = (int*)(fir_smem + 2 * tile_bytes + 2 * 4 * 64 * sizeof(float4));
-    const int nck = a.ntaps_pad >> 3;
-    const int c0 = nck * wave / 4;
-    const int c1 = nck * (wave + 1) / 4;
-
-    int ch = (int)(g0 / ntile);
-    int t = (int)(g0 - (long long)ch * ntile);
+    RunWalk<true> w(a.nch, a.nwin);
+    if (w.none()) return;
+    w.start(a.work_counter, (int*)(fir_smem + 2 * tile_bytes + 2 * 4 * 64 * sizeof(float4)));
+    int c0, c1;
+    tile_wave_steps(a.ntaps_pad >> 3, wave, c0, c1);
 
     auto issue = [&](int fch, int ft, int b) {
         const uint8_t* __restrict__ src = iq_base + (size_t)stream_of[fch] * a.pitch;
@@ -51,72 +41,32 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_u8_dma_kernel(const FirArgs a,
         }
     };
 
-    issue(ch, t, 0);
+    issue(w.u, w.t, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int cur = 0;
-    unsigned int pending_next = 0;
-    for (long long g = g0;;) {
-        if (g == g0 && tid == 0) request_ticket(a.work_counter, pending_next);
-        int nch_ = ch, nt_ = t + 1;
-        if (nt_ == ntile) { nt_ = 0; ++nch_; }
-        bool more = g + 1 < g1;
-        long long ng0 = g0, ng1 = g1, ng = g + 1;
-        if (!more) {
-            const long long nr = (g1 - g0 >= 2) ? (long long)*s_next : nrun;
-            if (nr < nrun) {
-                ng0 = nr * FIR_RUN;
-                ng1 = ng0 + FIR_RUN < G ? ng0 + FIR_RUN : G;
-                ng = ng0;
-                nch_ = (int)((unsigned int)ng0 / (unsigned int)ntile);      // G < 2^31 (launcher)
-                nt_ = (int)((unsigned int)ng0 - (unsigned int)nch_ * (unsigned int)ntile);
-                more = true;
-            }
-        }
-        if (more) issue(nch_, nt_, cur ^ 1);
+    for (long long g = w.g0;;) {
+        w.request(id.tid, g);
+        if (w.successor(g)) issue(w.nu, w.nt, cur ^ 1);
 
-        const float* __restrict__ taps = taps_base + (size_t)ch * a.ntaps_pad * 2;
+        const float* __restrict__ taps = taps_base + (size_t)w.u * a.ntaps_pad * 2;
         f2 accA = {0.f, 0.f};
         f2 accB = {0.f, 0.f};
         const unsigned char* rowp = buf0 + cur * tile_bytes + lane * a.row_bytes;
         for (int c = c0; c < c1; ++c) {
-            const uint4 q = *(const uint4*)(rowp + (c << 4));
-            const float* __restrict__ w = taps + (c << 4);
-            const unsigned int qq[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const unsigned int word = qq[j >> 1];
-                const unsigned int sh = (j & 1) * 16;
-                f2 tt;
-                tt.x = (float)((word >> sh) & 0xffu) - 127.37f;
-                tt.y = (float)((word >> (sh + 8)) & 0xffu) - 127.37f;
-                const f2 wv = {w[2 * j], w[2 * j + 1]};
-                const f2 ws = {w[2 * j + 1], w[2 * j]};
-                accA = __builtin_elementwise_fma(tt, wv, accA);
-                accB = __builtin_elementwise_fma(tt, ws, accB);
-            }
+            tile_mac_of<8>(ByteChunk<false>(rowp, c), taps + (c << 4), accA, accB);
         }
         float4* rd = red + cur * 256;
-        rd[wave * 64 + lane] = make_float4(accA.x, accA.y, accB.x, accB.y);
+        rd[wave * 64 + lane] = tile_partial(accA, accB);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's share of the next tile has landed
-        if (g == g0 && tid == 0) *s_next = (int)(gridDim.x + take_ticket(pending_next));     // published by the barrier below
+        w.publish(id.tid, g, w.g0);                            // on the run's first tile, published by the barrier below
         __syncthreads();
 
-        if (wave == 0) {
-            const float4 r0 = rd[lane], r1 = rd[64 + lane], r2 = rd[128 + lane], r3 = rd[192 + lane];
-            const float Dr = ((r0.x + r1.x) + (r2.x + r3.x)) - ((r0.y + r1.y) + (r2.y + r3.y));
-            const float Di = ((r0.z + r1.z) + (r2.z + r3.z)) + ((r0.w + r1.w) + (r2.w + r3.w));
-            const int m = t * ACG_TILE_WIN + lane;
-            if (m < a.nwin) dm_base[(size_t)ch * a.dm_pitch + m] = cabs_like_glibc(Dr, Di);
-        }
-        if (!more) break;
-        ch = nch_;
-        t = nt_;
-        g = ng;
-        g0 = ng0;
-        g1 = ng1;
+        if (wave == 0) tile_store_dm(dm_base + (size_t)w.u * a.dm_pitch, w.t * ACG_TILE_WIN + lane, a.nwin, tile_wave_sum(rd, 64, lane), 1.0f);
+        if (!w.more) break;
+        w.advance(g);
         cur ^= 1;
     }
-    if (tid == 0) dispenser_sign_off(a.work_counter, pending_next);
+    w.sign_off(id.tid);
 }
 

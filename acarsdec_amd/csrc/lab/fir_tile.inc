@@ -7,9 +7,8 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_u8_tile_kernel(const FirArgs a
                                                                   const int* __restrict__ stream_of,
                                                                   float* __restrict__ dm_base)
 {
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const TileIds id;
+    const int lane = id.lane, wave = id.wave;
     const int ch = blockIdx.x / a.nseg;
     const int seg = blockIdx.x - ch * a.nseg;
     const int ntile = (a.nwin + ACG_TILE_WIN - 1) / ACG_TILE_WIN;
@@ -19,98 +18,40 @@ __global__ __launch_bounds__(ACG_WG_FIR) void fir_u8_tile_kernel(const FirArgs a
 
     const uint8_t* __restrict__ src = iq_base + (size_t)stream_of[ch] * a.pitch;
     const float* __restrict__ taps = taps_base + (size_t)ch * a.ntaps_pad * 2;
-    float* __restrict__ dm = dm_base + (size_t)ch * a.dm_pitch;
 
-    const int cpr = a.cpr;
-    const int tile_chunks = ACG_TILE_WIN * cpr;
-    const int total_chunks = a.nwin * cpr;              // valid 16-byte chunks of this stream row
-    const int pad = a.row_stride - a.row_bytes;
-    const unsigned int magic = a.cpr_magic;
+    const int tile_chunks = ACG_TILE_WIN * a.cpr;
+    const int total_chunks = a.nwin * a.cpr;            // valid 16-byte chunks of this stream row
     unsigned char* tileL = fir_smem;
     float4* red = (float4*)(fir_smem + ACG_TILE_WIN * a.row_stride);
-
-    const int nck = a.ntaps_pad >> 3;                   // chunks that carry taps
-    const int c0 = nck * wave / 4;
-    const int c1 = nck * (wave + 1) / 4;
+    int c0, c1;
+    tile_wave_steps(a.ntaps_pad >> 3, wave, c0, c1);     // chunks that carry taps
     const int nld = (tile_chunks + ACG_WG_FIR - 1) / ACG_WG_FIR;
-
     uint4 stage[FIR_MAXLD];
+    auto fetch = [&](int t) {
+        const int base = t * tile_chunks;
+        tile_fetch_slots<false>(id.tid, nld, tile_chunks, stage, [&](int c, const tile_u4v*& p) {
+            p = (const tile_u4v*)(src + ((size_t)(base + c) << 4));
+            return base + c < total_chunks;
+        });
+    };
 
-    // ---- prologue: fetch the first tile
-    {
-        const int base = t0 * tile_chunks;
-#pragma unroll
-        for (int i = 0; i < FIR_MAXLD; ++i) {
-            if (i < nld) {
-                const int c = tid + i * ACG_WG_FIR;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (c < tile_chunks && base + c < total_chunks)
-                    v = *(const uint4*)(src + ((size_t)(base + c) << 4));
-                stage[i] = v;
-            }
-        }
-    }
-
+    fetch(t0);
     for (int t = t0; t < t1; ++t) {
-        // ---- registers -> LDS (padded rows)
-#pragma unroll
-        for (int i = 0; i < FIR_MAXLD; ++i) {
-            if (i < nld) {
-                const int c = tid + i * ACG_WG_FIR;
-                if (c < tile_chunks) {
-                    const int r = (int)(((unsigned int)c * magic) >> 20);
-                    *(uint4*)(tileL + (c << 4) + r * pad) = stage[i];
-                }
-            }
-        }
+        tile_store_slots(id.tid, nld, tile_chunks, stage, tileL, a.cpr_magic, a.row_stride - a.row_bytes);     // registers -> LDS (padded rows)
         __syncthreads();
-
-        // ---- issue the next tile's loads; they stay in flight during the compute below
-        if (t + 1 < t1) {
-            const int base = (t + 1) * tile_chunks;
-#pragma unroll
-            for (int i = 0; i < FIR_MAXLD; ++i) {
-                if (i < nld) {
-                    const int c = tid + i * ACG_WG_FIR;
-                    uint4 v = make_uint4(0, 0, 0, 0);
-                    if (c < tile_chunks && base + c < total_chunks)
-                        v = *(const uint4*)(src + ((size_t)(base + c) << 4));
-                    stage[i] = v;
-                }
-            }
-        }
+        if (t + 1 < t1) fetch(t + 1);                   // the next tile's loads stay in flight during the compute below
 
         // ---- this wave's share of the taps, lane = window
         f2 accA = {0.f, 0.f};       // (sum tr*wr, sum ti*wi)
         f2 accB = {0.f, 0.f};       // (sum tr*wi, sum ti*wr)
         const unsigned char* rowp = tileL + lane * a.row_stride;
         for (int c = c0; c < c1; ++c) {
-            const uint4 q = *(const uint4*)(rowp + (c << 4));
-            const float* __restrict__ w = taps + (c << 4);       // wave-uniform -> scalar loads
-            const unsigned int qq[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const unsigned int word = qq[j >> 1];
-                const unsigned int sh = (j & 1) * 16;
-                f2 t;
-                t.x = (float)((word >> sh) & 0xffu) - 127.37f;          // rtl.c:338 (exact in f32)
-                t.y = (float)((word >> (sh + 8)) & 0xffu) - 127.37f;    // rtl.c:339
-                const f2 wv = {w[2 * j], w[2 * j + 1]};
-                const f2 ws = {w[2 * j + 1], w[2 * j]};
-                accA = __builtin_elementwise_fma(t, wv, accA);
-                accB = __builtin_elementwise_fma(t, ws, accB);
-            }
+            tile_mac_of<8>(ByteChunk<false>(rowp, c), taps + (c << 4), accA, accB);    // wave-uniform -> scalar loads
         }
-        red[wave * 64 + lane] = make_float4(accA.x, accA.y, accB.x, accB.y);
+        red[wave * 64 + lane] = tile_partial(accA, accB);
         __syncthreads();
 
-        if (wave == 0) {
-            const float4 r0 = red[lane], r1 = red[64 + lane], r2 = red[128 + lane], r3 = red[192 + lane];
-            const float Dr = ((r0.x + r1.x) + (r2.x + r3.x)) - ((r0.y + r1.y) + (r2.y + r3.y));
-            const float Di = ((r0.z + r1.z) + (r2.z + r3.z)) + ((r0.w + r1.w) + (r2.w + r3.w));
-            const int m = t * ACG_TILE_WIN + lane;
-            if (m < a.nwin) dm[m] = cabs_like_glibc(Dr, Di);             // rtl.c:353
-        }
+        if (wave == 0) tile_store_dm(dm_base + (size_t)ch * a.dm_pitch, t * ACG_TILE_WIN + lane, a.nwin, tile_wave_sum(red, 64, lane), 1.0f);
         // the barrier at the top of the next iteration orders wave 0's reads of `red`
         // before anyone rewrites it.
     }

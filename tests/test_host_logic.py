@@ -66,7 +66,7 @@ def test_tuning_switches_go_through_one_table_not_the_environment():
     assert L.acg_is_lab_build() == 0 and K.load(lab=True).acg_is_lab_build() == 1
     assert L.acg_tune(b"ACG_FIR_VARIANT", b"3") == K.OK and L.acg_tune(b"ACG_FIR_VARIANT", None) == K.OK
     assert L.acg_tune(b"LD_PRELOAD", b"x") == K.EINVAL and L.acg_tune(None, b"1") == K.EINVAL
-    src = "".join(open(os.path.join(ROOT, "acarsdec_amd", "csrc", f)).read() for f in ("fir.hip", "fir_plan.h", "msk.hip", "msk_lean.hip", "msk_common.h"))
+    src = "".join(open(os.path.join(ROOT, "acarsdec_amd", "csrc", f)).read() for f in ("fir.hip", "fir_plan.h", "fir_common.h", "fir_tile_kernel.h", "fir_kernels.h", "msk.hip", "msk_lean.hip", "msk_common.h"))
     assert "getenv(" not in src                                   # no launch path reads the environment
     code = ("import os, sys; sys.path.insert(0, %r); os.environ['ACG_FIR_DEBUG_SHAPE'] = '1'\n"
             "from acarsdec_amd import _capi as K; K.tune('ACG_MSK_LPC', 4, lab=%%s)" % ROOT)
@@ -373,6 +373,26 @@ def test_grid_plan_is_the_two_plans_it_replaced(tmp_path):
                        ([] if "clang" in os.path.basename(cxx) else ["-static-libasan", "-static-libubsan"]) +      # (clang links them statically anyway)
                        ["-I" + os.path.join(ROOT, "acarsdec_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
                         os.path.join(ROOT, "tests", "fir_grid_plan_check.cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.stdout[-2000:], r.stderr[-2000:])
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-2000:]
+
+
+def test_tile_grid_is_the_six_grids_it_replaced(tmp_path):
+    """csrc/fir_plan.h's acg_fir_tile_grid sizes the grid of resident workgroups of every tile down-converter (fir_tile_kernel.h,
+    fir_grid_kernel.h).  tests/fir_tile_grid_check.cpp compiles the header for the host, under the address and undefined-behaviour
+    sanitizers, and sweeps CU counts, the context's ncu, LDS sizes from 1 KiB to 64 KiB, the caps of 5 / 4 / 3 workgroups per CU,
+    the wg_per_cu and ACG_FIR_WG_PER_CU overrides and channels x windows (ragged ones included): the grid equals the literal
+    restatement of each of the six computations it replaced, and what the lab's variants 1 and 2 took before the run clamp."""
+    import shutil
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "a host C++ compiler"
+    exe = str(tmp_path / "fir_tile_grid_check")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] +
+                       ([] if "clang" in os.path.basename(cxx) else ["-static-libasan", "-static-libubsan"]) +      # (clang links them statically anyway)
+                       ["-I" + os.path.join(ROOT, "acarsdec_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, "tests", "fir_tile_grid_check.cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.startswith("ok "), (r.stdout[-2000:], r.stderr[-2000:])
