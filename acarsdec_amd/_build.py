@@ -65,7 +65,10 @@ UNITS = [("fir.hip", ["-O3"], True),
          ("fir_iq.hip", ["-O3", "--offload-compress"], True), ("fir_mm.hip", ["-O3", "--offload-compress"], True),
          ("fir_rate.hip", ["-O3", "--offload-compress"], True),    # any input rate: four format instantiations, the same way
          ("fir_long.hip", ["-O3", "--offload-compress"], True),    # channel filters over several windows: one instantiation per sample size
-         ("msk.hip", MSK_FLAGS, True), ("msk_lean.hip", MSK_LEAN_FLAGS, True), ("msk2.hip", MSK_FLAGS, False), ("synth.hip", ["-O3"], True),
+         ("msk.hip", MSK_FLAGS, True), ("msk_lean.hip", MSK_LEAN_FLAGS, True), ("msk2.hip", MSK_FLAGS, False),
+         # msk_lean.hip's kernel with 16 lanes per channel, four-wave workgroups only.  A compressed bundle, and the signal
+         # generators (off every hot path) with it: the size rule of tests/test_host_logic.py (LEDGER, round 12)
+         ("msk_lean_wide.hip", MSK_LEAN_FLAGS + ["--offload-compress"], True), ("synth.hip", ["-O3", "--offload-compress"], True),
          ("blk.hip", ["-O3"], True), ("label.hip", ["-O3"], True),
          # the two resident tables (flight.hip's sort serves both) as compressed bundles, outs.hip's way: the size rule of
          # tests/test_host_logic.py (LEDGER, "Multi-block reassembly")

@@ -479,6 +479,7 @@ int acg_fir_device_cus(int* num_cu);                                 // CUs of t
 int acg_fir_lds_optin(const void* kernel, size_t bytes);             // opts `kernel` in for `bytes` of dynamic LDS on the current device
 int acg_launch_msk(const MskArgs* a, int lanes_per_channel, void* stream);
 int acg_launch_msk_lean(const MskArgs* a, int lanes_per_channel, int waves_per_group, unsigned int grid, void* stream);   // msk_lean.hip: the in_callback-shaped launches, with or without a bit log
+int acg_launch_msk_lean_wide(const MskArgs* a, int lanes_per_channel, int waves_per_group, unsigned int grid, void* stream);   // msk_lean_wide.hip: the same with 16 lanes per channel, four-wave workgroups
 int acg_launch_msk2(const MskArgs* a, int pairs_per_group, void* stream);     // msk2.hip: the stream split over two waves (8 lanes per channel)
 int acg_launch_blk_repair(AcgFrameRec* frames, unsigned int cap, const unsigned int* upto, unsigned int* done_upto,
                           unsigned int* done_ctr, const unsigned short* synd, const unsigned short* crctab, int nch, void* stream);

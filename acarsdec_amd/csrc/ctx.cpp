@@ -206,6 +206,18 @@ extern "C" int acg_create(acg_ctx** out, const acg_config* cfg)
     // MSK kernel shape: the chip has 1024 SIMDs; give every channel as many lanes as keeps the
     // wave count around one per SIMD (latency mode), down to one lane per channel (throughput mode)
     c->msk_lpc = cfg->nch <= 8192 ? 8 : cfg->nch <= 16384 ? 4 : cfg->nch <= 32768 ? 2 : 1;
+    // Up to 1024 channels: 16 lanes per channel (msk_lean_wide.hip, round 12).  The 8-lane kernel fills 128 of the chip's SIMDs
+    // there and 48 of its partition's 80 CUs carry no demodulator wave; a segment is cut wave-wide, so 4 channels per wave
+    // instead of 8 halve the cuts (6.91 -> 7.43 periods per segment on the bench's traffic).  Measured at 1024 channels: the
+    // kernel alone 0.944 -> 0.911 ms per call; the headline step, parent commit against this tree, 21.189 21.237 21.252 -> 20.496
+    // 20.528 20.529 ms (medians -3.3 %: the worst run of 16 lanes beats the best of 8 by 0.66 ms, ten times the 8-lane arm's
+    // max - min); the down-converter keeps its 176 CUs.  32 lanes (512 waves, a partition of 128 CUs) gave the same step
+    // (20.53-20.59 against 20.54-20.62 ms) with the down-converter 10-20 % longer: not in the tree.  2048 channels stay at 8
+    // lanes: 16 need 128 CUs, and the step went 9.67-10.58 -> 12.48-12.56 ms (the down-converter 1.08-1.20 -> 1.44-1.45 ms per
+    // launch, no longer hidden); ACG_MSK_LPC=16 selects them there.  profiles/LEDGER.md, round 12.
+#ifndef ACG_MSK_STAMP                              // (the stamp build measures msk.hip's kernel: 8 lanes)
+    if (cfg->nch <= 1024) c->msk_lpc = 16;
+#endif
     // pipeline chunk: 4 callbacks per launch pair.  Few large launches beat many small ones at every size
     // measured (1024 ... 16384 channels: launch tails, event packets); with the two dm buffers the chunks of a
     // call only serve to let its demodulator start before its down-converter has finished.  Up to 2048
@@ -227,13 +239,25 @@ extern "C" int acg_create(acg_ctx** out, const acg_config* cfg)
     // demodulator (whole job 0.53 -> 0.61 on the same box together with whole-call launches; 96: 0.60, 112: 0.59, 160: 0.52).
     // So: 2.5 n, at most 80.
     if (cfg->nch <= 2048) {
-        const int need = std::max(1, (cfg->nch * c->msk_lpc / 64 + 3) / 4);
+        const int need = std::max(1, (cfg->nch * 8 / 64 + 3) / 4);          // (n of the 8-lane kernel, whatever width runs)
         c->msk_cus_default = std::min(80, (5 * need + 1) / 2);
     }
     c->msk_high_prio = acg_tune_get("ACG_MSK_PRIO", c->msk_high_prio) ? 1 : 0;
     {
         const int v = acg_tune_get("ACG_MSK_LPC", c->msk_lpc);
-        if (v == 1 || v == 2 || v == 4 || v == 8) c->msk_lpc = v;
+        if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) c->msk_lpc = v;
+    }
+    // 16 lanes per channel (msk_lean_wide.hip) run in the four-wave workgroups of a context with a CU partition, one wave per
+    // SIMD: the partition grows to cover them, up to half the chip (2048 channels: 128 CUs); a context too wide for that keeps
+    // 8 lanes.  (Without a partition -- ACG_MSK_CUS=0 -- acg_launch_msk falls back to 8 lanes launch by launch.)
+    if (c->msk_lpc > 8) {
+#ifdef ACG_MSK_STAMP
+        c->msk_lpc = 8;
+#else
+        const int need = (cfg->nch * c->msk_lpc / 64 + 3) / 4;
+        if (cfg->nch <= 2048 && need <= 128) c->msk_cus_default = std::max(c->msk_cus_default, need);
+        else c->msk_lpc = 8;
+#endif
     }
 
     int rc = ACG_OK;
@@ -284,6 +308,7 @@ extern "C" int acg_create(acg_ctx** out, const acg_config* cfg)
                 if (cfg->nch >= 16384) HIPCHK(c, hipExtStreamCreateWithCUMask(&c->msk_stream, (uint32_t)mask_words, full_mask.data()));
                 else HIPCHK(c, hipStreamCreateWithPriority(&c->msk_stream, hipStreamNonBlocking, hi));
             }
+            if (c->msk_lpc > 8 && !c->fir_stream) c->msk_lpc = 8;       // (no partition: one-wave workgroups, which have no wide kernel)
         }
         // (round 4 tried a CU mask on this stream and on the repair stream -- the down-converter's side of the partition, to keep
         //  both off the demodulator's CUs: the runtime then performs the result copies as blit kernels on those saturated CUs,

@@ -453,13 +453,24 @@ extern "C" int acg_tune_get(const char* name, int dflt);
 
 extern "C" int acg_launch_msk(const MskArgs* a, int lpc, void* stream)
 {
+    const bool vec = ((uintptr_t)a->dm % 16 == 0) && (a->dm_pitch % 4 == 0) && (a->len % 32 == 0) && !acg_tune_has("ACG_MSK_NOVEC") && !a->precise_mixer;
+    // 16 lanes per channel (msk_lean_wide.hip) exist for the launches that qualify for the lean kernel in four-wave workgroups;
+    // every other launch takes 8 lanes (the channel state does not depend on the width: exact from launch to launch)
+    if (lpc > 8) {
+#ifndef ACG_MSK_STAMP
+        if (vec && a->waves_per_group == 4 && !acg_tune_get("ACG_MSK_NOLEAN", 0)) {
+            const unsigned int waves = (unsigned int)((a->nch + 64 / lpc - 1) / (64 / lpc));
+            return acg_launch_msk_lean_wide(a, lpc, 4, (waves + 3) / 4, stream);
+        }
+#endif
+        lpc = 8;
+    }
     const int cpw = 64 / lpc;
     const int wpg = (a->waves_per_group == 4 && lpc >= 4) ? 4 : 1;
     const unsigned int waves = (unsigned int)((a->nch + cpw - 1) / cpw);
     const unsigned int grid = (waves + wpg - 1) / wpg;
     const dim3 blk(64 * wpg);
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = ((uintptr_t)a->dm % 16 == 0) && (a->dm_pitch % 4 == 0) && (a->len % 32 == 0) && !acg_tune_has("ACG_MSK_NOVEC") && !a->precise_mixer;
     // Round 6: the in_callback-shaped launches go to msk_lean.hip (the framing state machine off the per-bit path: same bits,
     // blocks and state); ACG_MSK_NOLEAN=1 keeps this file's kernel for same-process A/B.  The stamp build measures this file's kernel.
 #ifndef ACG_MSK_STAMP

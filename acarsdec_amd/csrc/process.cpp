@@ -275,7 +275,7 @@ static int launch_msk(acg_ctx* c, const float* dm_dev, size_t pitch_floats, int 
     int lpc = c->msk_lpc;
     {                                                               // measurement aid: lanes per channel per launch (the channel state
         const int v = acg_tune_get("ACG_MSK_LPC_LIVE", lpc);          // does not depend on it), for same-context A/B (bench.py --ab)
-        if (v == 1 || v == 2 || v == 4 || v == 8) lpc = v;
+        if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) lpc = v;          // (16: on the context's CU mask as it is)
     }
     int e;
     {
@@ -283,7 +283,8 @@ static int launch_msk(acg_ctx* c, const float* dm_dev, size_t pitch_floats, int 
         // lab build: the two-wave kernel (msk2.hip: the per-bit instruction stream split over a wave pair on two SIMDs);
         // bit-identical to the one-wave kernel, so the switch may change from launch to launch -- and slower
 #ifdef ACG_LAB
-        if (lpc == 8 && acg_tune_get("ACG_MSK_SPLIT", c->msk_split)) e = acg_launch_msk2(&a, c->fir_stream ? 2 : 1, s);
+        // (the two-wave kernel has 8 lanes per channel, also where the one-wave kernel has 16)
+        if (lpc >= 8 && acg_tune_get("ACG_MSK_SPLIT", c->msk_split)) e = acg_launch_msk2(&a, c->fir_stream ? 2 : 1, s);
         else
 #endif
             e = acg_launch_msk(&a, lpc, s);

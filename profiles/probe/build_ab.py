@@ -42,9 +42,12 @@ for spec in sys.argv[1:]:
         # the revision's demodulator sources in a directory of their own, in front of the tree's on the include path
         srcdir = os.path.join(out, "src_%s" % name)
         os.makedirs(srcdir, exist_ok=True)
-        for f in SOURCES:
-            text = subprocess.run(["git", "show", "%s:acarsdec_amd/csrc/%s" % (rev, f)], cwd=ROOT, capture_output=True, text=True, check=True).stdout
-            open(os.path.join(srcdir, f), "w").write(text)
+        for f in SOURCES + ("msk_lean_kernel.h",):
+            r = subprocess.run(["git", "show", "%s:acarsdec_amd/csrc/%s" % (rev, f)], cwd=ROOT, capture_output=True, text=True)
+            if r.returncode != 0 and f == "msk_lean_kernel.h":
+                continue                               # (revisions before round 12 have the kernel's text in msk_lean.hip itself)
+            r.check_returncode()
+            open(os.path.join(srcdir, f), "w").write(r.stdout)
         inc = ["-I" + srcdir] + inc
     cc = [B.hipcc(), "--offload-arch=gfx950", "-std=c++17", "-fPIC"] + inc
     obj = os.path.join(out, "msk_%s.o" % name)
