@@ -1,5 +1,9 @@
 """Reassembly of multi-block messages on the device (reasm.hip) against its specification, tests/reasm_model.py: through the lab
-entry acg_selftest_reasm on hand-written and random records, and end to end on signal through a context."""
+entry acg_selftest_reasm on hand-written and random records, and end to end on signal through a context.  This file checks the
+status rule where the slot rules cannot be seen: its traffic can drop nobody and only idle slots are taken again.  The slots at full
+load (the take-over of an expired live entry, the probe bound inside a larger table, racing claims, sample indices above 2^32) are
+tests/test_gpu_reasm_pressure.py's; the context with channel numbers, the label pass, small takes, the outputs' entry points and
+large counters is tests/test_gpu_reasm_context.py's (here: three channels, no filter, identity numbers, counters from 0)."""
 import ctypes as C
 import os
 import sys
