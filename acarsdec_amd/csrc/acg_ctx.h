@@ -29,6 +29,31 @@ extern "C" int acg_tune_has(const char* name);
 
 struct EvPair { hipEvent_t a, b; };
 
+// The *_host entry points' way to the device: TWO staging buffers and a copy stream of their own, so that the host-to-device copy
+// of call i+1 runs while the kernels of call i read the other buffer (the caller's memory is free again when the call returns:
+// rtl.c:314-330 / soapy.c:220-254 hand over a buffer that is only valid during the callback).  Every entry point copies into
+// buf[cur] behind the buffer's last reader, runs its device path and turns the ring (process.cpp: stage_*); the carrying feeds
+// keep the samples of an incomplete window at the head of buf[cur].
+struct StageRing {
+    void* buf[2] = {nullptr, nullptr};
+    size_t bytes = 0;               // of EACH buffer
+    int cur = 0;                    // the buffer the next copy goes to
+    hipStream_t copy = nullptr;     // the copy stream
+    hipEvent_t copied = nullptr;    // the newest copy from the caller's memory is done
+    hipEvent_t free[2] = {nullptr, nullptr};    // the launches that read the buffer are done ...
+    bool free_valid[2] = {false, false};        // ... recorded, and the copy stream does not wait for it yet
+    int fmt = 0;                    // acg_feed_samples_host / acg_feed_rate_host: format and samples of the incomplete window carried
+    size_t fill = 0;
+    void reset() { cur = 0; fill = 0; free_valid[0] = free_valid[1] = false; }      // behind a device synchronise: nothing reads, nothing is carried
+    void destroy()
+    {
+        for (auto p : buf) hipFree(p);
+        if (copy) hipStreamDestroy(copy);
+        if (copied) hipEventDestroy(copied);
+        for (auto e : free) if (e) hipEventDestroy(e);
+    }
+};
+
 struct acg_ctx {
     // ---- ctx.cpp: the configuration and what acg_create derives from it, taps and stream map, the channels' device state, channel numbers
     acg_config cfg{};
@@ -77,7 +102,6 @@ struct acg_ctx {
     std::vector<unsigned int> rate_grid;    // floor(r P / Q), r <= Q ...
     unsigned int* d_rate_grid = nullptr;    // ... and on the device
     float* d_rate_tapsum = nullptr;         // [nch][4]: the taps' sums over [0, decim - 1) and [0, decim), re and im
-    const struct FirRateArgs* rate_call = nullptr;   // the rate call being issued: what its chunks' launches share (process.cpp)
     // acg_set_channel_filter: taps over long_nseg windows (fir_grid.h).  long_nseg == 0: off, none of this is used or allocated
     int long_nseg = 0;
     float* d_long_taps = nullptr;           // [nch][long_nseg * decim + 8][2], the last 8 of a channel zeros
@@ -88,9 +112,8 @@ struct acg_ctx {
     int long_fmt = -1;                      // the format the history is in
     hipEvent_t long_hist_ev = nullptr;      // the history is written: the next call's launches wait for it, whatever their stream
     bool long_hist_ev_valid = false;
-    const struct FirLongArgs* long_call = nullptr;   // as rate_call, while a filter is on
 
-    // ---- process.cpp: streams and events of the pipeline, call slots, dm buffers and guards, host staging, launch timing
+    // ---- process.cpp: streams and events of the pipeline, call slots, dm buffers and guards, the staging ring, launch timing
     hipStream_t stream = nullptr;
     hipStream_t msk_stream = nullptr;   // demodulator launches (they carry the channel state) run here, in order
     hipStream_t post_stream = nullptr;  // ACG_F_REPAIR: the block thread's pass over a call's blocks, OFF the demodulator's serial chain
@@ -121,19 +144,7 @@ struct acg_ctx {
     unsigned int* d_msk_done = nullptr;     // workgroups-finished counter of the demodulator kernel
     unsigned int* d_work = nullptr;     // FIR run dispensers, ACG_DISP_WORDS words per chunk slot
     unsigned int* d_rep_upto = nullptr; // blocks already through the repair kernel
-    // *_host entry points: TWO device staging buffers and a copy stream of their own, so that the host-to-device copy of
-    // call i+1 runs while the kernels of call i read the other buffer (the caller's memory is free again when the call
-    // returns: rtl.c:314-330 / soapy.c:220-254 hand over a buffer that is only valid during the callback)
-    void* d_stage[2] = {nullptr, nullptr};
-    size_t stage_bytes = 0;         // bytes of EACH buffer
-    hipStream_t h2d_stream = nullptr;
-    hipEvent_t h2d_done = nullptr;
-    hipEvent_t stage_free[2] = {nullptr, nullptr};   // the down-converter launches that read the buffer have been enqueued before it
-    bool stage_free_valid[2] = {false, false};
-    unsigned int stage_seq = 0;     // acg_process_iq_u8_host: calls so far (slot = seq & 1)
-    int feed_cur = 0;               // acg_feed_samples_host: the buffer whose head holds the carried samples
-    int feed_fmt = 0;               // acg_feed_samples_host: format and samples of the incomplete window carried
-    size_t feed_fill = 0;
+    StageRing stage;                // the *_host entry points' staging buffers
     std::vector<EvPair> fir_ev, msk_ev;
     std::vector<hipEvent_t> ev_pool;
 

@@ -74,7 +74,7 @@ static void free_all(acg_ctx* c)
     c->text = nullptr;
     outputs_destroy(c->outs);
     c->outs = nullptr;
-    hipFree(c->d_bits); hipFree(c->d_nbits); hipFree(c->d_stage[0]); hipFree(c->d_stage[1]); hipFree(c->d_work); hipFree(c->d_msk_done); std::free(c->h_stage); hipFree(c->d_crctab); hipFree(c->d_rep_upto);
+    hipFree(c->d_bits); hipFree(c->d_nbits); hipFree(c->d_work); hipFree(c->d_msk_done); std::free(c->h_stage); hipFree(c->d_crctab); hipFree(c->d_rep_upto);
     for (auto& p : c->fir_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& p : c->msk_ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : c->ev_pool) hipEventDestroy(e);
@@ -91,9 +91,7 @@ static void free_all(acg_ctx* c)
     if (c->copy_stream) hipStreamDestroy(c->copy_stream);
     if (c->post_stream) hipStreamDestroy(c->post_stream);
     for (auto e : c->msk_end) if (e) hipEventDestroy(e);
-    if (c->h2d_stream) hipStreamDestroy(c->h2d_stream);
-    if (c->h2d_done) hipEventDestroy(c->h2d_done);
-    for (auto e : c->stage_free) if (e) hipEventDestroy(e);
+    c->stage.destroy();
     if (c->stream) hipStreamDestroy(c->stream);
 }
 
@@ -407,12 +405,9 @@ extern "C" int acg_reset(acg_ctx* ctx)
     ctx->consumed = 0;
     ctx->call_seq = 0;
     ctx->last_guard = nullptr;
-    ctx->feed_fill = 0;
-    ctx->feed_cur = 0;
+    ctx->stage.reset();                                  // no reader is left and the carried samples are dropped
     ctx->rate_k = 0;                                     // the grid restarts at window 0
     ctx->long_have = 0;                                  // ... and a channel filter, which stays on, has nothing before it
-    ctx->stage_seq = 0;
-    ctx->stage_free_valid[0] = ctx->stage_free_valid[1] = false;
     std::fill(ctx->msk_done_owner.begin(), ctx->msk_done_owner.end(), -1);
     // initMsk (msk.c:34-41): MskPhi = MskClk = MskS = MskDf = idx = 0, inb zeroed;
     // static storage: MskLvlSum = MskBitCount = 0; initAcars (acars.c:230-234): outbits 0, nbits 8, WSYN
@@ -474,7 +469,7 @@ const char* const RATE_SET_MSG = "an input rate is set (acg_set_input_rate): thi
 extern "C" int acg_set_input_rate(acg_ctx* ctx, unsigned int rate_hz)
 {
     if (!ctx) return ACG_EINVAL;
-    if (ctx->feed_fill) return fail(ctx, ACG_ESTATE, "the input rate cannot change while a host feed carries samples (acg_reset drops them)");
+    if (ctx->stage.fill) return fail(ctx, ACG_ESTATE, "the input rate cannot change while a host feed carries samples (acg_reset drops them)");
     if (rate_hz != 0 && (acg_rate_decim(rate_hz) != ctx->cfg.decim || ctx->cfg.ntaps != ctx->cfg.decim))
         return fail(ctx, ACG_EINVAL, "input rate: the context needs decim == ntaps == acg_rate_decim(rate_hz)");
     HIPCHK_OL(ctx, hipSetDevice(ctx->cfg.device));
@@ -508,7 +503,7 @@ extern "C" int acg_set_channel_filter(acg_ctx* ctx, int nseg, const float* taps)
     if (!ctx->rate_hz) return fail(ctx, ACG_ESTATE, "channel filter: no input rate is set (acg_set_input_rate)");
     if (ctx->rate_Q != 1) return fail(ctx, ACG_EINVAL, "channel filter: the input rate must be a multiple of 12 500 Hz");
     if (!off && (nseg < 2 || nseg > ACG_MAXSEG)) return fail(ctx, ACG_EINVAL, "channel filter: nseg outside 2 .. ACG_MAXSEG (0 = off)");
-    if (ctx->feed_fill) return fail(ctx, ACG_ESTATE, "the channel filter cannot change while a host feed carries samples (acg_reset drops them)");
+    if (ctx->stage.fill) return fail(ctx, ACG_ESTATE, "the channel filter cannot change while a host feed carries samples (acg_reset drops them)");
     if (!off && !acg_launch_fir_long) return fail(ctx, ACG_ESTATE, "this build has no channel-filter unit");
     HIPCHK_OL(ctx, hipSetDevice(ctx->cfg.device));
     HIPCHK_OL(ctx, hipDeviceSynchronize());                 // down-converter launches that read the table run on the callers' streams

@@ -1,6 +1,7 @@
 // process.cpp -- the whole launch path: every acg_process_* / acg_feed_* entry point, the software pipeline of a call, the
-// down-converter's kernel choice and the demodulator launch, the placement trials and the launch timing.  One unit, so that
-// the compiler inlines in it what it likes.
+// down-converter's kernel choice and the demodulator launch, the staging ring every *_host entry point copies through and the
+// one loop of the carrying feeds, the placement trials and the launch timing.  One unit, so that the compiler inlines in it
+// what it likes.
 #include <dlfcn.h>
 #include <chrono>
 #include <mutex>
@@ -81,6 +82,19 @@ static void begin_dm(acg_ctx* ctx)
     ctx->dm_par ^= 1;
     ctx->d_dm = ctx->d_dm_all + (size_t)ctx->dm_par * (size_t)ctx->cfg.nch * ctx->dm_pitch;
     ctx->gbase = ctx->dm_par * ctx->cfg.max_blocks;
+}
+
+// the dm blocks (and their guards) that len outputs per channel touch
+static int blocks_of(const acg_ctx* ctx, int len)
+{
+    return std::min(ctx->cfg.max_blocks, (len + ACG_BLOCK - 1) / ACG_BLOCK);
+}
+
+// Windows per pipeline chunk: the u8 path's bytes per launch, for samples `per` times the u8 sample's size (2-byte samples: its
+// callbacks; 4-byte samples: half of them; 8-byte samples: a quarter)
+static int chunk_windows(const acg_ctx* ctx, int per)
+{
+    return (ctx->pipe_blocks > 0 ? (ctx->pipe_blocks + per - 1) / per : ctx->cfg.max_blocks) * ACG_BLOCK;
 }
 
 // The down-converter's arguments that do not depend on the input format.  The caller adds its format's geometry; the
@@ -420,7 +434,7 @@ static int run_pipeline(acg_ctx* ctx, hipStream_t caller, FirArgs& a, size_t win
     for (int w0 = 0; w0 < nwin; w0 += chunk_win, ++k) {
         const int nw = std::min(chunk_win, nwin - w0);
         const int j0 = w0 / ACG_BLOCK;
-        const int j1 = std::min(ctx->cfg.max_blocks, (w0 + nw + ACG_BLOCK - 1) / ACG_BLOCK);
+        const int j1 = blocks_of(ctx, w0 + nw);
         // dm blocks [j0, j1) may still be read by demodulator launches of the previous call
         if ((r = guard_wait(ctx, s, j0, j1)) != ACG_OK) return r;
         if (order_dispatch && ctx->msk_go_valid) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->msk_go, 0));
@@ -461,31 +475,73 @@ extern "C" int acg_process_iq_u8_dev(acg_ctx* ctx, const uint8_t* iq_dev, size_t
                         cb * ACG_BLOCK, launch_fir_u8);
 }
 
-static int ensure_stage(acg_ctx* c, size_t bytes)
+// ---- the staging ring (StageRing, acg_ctx.h): how every *_host entry point moves the caller's memory to the device ----
+// A round of an entry point: stage_claim, copy into buf[cur] on the copy stream, stage_copied, the device path on the context's
+// stream, stage_turn; stage_return before the caller gets its memory back, on the error paths too.  The one invariant all of them
+// rest on: the only way to a buffer is stage_claim, which puts the wait for the buffer's last reader -- whichever entry point
+// that was -- on the copy stream before any copy into it.  So the copy of a round runs beside the kernels of the round before,
+// which read the other buffer.
+static const char* const CARRY_MSG = "a host feed is carrying a partial window in the staging buffers (acg_reset drops it)";
+
+// two buffers of at least `bytes` each
+static int stage_reserve(acg_ctx* c, size_t bytes)
 {
-    if (!c->h2d_stream) {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
-        HIPCHK(c, hipEventCreateWithFlags(&c->h2d_done, hipEventDisableTiming));
-        for (auto& e : c->stage_free) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    StageRing& st = c->stage;
+    if (!st.copy) {
+        HIPCHK(c, hipStreamCreateWithFlags(&st.copy, hipStreamNonBlocking));
+        HIPCHK(c, hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+        for (auto& e : st.free) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    if (c->stage_bytes >= bytes) return ACG_OK;
-    if (c->feed_fill) return fail(c, ACG_ESTATE, "staging buffers cannot grow while a partial window is carried");
+    if (st.bytes >= bytes) return ACG_OK;
+    if (st.fill) return fail(c, ACG_ESTATE, "staging buffers cannot grow while a partial window is carried");
     HIPCHK(c, hipDeviceSynchronize());                    // nothing may still read the buffers that go away
-    for (auto& p : c->d_stage) {
-        if (p) hipFree(p);
-        p = nullptr;
-    }
-    c->stage_bytes = 0;
-    c->stage_free_valid[0] = c->stage_free_valid[1] = false;
-    c->feed_cur = 0;
-    for (auto& p : c->d_stage) HIPCHK(c, hipMalloc(&p, bytes));
-    c->stage_bytes = bytes;
+    for (auto& p : st.buf) { (void)hipFree(p); p = nullptr; }
+    st.bytes = 0;
+    st.reset();                                           // (nothing is carried: checked above)
+    for (auto& p : st.buf) HIPCHK(c, hipMalloc(&p, bytes));
+    st.bytes = bytes;
     return ACG_OK;
 }
 
-// Host input: the copy of THIS call goes to the staging buffer the call before the previous one used, on the copy stream,
-// as soon as the down-converter launches that read that buffer are done -- i.e. it runs beside the kernels of the previous
-// call.  The call returns when the copy has left the caller's memory (rtl.c:314-330: the buffer belongs to the driver
+// the copies into buf[cur] are enqueued: the context's stream, where the device path runs, waits for them
+static int stage_copied(acg_ctx* c)
+{
+    HIPCHK(c, hipEventRecord(c->stage.copied, c->stage.copy));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->stage.copied, 0));
+    return ACG_OK;
+}
+
+// The device path that reads buf[cur] is enqueued: the context's stream is ordered behind its last reader, whichever stream that
+// ran on.  The other buffer becomes the current one.  (The wait for ITS last reader is stage_claim's: put on the copy stream
+// here, while the kernels of the round before may still run, it cost bench.py's hostfed case 1.2 % of its input rate.)
+static int stage_turn(acg_ctx* c)
+{
+    StageRing& st = c->stage;
+    HIPCHK(c, hipEventRecord(st.free[st.cur], c->stream));
+    st.free_valid[st.cur] = true;
+    st.cur ^= 1;
+    return ACG_OK;
+}
+
+// The current buffer, for copies into it: the copy stream waits for the buffer's last reader first (once: the stream runs in order).
+static int stage_claim(acg_ctx* c, unsigned char*& buf)
+{
+    StageRing& st = c->stage;
+    if (st.free_valid[st.cur]) HIPCHK(c, hipStreamWaitEvent(st.copy, st.free[st.cur], 0));
+    st.free_valid[st.cur] = false;
+    buf = (unsigned char*)st.buf[st.cur];
+    return ACG_OK;
+}
+
+// The caller's memory is free again: the newest copy has left it, and the copy stream runs in order.  rc is what the entry
+// point has to say so far: after an error too a copy may still be reading the caller's buffer, and must not after we return.
+static int stage_return(acg_ctx* c, int rc)
+{
+    const hipError_t e = hipEventSynchronize(c->stage.copied);
+    return rc != ACG_OK || e == hipSuccess ? rc : hip_fail(c, e, "hipEventSynchronize(stage.copied)");
+}
+
+// Host input: the call returns when the copy has left the caller's memory (rtl.c:314-330: the buffer belongs to the driver
 // again after the callback); its kernels run after the return, beside the host's next call.  From pinned memory
 // (acg_host_alloc / acg_host_register) the copy is one DMA at the link's rate; from pageable memory the runtime stages it.
 extern "C" int acg_process_iq_u8_host(acg_ctx* ctx, const uint8_t* iq_host, size_t pitch_bytes, int nblocks)
@@ -496,25 +552,15 @@ extern "C" int acg_process_iq_u8_host(acg_ctx* ctx, const uint8_t* iq_host, size
     const size_t row = (size_t)nblocks * ACG_BLOCK * ctx->cfg.decim * 2;
     const size_t dpitch = (row + 15) & ~(size_t)15;
     const size_t max_row = (((size_t)ctx->cfg.max_blocks * ACG_BLOCK * ctx->cfg.decim * 2) + 15) & ~(size_t)15;
-    // (acg_feed_samples_host keeps the samples of an incomplete window at the head of the same staging buffers)
-    if (ctx->feed_fill) return fail(ctx, ACG_ESTATE, "acg_feed_samples_host is carrying a partial window in the staging buffers (acg_reset drops it)");
-    if ((r = ensure_stage(ctx, max_row * ctx->cfg.nstreams)) != ACG_OK) return r;
-    const int slot = (int)(ctx->stage_seq++ & 1u);
-    if (ctx->stage_free_valid[slot]) HIPCHK(ctx, hipStreamWaitEvent(ctx->h2d_stream, ctx->stage_free[slot], 0));
-    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_stage[slot], dpitch, iq_host, ctx->cfg.nstreams > 1 ? pitch_bytes : row,
-                                 row, (size_t)ctx->cfg.nstreams, hipMemcpyHostToDevice, ctx->h2d_stream));
-    HIPCHK(ctx, hipEventRecord(ctx->h2d_done, ctx->h2d_stream));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->h2d_done, 0));
-    r = acg_process_iq_u8_dev(ctx, (const uint8_t*)ctx->d_stage[slot], dpitch, nblocks, nullptr);
-    if (r != ACG_OK) {
-        (void)hipEventSynchronize(ctx->h2d_done);           // the copy may still be reading the caller's buffer: not after we return
-        return r;
-    }
-    // (the context's stream is ordered behind the call's last down-converter launch, whichever stream that ran on)
-    HIPCHK(ctx, hipEventRecord(ctx->stage_free[slot], ctx->stream));
-    ctx->stage_free_valid[slot] = true;
-    HIPCHK(ctx, hipEventSynchronize(ctx->h2d_done));       // the caller's buffer is free again
-    return ACG_OK;
+    if (ctx->stage.fill) return fail(ctx, ACG_ESTATE, CARRY_MSG);          // (it waits at the head of the same buffers)
+    if ((r = stage_reserve(ctx, max_row * ctx->cfg.nstreams)) != ACG_OK) return r;
+    unsigned char* dev;
+    if ((r = stage_claim(ctx, dev)) != ACG_OK) return r;
+    HIPCHK(ctx, hipMemcpy2DAsync(dev, dpitch, iq_host, ctx->cfg.nstreams > 1 ? pitch_bytes : row, row, (size_t)ctx->cfg.nstreams,
+                                 hipMemcpyHostToDevice, ctx->stage.copy));
+    if ((r = stage_copied(ctx)) == ACG_OK) r = acg_process_iq_u8_dev(ctx, dev, dpitch, nblocks, nullptr);
+    if (r == ACG_OK) r = stage_turn(ctx);
+    return stage_return(ctx, r);
 }
 
 extern "C" int acg_process_dm_dev(acg_ctx* ctx, const float* dm_dev, size_t pitch_floats, int len,
@@ -551,7 +597,7 @@ extern "C" int acg_process_dm_host(acg_ctx* ctx, const float* dm_host, size_t pi
     }
     int r = launch_msk(ctx, ctx->d_dm, ctx->dm_pitch, len, ctx->msk_stream);
     if (r != ACG_OK) return r;
-    if (len > 0 && (r = guard_record(ctx, 0, std::min(ctx->cfg.max_blocks, (len + ACG_BLOCK - 1) / ACG_BLOCK))) != ACG_OK) return r;
+    if (len > 0 && (r = guard_record(ctx, 0, blocks_of(ctx, len))) != ACG_OK) return r;
     return end_of_call(ctx);
 }
 
@@ -596,48 +642,39 @@ extern "C" int acg_process_pcm_dev(acg_ctx* ctx, int fmt, const void* frames_dev
     if (nframes > 0) {
         // the dm image may still be read by the demodulator launch of the call before (the guard acg_process_dm_host and the
         // pipeline record); then the kernel, on the CALLER's stream like the down-converter's chunks
-        const int nb = std::min(ctx->cfg.max_blocks, (nframes + ACG_BLOCK - 1) / ACG_BLOCK);
-        if ((r = guard_wait(ctx, s, 0, nb)) != ACG_OK) return r;
+        if ((r = guard_wait(ctx, s, 0, blocks_of(ctx, nframes))) != ACG_OK) return r;
         if ((r = launch_pcm(ctx, fmt, frames_dev, nframes, ctx->d_dm, ctx->dm_pitch, s)) != ACG_OK) return r;
         HIPCHK(ctx, hipEventRecord(ctx->in_ev, s));
         HIPCHK(ctx, hipStreamWaitEvent(ctx->msk_stream, ctx->in_ev, 0));
     }
     if ((r = launch_msk(ctx, ctx->d_dm, ctx->dm_pitch, nframes, ctx->msk_stream)) != ACG_OK) return r;
-    if (nframes > 0 && (r = guard_record(ctx, 0, std::min(ctx->cfg.max_blocks, (nframes + ACG_BLOCK - 1) / ACG_BLOCK))) != ACG_OK) return r;
+    if (nframes > 0 && (r = guard_record(ctx, 0, blocks_of(ctx, nframes))) != ACG_OK) return r;
     return end_of_call(ctx);
 }
 
-// Host frames of any count: chunks of at most max_len frames, each ONE contiguous copy into the staging buffer the chunk before
-// the previous one used (acg_process_iq_u8_host's scheme: the copy of chunk k + 1 runs beside the kernels of chunk k), then the
-// device path.  Returns when the last copy has left the caller's buffer.
+// Host frames of any count: chunks of at most max_len frames, each ONE contiguous copy and one round of the staging ring (the
+// copy of chunk k + 1 runs beside the kernels of chunk k), then the device path.  Returns when the last copy has left the
+// caller's buffer.
 extern "C" int acg_feed_pcm_host(acg_ctx* ctx, int fmt, const void* frames, size_t nframes)
 {
     int r = check_pcm_args(ctx, fmt, frames);
     if (r != ACG_OK) return r;
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-    if (ctx->feed_fill) return fail(ctx, ACG_ESTATE, "acg_feed_samples_host is carrying a partial window in the staging buffers (acg_reset drops it)");
+    if (ctx->stage.fill) return fail(ctx, ACG_ESTATE, CARRY_MSG);
     if (nframes == 0) return acg_process_pcm_dev(ctx, fmt, frames, 0, nullptr);
     const size_t fb = (size_t)ctx->cfg.nch * pcm_elem(fmt);          // bytes per frame
-    if ((r = ensure_stage(ctx, ((size_t)ctx->max_len * fb + 3) & ~(size_t)3)) != ACG_OK) return r;
-    for (size_t done = 0; done < nframes;) {
+    if ((r = stage_reserve(ctx, ((size_t)ctx->max_len * fb + 3) & ~(size_t)3)) != ACG_OK) return r;
+    for (size_t done = 0; done < nframes && r == ACG_OK;) {
         const size_t take = std::min(nframes - done, (size_t)ctx->max_len);
-        const int slot = (int)(ctx->stage_seq++ & 1u);
-        if (ctx->stage_free_valid[slot]) HIPCHK(ctx, hipStreamWaitEvent(ctx->h2d_stream, ctx->stage_free[slot], 0));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[slot], (const unsigned char*)frames + done * fb, take * fb, hipMemcpyHostToDevice, ctx->h2d_stream));
-        HIPCHK(ctx, hipEventRecord(ctx->h2d_done, ctx->h2d_stream));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->h2d_done, 0));
-        r = acg_process_pcm_dev(ctx, fmt, ctx->d_stage[slot], (int)take, nullptr);
-        if (r != ACG_OK) {
-            (void)hipEventSynchronize(ctx->h2d_done);           // the copy may still be reading the caller's buffer: not after we return
-            return r;
-        }
-        // (the context's stream is ordered behind the de-interleave kernel, the buffer's only reader)
-        HIPCHK(ctx, hipEventRecord(ctx->stage_free[slot], ctx->stream));
-        ctx->stage_free_valid[slot] = true;
+        unsigned char* dev;
+        if ((r = stage_claim(ctx, dev)) != ACG_OK) break;
+        HIPCHK(ctx, hipMemcpyAsync(dev, (const unsigned char*)frames + done * fb, take * fb, hipMemcpyHostToDevice, ctx->stage.copy));
+        // (the de-interleave kernel is the buffer's only reader)
+        if ((r = stage_copied(ctx)) == ACG_OK) r = acg_process_pcm_dev(ctx, fmt, dev, (int)take, nullptr);
+        if (r == ACG_OK) r = stage_turn(ctx);
         done += take;
     }
-    HIPCHK(ctx, hipEventSynchronize(ctx->h2d_done));           // the caller's buffer is free again (the copy stream runs in order)
-    return ACG_OK;
+    return stage_return(ctx, r);
 }
 
 // Only the kernel, into a scratch image of nch x pitch_floats words pre-filled with `fill`; the input lies in a device buffer
@@ -717,12 +754,10 @@ static int fmt_args(acg_ctx* ctx, int fmt, FirArgs* a)
     return ACG_OK;
 }
 
-// pipeline chunk of the formats: the u8 path's bytes per launch (2-byte samples: its callbacks; 4-byte samples: half of them;
-// 8-byte samples: a quarter)
+// pipeline chunk of the formats (chunk_windows; split planes: two 2-byte samples)
 static int fmt_chunk_win(const acg_ctx* ctx, int fmt)
 {
-    const int per = fmt == ACG_FMT_CS8 ? 1 : fmt == ACG_FMT_CF32 ? 4 : 2;
-    return (ctx->pipe_blocks > 0 ? (ctx->pipe_blocks + per - 1) / per : ctx->cfg.max_blocks) * ACG_BLOCK;
+    return chunk_windows(ctx, fmt == ACG_FMT_CS8 ? 1 : fmt == ACG_FMT_CF32 ? 4 : 2);
 }
 
 // the format's down-converter launch (see fir_launch)
@@ -753,6 +788,50 @@ extern "C" int acg_process_samples_dev(acg_ctx* ctx, int fmt, const void* dev, s
 // Host feed with carry: windows may straddle feeds of any size (soapy.c:232-254, sdrplay.c:215-236,
 // air.c:299-338 carry D / the index across buffers; here the incomplete window's SAMPLES wait at the
 // head of a device staging row -- the sums are then the same sequential windows).
+// The one loop of acg_feed_samples_host and acg_feed_rate_host, a round of the staging ring each time: up to a staging row of
+// samples (bps bytes each in the plane p0, and in p1 where the format has two) goes behind the carried ones; fit(have) says how
+// many whole windows that makes and how many samples they use; run(base, pitch, plane, have, nwin) is their device path; the
+// rest moves to the head of the buffer that is the current one from then on -- on the copy stream, beside the kernels.
+struct FeedFit { int nwin; size_t used; };
+template <class Fit, class Run>
+static int feed_carry(acg_ctx* ctx, int fmt, size_t bps, const void* p0, const void* p1, size_t pitch_samples, size_t nsamples, Fit&& fit,
+                      Run&& run)
+{
+    StageRing& st = ctx->stage;
+    if (st.fmt != fmt) { st.fmt = fmt; st.fill = 0; }
+    const size_t ns = (size_t)ctx->cfg.nstreams;
+    const size_t cap = (size_t)ctx->max_len * (size_t)ctx->cfg.decim;         // samples a staging row holds: max_len windows always fit
+    const size_t plane = ((cap * bps) + 15) & ~(size_t)15;
+    const size_t rowb = p1 ? 2 * plane : plane, hpitch = (ns > 1 ? pitch_samples : nsamples) * bps;
+    const void* const host[2] = {p0, p1};
+    int r = stage_reserve(ctx, rowb * ns);
+    if (r != ACG_OK) return r;
+    // (no samples left: a round for whole windows that a launch capped at max_len left behind)
+    for (size_t done = 0; done < nsamples || fit(st.fill).nwin > 0;) {
+        const size_t take = std::min(nsamples - done, cap - st.fill), have = st.fill + take;
+        unsigned char *base = nullptr, *next = nullptr;
+        if ((r = stage_claim(ctx, base)) != ACG_OK) break;
+        for (int k = 0; k < 2 && host[k] && take; ++k)
+            HIPCHK_OL(ctx, hipMemcpy2DAsync(base + k * plane + st.fill * bps, rowb, (const unsigned char*)host[k] + done * bps, hpitch,
+                                            take * bps, ns, hipMemcpyHostToDevice, st.copy));
+        done += take;
+        if ((r = stage_copied(ctx)) != ACG_OK) break;                      // (also where no window gets whole: stage_return waits for this)
+        const FeedFit f = fit(have);
+        if (f.nwin == 0) {
+            st.fill = have;
+            break;                                                          // (have < cap here: the input is used up)
+        }
+        if ((r = run(base, rowb, plane, have, f.nwin)) != ACG_OK || (r = stage_turn(ctx)) != ACG_OK) break;
+        const size_t left = have - f.used;
+        if (left && (r = stage_claim(ctx, next)) != ACG_OK) break;
+        for (int k = 0; k < 2 && host[k] && left; ++k)
+            HIPCHK_OL(ctx, hipMemcpy2DAsync(next + k * plane, rowb, base + k * plane + f.used * bps, rowb, left * bps,
+                                            ns, hipMemcpyDeviceToDevice, st.copy));
+        st.fill = left;
+    }
+    return stage_return(ctx, r);
+}
+
 extern "C" int acg_feed_samples_host(acg_ctx* ctx, int fmt, const void* p0, const void* p1, size_t pitch_samples,
                                      size_t nsamples)
 {
@@ -762,65 +841,15 @@ extern "C" int acg_feed_samples_host(acg_ctx* ctx, int fmt, const void* p0, cons
     FirArgs a;
     int r = fmt_args(ctx, fmt, &a);
     if (r != ACG_OK) return r;
-    if (ctx->feed_fmt != fmt) { ctx->feed_fmt = fmt; ctx->feed_fill = 0; }
-    const acg_config& g = ctx->cfg;
-    const size_t M = (size_t)g.decim;
-    const size_t bps = fmt_sample_bytes(fmt);                                 // bytes per sample per plane
-    const size_t cap = (size_t)ctx->max_len * M;                              // samples a staging row holds (<= max_len windows per launch)
-    const size_t plane = ((cap * bps) + 15) & ~(size_t)15;
-    const size_t rowb = fmt == ACG_FMT_S16_SPLIT ? 2 * plane : plane;
-    if ((r = ensure_stage(ctx, rowb * (size_t)g.nstreams)) != ACG_OK) return r;
-    hipStream_t s = ctx->stream, hs = ctx->h2d_stream;
-    size_t done = 0;
-    while (done < nsamples) {
-        const size_t take = std::min(nsamples - done, cap - ctx->feed_fill);
-        const int cur = ctx->feed_cur;
-        unsigned char* base = (unsigned char*)ctx->d_stage[cur];
-        // new samples behind the carried ones, on the copy stream (which already waits for the last reader of this buffer
-        // and carries the copy of the carried samples: both were enqueued when the buffer became the current one)
-        HIPCHK(ctx, hipMemcpy2DAsync(base + ctx->feed_fill * bps, rowb, (const unsigned char*)p0 + done * bps,
-                                     (g.nstreams > 1 ? pitch_samples : nsamples) * bps, take * bps, (size_t)g.nstreams,
-                                     hipMemcpyHostToDevice, hs));
-        if (fmt == ACG_FMT_S16_SPLIT)
-            HIPCHK(ctx, hipMemcpy2DAsync(base + plane + ctx->feed_fill * bps, rowb, (const unsigned char*)p1 + done * bps,
-                                         (g.nstreams > 1 ? pitch_samples : nsamples) * bps, take * bps, (size_t)g.nstreams,
-                                         hipMemcpyHostToDevice, hs));
-        HIPCHK(ctx, hipEventRecord(ctx->h2d_done, hs));
-        done += take;
-        const size_t have = ctx->feed_fill + take;
-        const size_t nwin = have / M;
-        if (nwin > 0) {
-            HIPCHK(ctx, hipStreamWaitEvent(s, ctx->h2d_done, 0));
-            a.iq = base;
-            a.pitch = rowb;
-            a.plane = plane;
-            if ((r = run_pipeline(ctx, s, a, M * bps, (int)nwin, fmt_chunk_win(ctx, fmt), fmt_launch(fmt))) != ACG_OK) {
-                (void)hipEventSynchronize(ctx->h2d_done);   // the copy may still be reading the caller's buffers: not after we return
-                return r;
-            }
-            HIPCHK(ctx, hipEventRecord(ctx->stage_free[cur], s));      // behind the last down-converter launch that reads `cur`
-            ctx->stage_free_valid[cur] = true;
-            // the other buffer becomes the current one: once its last reader (the launches of the feed before this one) is
-            // done, the < M samples of the incomplete window move to its head -- on the copy stream, beside the kernels
-            const int nxt = cur ^ 1;
-            const size_t left = have - nwin * M;
-            if (ctx->stage_free_valid[nxt]) HIPCHK(ctx, hipStreamWaitEvent(hs, ctx->stage_free[nxt], 0));
-            if (left) {
-                unsigned char* nb = (unsigned char*)ctx->d_stage[nxt];
-                HIPCHK(ctx, hipMemcpy2DAsync(nb, rowb, base + nwin * M * bps, rowb, left * bps, (size_t)g.nstreams,
-                                             hipMemcpyDeviceToDevice, hs));
-                if (fmt == ACG_FMT_S16_SPLIT)
-                    HIPCHK(ctx, hipMemcpy2DAsync(nb + plane, rowb, base + plane + nwin * M * bps, rowb, left * bps,
-                                                 (size_t)g.nstreams, hipMemcpyDeviceToDevice, hs));
-            }
-            ctx->feed_fill = left;
-            ctx->feed_cur = nxt;
-        } else {
-            ctx->feed_fill = have;
-        }
-        HIPCHK(ctx, hipEventSynchronize(ctx->h2d_done));   // the caller's buffers may be reused after return
-    }
-    return ACG_OK;
+    const size_t M = (size_t)ctx->cfg.decim, bps = fmt_sample_bytes(fmt);      // bytes per sample per plane
+    return feed_carry(ctx, fmt, bps, p0, fmt == ACG_FMT_S16_SPLIT ? p1 : nullptr, pitch_samples, nsamples,
+                      [&](size_t have) { return FeedFit{(int)(have / M), have / M * M}; },
+                      [&](const unsigned char* base, size_t pitch, size_t plane, size_t, int nwin) {
+                          a.iq = base;
+                          a.pitch = pitch;
+                          a.plane = plane;
+                          return run_pipeline(ctx, ctx->stream, a, M * bps, nwin, fmt_chunk_win(ctx, fmt), fmt_launch(fmt));
+                      });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -878,26 +907,6 @@ static int rate_windows_fit(const acg_ctx* ctx, size_t nsamples)
     return (int)n;
 }
 
-// One chunk's launch of a rate call (see fir_launch).  A plain function of launch_fir_u8's type, so that the pipeline is the
-// instantiation the u8 path already has; what the chunks share waits in the context while the call is issued.
-static int launch_fir_rate_chunk(acg_ctx* c, FirArgs& f, hipStream_t st)
-{
-    auto chunk = [&](FirGridArgs& b) {
-        b.dm = f.dm;
-        b.win0 = (int)(f.dm - c->d_dm);                          // the chunk's first window
-        b.nwin = f.nwin;
-        b.ncu = f.ncu;
-    };
-    if (c->long_call) {                                          // a channel filter is on: the same chunk, fir_long.hip's kernel
-        FirLongArgs b = *c->long_call;
-        chunk(b);
-        return acg_launch_fir_long(&b, st);
-    }
-    FirRateArgs b = *c->rate_call;
-    chunk(b);
-    return acg_launch_fir_rate(&b, st);
-}
-
 // nwin windows of the rows at dev (nsamples presented each) through the pipeline; advances the grid
 static int rate_run(acg_ctx* ctx, FirRateArgs& r, const void* dev, size_t pitch, size_t nsamples, int nwin, hipStream_t s)
 {
@@ -907,8 +916,6 @@ static int rate_run(acg_ctx* ctx, FirRateArgs& r, const void* dev, size_t pitch,
     FirArgs a = fir_args(ctx);
     a.iq = r.in;
     a.pitch = pitch;
-    const int per = r.bps == 2 ? 1 : r.bps == 4 ? 2 : 4;         // the formats' pipeline chunk (fmt_chunk_win): the u8 path's bytes per launch
-    const int chunk = (ctx->pipe_blocks > 0 ? (ctx->pipe_blocks + per - 1) / per : ctx->cfg.max_blocks) * ACG_BLOCK;
     FirLongArgs l{};
     if (ctx->long_nseg) {
         // A channel filter (acg_set_channel_filter): the rows and the chunks are the same, the kernel is fir_long.hip's, and the
@@ -925,12 +932,16 @@ static int rate_run(acg_ctx* ctx, FirRateArgs& r, const void* dev, size_t pitch,
         l.nprev = ctx->long_have;
         l.scale = ACG_FIR_GRID_FMT[r.fmt].scale;
         acg_fir_long_plan(&l);
-        ctx->long_call = &l;
     }
-    ctx->rate_call = &r;
-    const int rc = run_pipeline(ctx, s, a, 0, nwin, chunk, launch_fir_rate_chunk);
-    ctx->rate_call = nullptr;
-    ctx->long_call = nullptr;
+    // one chunk's launch (see fir_launch): the call's arguments with the chunk's windows
+    const int rc = run_pipeline(ctx, s, a, 0, nwin, chunk_windows(ctx, r.bps / 2), [&](acg_ctx* c, FirArgs& f, hipStream_t st) {
+        FirGridArgs& b = c->long_nseg ? static_cast<FirGridArgs&>(l) : r;
+        b.dm = f.dm;
+        b.win0 = (int)(f.dm - c->d_dm);                              // the chunk's first window
+        b.nwin = f.nwin;
+        b.ncu = f.ncu;
+        return c->long_nseg ? acg_launch_fir_long(&l, st) : acg_launch_fir_rate(&r, st);
+    });
     if (rc == ACG_OK) ctx->rate_k += (unsigned long long)nwin;
     if (rc == ACG_OK && ctx->long_nseg) {
         // The history of the next call: the last nseg - 1 windows of (this call's history, this call's windows), into the other
@@ -965,7 +976,7 @@ extern "C" int acg_process_rate_dev(acg_ctx* ctx, int fmt, const void* dev, size
     if ((((uintptr_t)dev | pitch_bytes) & 15)) return fail(ctx, ACG_EINVAL, "base and pitch must be 16-byte aligned");
     if (pitch_bytes < (((unsigned long long)nsamples * r.bps + 15) & ~15ull))
         return fail(ctx, ACG_EINVAL, "pitch smaller than a row: nsamples * bytes per sample, rounded up to 16");
-    if (ctx->feed_fill) return fail(ctx, ACG_ESTATE, "acg_feed_rate_host is carrying a partial window (acg_reset drops it)");
+    if (ctx->stage.fill) return fail(ctx, ACG_ESTATE, CARRY_MSG);
     HIPCHK_OL(ctx, hipSetDevice(ctx->cfg.device));
     const int n = rate_windows_fit(ctx, nsamples);
     if (n == 0) return ACG_OK;
@@ -978,7 +989,7 @@ extern "C" int acg_process_rate_dev(acg_ctx* ctx, int fmt, const void* dev, size
 }
 
 // acg_feed_samples_host's scheme with variable windows: the samples behind the last whole window wait at the head of the other
-// staging row -- always a window start -- and the copy of feed i + 1 runs beside the kernels of feed i.
+// staging row -- always a window start.
 extern "C" int acg_feed_rate_host(acg_ctx* ctx, int fmt, const void* samples, size_t pitch_samples, size_t nsamples)
 {
     if (!ctx || !samples) return ACG_EINVAL;
@@ -986,53 +997,15 @@ extern "C" int acg_feed_rate_host(acg_ctx* ctx, int fmt, const void* samples, si
     int rc = rate_fmt(ctx, fmt, &r);
     if (rc != ACG_OK) return rc;
     HIPCHK_OL(ctx, hipSetDevice(ctx->cfg.device));
-    if (ctx->feed_fmt != fmt) { ctx->feed_fmt = fmt; ctx->feed_fill = 0; }
-    const acg_config& g = ctx->cfg;
-    const size_t bps = (size_t)r.bps;
-    const size_t cap = (size_t)ctx->max_len * (size_t)g.decim;                // samples a staging row holds: max_len windows always fit
-    const size_t rowb = ((cap * bps) + 15) & ~(size_t)15;
-    if ((rc = ensure_stage(ctx, rowb * (size_t)g.nstreams)) != ACG_OK) return rc;
-    hipStream_t s = ctx->stream, hs = ctx->h2d_stream;
-    size_t done = 0;
-    for (;;) {
-        const size_t take = std::min(nsamples - done, cap - ctx->feed_fill);
-        const int cur = ctx->feed_cur;
-        unsigned char* base = (unsigned char*)ctx->d_stage[cur];
-        // new samples behind the carried ones, on the copy stream (which already waits for the last reader of this buffer and
-        // carries the copy of the carried samples); no new ones: a round for whole windows the last launch left behind
-        if (take)
-            HIPCHK_OL(ctx, hipMemcpy2DAsync(base + ctx->feed_fill * bps, rowb, (const unsigned char*)samples + done * bps,
-                                         (g.nstreams > 1 ? pitch_samples : nsamples) * bps, take * bps, (size_t)g.nstreams,
-                                         hipMemcpyHostToDevice, hs));
-        HIPCHK_OL(ctx, hipEventRecord(ctx->h2d_done, hs));
-        done += take;
-        const size_t have = ctx->feed_fill + take;
-        const int nwin = rate_windows_fit(ctx, have);
-        if (nwin == 0) {
-            ctx->feed_fill = have;
-            HIPCHK_OL(ctx, hipEventSynchronize(ctx->h2d_done));
-            break;                                                          // (have < cap here: the input is used up)
-        }
-        const size_t used = (size_t)rate_span(ctx, (unsigned long long)nwin);
-        HIPCHK_OL(ctx, hipStreamWaitEvent(s, ctx->h2d_done, 0));
-        r.r0 = (unsigned int)(ctx->rate_k % ctx->rate_Q);
-        if ((rc = rate_run(ctx, r, base, rowb, have, nwin, s)) != ACG_OK) {
-            (void)hipEventSynchronize(ctx->h2d_done);           // the copy may still be reading the caller's buffer: not after we return
-            return rc;
-        }
-        HIPCHK_OL(ctx, hipEventRecord(ctx->stage_free[cur], s));      // behind the last down-converter launch that reads `cur`
-        ctx->stage_free_valid[cur] = true;
-        const int nxt = cur ^ 1;
-        const size_t left = have - used;
-        if (ctx->stage_free_valid[nxt]) HIPCHK_OL(ctx, hipStreamWaitEvent(hs, ctx->stage_free[nxt], 0));
-        if (left)
-            HIPCHK_OL(ctx, hipMemcpy2DAsync(ctx->d_stage[nxt], rowb, base + used * bps, rowb, left * bps, (size_t)g.nstreams,
-                                         hipMemcpyDeviceToDevice, hs));
-        ctx->feed_fill = left;
-        ctx->feed_cur = nxt;
-        HIPCHK_OL(ctx, hipEventSynchronize(ctx->h2d_done));   // the caller's buffer may be reused after return
-    }
-    return ACG_OK;
+    return feed_carry(ctx, fmt, (size_t)r.bps, samples, nullptr, pitch_samples, nsamples,
+                      [&](size_t have) {
+                          const int n = rate_windows_fit(ctx, have);
+                          return FeedFit{n, (size_t)rate_span(ctx, (unsigned long long)n)};
+                      },
+                      [&](const unsigned char* base, size_t pitch, size_t, size_t have, int nwin) {
+                          r.r0 = (unsigned int)(ctx->rate_k % ctx->rate_Q);
+                          return rate_run(ctx, r, base, pitch, have, nwin, ctx->stream);
+                      });
 }
 
 // A placement trial: one untimed process call (it also checks the arguments), `repeats` timed ones, then a reset

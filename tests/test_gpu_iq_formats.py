@@ -297,6 +297,70 @@ def test_host_feed_with_carry_equals_one_device_call(D, S, K, fmt, tune):
     dec.close()
 
 
+def test_u8_host_calls_and_carrying_feeds_alternate_on_one_context(D, K, tune):
+    """acg_process_iq_u8_host and acg_feed_samples_host(ACG_FMT_CS8) share the two staging buffers of a context and may alternate
+    on it: feed of exactly one window, u8 call, u8 call, feed of 3 M + 7 samples, u8 call, feed of M - 7 samples, every call with
+    data of its own.  After each call dm (acg_read_dm_n) is bit for bit what a twin context makes of the same samples in one
+    device call: acg_process_iq_u8_dev per u8 block, one acg_process_samples_dev call over the feeds' 5 M samples (held to the
+    workgroup-granular kernel, which the feeds' launches of 1, 3 and 1 windows take: see the test above).
+    The third u8 call comes while 7 samples are carried: it is refused (ACG_ESTATE, include/acarsdec_amd.h) and must leave dm,
+    the carried samples and the buffers as they were -- the last feed completes the window the 7 samples began."""
+    import torch
+    M, ns, nwin = 160, 3, 1024
+    rng = np.random.default_rng(31)
+    fc = D.choose_fc(FREQS3, M)[0]
+    taps = np.stack([D.soapy_taps(float(f), fc, M) for f in FREQS3])
+    u8 = [rng.integers(0, 256, size=(ns, nwin * M * 2), dtype=np.uint8) for _ in range(3)]
+    s8 = rng.integers(-128, 128, size=(ns, nwin * M * 2), dtype=np.int8)          # the feeds' samples are its first 5 M
+
+    def context():
+        d = D.Decoder(ns, decim=M, nstreams=ns, max_blocks=1, bitlog=False)
+        d.set_taps(taps)
+        return d
+
+    def dm_of(d, n):
+        dm = np.zeros((ns, n), dtype=np.float32)
+        assert d.L.acg_read_dm_n(d.ctx, 0, ns, dm.ctypes.data, n, n) == K.OK
+        return dm.view(np.uint32)
+
+    twin = context()
+    want_u8 = []
+    for x in u8[:2]:
+        twin.in_callback(torch.from_numpy(x).cuda(), 1)
+        want_u8.append(dm_of(twin, nwin))
+    tune("ACG_FIR_VARIANT", "3")
+    assert twin.samples_launch(K.FMT_CS8, 1).family == K.FIR_WORKGROUP
+    t, pitch, _ = to_device(Q.CS8, s8)
+    twin.process_samples(K.FMT_CS8, t, 1, pitch, 0)
+    want_s8 = dm_of(twin, 5)
+    tune("ACG_FIR_VARIANT", None)
+    twin.close()
+    assert not np.array_equal(want_u8[0], want_u8[1])
+
+    dec = context()
+    pos = [0]
+
+    def feed(n, w0, w1):
+        dec.feed(K.FMT_CS8, s8[:, 2 * pos[0]: 2 * (pos[0] + n)])
+        pos[0] += n
+        assert np.array_equal(dm_of(dec, w1 - w0), want_s8[:, w0: w1]), (w0, w1)
+
+    def u8_host(k):
+        dec.in_callback(u8[k], 1)
+        assert np.array_equal(dm_of(dec, nwin), want_u8[k]), k
+
+    feed(M, 0, 1)
+    u8_host(0)
+    u8_host(1)
+    feed(3 * M + 7, 1, 4)
+    assert dec.L.acg_process_iq_u8_host(dec.ctx, u8[2].ctypes.data, u8[2].shape[1], 1) == K.ESTATE
+    assert b"partial window" in dec.L.acg_last_error(dec.ctx)
+    assert np.array_equal(dm_of(dec, 3), want_s8[:, 1: 4])
+    feed(M - 7, 4, 5)
+    assert pos[0] == 5 * M
+    dec.close()
+
+
 @pytest.mark.parametrize("fmt", [Q.CF32, Q.CS8])
 def test_end_to_end_three_channels_on_one_stream(D, O, S, K, fmt):
     """Three synthetic ACARS channels on one clean stream, M = 200: every transmitted frame is delivered field for field by
